@@ -17,7 +17,14 @@ all-reduce of the pixel gradient per step (strong scaling; the trunk is replicat
 A bare `python bench.py --gpus N` (no torchrun around it) starts the N ranks itself: it re-launches this script under
 `python -m torch.distributed.run` as a CHILD process before anything touches the GPU and exits with the child's code.
 
-Rank 0 prints ONE JSON line.  Besides the contract keys it carries
+A plain run sets up, warms up, times the --steps steps, writes --dump-outputs if asked and prints the line: its
+`value` / `ms_per_step` are those of the timed steps.  `--dump-outputs DIR` writes what the timed path computed in its
+last step as DIR/<name>.npy (dump_outputs); the inputs are seeded, so two builds run with the same arguments can be
+compared output for output: every engine of the run sums its tap adjoint in a fixed order
+(default_to_deterministic_adjoint), so two runs of one build write identical files.
+
+Rank 0 prints ONE JSON line.  With `--full` (the `--no-*` switches act within it) it also carries
+  long_window / box_calibration / normalised : a >= 200-replay window and what this box sustains (box_calibration);
   roofline      : the kernel class with the largest share of the step (at 1024 px: the fused F(4x4,3x3) Winograd kernel
                   on the f32 MFMA) against ITS bound, from the routing the library actually took per layer and direction
                   (strotss_conv3x3_winograd_route); `by_path` holds all three classes, each against its own bound:
@@ -29,13 +36,15 @@ Rank 0 prints ONE JSON line.  Besides the contract keys it carries
   cpu_baseline  : the oracle (oracle/strotss_oracle.py, fp32 torch-CPU restatement of the
                   reference) timed on the host cores on a bounded sample of the same workload;
   pyramid       : steps/s at every scale 64..1024 and the projected optimisation wall-clock of the
-                  full 5-scale x 200-step run.
+                  full 5-scale x 200-step run;
+  wall_clock_to_output : the CLI's whole 5-scale schedule, model build to output JPEG.
 """
 import argparse
 import json
 import os
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 for p in (ROOT, os.path.join(ROOT, "strotss-tensorflow_amd")):
@@ -79,6 +88,15 @@ def region_masks(scale, regions):
         m[:, a:b] = True
         out.append(m)
     return out
+
+
+def default_to_deterministic_adjoint():
+    """Every engine of a bench run (the timed one, the traffic child, the pyramid, the CLI's wall-clock run) sums the tap
+    adjoint in a fixed order (StepEngine's deterministic mode: a planned, sorted scatter instead of float atomics,
+    DESIGN.md 6), so the same arguments compute the same outputs in every run -- the first, sign-like RMSprop steps would
+    otherwise amplify the atomics' last-bit differences.  STROTSS_DETERMINISTIC=0 in the environment runs the
+    float-atomic form everywhere instead."""
+    os.environ.setdefault("STROTSS_DETERMINISTIC", "1")
 
 
 def build_engine(params, scale, dev, seed, sample_size=SAMPLES, strips=None, regions=1, dist_group=None):
@@ -130,6 +148,36 @@ def run_steps(eng, idx, first, count):
         return
     for i in range(first, first + count):
         eng.step(list(idx[i % idx.shape[0]]))
+
+
+DUMP_BUDGET_BYTES = 60 * 10**6       # the .npy files stay under 64 MB in all, headers included
+LOSS_KEYS = ("loss", "loss_c", "loss_s", "l_moment", "l_remd", "l_palette")
+
+
+def dump_outputs(eng, out_dir, budget=DUMP_BUDGET_BYTES):
+    """What a caller of the timed step holds after its last step, as out_dir/<name>.npy: `stylized` (the folded image the
+    CLI writes, (1, S, S, 3) float32), `pyramid_0`..`pyramid_5` (the Laplacian-pyramid variables the step updates, float32),
+    `losses` (float64, in the order of LOSS_KEYS) and `region_loss_terms` ((R, 4) float32: loss_c, l_moment, l_remd,
+    l_palette per mask region).  When the arrays exceed `budget` together (scales above 1024 px), every large one is
+    replaced by the same fraction of its elements at sorted flat positions drawn with a seed fixed per name (1-D)."""
+    torch.cuda.synchronize()
+    arrays = {"stylized": eng.stylized().cpu().numpy()}
+    for k, v in enumerate(eng.variables):
+        arrays[f"pyramid_{k}"] = v.detach().cpu().numpy()
+    losses = eng.losses()
+    arrays["losses"] = np.array([losses[k] for k in LOSS_KEYS], dtype=np.float64)
+    arrays["region_loss_terms"] = eng.scalars[:, :eng.N_SCALARS].detach().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        keep = budget / total
+        for name, a in arrays.items():
+            if a.size > 4096:
+                rng = np.random.default_rng(zlib.crc32(name.encode()))
+                pos = np.sort(rng.choice(a.size, int(a.size * keep), replace=False))
+                arrays[name] = a.reshape(-1)[pos]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 # reference device for `normalised`: the nominal figures of MI355X_MICROARCH.md (f32 MFMA 155 TF measured back to back,
@@ -797,6 +845,11 @@ def main():
     ap.add_argument("--host-draw", action="store_true", help="pre-drawn, pre-uploaded index sets (rounds 1-3) instead of the "
                                                              "draw kernel at the head of every timed step")
     ap.add_argument("--scale", type=int, default=1024)
+    ap.add_argument("--full", action="store_true", help="after the timed steps, every other measurement too: the long window and "
+                                                        "box calibration, per-kernel-family timing and roofline, live PMC traffic, "
+                                                        "the 64..512 px pyramid, the wall clock to output and the CPU baseline "
+                                                        "(the --no-* switches leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path computed in its last step as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pyramid", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of one hipGraph per step")
@@ -814,6 +867,12 @@ def main():
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rehearse", action="store_true", help="N-rank harness only (gloo, sleeping stand-in step, no GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    default_to_deterministic_adjoint()
+    if not args.full:                 # a plain run measures the headline figure and nothing else
+        args.no_long_window = args.no_families = args.no_live_pmc = True
+        args.no_pyramid = args.no_e2e = args.no_cpu_baseline = True
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -886,6 +945,8 @@ def main():
     if one_job:
         value /= world                    # ONE job: its steps are not multiplied by the ranks
     losses = eng.losses()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs)     # before any --full pass steps the engine further
     # a window long enough to compare across runs whatever --steps was (the driver asks for 20 = 0.09 s): >= 200 replays
     long_window = None
     if world == 1 and not args.no_long_window:
@@ -918,7 +979,8 @@ def main():
                "config": {"workload": f"{S}px content/style pair, {S}x{S} scale of the coarse-to-fine pyramid, "
                                       f"{SAMPLES} samples x D={D}, VGG16 (seeded He-normal weights), "
                                       f"RMSprop pixel update" + (f", {regions} mask regions" if regions > 1 else ""),
-                          "scale_px": S, "samples": SAMPLES, "parallelism": par_desc},
+                          "scale_px": S, "samples": SAMPLES, "parallelism": par_desc,
+                          "tap_adjoint": "deterministic (planned, sorted scatter)" if eng.deterministic else "float atomics"},
                "loss_after": round(losses["loss"], 5), "launch_mode": graph_mode,
                "index_draw": ("inside the timed step: strotss_index_draw is the first kernel of every step's graph (Philox "
                               "stream, csrc/draw.hip; reference: strotss_utils.py:83-121 inside the traced step)" if drawn else
