@@ -413,6 +413,34 @@ int strotss_step_losses_fwd_bwd(const float* pred, const float* content, int n, 
                                 const float* style_cov, float g_content, float g_moment, float g_remd, float g_palette,
                                 float* gpred, float* loss_content, float* loss_moment, float* loss_remd, float* loss_palette,
                                 void* workspace, size_t workspace_bytes, void* stream);
+/* Style blending: the same step against a weighted set of 1 .. STROTSS_MAX_STYLES style targets.  Style k is what
+ * strotss_step_losses_fwd_bwd takes for one style (feats[k] = its ns[k] sampled rows, inv_norm / panels =
+ * strotss_row_inv_norm_x3(feats[k]), mean / cov = strotss_moment_stats(feats[k])); weight[k] >= 0, finite (the caller
+ * normalises them).  loss_content[0] as above; loss_moment[k], loss_remd[k], loss_palette[k] = the UNWEIGHTED terms of
+ * style k;  gpred += g_content * dLc + sum_k weight[k] * (g_moment * dLm_k + g_remd * dLr_k + g_palette * dLp_k).
+ * n_styles == 1 is strotss_step_losses_fwd_bwd itself (g_moment, g_remd, g_palette times weight[0]).  n_styles > 1: the
+ * same 9 launches whatever the count -- one covariance of the prediction rows compared with every style's, one
+ * prediction x style cost matrix per style in the grouped forward launch, statistics, selections and sparse backward
+ * passes segmented per style, ONE moment backward product on the weighted sign matrix.
+ * STROTSS_EINVAL: null pointers, bad sizes or weights, bf16x3 core switched off; STROTSS_ERANGE: n_styles outside
+ * 1 .. STROTSS_MAX_STYLES or a style with more rows than the tie lists hold (2048); STROTSS_EALIGN: ld % 32 != 0. */
+#define STROTSS_MAX_STYLES 4
+typedef struct {
+  int n_styles;
+  const float* feats[STROTSS_MAX_STYLES];      /* (ns[k], ld) rows */
+  const float* inv_norm[STROTSS_MAX_STYLES];   /* (ns[k]) */
+  const void* panels[STROTSS_MAX_STYLES];      /* x3 panels of feats[k] */
+  int ns[STROTSS_MAX_STYLES];
+  const float* mean[STROTSS_MAX_STYLES];       /* (ld) */
+  const float* cov[STROTSS_MAX_STYLES];        /* (ld, ld) */
+  float weight[STROTSS_MAX_STYLES];
+} strotss_style_set_t;
+size_t strotss_step_losses_blend_workspace_bytes(const strotss_style_set_t* styles, int n, int ld);
+int strotss_step_losses_blend_fwd_bwd(const float* pred, const float* content, int n, int d, int ld,
+                                      const strotss_style_set_t* styles, float g_content, float g_moment, float g_remd,
+                                      float g_palette, float* gpred, float* loss_content, float* loss_moment,
+                                      float* loss_remd, float* loss_palette, void* workspace, size_t workspace_bytes,
+                                      void* stream);
 size_t strotss_moment_workspace_bytes(int n, int ld);
 /* style side of moment_matching, once per scale: mean_out(ld), cov_out(ld,ld) = biased covariance */
 int strotss_moment_stats(const float* x, int n, int d, int ld, float* mean_out, float* cov_out,

@@ -642,6 +642,66 @@ int st_loss_forward_group_x3(const void* Pt, int npad, int ld, const float* Sx, 
   ST_LAUNCH_RET();
 }
 
+// XCD blocking of a full (non-symmetric) gy x gx tile grid as in st_cosine_distance_x3 (bh = 0: plain row order)
+static void x3_xcd_block(unsigned gy, unsigned gx, int* bh, int* bw) {
+  *bh = 0; *bw = 0;
+  if ((gx * gy) % 8) return;
+  const unsigned per = gx * gy / 8;
+  unsigned best = 0;
+  for (unsigned h = 1; h <= per; ++h) {
+    if (per % h || gy % h) continue;
+    const unsigned w = per / h;
+    if (gx % w) continue;
+    if (!best || h + w < best + per / best) best = h;
+  }
+  if (best) { *bh = (int)best; *bw = (int)(per / best); }
+}
+
+// The forward products of a BLENDED step's loss section in ONE launch (gemm_x3_group_set_kernel): the covariance of the
+// centred prediction rows itself, Sigma = inv_n Pt^T Pt (st_gram_tn_x3's tiles and product order, written whole and bitwise
+// symmetric: every style's sign matrix and |difference| are taken from it afterwards), the two self-similarity cost
+// matrices and one prediction-major cost matrix per style, Ct[k][j][i] = 1 - <yhat_j, xhat_ki> (the tiles of
+// st_loss_forward_group_x3's third problem).  Bitwise the matrices of the separate launches.
+int st_loss_forward_blend_x3(const void* Pt, int npad, int ld, float inv_n, float* Sigma, const void* xp, const float* rp,
+                             int n, long long pstride, long long rstride, float* Dx, int ldc, long long dstride, int n_styles,
+                             const void* const* xs, const float* const* rs, const int* ns, float* const* Ct, const int* ldt,
+                             hipStream_t s) {
+  using CM = X3CfgK16<3>;
+  using CC = X3Cfg<64>;
+  if (n_styles < 1 || n_styles > X3_MAX_SET) return (int)hipErrorInvalidValue;
+  const unsigned gm = cdiv(ld, 128), nm = gm * (gm + 1) / 2;
+  const unsigned g = cdiv(n, 64), nc = g * (g + 1) / 2 * 2;
+  X3Problem<EpiSymScaleX3> p0{(const __bf16*)Pt, ld, 0LL, (const __bf16*)Pt, ld, 0LL, npad,
+                              EpiSymScaleX3{{}, Sigma, ld, ld, ld, inv_n}, 0, 0, nm};
+  X3Problem<EpiCosDistX3> p1{(const __bf16*)xp, n, pstride, (const __bf16*)xp, n, pstride, ld,
+                             EpiCosDistX3{{rp, rp, Dx, ldc, n, n, 1}, {}, rstride, dstride}, 0, 0, nc};
+  X3ProblemSet<EpiCosDistX3> ps{};
+  ps.count = n_styles;
+  unsigned grid = x3_pad8(nm) + x3_pad8(nc);
+  for (int k = 0; k < n_styles; ++k) {
+    const unsigned gs = cdiv(ns[k], 64), nr = g * gs;
+    int bh, bw;
+    x3_xcd_block(g, gs, &bh, &bw);
+    ps.q[k] = X3Problem<EpiCosDistX3>{(const __bf16*)xp, n, 0LL, (const __bf16*)xs[k], ns[k], 0LL, ld,
+                                      EpiCosDistX3{{rp, rs[k], Ct[k], ldt[k], n, ns[k], 0}, {}, 0LL, 0LL}, bh, bw, nr};
+    grid += x3_pad8(nr);
+  }
+  hipLaunchKernelGGL((gemm_x3_group_set_kernel<CM, EpiSymScaleX3, X3Mirror<CM>, CC, EpiCosDistX3, X3Mirror<CC>, CC, EpiCosDistX3,
+                                               X3Mirror<CC>>), dim3(grid), dim3(256), 0, s, p0, p1, ps);
+  ST_LAUNCH_RET();
+}
+
+// st_moment_bwd_x3 with a general f32 right-hand matrix (three planes): the weighted sum of the styles' sign matrices
+int st_moment_bwd_x3_full(const void* Pc, int n, int ld, const void* Sp, float alpha, const float* bias, float bias_scale,
+                          float* dY, hipStream_t s) {
+  using Cfg = X3Cfg<128>;
+  EpiAxpbyBiasX3 e{{dY, ld, n, ld, alpha, bias, bias_scale}};
+  dim3 grid((unsigned)cdiv(ld, 128) * cdiv(n, 128));
+  hipLaunchKernelGGL((gemm_x3_kernel<Cfg, EpiAxpbyBiasX3, X3NoMirror>), grid, dim3(Cfg::NT), 0, s, (const __bf16*)Pc, n, 0LL,
+                     (const __bf16*)Sp, ld, 0LL, ld, e, X3NoMirror{});
+  ST_LAUNCH_RET();
+}
+
 // dY(n x ld) += alpha * c(n x ld) @ T(ld x ld, symmetric) + bias_scale * bias[c]: c as x3 panels, T as the
 // single-plane panel written by st_moment_fwd_x3 (three partial products instead of six).
 int st_moment_bwd_x3(const void* Pc, int n, int ld, const void* Tp, float alpha, const float* bias, float bias_scale,

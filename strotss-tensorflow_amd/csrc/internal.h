@@ -43,6 +43,12 @@ int st_loss_forward_group_x3(const void* Pt, int npad, int ld, const float* Sx, 
                              int* n_partial, const void* xp, const float* rp, int n, long long pstride, long long rstride,
                              float* Dx, int ldc, long long dstride, const void* xs, const float* rs, int ns, float* Ct,
                              int ldt, hipStream_t s);
+int st_loss_forward_blend_x3(const void* Pt, int npad, int ld, float inv_n, float* Sigma, const void* xp, const float* rp,
+                             int n, long long pstride, long long rstride, float* Dx, int ldc, long long dstride, int n_styles,
+                             const void* const* xs, const float* const* rs, const int* ns, float* const* Ct, const int* ldt,
+                             hipStream_t s);
+int st_moment_bwd_x3_full(const void* Pc, int n, int ld, const void* Sp, float alpha, const float* bias, float bias_scale,
+                          float* dY, hipStream_t s);
 int st_moment_bwd_x3(const void* Pc, int n, int ld, const void* Tp, float alpha, const float* bias, float bias_scale,
                      float* dY, hipStream_t s);
 int st_gemm_x3_batched(const void* A, const void* B, float* C, int ldc, long long strideC, int M, int N, int K,

@@ -350,16 +350,14 @@ __global__ __launch_bounds__(1024) void col_min_final_select_kernel(const float*
 // One block per pred sample j.  Builds the (ordered) list of style rows whose cost entry
 // carries gradient for column j, then dY_j += g * ry_j (ghat - yhat (yhat.ghat)), ghat = -sum w xhat_i.
 // C is the PRED-major cost matrix Ct[j][i] (row j contiguous: the two scans of "column j" are coalesced).
-__global__ __launch_bounds__(256) void remd_cos_bwd_kernel(
+// (body of the kernel: block j, its LDS lists passed in -- the blended step walks several styles' lists in one workgroup)
+__device__ __forceinline__ void remd_cos_bwd_body(
     const float* __restrict__ C, int ldc, const float* __restrict__ style, const float* __restrict__ rs,
     int ns, const float* __restrict__ pred, const float* __restrict__ rp, int n, int ld,
     const float* __restrict__ rmin, const float* __restrict__ rcnt, const float* __restrict__ cmin,
-    const float* __restrict__ ccnt, const int* __restrict__ sel, float gscale, float* __restrict__ gpred) {
-  __shared__ int li[REMD_MAX_LIST];
-  __shared__ float lw[REMD_MAX_LIST];
-  __shared__ int cnts[256];
-  __shared__ float red[4];
-  const int j = blockIdx.x, t = threadIdx.x;
+    const float* __restrict__ ccnt, const int* __restrict__ sel, float gscale, float* __restrict__ gpred, const int j,
+    int* li, float* lw, int* cnts, float* red) {
+  const int t = threadIdx.x;
   const int row_branch = sel[0];
   const int per = (ns + 255) / 256;
   const int i0 = t * per, i1 = min(ns, i0 + per);
@@ -463,6 +461,18 @@ __global__ __launch_bounds__(256) void remd_cos_bwd_kernel(
       gy4[k2] = g;
     }
   }
+}
+__global__ __launch_bounds__(256) void remd_cos_bwd_kernel(
+    const float* __restrict__ C, int ldc, const float* __restrict__ style, const float* __restrict__ rs,
+    int ns, const float* __restrict__ pred, const float* __restrict__ rp, int n, int ld,
+    const float* __restrict__ rmin, const float* __restrict__ rcnt, const float* __restrict__ cmin,
+    const float* __restrict__ ccnt, const int* __restrict__ sel, float gscale, float* __restrict__ gpred) {
+  __shared__ int li[REMD_MAX_LIST];
+  __shared__ float lw[REMD_MAX_LIST];
+  __shared__ int cnts[256];
+  __shared__ float red[4];
+  remd_cos_bwd_body(C, ldc, style, rs, ns, pred, rp, n, ld, rmin, rcnt, cmin, ccnt, sel, gscale, gpred, (int)blockIdx.x, li, lw,
+                    cnts, red);
 }
 
 // The same for dist_metrics 'l2' (metric 1) and 'both' (metric 2) at any width (losses.py:18-28, 69-80).  C: the cost
@@ -614,12 +624,12 @@ __global__ __launch_bounds__(256) void palette_minima_kernel(const f32x4* __rest
   palette_minima_kernel_body(ys, ns, yp, n, rmin, rcnt, cmin, ccnt, (int)blockIdx.x);
 }
 // One wave per pred sample j.
-__global__ __launch_bounds__(64) void palette_bwd_kernel(
+__device__ __forceinline__ void palette_bwd_body(
     const f32x4* __restrict__ ys, int ns, const f32x4* __restrict__ yp,
     int n, const float* __restrict__ rmin, const float* __restrict__ rcnt, const float* __restrict__ cmin,
     const float* __restrict__ ccnt, const int* __restrict__ sel, float gscale, float* __restrict__ gpred,
-    int ld, int convert) {
-  const int j = blockIdx.x, lane = threadIdx.x;
+    int ld, int convert, const int j) {
+  const int lane = threadIdx.x;
   const int row_branch = sel[0];
   const f32x4 y = yp[j];
   const float cm = cmin[j], cc = ccnt[j];
@@ -658,6 +668,13 @@ __global__ __launch_bounds__(64) void palette_bwd_kernel(
       g[0] += gscale * d0; g[1] += gscale * d1; g[2] += gscale * d2;
     }
   }
+}
+__global__ __launch_bounds__(64) void palette_bwd_kernel(
+    const f32x4* __restrict__ ys, int ns, const f32x4* __restrict__ yp,
+    int n, const float* __restrict__ rmin, const float* __restrict__ rcnt, const float* __restrict__ cmin,
+    const float* __restrict__ ccnt, const int* __restrict__ sel, float gscale, float* __restrict__ gpred,
+    int ld, int convert) {
+  palette_bwd_body(ys, ns, yp, n, rmin, rcnt, cmin, ccnt, sel, gscale, gpred, ld, convert, (int)blockIdx.x);
 }
 
 // ---------------------------------------------------------------- moment matching helpers
@@ -963,6 +980,194 @@ __global__ __launch_bounds__(1024) void step_losses_select_sym_kernel(SelectArgs
   selfsim_sym_body(y, ((int)blockIdx.x - 2) * 4 + g, (int)threadIdx.x & 255, red + 4 * g, blockIdx.x == 2);
 }
 
+// ---- style blending (strotss_step_losses_blend_fwd_bwd): the launches of the step above with the style side segmented per
+// style.  Every per-style range runs the single-style body on that style's operands; what is shared (prediction and content
+// rows, the prediction covariance, the self-similarity term) is computed once.
+#define BLEND_MAX STROTSS_MAX_STYLES
+struct BlendStyle {
+  const float* feats; const float* rs; int ns, ldt; float w;
+  const float* mean; const float* cov;
+  float *C, *rmin, *rcnt, *cmin, *ccnt, *pmin, *pcnt; int* sel;          // cosine REMD (pred-major Ct, row stride ldt)
+  f32x4* ys; float *p_rmin, *p_rcnt, *p_cmin, *p_ccnt; int* p_sel;        // palette
+};
+struct BlendArgs {
+  int K;
+  BlendStyle s[BLEND_MAX];
+};
+// Prologue: [A] norms + x3 panels of prediction and content rows, [B] column partial sums of the prediction rows, [C] YUV
+// rows of the prediction (nC0 blocks) and then of every style, [D] the prediction rows transposed as x3 panels.
+struct BlendPrologueArgs {
+  const float* pred; const float* content; int n; int ld;
+  float* rp; __bf16* xp; float* rc; __bf16* xc;                 // A
+  float* psum;                                                  // B
+  f32x4* yp; int nC0;                                           // C
+  int ldc; __bf16* xt;                                          // D
+  int nA, nB, nC;
+};
+__global__ __launch_bounds__(256) void blend_prologue_kernel(BlendPrologueArgs a, BlendArgs s) {
+  int b = (int)blockIdx.x;
+  if (b < a.nA) {
+    const int half = a.nA / 2;
+    row_inv_norm_x3_kernel_body(a.pred, a.n, a.ld, a.rp, a.xp, a.content, a.n, a.rc, a.xc, b % half, b / half);
+    return;
+  }
+  b -= a.nA;
+  if (b < a.nB) {
+    const int gx = (a.ld + 63) / 64;
+    col_sum_partial_kernel_body(a.pred, a.n, a.ld, a.psum, b % gx, b / gx);
+    return;
+  }
+  b -= a.nB;
+  if (b < a.nC) {
+    if (b < a.nC0) {
+      palette_prepare_kernel_body(a.pred, a.n, a.ld, a.yp, 1, nullptr, 0, nullptr, b, 0);
+      return;
+    }
+    b -= a.nC0;
+    for (int k = 0; k < s.K; ++k) {
+      const int nb = (s.s[k].ns + 255) / 256;
+      if (b < nb) {
+        palette_prepare_kernel_body(s.s[k].feats, s.s[k].ns, a.ld, s.s[k].ys, 1, nullptr, 0, nullptr, b, 0);
+        return;
+      }
+      b -= nb;
+    }
+    return;
+  }
+  b -= a.nC;
+  const int gx = a.ld / 32;
+  center_x3_kernel_body(a.pred, a.n, a.ldc, a.ld, (const float*)nullptr, (__bf16*)nullptr, a.xt, (const float*)nullptr,
+                        (float*)nullptr, b % gx, b / gx);
+}
+// Row r of the moment comparison: sigma = the prediction covariance (whole, bitwise symmetric; style covariances likewise).
+//   mpart[k * ld + r] = sum_c |sigma[r,c] - cov_k[r,c]|   (the whole matrix: the diagonal once, every other entry twice --
+//                                                          the weighting of the single-style epilogue's upper triangle)
+//   row r of S = sum_k w_k sign(sigma - cov_k) as x3 panels (rows = ld, K = ld): B operand of the ONE moment backward
+__device__ __forceinline__ void blend_moment_row(const float* __restrict__ sigma, int ld, __bf16* __restrict__ sp,
+                                                 float* __restrict__ mpart, const BlendArgs& s, const int r) {
+  __shared__ float red[4];
+  const f32x4* P = reinterpret_cast<const f32x4*>(sigma + (size_t)r * ld);
+  float acc[BLEND_MAX];
+#pragma unroll
+  for (int k = 0; k < BLEND_MAX; ++k) acc[k] = 0.f;
+  for (int c4 = threadIdx.x; c4 < ld / 4; c4 += 256) {
+    const f32x4 p = P[c4];
+    f32x4 sg = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < BLEND_MAX; ++k) {
+      if (k < s.K) {
+        const f32x4 x = reinterpret_cast<const f32x4*>(s.s[k].cov + (size_t)r * ld)[c4];
+        const float w = s.s[k].w;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float df = p[q] - x[q];
+          acc[k] += fabsf(df);
+          sg[q] += w * signf(df);
+        }
+      }
+    }
+    x3_store4(sp, ld, r, 4 * c4, sg);
+  }
+#pragma unroll
+  for (int k = 0; k < BLEND_MAX; ++k) {
+    if (k < s.K) {
+      const float v = block_sum_256(acc[k], red);
+      if (threadIdx.x == 0) mpart[(size_t)k * ld + r] = v;
+    }
+  }
+}
+// [self-similarity row statistics (n) | moment rows (ld) | per style: REMD row minima + stage 1 of the column minima
+// (n + cdiv(ns_k, 64) * COL_CHUNKS) | per style: palette minima (ns_k + n)]
+struct BlendStatsArgs {
+  const float *Dx, *Dy; int n, ldc; float sscale; float *isx, *isy, *tt, *lossrow;
+  const float* sigma; int ld; __bf16* sp; float* mpart;
+  const f32x4* yp;
+};
+__global__ __launch_bounds__(256) void blend_stats_kernel(BlendStatsArgs a, BlendArgs s) {
+  int b = (int)blockIdx.x;
+  if (b < a.n) { selfsim_rowstat_kernel_body(a.Dx, a.Dy, a.n, a.ldc, a.sscale, a.isx, a.isy, a.tt, a.lossrow, b, 0); return; }
+  b -= a.n;
+  if (b < a.ld) { blend_moment_row(a.sigma, a.ld, a.sp, a.mpart, s, b); return; }
+  b -= a.ld;
+  for (int k = 0; k < s.K; ++k) {
+    const BlendStyle& t = s.s[k];
+    const int nmin = a.n + ((t.ns + 63) / 64) * COL_CHUNKS;
+    if (b < nmin) { row_col_min_kernel_body(t.C, a.n, t.ns, t.ldt, t.cmin, t.ccnt, t.pmin, t.pcnt, b); return; }
+    b -= nmin;
+  }
+  for (int k = 0; k < s.K; ++k) {
+    const BlendStyle& t = s.s[k];
+    const int np = t.ns + a.n;
+    if (b < np) { palette_minima_kernel_body(t.ys, t.ns, a.yp, a.n, t.p_rmin, t.p_rcnt, t.p_cmin, t.p_ccnt, b); return; }
+    b -= np;
+  }
+}
+// [REMD branch of style k (K blocks) | palette branch of style k (K) | moment scalars of every style + the weighted signs of the
+// mean differences (1) | the symmetrised self-similarity gradient matrix, four rows per block]
+struct BlendMomentArgs {
+  const float* mpart; int ld, d, n; const float* my; float* msgn; float* loss_moment; float* loss_remd; float* loss_palette;
+};
+__global__ __launch_bounds__(1024) void blend_select_sym_kernel(BlendArgs s, BlendMomentArgs m, SelfsimSymArgs y) {
+  __shared__ float red[16];
+  const int K = s.K, b = (int)blockIdx.x;
+  if (b < K) {
+    const BlendStyle& t = s.s[b];
+    col_min_final_select_kernel_body(t.pmin, t.pcnt, t.ns, t.ldt, t.rmin, t.rcnt, t.cmin, m.n, 1, m.loss_remd + b, t.sel, 0,
+                                     red);
+    return;
+  }
+  if (b < 2 * K) {
+    const BlendStyle& t = s.s[b - K];
+    col_min_final_select_kernel_body(nullptr, nullptr, m.n, 0, t.p_cmin, t.p_ccnt, t.p_rmin, t.ns, 0, m.loss_palette + (b - K),
+                                     t.p_sel, 0, red);
+    return;
+  }
+  if (b == 2 * K) {
+    // moment_finalize_kernel's scalars per style: sum(|dSigma|) / d^2 + sum_c |my - mx_k| / d
+    for (int k = 0; k < K; ++k) {
+      const float* mx = s.s[k].mean;
+      float a = 0.f, c = 0.f;
+      for (int i = threadIdx.x; i < m.ld; i += 1024) a += m.mpart[(size_t)k * m.ld + i];
+      for (int i = threadIdx.x; i < m.d; i += 1024) c += fabsf(m.my[i] - mx[i]);
+      a = block_sum_1024(a, red);
+      c = block_sum_1024(c, red);
+      if (threadIdx.x == 0) m.loss_moment[k] = a / ((float)m.d * (float)m.d) + c / (float)m.d;
+    }
+    for (int i = threadIdx.x; i < m.ld; i += 1024) {
+      float g = 0.f;
+      for (int k = 0; k < K; ++k) g += s.s[k].w * signf(i < m.d ? m.my[i] - s.s[k].mean[i] : 0.f);
+      m.msgn[i] = g;
+    }
+    return;
+  }
+  const int g = (int)threadIdx.x >> 8, blk = b - (2 * K + 1);
+  selfsim_sym_body(y, blk * 4 + g, (int)threadIdx.x & 255, red + 4 * g, blk == 0);
+}
+// Sparse backward passes: one workgroup (REMD) / wave (palette) per prediction row walks the K styles' argmin lists in style
+// order, each with gscale * w_k -- the additions of K single-style calls in the same order.
+__global__ __launch_bounds__(256) void blend_remd_bwd_kernel(BlendArgs s, const float* __restrict__ pred,
+                                                             const float* __restrict__ rp, int n, int ld, float g_remd,
+                                                             float* __restrict__ gpred) {
+  __shared__ int li[REMD_MAX_LIST];
+  __shared__ float lw[REMD_MAX_LIST];
+  __shared__ int cnts[256];
+  __shared__ float red[4];
+  for (int k = 0; k < s.K; ++k) {
+    if (k) __syncthreads();                            // the previous style's lists are read to the end
+    const BlendStyle& t = s.s[k];
+    remd_cos_bwd_body(t.C, t.ldt, t.feats, t.rs, t.ns, pred, rp, n, ld, t.rmin, t.rcnt, t.cmin, t.ccnt, t.sel, g_remd * t.w,
+                      gpred, (int)blockIdx.x, li, lw, cnts, red);
+  }
+}
+__global__ __launch_bounds__(64) void blend_palette_bwd_kernel(BlendArgs s, const f32x4* __restrict__ yp, int n, float g_palette,
+                                                               float* __restrict__ gpred, int ld) {
+  for (int k = 0; k < s.K; ++k) {
+    const BlendStyle& t = s.s[k];
+    palette_bwd_body(t.ys, t.ns, yp, n, t.p_rmin, t.p_rcnt, t.p_cmin, t.p_ccnt, t.p_sel, g_palette * t.w, gpred, ld, 1,
+                     (int)blockIdx.x);
+  }
+}
+
 // The same assembly for dist_metrics 'l2' / 'both' (losses.py:18-28): M = l2 or cosine + l2; S holds the l2 part with the sign
 // of tf.maximum(m, 1e-6)'s gradient rule (EpiRemdCost).  dM as above, then per metric
 //   l2 part:      w2 = dM * [S > 0] / (D |S|);   W2[j][i] = -w2,  q2[j] = -sum_i w2      (dy_j = y_j sum w2 - sum w2 x_i, r = 1)
@@ -1122,6 +1327,20 @@ struct MomentWs {
     sgn = w.take<float>(ld);
     psum = w.take<float>((size_t)COL_CHUNKS * ld);
     return w.ok();
+  }
+};
+
+// Workspace of the blended step: the single-style step's (self-similarity, moment) + every style's REMD / palette lists +
+// the whole prediction covariance, the weighted sign matrix (x3 panels), per-style moment partials, weighted mean signs.
+struct BlendWs {
+  SelfsimWs s; MomentWs m; RemdWs r[BLEND_MAX], pl[BLEND_MAX];
+  float *sigma, *mpart, *msgn; __bf16* sp;
+  bool plan(Workspace& w, const strotss_style_set_t& st, int n, int ld) {
+    bool ok = s.plan(w, n, ld) && m.plan(w, n, ld);
+    for (int k = 0; k < st.n_styles && k < BLEND_MAX; ++k) ok = ok && r[k].plan(w, st.ns[k], n, 0) && pl[k].plan(w, st.ns[k], n, 0);
+    sigma = w.take<float>((size_t)ld * ld); sp = w.take<__bf16>((size_t)3 * ld * ld);
+    mpart = w.take<float>((size_t)BLEND_MAX * ld); msgn = w.take<float>(ld);
+    return ok && w.ok();
   }
 };
 
@@ -1610,6 +1829,106 @@ int strotss_step_losses_fwd_bwd(const float* pred, const float* content, int n, 
                      ld, r.rmin, r.rcnt, r.cmin, r.ccnt, r.sel, g_remd, gpred);
   hipLaunchKernelGGL(palette_bwd_kernel, dim3(n), dim3(64), 0, st, pl.ys, ns, pl.yp, n, pl.rmin, pl.rcnt, pl.cmin, pl.ccnt,
                      pl.sel, g_palette, gpred, ld, 1);
+  ST_LAUNCH_RET();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Style blending: the step's four terms against a weighted set of styles (include/strotss_hip.h).  One style: the
+// single-style entry point itself.  Several: the same nine launches -- prologue, centring, ONE grouped forward launch (the
+// prediction covariance, the two self-similarity matrices, one prediction x style cost matrix per style), statistics and
+// selections segmented per style, and the moment backward ONCE: its gradient is linear in the sign matrices, so the product
+// runs on sum_k w_k sign(Sigma_P - Sigma_k) (three x3 planes: the weighted sum is not exact in one bf16) with the weighted
+// mean signs as its bias.  The REMD and palette backward kernels walk the styles' argmin lists per prediction row.
+static int blend_check(const strotss_style_set_t* st) {
+  ST_CHECK_ARG(st, STROTSS_EINVAL);
+  ST_CHECK_ARG(st->n_styles >= 1 && st->n_styles <= STROTSS_MAX_STYLES, STROTSS_ERANGE);
+  float wsum = 0.f;
+  for (int k = 0; k < st->n_styles; ++k) {
+    ST_CHECK_ARG(st->feats[k] && st->inv_norm[k] && st->panels[k] && st->mean[k] && st->cov[k] && st->ns[k] > 0,
+                 STROTSS_EINVAL);
+    ST_CHECK_ARG(st->weight[k] >= 0.f && st->weight[k] <= 3.0e38f, STROTSS_EINVAL);      // (NaN fails both)
+    wsum += st->weight[k];
+  }
+  ST_CHECK_ARG(wsum > 0.f, STROTSS_EINVAL);
+  return 0;
+}
+
+size_t strotss_step_losses_blend_workspace_bytes(const strotss_style_set_t* styles, int n, int ld) {
+  if (blend_check(styles) != 0 || n <= 0 || ld <= 0) return 0;
+  if (styles->n_styles == 1) return strotss_step_losses_workspace_bytes(styles->ns[0], n, ld);
+  Workspace w = Workspace::planner();
+  BlendWs b;
+  b.plan(w, *styles, n, ld);
+  return w.off;
+}
+
+int strotss_step_losses_blend_fwd_bwd(const float* pred, const float* content, int n, int d, int ld,
+                                      const strotss_style_set_t* styles, float g_content, float g_moment, float g_remd,
+                                      float g_palette, float* gpred, float* loss_content, float* loss_moment,
+                                      float* loss_remd, float* loss_palette, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  ST_CHECK_ARG(pred && content && styles && gpred && loss_content && loss_moment && loss_remd && loss_palette && workspace &&
+               feat_ok(n, d, ld), STROTSS_EINVAL);
+  CHK(blend_check(styles));
+  ST_CHECK_ARG(ld % 32 == 0, STROTSS_EALIGN);
+  const strotss_style_set_t& ss = *styles;
+  const int K = ss.n_styles;
+  for (int k = 0; k < K; ++k) ST_CHECK_ARG(ss.ns[k] <= REMD_MAX_LIST, STROTSS_ERANGE);
+  ST_CHECK_ARG(cost_x3() && moment_x3(), STROTSS_EINVAL);
+  if (K == 1) {
+    const float w = ss.weight[0];
+    return strotss_step_losses_fwd_bwd(pred, content, n, d, ld, ss.feats[0], ss.inv_norm[0], ss.panels[0], ss.ns[0], ss.mean[0],
+                                       ss.cov[0], g_content, g_moment * w, g_remd * w, g_palette * w, gpred, loss_content,
+                                       loss_moment, loss_remd, loss_palette, workspace, workspace_bytes, stream);
+  }
+  Workspace w(workspace, workspace_bytes);
+  BlendWs b;
+  ST_CHECK_ARG(b.plan(w, ss, n, ld), STROTSS_EINVAL);
+  hipStream_t st = (hipStream_t)stream;
+  SelfsimWs& s = b.s;
+  MomentWs& m = b.m;
+  const int ldc = s.ldc;
+  BlendArgs ba{};
+  ba.K = K;
+  const void* xs[BLEND_MAX]; const float* rs[BLEND_MAX]; int nsv[BLEND_MAX]; float* Ct[BLEND_MAX]; int ldt[BLEND_MAX];
+  int nC = cdiv(n, 256), nStats = n + ld, nRemd = 0, nPal = 0;
+  for (int k = 0; k < K; ++k) {
+    RemdWs& r = b.r[k];
+    RemdWs& p = b.pl[k];
+    ba.s[k] = BlendStyle{ss.feats[k], ss.inv_norm[k], ss.ns[k], r.ldt, ss.weight[k], ss.mean[k], ss.cov[k],
+                         r.C, r.rmin, r.rcnt, r.cmin, r.ccnt, r.pmin, r.pcnt, r.sel,
+                         p.ys, p.rmin, p.rcnt, p.cmin, p.ccnt, p.sel};
+    xs[k] = ss.panels[k]; rs[k] = ss.inv_norm[k]; nsv[k] = ss.ns[k]; Ct[k] = r.C; ldt[k] = r.ldt;
+    nC += cdiv(ss.ns[k], 256);
+    nRemd += n + cdiv(ss.ns[k], 64) * COL_CHUNKS;
+    nPal += ss.ns[k] + n;
+  }
+  f32x4* yp = b.pl[0].yp;                              // the prediction's YUV rows, shared by every style
+  // ---- ONE prologue launch, then the centring (needs the column sums)
+  BlendPrologueArgs pa{pred, content, n, ld, s.rp, s.xp, s.rc, s.xc, m.psum, yp, cdiv(n, 256), ldc, s.xt,
+                       2 * cdiv(n, 4), cdiv(ld, 64) * COL_CHUNKS, nC};
+  hipLaunchKernelGGL(blend_prologue_kernel, dim3((unsigned)(pa.nA + pa.nB + pa.nC + (ld / 32) * (ldc / 32))), dim3(256), 0, st,
+                     pa, ba);
+  hipLaunchKernelGGL(center_x3_kernel, dim3(ld / 32, m.rows / 32), dim3(256), 0, st, pred, n, m.rows, ld,
+                     (const float*)nullptr, m.Pc, m.Pt, (const float*)m.psum, m.mean);
+  LAUNCH_OK();
+  // ---- the forward products, one launch
+  CHK(st_loss_forward_blend_x3(m.Pt, m.rows, ld, 1.0f / (float)n, b.sigma, s.xp, s.rp, n, s.xc - s.xp, s.rc - s.rp, s.Dx, ldc,
+                               s.Dy - s.Dx, K, xs, rs, nsv, Ct, ldt, st));
+  // ---- statistics: self-similarity rows | moment rows | REMD minima per style | palette minima per style
+  BlendStatsArgs sa{s.Dx, s.Dy, n, ldc, 1.0f / (float)n, s.sx, s.sy, s.tt, s.lossrow, b.sigma, ld, b.sp, b.mpart, yp};
+  hipLaunchKernelGGL(blend_stats_kernel, dim3((unsigned)(nStats + nRemd + nPal)), dim3(256), 0, st, sa, ba);
+  // ---- branch selections per style | moment scalars + weighted mean signs | the self-similarity gradient matrix
+  hipLaunchKernelGGL(blend_select_sym_kernel, dim3((unsigned)(2 * K + 1 + cdiv(n, 4))), dim3(1024), 0, st, ba,
+                     BlendMomentArgs{b.mpart, ld, d, n, m.mean, b.msgn, loss_moment, loss_remd, loss_palette},
+                     SelfsimSymArgs{s.Dx, s.Dy, s.sx, s.sy, s.tt, s.rp, n, ldc, ldc, 1.0f / (float)n, s.Mq, s.qdot, s.mp,
+                                    s.lossrow, 1.0f / (float)n, loss_content});
+  LAUNCH_OK();
+  CHK(st_selfsim_bwd_x3(s.mp, ldc, s.xt, pred, s.rp, s.qdot, n, ld, g_content, gpred, st));
+  CHK(st_moment_bwd_x3_full(m.Pc, n, ld, b.sp, g_moment * 2.0f / ((float)n * (float)d * (float)d), b.msgn,
+                            g_moment / ((float)d * (float)n), gpred, st));
+  hipLaunchKernelGGL(blend_remd_bwd_kernel, dim3(n), dim3(256), 0, st, ba, pred, s.rp, n, ld, g_remd, gpred);
+  hipLaunchKernelGGL(blend_palette_bwd_kernel, dim3(n), dim3(64), 0, st, ba, (const f32x4*)yp, n, g_palette, gpred, ld);
   ST_LAUNCH_RET();
 }
 

@@ -518,6 +518,38 @@ __global__ __launch_bounds__(256) void gemm_x3_group3_kernel(X3Problem<E0> p0, X
   if (b < p2.n) { M2 m; gemm_x3_tile<C2, E2, M2>(lds, b, p2.n, p2.A, p2.M, p2.strideA, p2.B, p2.N, p2.strideB, p2.K, p2.epi, m, p2.xbh, p2.xbw); }
 }
 
+// The same with the third slot holding up to X3_MAX_SET products of one kind (style blending: one prediction x style cost
+// matrix per style, ragged row counts).  Problem q[k] owns the x3_pad8-aligned range after q[k-1]'s.
+#define X3_MAX_SET 4
+template <class Epi>
+struct X3ProblemSet {
+  X3Problem<Epi> q[X3_MAX_SET];
+  int count;
+};
+template <class C0, class E0, class M0, class C1, class E1, class M1, class C2, class E2, class M2>
+__global__ __launch_bounds__(256) void gemm_x3_group_set_kernel(X3Problem<E0> p0, X3Problem<E1> p1, X3ProblemSet<E2> ps) {
+  static_assert(C0::NT == 256 && C1::NT == 256 && C2::NT == 256, "grouped x3 launch: 256-thread workgroups");
+  constexpr int L01 = C0::LDS_BYTES > C1::LDS_BYTES ? C0::LDS_BYTES : C1::LDS_BYTES;
+  constexpr int LDSB = L01 > C2::LDS_BYTES ? L01 : C2::LDS_BYTES;
+  __shared__ __attribute__((aligned(1024))) unsigned char lds[LDSB];
+  unsigned b = blockIdx.x;
+  if (b < x3_pad8(p0.n)) {
+    if (b < p0.n) { M0 m; gemm_x3_tile<C0, E0, M0>(lds, b, p0.n, p0.A, p0.M, p0.strideA, p0.B, p0.N, p0.strideB, p0.K, p0.epi, m, p0.xbh, p0.xbw); }
+    return;
+  }
+  b -= x3_pad8(p0.n);
+  if (b < x3_pad8(p1.n)) {
+    if (b < p1.n) { M1 m; gemm_x3_tile<C1, E1, M1>(lds, b, p1.n, p1.A, p1.M, p1.strideA, p1.B, p1.N, p1.strideB, p1.K, p1.epi, m, p1.xbh, p1.xbw); }
+    return;
+  }
+  b -= x3_pad8(p1.n);
+  int k = 0;                                        // which product of the set (one tile call site: no code copies)
+  while (k < ps.count && k < X3_MAX_SET && b >= x3_pad8(ps.q[k].n)) { b -= x3_pad8(ps.q[k].n); ++k; }
+  if (k >= ps.count || k >= X3_MAX_SET) return;
+  const X3Problem<E2>& p = ps.q[k];
+  if (b < p.n) { M2 m; gemm_x3_tile<C2, E2, M2>(lds, b, p.n, p.A, p.M, p.strideA, p.B, p.N, p.strideB, p.K, p.epi, m, p.xbh, p.xbw); }
+}
+
 // Row-major f32 (rows x ld, K <= ld columns used, K % 32 == 0) -> x3 panels, batched over blockIdx.y.
 // Lane order: 8 lanes cover one row's 32 k (128 B read), consecutive rows follow: 512 contiguous bytes per plane
 // and wave store.

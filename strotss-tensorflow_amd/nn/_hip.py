@@ -56,6 +56,18 @@ class TensorsT(C.Structure):
                 ("grad", C.c_void_p * MAX_TENSORS), ("numel", C.c_int64 * MAX_TENSORS)]
 
 
+MAX_STYLES = 4
+
+
+class StyleSetT(C.Structure):
+    """strotss_style_set_t (include/strotss_hip.h): the weighted style targets of a blended step"""
+    _fields_ = [("n_styles", C.c_int),
+                ("feats", C.c_void_p * MAX_STYLES), ("inv_norm", C.c_void_p * MAX_STYLES),
+                ("panels", C.c_void_p * MAX_STYLES), ("ns", C.c_int * MAX_STYLES),
+                ("mean", C.c_void_p * MAX_STYLES), ("cov", C.c_void_p * MAX_STYLES),
+                ("weight", C.c_float * MAX_STYLES)]
+
+
 _P, _I, _F, _Z, _L = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
 # name -> (restype, argtypes); must list EVERY symbol include/strotss_hip.h declares
 SIGNATURES = {
@@ -117,6 +129,9 @@ SIGNATURES = {
     "strotss_remd_metric_fwd_bwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _F, _P, _P, _I, _P, _Z, _P]),
     "strotss_step_losses_workspace_bytes": (_Z, [_I, _I, _I]),
     "strotss_step_losses_fwd_bwd": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "strotss_step_losses_blend_workspace_bytes": (_Z, [C.POINTER(StyleSetT), _I, _I]),
+    "strotss_step_losses_blend_fwd_bwd": (_I, [_P, _P, _I, _I, _I, C.POINTER(StyleSetT), _F, _F, _F, _F, _P, _P, _P, _P, _P, _P,
+                                               _Z, _P]),
     "strotss_moment_workspace_bytes": (_Z, [_I, _I]),
     "strotss_moment_stats": (_I, [_P, _I, _I, _I, _P, _P, _P, _Z, _P]),
     "strotss_moment_fwd_bwd": (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _Z, _P]),

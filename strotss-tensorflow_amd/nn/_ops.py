@@ -585,6 +585,37 @@ def step_losses_fwd_bwd(pred, content, n, d, style, rs, style_panels, ns, style_
                                         ptr(loss_palette), ptr(ws), nb, stream_ptr()), "step_losses_fwd_bwd")
 
 
+def make_style_set(targets, weights) -> "_hip.StyleSetT":
+    """strotss_style_set_t of StyleTargets (feats, inv_norm, panels, ns, mean, cov) and their weights"""
+    if not 1 <= len(targets) <= _hip.MAX_STYLES or len(weights) != len(targets):
+        raise ValueError(f"a style set holds 1..{_hip.MAX_STYLES} targets with one weight each")
+    s = _hip.StyleSetT()
+    s.n_styles = len(targets)
+    for k, (t, w) in enumerate(zip(targets, weights)):
+        if t.panels is None:
+            raise _hip.StrotssHipError("blended step: every style target needs its x3 panels (ld % 32 == 0)")
+        s.feats[k], s.inv_norm[k], s.panels[k] = ptr(t.feats), ptr(t.inv_norm), ptr(t.panels)
+        s.ns[k], s.mean[k], s.cov[k], s.weight[k] = int(t.ns), ptr(t.mean), ptr(t.cov), float(w)
+    return s
+
+
+def step_losses_blend_fwd_bwd(pred, content, n, d, style_set, g_content, g_moment, g_remd, g_palette, gpred, loss_content,
+                              loss_moment, loss_remd, loss_palette):
+    """The four loss terms against a weighted style set (make_style_set) in ONE call (strotss_step_losses_blend_fwd_bwd):
+    the launch count of step_losses_fwd_bwd whatever the number of styles.  loss_moment / loss_remd / loss_palette receive
+    one UNWEIGHTED value per style; gpred += g_content dLc + sum_k w_k (g_moment dLm_k + g_remd dLr_k + g_palette dLp_k)."""
+    l = _hip.lib()
+    ld = int(pred.shape[1])
+    nb = l.strotss_step_losses_blend_workspace_bytes(C.byref(style_set), n, ld)
+    if nb == 0:
+        raise _hip.StrotssHipError("step_losses_blend: invalid style set")
+    ws = workspaces.get("step_losses_blend", nb, pred.device)
+    check(l.strotss_step_losses_blend_fwd_bwd(ptr(pred), ptr(content), n, d, ld, C.byref(style_set), float(g_content),
+                                              float(g_moment), float(g_remd), float(g_palette), ptr(gpred), ptr(loss_content),
+                                              ptr(loss_moment), ptr(loss_remd), ptr(loss_palette), ptr(ws), nb, stream_ptr()),
+          "step_losses_blend_fwd_bwd")
+
+
 def sinkhorn_cos_fwd_bwd(style, rs, ns, pred, n, d, l, n_iter, gscale, gpred, loss_out):
     lib = _hip.lib()
     nb = lib.strotss_sinkhorn_workspace_bytes(ns, n, n_iter)

@@ -41,6 +41,34 @@ class StyleTarget:
         return StyleTarget(feats, ns, rs, mean, cov, panels)
 
 
+def normalise_style_weights(weights: Sequence[float]) -> List[float]:
+    """w / sum(w) for 1..MAX_STYLES finite weights >= 0 with a positive sum (ValueError otherwise)"""
+    w = [float(x) for x in weights]
+    if not 1 <= len(w) <= _hip.MAX_STYLES:
+        raise ValueError(f"style blending takes 1..{_hip.MAX_STYLES} styles, got {len(w)}")
+    if any(not np.isfinite(x) or x < 0 for x in w):
+        raise ValueError(f"style weights must be finite and >= 0, got {w}")
+    total = sum(w)
+    if total <= 0:
+        raise ValueError("style weights must not all be zero")
+    return [x / total for x in w]
+
+
+@dataclass
+class StyleBlend:
+    """Style blending: a weighted set of StyleTargets, loss_s = sum_k w_k * style_loss(T_k, P).  The weights are normalised
+    to sum to 1 here.  StepEngine runs a one-target blend exactly as its StyleTarget, a larger one in one call
+    (strotss_step_losses_blend_fwd_bwd)."""
+    targets: List[StyleTarget]
+    weights: List[float]
+
+    def __post_init__(self):
+        self.targets = list(self.targets)
+        if len(self.weights) != len(self.targets):
+            raise ValueError(f"{len(self.targets)} style targets but {len(self.weights)} weights")
+        self.weights = normalise_style_weights(self.weights)
+
+
 def extract_features(params: VGGParams, image: torch.Tensor) -> List[torch.Tensor]:
     """[image] + vgg(image)  (run_strotss.py:95-96), taps cloned out of a temporary trunk."""
     h, w = int(image.shape[1]), int(image.shape[2])
@@ -101,8 +129,13 @@ class StepEngine:
         self.alpha, self.loss_denom, self.lr, self.rho, self.eps = float(alpha), float(loss_denom), float(lr), rho, eps
         self.inv_alpha = 1.0 / max(self.alpha, 1.0)
         self.content_feat = [c.contiguous() for c in content_feat]
-        self.style_targets = list(style_targets)
+        # a one-target StyleBlend IS its target (same code path, bit for bit); larger blends: one region, no sharding
+        self.style_targets = [t.targets[0] if isinstance(t, StyleBlend) and len(t.targets) == 1 else t for t in style_targets]
         self.R = len(self.style_targets)
+        self._blended = any(isinstance(t, StyleBlend) for t in self.style_targets)
+        if self._blended and (self.R > 1 or strips is not None or dist_group is not None):
+            raise ValueError("style blending runs one region on one GPU: masks, image strips and region sharding are not "
+                             "supported with several styles")
         h, w = int(stylized.shape[1]), int(stylized.shape[2])
         self.h, self.w = h, w
         # --- variables = make_laplacian_pyramid(stylized) (run_strotss.py:89), rms slots start at 0
@@ -144,6 +177,11 @@ class StepEngine:
         self.gp = [torch.zeros((rows, self.ld), dtype=torch.float32, device=dev) for _ in range(self.R)]
         self.scalars = (torch.zeros((self.R, 8), dtype=torch.float32, device=dev) if self._reduce_buf is None
                         else self._reduce_buf[3 * h * w:].view(self.R, 8))
+        # blended regions: the UNWEIGHTED moment / REMD / palette terms of every style (rows), losses() weighs them
+        self._style_scalars = (torch.zeros((self.R, 3, _hip.MAX_STYLES), dtype=torch.float32, device=dev) if self._blended
+                               else None)
+        self._style_sets = [_ops.make_style_set(t.targets, t.weights) if isinstance(t, StyleBlend) else None
+                            for t in self.style_targets]
         # gradient of the variables: level 0 aliases the pixel gradient
         if strips is not None:
             # full-size pixel gradient, zero outside the window; the trunk writes its window rows in place
@@ -249,6 +287,9 @@ class StepEngine:
         if not zeroed:
             gp.zero_()
         base = 1.0 / (self.loss_denom * self.R)
+        if isinstance(st, StyleBlend):
+            self._losses_blend(r, st, n, base)
+            return
         if st.panels is not None and _ops.step_losses_available():
             # one call: 13 launches instead of 21, the three forward GEMMs in one of them (bit for bit the four calls below)
             _ops.step_losses_fwd_bwd(pf, cf, n, self.d, st.feats, st.inv_norm, st.panels, st.ns, st.mean, st.cov,
@@ -260,6 +301,20 @@ class StepEngine:
         # term has its own) and the style rows' panels from the StyleTarget
         _ops.remd_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, base, gp, sc[2:])
         _ops.palette_remd_fwd_bwd(st.feats, st.ns, pf, n, self.inv_alpha * base, gp, sc[3:])
+
+    def _losses_blend(self, r: int, blend: StyleBlend, n: int, base: float) -> None:
+        """_losses for a blend of K > 1 styles: ONE call (the launches of the single-style call), or -- with the grouped loss
+        section switched off -- the content term once and each style's three separate entries with gscale w_k * base."""
+        pf, cf, gp, sc, ss = self.pf[r], self.cf[r], self.gp[r], self.scalars[r], self._style_scalars[r]
+        if _ops.step_losses_available():
+            _ops.step_losses_blend_fwd_bwd(pf, cf, n, self.d, self._style_sets[r], self.alpha * base, base, base,
+                                           self.inv_alpha * base, gp, sc[0:], ss[0], ss[1], ss[2])
+            return
+        _ops.selfsim_fwd_bwd(pf, cf, n, self.d, self.alpha * base, gp, sc[0:])
+        for k, (st, w) in enumerate(zip(blend.targets, blend.weights)):
+            _ops.moment_fwd_bwd(st.mean, st.cov, pf, n, self.d, base * w, gp, ss[0, k:])
+            _ops.remd_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, base * w, gp, ss[1, k:])
+            _ops.palette_remd_fwd_bwd(st.feats, st.ns, pf, n, self.inv_alpha * base * w, gp, ss[2, k:])
 
     def _scatter_maps(self, r: int):
         """descriptor + sample count of region r's tap adjoint: strips (recompute margin) = this rank's block of the samples
@@ -549,12 +604,30 @@ class StepEngine:
 
     def losses(self) -> dict:
         s = self.scalars.detach().cpu().numpy().astype(np.float64)
+        per_style = None
+        if self._blended:
+            # blended regions: the three style terms are the weighted sums of the per-style (unweighted) ones
+            terms = self._style_scalars.detach().cpu().numpy().astype(np.float64)
+            per_style = []
+            for r, t in enumerate(self.style_targets):
+                if not isinstance(t, StyleBlend):
+                    continue
+                w = np.asarray(t.weights, dtype=np.float64)
+                k = len(w)
+                s[r, 1:4] = terms[r, :, :k] @ w
+                per_style = [{"weight": float(w[i]), "l_moment": float(terms[r, 0, i]), "l_remd": float(terms[r, 1, i]),
+                              "l_palette": float(terms[r, 2, i]),
+                              "loss_s": float(terms[r, 0, i] + terms[r, 1, i] + self.inv_alpha * terms[r, 2, i])}
+                             for i in range(k)]
         lc = s[:, 0]
         ls = s[:, 1] + s[:, 2] + self.inv_alpha * s[:, 3]
         loss = ((self.alpha * lc + ls) / self.loss_denom).mean()
-        return {"loss": float(loss), "loss_c": float(lc.mean()), "loss_s": float(ls.mean()),
-                "l_moment": float(s[:, 1].mean()), "l_remd": float(s[:, 2].mean()),
-                "l_palette": float(s[:, 3].mean())}
+        out = {"loss": float(loss), "loss_c": float(lc.mean()), "loss_s": float(ls.mean()),
+               "l_moment": float(s[:, 1].mean()), "l_remd": float(s[:, 2].mean()),
+               "l_palette": float(s[:, 3].mean())}
+        if per_style is not None:
+            out["per_style"] = per_style         # one dict per style of the blend: its weight and unweighted terms
+        return out
 
     def stylized(self) -> torch.Tensor:
         return self.fold_forward().clone()

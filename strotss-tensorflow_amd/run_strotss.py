@@ -11,6 +11,10 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
   --log_every N     read the three scalars back every N steps (the reference formats them every step,
                     i.e. one device->host sync per step; default 10, 1 restores that)
   --no_graph        launch kernels one by one instead of replaying one hipGraph per step
+  --style_mix P [P ...], --style_weights W [W ...]
+                    style blending: stylise toward a weighted mix of style_path and the --style_mix images (1 + len(mix)
+                    weights, default equal; normalised to sum to 1; zero-weight styles are dropped before they are loaded).
+                    Not combined with masks or --strips.
   --strips          under torchrun (one process per GPU): ONE image on all GPUs -- every rank runs the trunk on its strip
                     of the image (+ halo) at the scales where that pays, two all-reduces per step (nn/parallel.py);
                     rank 0 writes the output
@@ -56,7 +60,50 @@ class StyleLoss:
                 + self.inv_alpha * relaxed_emd(yuv(self.target), yuv(prediction), distance='both'))
 
 
+class BlendedStyleLoss:
+    """Style blending: BlendedStyleLoss(targets, weights, alpha)(prediction) = sum_k w_k * StyleLoss(targets[k], alpha)(prediction),
+    the weights normalised to sum to 1"""
+
+    def __init__(self, targets, weights, alpha: float, **kwargs):
+        if len(targets) != len(weights):
+            raise ValueError(f"{len(targets)} style targets but {len(weights)} weights")
+        self.weights = strotss_engine.normalise_style_weights(weights)
+        self.losses = [StyleLoss(t, alpha) for t in targets]
+
+    def __call__(self, prediction: torch.Tensor) -> torch.Tensor:
+        total = None
+        for w, loss in zip(self.weights, self.losses):
+            term = w * loss(prediction)
+            total = term if total is None else total + term
+        return total
+
+
 # --------------------------------------------------------------------------------------------------
+def _style_inputs(args):
+    """(style paths, normalised weights) of the run: style_path alone, or style_path + --style_mix with --style_weights
+    (1 + len(style_mix) values, default equal).  Zero-weight styles are dropped here, before anything is loaded or sampled,
+    so `--style_weights 1 0` is the single-style run.  Blends with masks or --strips: ValueError."""
+    mix = list(getattr(args, "style_mix", None) or [])
+    weights = getattr(args, "style_weights", None)
+    paths = [args.style_path] + mix
+    if weights is None:
+        weights = [1.0] * len(paths)
+    weights = [float(w) for w in weights]
+    if len(weights) != len(paths):
+        raise ValueError(f"--style_weights takes {len(paths)} values (style_path + {len(mix)} --style_mix images), "
+                         f"got {len(weights)}")
+    if len(paths) > strotss_engine._hip.MAX_STYLES:
+        raise ValueError(f"style blending takes at most {strotss_engine._hip.MAX_STYLES} styles, got {len(paths)}")
+    weights = strotss_engine.normalise_style_weights(weights)        # finite, >= 0, not all zero
+    if mix and (getattr(args, "content_mask", None) or getattr(args, "style_mask", None)):
+        raise ValueError("style blending (--style_mix) cannot be combined with masks")
+    if mix and getattr(args, "strips", False):
+        raise ValueError("style blending (--style_mix) cannot be combined with --strips")
+    kept = [(p, w) for p, w in zip(paths, weights) if w > 0]
+    paths, weights = [p for p, _ in kept], [w for _, w in kept]
+    return paths, strotss_engine.normalise_style_weights(weights)
+
+
 def _load_masks(args):
     """(content_masks, style_masks) or ([None], [None]); one of the two flags alone is an error."""
     if bool(args.content_mask) != bool(args.style_mask):
@@ -68,21 +115,39 @@ def _load_masks(args):
     return c_masks, s_masks
 
 
-def _initial_image(position: int, is_last: bool, previous, content, style, base_lr: float):
+def _initial_image(position: int, is_last: bool, previous, content, style, base_lr: float, weights=None):
     """The image a scale starts from and its learning rate (reference run_strotss.py:78-88):
     first executed scale: Laplacian of the content + mean style colour; middle scales: upsampled previous
-    result + Laplacian; last scale (when more than one runs): upsampled previous result, lr halved."""
+    result + Laplacian; last scale (when more than one runs): upsampled previous result, lr halved.
+    Style blending: `style` a list of images with `weights`, the mean colour is sum_k w_k * mean(style_k)."""
     laplacian = strotss.make_laplacian(content)
     if position == 0:
+        if isinstance(style, (list, tuple)):
+            if len(style) == 1:
+                style = style[0]
+            else:
+                mix = None
+                for w, s_k in zip(weights, style):
+                    term = w * s_k.mean(dim=(1, 2), keepdim=True)
+                    mix = term if mix is None else mix + term
+                return laplacian + mix, base_lr
         return laplacian + style.mean(dim=(1, 2), keepdim=True), base_lr
     if not is_last:
         return utils.resize_like(previous, content) + laplacian, base_lr
     return utils.resize_like(previous, content), base_lr / 2
 
 
-def _style_targets(params, style, style_masks, sampling):
+def _style_targets(params, style, style_masks, sampling, weights=None):
     """One StyleTarget per region: <= 1024 nearest-sampled hypercolumns of the style image (fixed for the
-    scale), their inverse norms and first/second moments."""
+    scale), their inverse norms and first/second moments.  Style blending (`style` a list of images, `weights`): one
+    StyleBlend of one target per style, drawn in style order (one style: exactly the single-style draws)."""
+    if isinstance(style, (list, tuple)):
+        if len(style) == 1:
+            return _style_targets(params, style[0], style_masks, sampling)
+        if list(style_masks) != [None]:
+            raise ValueError("style blending cannot be combined with masks")
+        targets = [_style_targets(params, s_k, [None], sampling)[0] for s_k in style]
+        return [strotss_engine.StyleBlend(targets, list(weights))]
     feats = strotss_engine.extract_features(params, style)
     width = sum(int(m.shape[-1]) for m in feats)
     targets = []
@@ -179,7 +244,8 @@ def run(args: argparse.Namespace, trace=None):
 
     vgg = VGG(use_keras_weight=args.use_keras_weight, weights=getattr(args, "weights", None), seed=seed, device=dev)
     content = utils.load_image(args.content_path, max_size=args.max_size)
-    style = utils.load_image(args.style_path, max_size=args.max_size)
+    style_paths, style_weights = _style_inputs(args)
+    styles = [utils.load_image(p, max_size=args.max_size) for p in style_paths]
     content_masks, style_masks = _load_masks(args)
     sampling = strotss.Sampling(SAMPLE_SIZE)
 
@@ -188,16 +254,19 @@ def run(args: argparse.Namespace, trace=None):
     stylized = None
     for position, i in enumerate(range(first, level)):
         scl = 2 << (5 + i)                                   # long side 64, 128, 256, ...
-        scl_content, scl_style = utils.resize(content, scl), utils.resize(style, scl)
+        scl_content = utils.resize(content, scl)
+        scl_style = [utils.resize(s_k, scl) for s_k in styles]
+        if len(scl_style) == 1:
+            scl_style = scl_style[0]
         stylized, lr = _initial_image(position, position > 0 and i == level - 1, stylized, scl_content, scl_style,
-                                      args.lr)
+                                      args.lr, style_weights)
         # --strips: ONE image sharded by rows (the only sharding that cuts trunk work), with or without mask regions; where
         # a scale is too small for strips to pay (strip_plan -> None) a masked run falls back to dealing its regions out
         plan = (parallel.strip_plan(int(scl_content.shape[1]), world, rank, halo=bool(getattr(args, "halo", False)))
                 if world > 1 and getattr(args, "strips", False) else None)
         eng = strotss_engine.StepEngine(
             vgg.params, strotss_engine.extract_features(vgg.params, scl_content),
-            _style_targets(vgg.params, scl_style, style_masks, sampling), stylized, alpha,
+            _style_targets(vgg.params, scl_style, style_masks, sampling, style_weights), stylized, alpha,
             loss_denom=2. + alpha + 1. / max(alpha, 1.), lr=lr, sample_size=SAMPLE_SIZE, strips=plan,
             dist_group=parallel.WORLD if (world > 1 and masked and plan is None) else None)
         rec = None
@@ -235,6 +304,10 @@ _FLAGS = (
     (("--no_graph",), dict(action='store_true', help="eager kernel launches instead of one hipGraph per step")),
     (("--host_draw",), dict(action='store_true', help="draw the sample coordinates on the host every step (the same sequence; "
                                                       "the default draws them on the device inside the step)")),
+    (("--style_mix",), dict(type=str, nargs='+', default=None, metavar='PATH',
+                            help="style blending: further style images mixed with style_path")),
+    (("--style_weights",), dict(type=float, nargs='+', default=None, metavar='W',
+                                help="style blending: one weight per style (style_path first), default equal")),
     (("--strips",), dict(action='store_true', help="under torchrun: shard ONE image over the GPUs by image strips")),
     (("--halo",), dict(action='store_true', help="with --strips: per-layer halo EXCHANGE with the neighbouring ranks (16-row "
                                                  "windows margins, one row per layer and direction) instead of a 128-row recompute margin")),
