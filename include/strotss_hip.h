@@ -233,6 +233,12 @@ int strotss_hypercol_gather(const strotss_maps_t* maps, const float* idx, int n,
 int strotss_hypercol_gather2(const strotss_maps_t* maps_a, const strotss_maps_t* maps_b, const float* idx, int n,
                              int bilinear, float* out_a, float* out_b, int ld, float* zero, int zero_rows,
                              void* stream);
+/* strotss_hypercol_gather2 + the content weights of the same n samples in the SAME launch: maps_w holds ONE map of ONE channel
+ * (the scale's (h, w) content-weight map, no divisors, no row window), weight_out[s] = strotss_hypercol_gather(maps_w, idx)[s]
+ * bit for bit for s < n, weight_out[s] = 0 for n <= s < weight_rows (weight_rows >= n). */
+int strotss_hypercol_gather2_cw(const strotss_maps_t* maps_a, const strotss_maps_t* maps_b, const strotss_maps_t* maps_w,
+                                const float* idx, int n, int bilinear, float* out_a, float* out_b, int ld, float* zero,
+                                int zero_rows, float* weight_out, int weight_rows, void* stream);
 /* Adjoint (bilinear only): gmap_k[pixel, c] += w * gfeat[s, off_k + c] * (relu_mask ? map_k>0 : 1)
  * for the maps k in [map_begin, map_end) only (the backward pass of the trunk needs the taps'
  * contributions one layer at a time); gmap[k] may be NULL outside that range.
@@ -337,6 +343,14 @@ size_t strotss_selfsim_workspace_bytes(int n, int ld);
 int strotss_selfsim_fwd_bwd(const float* pred, const float* content, int n, int d, int ld,
                             float gscale, float* gpred, float* loss_out, void* workspace,
                             size_t workspace_bytes, void* stream);
+/* Content-weighted self-similarity: with Dx, Dy the cosine matrices of pred and content and A, B their column-normalised forms,
+ *   loss_out[0] = (1/n) sum_j col_weight[j] sum_i |A[i,j] - B[i,j]|,   gpred += gscale * dloss/dpred.
+ * col_weight: n finite values >= 0 on the device (a device pointer), or NULL = strotss_selfsim_fwd_bwd.  All-ones weights give
+ * that entry's results bit for bit.  Same workspace (strotss_selfsim_workspace_bytes) and the same contents left in it:
+ * strotss_selfsim_pred_panels borrows from it as from the unweighted call. */
+int strotss_selfsim_weighted_fwd_bwd(const float* pred, const float* content, const float* col_weight, int n, int d, int ld,
+                                     float gscale, float* gpred, float* loss_out, void* workspace, size_t workspace_bytes,
+                                     void* stream);
 /* Sinkhorn-Knopp transport cost between the style rows (ns) and the prediction rows (n) on the cosine cost matrix.
  * BUILD-DEFINED: the reference's sinkhorn_knopp (losses.py:83-105) is marked untested, is never called and cannot
  * execute (`tf.ones_like` of a Python tuple); this implements its evident intent:
@@ -441,6 +455,13 @@ int strotss_step_losses_blend_fwd_bwd(const float* pred, const float* content, i
                                       float g_palette, float* gpred, float* loss_content, float* loss_moment,
                                       float* loss_remd, float* loss_palette, void* workspace, size_t workspace_bytes,
                                       void* stream);
+/* strotss_step_losses_blend_fwd_bwd with the content term weighted per sampled column as strotss_selfsim_weighted_fwd_bwd
+ * (col_weight: n device floats, finite, >= 0; NULL = that entry).  Same workspace (strotss_step_losses_blend_workspace_bytes),
+ * same launches: n_styles == 1 the single-style structure, n_styles > 1 the blended one.  All-ones weights: bit for bit. */
+int strotss_step_losses_cw_fwd_bwd(const float* pred, const float* content, int n, int d, int ld, const float* col_weight,
+                                   const strotss_style_set_t* styles, float g_content, float g_moment, float g_remd,
+                                   float g_palette, float* gpred, float* loss_content, float* loss_moment, float* loss_remd,
+                                   float* loss_palette, void* workspace, size_t workspace_bytes, void* stream);
 size_t strotss_moment_workspace_bytes(int n, int ld);
 /* style side of moment_matching, once per scale: mean_out(ld), cov_out(ld,ld) = biased covariance */
 int strotss_moment_stats(const float* x, int n, int d, int ld, float* mean_out, float* cov_out,

@@ -393,12 +393,10 @@ __global__ __launch_bounds__(256) void hypercol_gather_kernel(strotss_maps_t m, 
 }
 // two gathers at the same sample positions in one launch (blocks [0, n): maps a, [n, 2n): maps b) + an optional zero fill of
 // `zero_rows` rows of `zero` (block s of the first half clears row s, the last one also the rows from n on)
-__global__ __launch_bounds__(256) void hypercol_gather2_kernel(strotss_maps_t ma, strotss_maps_t mb,
-                                                               const float* __restrict__ idx, int n, int bilinear,
-                                                               float* __restrict__ out_a, float* __restrict__ out_b, int ld,
-                                                               int dtotal_a, int dtotal_b, float* __restrict__ zero,
-                                                               int zero_rows) {
-  const int b = blockIdx.x;
+__device__ __forceinline__ void gather2_body(const strotss_maps_t& ma, const strotss_maps_t& mb,
+                                             const float* __restrict__ idx, int n, int bilinear, float* __restrict__ out_a,
+                                             float* __restrict__ out_b, int ld, int dtotal_a, int dtotal_b,
+                                             float* __restrict__ zero, int zero_rows, const int b) {
   if (b < n) {
     gather_row(ma, idx, b, bilinear, out_a, ld, dtotal_a);
     if (zero) {
@@ -408,6 +406,29 @@ __global__ __launch_bounds__(256) void hypercol_gather2_kernel(strotss_maps_t ma
     }
   } else {
     gather_row(mb, idx, b - n, bilinear, out_b, ld, dtotal_b);
+  }
+}
+__global__ __launch_bounds__(256) void hypercol_gather2_kernel(strotss_maps_t ma, strotss_maps_t mb,
+                                                               const float* __restrict__ idx, int n, int bilinear,
+                                                               float* __restrict__ out_a, float* __restrict__ out_b, int ld,
+                                                               int dtotal_a, int dtotal_b, float* __restrict__ zero,
+                                                               int zero_rows) {
+  gather2_body(ma, mb, idx, n, bilinear, out_a, out_b, ld, dtotal_a, dtotal_b, zero, zero_rows, (int)blockIdx.x);
+}
+// The same + the content weights of the samples: block s < n also gathers sample s from the ONE-channel
+// map of mw -- gather_row itself with ld = 1, i.e. strotss_hypercol_gather of that map, bit for bit -- into wout[s]; the last
+// of them clears wout[n .. wrows).  No extra launch.
+__global__ __launch_bounds__(256) void hypercol_gather2_cw_kernel(strotss_maps_t ma, strotss_maps_t mb, strotss_maps_t mw,
+                                                                  const float* __restrict__ idx, int n, int bilinear,
+                                                                  float* __restrict__ out_a, float* __restrict__ out_b, int ld,
+                                                                  int dtotal_a, int dtotal_b, float* __restrict__ zero,
+                                                                  int zero_rows, float* __restrict__ wout, int wrows) {
+  const int b = blockIdx.x;
+  gather2_body(ma, mb, idx, n, bilinear, out_a, out_b, ld, dtotal_a, dtotal_b, zero, zero_rows, b);
+  if (b < n) {
+    gather_row(mw, idx, b, bilinear, wout, 1, 1);
+    if (b == n - 1)
+      for (int r = n + (int)threadIdx.x; r < wrows; r += 256) wout[r] = 0.f;
   }
 }
 // Tiny maps (at most SCATTER_DENSE_MAX_PIX pixels: the 4 x 4 and 8 x 8 maps of the 64 / 128-px scales): 4096 taps land on 16-64
@@ -816,6 +837,25 @@ int strotss_hypercol_gather2(const strotss_maps_t* maps_a, const strotss_maps_t*
   a.window_drop = b.window_drop = 0;        // the gather always clamps into the window (see strotss_hypercol_gather)
   hipLaunchKernelGGL(hypercol_gather2_kernel, dim3(2 * n), dim3(256), 0, (hipStream_t)stream, a, b, idx, n, bilinear, out_a,
                      out_b, ld, da, db, zero, zero_rows);
+  ST_LAUNCH_RET();
+}
+
+int strotss_hypercol_gather2_cw(const strotss_maps_t* maps_a, const strotss_maps_t* maps_b, const strotss_maps_t* maps_w,
+                                const float* idx, int n, int bilinear, float* out_a, float* out_b, int ld, float* zero,
+                                int zero_rows, float* weight_out, int weight_rows, void* stream) {
+  ST_CHECK_ARG(maps_ok(maps_a) && maps_ok(maps_b) && maps_ok(maps_w) && idx && out_a && out_b && weight_out && n > 0,
+               STROTSS_EINVAL);
+  ST_CHECK_ARG(maps_w->n_maps == 1 && maps_w->c[0] == 1 && maps_w->rows[0] == 0 && weight_rows >= n, STROTSS_EINVAL);
+  ST_CHECK_ARG(!zero || zero_rows > 0, STROTSS_EINVAL);
+  int da = 0, db = 0;
+  for (int k = 0; k < maps_a->n_maps; ++k) da += maps_a->c[k];
+  for (int k = 0; k < maps_b->n_maps; ++k) db += maps_b->c[k];
+  ST_CHECK_ARG(ld >= da && ld >= db, STROTSS_EINVAL);
+  strotss_maps_t a = *maps_a, b = *maps_b, wm = *maps_w;
+  a.window_drop = b.window_drop = wm.window_drop = 0;
+  wm.sample_range = nullptr;                  // every sample has a weight
+  hipLaunchKernelGGL(hypercol_gather2_cw_kernel, dim3(2 * n), dim3(256), 0, (hipStream_t)stream, a, b, wm, idx, n, bilinear,
+                     out_a, out_b, ld, da, db, zero, zero_rows, weight_out, weight_rows);
   ST_LAUNCH_RET();
 }
 

@@ -87,6 +87,8 @@ __global__ __launch_bounds__(256) void row_sum_kernel(const float* __restrict__ 
 // Row j, ONE pass over its two rows (held in registers up to n = 1024, re-read beyond):
 //   sx_j = sum Dx[j,:], sy_j likewise;  A' = Dx[j,:]/sx_j, B' = Dy[j,:]/sy_j, loss_j = sum |A'-B'|,
 //   S' = sign(A'-B') * sscale,  t_j = sum S' A' (0 when the clamp is active).
+// cw != NULL (content-weight map): row j is column j of the reference's matrices, so its weight c_j = cw[j] is ONE scalar per
+// block: S' uses sscale * c_j and loss_j is scaled by c_j (c_j = 1.0f is exact: bit for bit the unweighted row).
 // Out: isx[j] = 1/max(sx_j, 1e-12), isy[j], t[j], lossrow[j] -- all the backward needs of row j:
 //   dL/dDx[:,j] = Q[j,:] = (S' - t_j) * isx_j   is recomputed where it is used (selfsim_sym_kernel), never stored.
 #define SS_REG 4
@@ -94,9 +96,11 @@ __device__ __forceinline__ void selfsim_rowstat_kernel_body(const float* __restr
                                                               const float* __restrict__ Dy, int n, int ldc,
                                                               float sscale, float* __restrict__ isx_out,
                                                               float* __restrict__ isy_out, float* __restrict__ t_out,
-                                                              float* __restrict__ lossrow, const int bx, const int by) {
+                                                              float* __restrict__ lossrow, const float* __restrict__ cw,
+                                                              const int bx, const int by) {
   __shared__ float red[4];
   const int j = bx;
+  if (cw) sscale *= cw[j];
   const float* px = Dx + (size_t)j * ldc;
   const float* py = Dy + (size_t)j * ldc;
   float vx[SS_REG], vy[SS_REG];
@@ -131,21 +135,23 @@ __device__ __forceinline__ void selfsim_rowstat_kernel_body(const float* __restr
   l = block_sum_256(l, red);
   t = block_sum_256(t, red);
   if (!(sxr >= 1e-12f)) t = 0.f;
+  if (cw) l *= cw[j];
   if (threadIdx.x == 0) { isx_out[j] = isx; isy_out[j] = isy; t_out[j] = t; lossrow[j] = l; }
 }
 __global__ __launch_bounds__(256) void selfsim_rowstat_kernel(const float* __restrict__ Dx,
                                                               const float* __restrict__ Dy, int n, int ldc,
                                                               float sscale, float* __restrict__ isx_out,
                                                               float* __restrict__ isy_out, float* __restrict__ t_out,
-                                                              float* __restrict__ lossrow) {
-  selfsim_rowstat_kernel_body(Dx, Dy, n, ldc, sscale, isx_out, isy_out, t_out, lossrow, (int)blockIdx.x, (int)blockIdx.y);
+                                                              float* __restrict__ lossrow, const float* __restrict__ cw) {
+  selfsim_rowstat_kernel_body(Dx, Dy, n, ldc, sscale, isx_out, isy_out, t_out, lossrow, cw, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 // M[i,j] = -(Q[i,j] + Q[j,i]) with Q[i,j] = (sign(Dx[i,j] isx_i - Dy[i,j] isy_i) sscale - t_i) isx_i and, the cosine
 // matrices being bitwise symmetric, Q[j,i] from the SAME two entries with row j's statistics: one coalesced pass over
 // rows i of Dx and Dy, no N x N intermediate.  Mq[i,j] = M[i,j] * r[j] (zero for n <= j < kpad);
 // qdot[i] = sum_j M[i,j] (1 - Dx[i,j])   (= xhat_i . dL/dxhat_i).  Workgroup 0 also reduces the rows' losses:
-// loss_out[0] = loss_scale * sum_j lossrow[j] (fixed order).
+// loss_out[0] = loss_scale * sum_j lossrow[j] (fixed order).  cw != NULL: row i's and row j's sign terms use sscale * cw[i] and
+// sscale * cw[j] (the S' of selfsim_rowstat_kernel_body, whose t already carries the weight).
 // group_sum_256: block_sum_256's arithmetic for a GROUP of 256 threads (tid = index in the group, red = the group's four
 // floats of LDS) -- the whole workgroup of the stand-alone kernel, or one quarter of a 1024-thread workgroup of
 // select_sym_kernel; every thread of the workgroup reaches its barriers.
@@ -160,6 +166,7 @@ struct SelfsimSymArgs {
   const float *Dx, *Dy, *isx, *isy, *tt, *r;
   int n, ldc, kpad; float sscale;
   float *Mq, *qdot; __bf16* Mp; const float* lossrow; float loss_scale; float* loss_out;
+  const float* cw;                                      // column weights or NULL (left out of an initializer: NULL)
 };
 // row i by the 256 threads of one group; i >= n: no loads or stores, barriers only.  with_loss (uniform over the WORKGROUP):
 // every group also reduces the rows' losses the same way, group i == 0 writes it.
@@ -175,14 +182,17 @@ __device__ __forceinline__ void selfsim_sym_body(const SelfsimSymArgs& a, const 
   const bool live = i < n;
   const int ic = live ? i : 0;
   const float isx_i = isx[ic], isy_i = isy[ic], t_i = tt[ic];
+  const float* __restrict__ cw = a.cw;
+  const float s_i = cw ? sscale * cw[ic] : sscale;
   float acc = 0.f;
   for (int j = tid; live && j < kpad; j += 256) {
     float out = 0.f;
     if (j < n) {
       const float dx = Dx[(size_t)i * ldc + j], dy = Dy[(size_t)i * ldc + j];
       const float isx_j = isx[j];
-      const float q_ij = (signf(dx * isx_i - dy * isy_i) * sscale - t_i) * isx_i;
-      const float q_ji = (signf(dx * isx_j - dy * isy[j]) * sscale - tt[j]) * isx_j;
+      const float s_j = cw ? sscale * cw[j] : sscale;
+      const float q_ij = (signf(dx * isx_i - dy * isy_i) * s_i - t_i) * isx_i;
+      const float q_ji = (signf(dx * isx_j - dy * isy[j]) * s_j - tt[j]) * isx_j;
       const float m = -(q_ij + q_ji);
       acc += m * (1.0f - dx);
       out = m * r[j];
@@ -950,10 +960,11 @@ struct StepStatsArgs {
   const float* partial; int count; const float *mx, *my; int d, ld; float *sgn, *loss_moment;       // moment finalisation
   const float* C; int ns, ldt; float *rmin, *rcnt, *pmin, *pcnt;                                   // REMD minima
   const f32x4 *ys, *yp; float *prmin, *prcnt, *pcmin, *pccnt;                                      // palette minima
+  const float* cw;                                                                                  // column weights or NULL
 };
 __global__ __launch_bounds__(256) void step_losses_stats_kernel(StepStatsArgs a) {
   int b = (int)blockIdx.x;
-  if (b < a.n) { selfsim_rowstat_kernel_body(a.Dx, a.Dy, a.n, a.ldc, a.sscale, a.isx, a.isy, a.tt, a.lossrow, b, 0); return; }
+  if (b < a.n) { selfsim_rowstat_kernel_body(a.Dx, a.Dy, a.n, a.ldc, a.sscale, a.isx, a.isy, a.tt, a.lossrow, a.cw, b, 0); return; }
   b -= a.n;
   if (b == 0) { moment_finalize_kernel_body(a.partial, a.count, a.mx, a.my, a.d, a.ld, a.sgn, a.loss_moment, 0, 0); return; }
   b -= 1;
@@ -1082,10 +1093,11 @@ struct BlendStatsArgs {
   const float *Dx, *Dy; int n, ldc; float sscale; float *isx, *isy, *tt, *lossrow;
   const float* sigma; int ld; __bf16* sp; float* mpart;
   const f32x4* yp;
+  const float* cw;
 };
 __global__ __launch_bounds__(256) void blend_stats_kernel(BlendStatsArgs a, BlendArgs s) {
   int b = (int)blockIdx.x;
-  if (b < a.n) { selfsim_rowstat_kernel_body(a.Dx, a.Dy, a.n, a.ldc, a.sscale, a.isx, a.isy, a.tt, a.lossrow, b, 0); return; }
+  if (b < a.n) { selfsim_rowstat_kernel_body(a.Dx, a.Dy, a.n, a.ldc, a.sscale, a.isx, a.isy, a.tt, a.lossrow, a.cw, b, 0); return; }
   b -= a.n;
   if (b < a.ld) { blend_moment_row(a.sigma, a.ld, a.sp, a.mpart, s, b); return; }
   b -= a.ld;
@@ -1398,9 +1410,9 @@ size_t strotss_selfsim_workspace_bytes(int n, int ld) {
   return w.off;
 }
 
-int strotss_selfsim_fwd_bwd(const float* pred, const float* content, int n, int d, int ld, float gscale,
-                            float* gpred, float* loss_out, void* workspace, size_t workspace_bytes,
-                            void* stream) {
+// cw: per-row (= per-column of the reference's matrices) content weights, NULL = unweighted
+static int selfsim_impl(const float* pred, const float* content, const float* cw, int n, int d, int ld, float gscale,
+                        float* gpred, float* loss_out, void* workspace, size_t workspace_bytes, void* stream) {
   ST_CHECK_ARG(pred && content && gpred && loss_out && workspace && feat_ok(n, d, ld), STROTSS_EINVAL);
   ST_CHECK_ARG(ld % 32 == 0, STROTSS_EALIGN);
   Workspace w(workspace, workspace_bytes);
@@ -1424,17 +1436,29 @@ int strotss_selfsim_fwd_bwd(const float* pred, const float* content, int n, int 
   // loss = mean(|A-B|) * n = (1/n) sum |A-B|  ->  dL/dA = sign/n.  Two passes over the two matrices in all: the rows'
   // statistics (sx and sy hold the RECIPROCAL clamped row sums), then the symmetrised gradient + the loss
   hipLaunchKernelGGL(selfsim_rowstat_kernel, dim3(n), dim3(256), 0, st, s.Dx, s.Dy, n, ldc, 1.0f / (float)n, s.sx, s.sy,
-                     s.tt, s.lossrow);
+                     s.tt, s.lossrow, cw);
   const bool bx3 = cost_x3();
   hipLaunchKernelGGL(selfsim_sym_kernel, dim3(n), dim3(256), 0, st,
                      SelfsimSymArgs{s.Dx, s.Dy, s.sx, s.sy, s.tt, s.rp, n, ldc, ldc, 1.0f / (float)n, s.Mq, s.qdot,
-                                    bx3 ? s.mp : (__bf16*)nullptr, s.lossrow, 1.0f / (float)n, loss_out});
+                                    bx3 ? s.mp : (__bf16*)nullptr, s.lossrow, 1.0f / (float)n, loss_out, cw});
   if (bx3)
     hipLaunchKernelGGL(center_x3_kernel, dim3(ld / 32, ldc / 32), dim3(256), 0, st, pred, n, ldc, ld, (const float*)nullptr,
                        (__bf16*)nullptr, s.xt);
   LAUNCH_OK();
   if (bx3) return st_selfsim_bwd_x3(s.mp, ldc, s.xt, pred, s.rp, s.qdot, n, ld, gscale, gpred, st);
   return st_selfsim_bwd_gemm(s.Mq, ldc, ldc, pred, pred, s.rp, s.qdot, n, ld, gscale, gpred, st);
+}
+
+int strotss_selfsim_fwd_bwd(const float* pred, const float* content, int n, int d, int ld, float gscale,
+                            float* gpred, float* loss_out, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+  return selfsim_impl(pred, content, nullptr, n, d, ld, gscale, gpred, loss_out, workspace, workspace_bytes, stream);
+}
+
+int strotss_selfsim_weighted_fwd_bwd(const float* pred, const float* content, const float* col_weight, int n, int d, int ld,
+                                     float gscale, float* gpred, float* loss_out, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+  return selfsim_impl(pred, content, col_weight, n, d, ld, gscale, gpred, loss_out, workspace, workspace_bytes, stream);
 }
 
 size_t strotss_sinkhorn_workspace_bytes(int ns, int n, int n_iter) {
@@ -1777,11 +1801,11 @@ size_t strotss_step_losses_workspace_bytes(int ns, int n, int ld) {
   return w.off;
 }
 
-int strotss_step_losses_fwd_bwd(const float* pred, const float* content, int n, int d, int ld, const float* style,
-                                const float* style_inv_norm, const void* style_panels, int ns, const float* style_mean,
-                                const float* style_cov, float g_content, float g_moment, float g_remd, float g_palette,
-                                float* gpred, float* loss_content, float* loss_moment, float* loss_remd, float* loss_palette,
-                                void* workspace, size_t workspace_bytes, void* stream) {
+static int step_losses_impl(const float* pred, const float* content, const float* cw, int n, int d, int ld, const float* style,
+                            const float* style_inv_norm, const void* style_panels, int ns, const float* style_mean,
+                            const float* style_cov, float g_content, float g_moment, float g_remd, float g_palette,
+                            float* gpred, float* loss_content, float* loss_moment, float* loss_remd, float* loss_palette,
+                            void* workspace, size_t workspace_bytes, void* stream) {
   ST_CHECK_ARG(pred && content && style && style_inv_norm && style_panels && style_mean && style_cov && gpred && loss_content &&
                loss_moment && loss_remd && loss_palette && workspace && ns > 0 && feat_ok(n, d, ld), STROTSS_EINVAL);
   ST_CHECK_ARG(ld % 32 == 0, STROTSS_EALIGN);
@@ -1812,14 +1836,14 @@ int strotss_step_losses_fwd_bwd(const float* pred, const float* content, int n, 
   StepStatsArgs sa{s.Dx, s.Dy, n, ldc, 1.0f / (float)n, s.sx, s.sy, s.tt, s.lossrow,
                    m.partial, n_partial, style_mean, m.mean, d, ld, m.sgn, loss_moment,
                    r.C, ns, ldt, r.cmin, r.ccnt, r.pmin, r.pcnt,
-                   pl.ys, pl.yp, pl.rmin, pl.rcnt, pl.cmin, pl.ccnt};
+                   pl.ys, pl.yp, pl.rmin, pl.rcnt, pl.cmin, pl.ccnt, cw};
   hipLaunchKernelGGL(step_losses_stats_kernel, dim3((unsigned)(n + 1 + n + cdiv(ns, 64) * COL_CHUNKS + ns + n)), dim3(256), 0, st, sa);
   // ---- the two branch selections (+ stage 2 of the REMD column minima) | the self-similarity gradient matrix: one launch
   hipLaunchKernelGGL(step_losses_select_sym_kernel, dim3((unsigned)(2 + cdiv(n, 4))), dim3(1024), 0, st,
                      SelectArgs{r.pmin, r.pcnt, ns, ldt, r.rmin, r.rcnt, r.cmin, n, 1, loss_remd, r.sel, 0},
                      SelectArgs{nullptr, nullptr, n, 0, pl.cmin, pl.ccnt, pl.rmin, ns, 0, loss_palette, pl.sel, 0},
                      SelfsimSymArgs{s.Dx, s.Dy, s.sx, s.sy, s.tt, s.rp, n, ldc, ldc, 1.0f / (float)n, s.Mq, s.qdot, s.mp,
-                                    s.lossrow, 1.0f / (float)n, loss_content});
+                                    s.lossrow, 1.0f / (float)n, loss_content, cw});
   LAUNCH_OK();
   CHK(st_selfsim_bwd_x3(s.mp, ldc, s.xt, pred, s.rp, s.qdot, n, ld, g_content, gpred, st));
   CHK(st_moment_bwd_x3(m.Pc, n, ld, m.Tp, g_moment * 2.0f / ((float)n * (float)d * (float)d), m.sgn,
@@ -1830,6 +1854,16 @@ int strotss_step_losses_fwd_bwd(const float* pred, const float* content, int n, 
   hipLaunchKernelGGL(palette_bwd_kernel, dim3(n), dim3(64), 0, st, pl.ys, ns, pl.yp, n, pl.rmin, pl.rcnt, pl.cmin, pl.ccnt,
                      pl.sel, g_palette, gpred, ld, 1);
   ST_LAUNCH_RET();
+}
+
+int strotss_step_losses_fwd_bwd(const float* pred, const float* content, int n, int d, int ld, const float* style,
+                                const float* style_inv_norm, const void* style_panels, int ns, const float* style_mean,
+                                const float* style_cov, float g_content, float g_moment, float g_remd, float g_palette,
+                                float* gpred, float* loss_content, float* loss_moment, float* loss_remd, float* loss_palette,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+  return step_losses_impl(pred, content, nullptr, n, d, ld, style, style_inv_norm, style_panels, ns, style_mean, style_cov,
+                          g_content, g_moment, g_remd, g_palette, gpred, loss_content, loss_moment, loss_remd, loss_palette,
+                          workspace, workspace_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1862,11 +1896,10 @@ size_t strotss_step_losses_blend_workspace_bytes(const strotss_style_set_t* styl
   return w.off;
 }
 
-int strotss_step_losses_blend_fwd_bwd(const float* pred, const float* content, int n, int d, int ld,
-                                      const strotss_style_set_t* styles, float g_content, float g_moment, float g_remd,
-                                      float g_palette, float* gpred, float* loss_content, float* loss_moment,
-                                      float* loss_remd, float* loss_palette, void* workspace, size_t workspace_bytes,
-                                      void* stream) {
+static int blend_impl(const float* pred, const float* content, const float* cw, int n, int d, int ld,
+                      const strotss_style_set_t* styles, float g_content, float g_moment, float g_remd, float g_palette,
+                      float* gpred, float* loss_content, float* loss_moment, float* loss_remd, float* loss_palette,
+                      void* workspace, size_t workspace_bytes, void* stream) {
   ST_CHECK_ARG(pred && content && styles && gpred && loss_content && loss_moment && loss_remd && loss_palette && workspace &&
                feat_ok(n, d, ld), STROTSS_EINVAL);
   CHK(blend_check(styles));
@@ -1877,9 +1910,9 @@ int strotss_step_losses_blend_fwd_bwd(const float* pred, const float* content, i
   ST_CHECK_ARG(cost_x3() && moment_x3(), STROTSS_EINVAL);
   if (K == 1) {
     const float w = ss.weight[0];
-    return strotss_step_losses_fwd_bwd(pred, content, n, d, ld, ss.feats[0], ss.inv_norm[0], ss.panels[0], ss.ns[0], ss.mean[0],
-                                       ss.cov[0], g_content, g_moment * w, g_remd * w, g_palette * w, gpred, loss_content,
-                                       loss_moment, loss_remd, loss_palette, workspace, workspace_bytes, stream);
+    return step_losses_impl(pred, content, cw, n, d, ld, ss.feats[0], ss.inv_norm[0], ss.panels[0], ss.ns[0], ss.mean[0],
+                            ss.cov[0], g_content, g_moment * w, g_remd * w, g_palette * w, gpred, loss_content,
+                            loss_moment, loss_remd, loss_palette, workspace, workspace_bytes, stream);
   }
   Workspace w(workspace, workspace_bytes);
   BlendWs b;
@@ -1916,13 +1949,13 @@ int strotss_step_losses_blend_fwd_bwd(const float* pred, const float* content, i
   CHK(st_loss_forward_blend_x3(m.Pt, m.rows, ld, 1.0f / (float)n, b.sigma, s.xp, s.rp, n, s.xc - s.xp, s.rc - s.rp, s.Dx, ldc,
                                s.Dy - s.Dx, K, xs, rs, nsv, Ct, ldt, st));
   // ---- statistics: self-similarity rows | moment rows | REMD minima per style | palette minima per style
-  BlendStatsArgs sa{s.Dx, s.Dy, n, ldc, 1.0f / (float)n, s.sx, s.sy, s.tt, s.lossrow, b.sigma, ld, b.sp, b.mpart, yp};
+  BlendStatsArgs sa{s.Dx, s.Dy, n, ldc, 1.0f / (float)n, s.sx, s.sy, s.tt, s.lossrow, b.sigma, ld, b.sp, b.mpart, yp, cw};
   hipLaunchKernelGGL(blend_stats_kernel, dim3((unsigned)(nStats + nRemd + nPal)), dim3(256), 0, st, sa, ba);
   // ---- branch selections per style | moment scalars + weighted mean signs | the self-similarity gradient matrix
   hipLaunchKernelGGL(blend_select_sym_kernel, dim3((unsigned)(2 * K + 1 + cdiv(n, 4))), dim3(1024), 0, st, ba,
                      BlendMomentArgs{b.mpart, ld, d, n, m.mean, b.msgn, loss_moment, loss_remd, loss_palette},
                      SelfsimSymArgs{s.Dx, s.Dy, s.sx, s.sy, s.tt, s.rp, n, ldc, ldc, 1.0f / (float)n, s.Mq, s.qdot, s.mp,
-                                    s.lossrow, 1.0f / (float)n, loss_content});
+                                    s.lossrow, 1.0f / (float)n, loss_content, cw});
   LAUNCH_OK();
   CHK(st_selfsim_bwd_x3(s.mp, ldc, s.xt, pred, s.rp, s.qdot, n, ld, g_content, gpred, st));
   CHK(st_moment_bwd_x3_full(m.Pc, n, ld, b.sp, g_moment * 2.0f / ((float)n * (float)d * (float)d), b.msgn,
@@ -1930,6 +1963,25 @@ int strotss_step_losses_blend_fwd_bwd(const float* pred, const float* content, i
   hipLaunchKernelGGL(blend_remd_bwd_kernel, dim3(n), dim3(256), 0, st, ba, pred, s.rp, n, ld, g_remd, gpred);
   hipLaunchKernelGGL(blend_palette_bwd_kernel, dim3(n), dim3(64), 0, st, ba, (const f32x4*)yp, n, g_palette, gpred, ld);
   ST_LAUNCH_RET();
+}
+
+int strotss_step_losses_blend_fwd_bwd(const float* pred, const float* content, int n, int d, int ld,
+                                      const strotss_style_set_t* styles, float g_content, float g_moment, float g_remd,
+                                      float g_palette, float* gpred, float* loss_content, float* loss_moment,
+                                      float* loss_remd, float* loss_palette, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  return blend_impl(pred, content, nullptr, n, d, ld, styles, g_content, g_moment, g_remd, g_palette, gpred, loss_content,
+                    loss_moment, loss_remd, loss_palette, workspace, workspace_bytes, stream);
+}
+
+// Content-weight map: the step of strotss_step_losses_blend_fwd_bwd (any K, one style included) with
+// the self-similarity term weighted per sampled column.  col_weight NULL: that entry itself.
+int strotss_step_losses_cw_fwd_bwd(const float* pred, const float* content, int n, int d, int ld, const float* col_weight,
+                                   const strotss_style_set_t* styles, float g_content, float g_moment, float g_remd,
+                                   float g_palette, float* gpred, float* loss_content, float* loss_moment, float* loss_remd,
+                                   float* loss_palette, void* workspace, size_t workspace_bytes, void* stream) {
+  return blend_impl(pred, content, col_weight, n, d, ld, styles, g_content, g_moment, g_remd, g_palette, gpred, loss_content,
+                    loss_moment, loss_remd, loss_palette, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -99,6 +99,8 @@ SIGNATURES = {
     "strotss_maxpool2_bwd": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P]),
     "strotss_hypercol_gather": (_I, [C.POINTER(MapsT), _P, _I, _I, _P, _I, _P]),
     "strotss_hypercol_gather2": (_I, [C.POINTER(MapsT), C.POINTER(MapsT), _P, _I, _I, _P, _P, _I, _P, _I, _P]),
+    "strotss_hypercol_gather2_cw": (_I, [C.POINTER(MapsT), C.POINTER(MapsT), C.POINTER(MapsT), _P, _I, _I, _P, _P, _I, _P, _I,
+                                         _P, _I, _P]),
     "strotss_hypercol_scatter": (_I, [C.POINTER(MapsT), _P, _I, _P, _I, _I, _I, _I, _P]),
     "strotss_hypercol_scatter_plan_bytes": (_Z, [_I]),
     "strotss_hypercol_scatter_plan": (_I, [C.POINTER(MapsT), _P, _I, _P, _Z, _P]),
@@ -116,6 +118,7 @@ SIGNATURES = {
     "strotss_rows_gemm_bwd": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _I, _F, _P, _P]),
     "strotss_selfsim_workspace_bytes": (_Z, [_I, _I]),
     "strotss_selfsim_fwd_bwd": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P, _Z, _P]),
+    "strotss_selfsim_weighted_fwd_bwd": (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _Z, _P]),
     "strotss_sinkhorn_workspace_bytes": (_Z, [_I, _I, _I]),
     "strotss_sinkhorn_cos_fwd_bwd": (_I, [_P, _P, _I, _P, _I, _I, _I, _F, _I, _F, _P, _P, _P, _Z, _P]),
     "strotss_sinkhorn_metric_workspace_bytes": (_Z, [_I, _I, _I]),
@@ -132,6 +135,8 @@ SIGNATURES = {
     "strotss_step_losses_blend_workspace_bytes": (_Z, [C.POINTER(StyleSetT), _I, _I]),
     "strotss_step_losses_blend_fwd_bwd": (_I, [_P, _P, _I, _I, _I, C.POINTER(StyleSetT), _F, _F, _F, _F, _P, _P, _P, _P, _P, _P,
                                                _Z, _P]),
+    "strotss_step_losses_cw_fwd_bwd": (_I, [_P, _P, _I, _I, _I, _P, C.POINTER(StyleSetT), _F, _F, _F, _F, _P, _P, _P, _P, _P,
+                                            _P, _Z, _P]),
     "strotss_moment_workspace_bytes": (_Z, [_I, _I]),
     "strotss_moment_stats": (_I, [_P, _I, _I, _I, _P, _P, _P, _Z, _P]),
     "strotss_moment_fwd_bwd": (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _Z, _P]),

@@ -524,6 +524,23 @@ def selfsim_fwd_bwd(pred, content, n, d, gscale, gpred, loss_out):
     _selfsim_record = (ws.data_ptr(), nb, ptr(pred), n, int(pred.shape[1]), stream_ptr())
 
 
+def selfsim_weighted_fwd_bwd(pred, content, col_weight, n, d, gscale, gpred, loss_out):
+    """selfsim_fwd_bwd with the content term weighted per sampled column (strotss_selfsim_weighted_fwd_bwd): col_weight is a
+    float32 device vector of >= n values, finite and >= 0 (None: selfsim_fwd_bwd itself).  Same workspace, same record: the
+    relaxed EMD borrows the prediction rows' norms and panels from it as after the unweighted call."""
+    if col_weight is None:
+        return selfsim_fwd_bwd(pred, content, n, d, gscale, gpred, loss_out)
+    require(col_weight, "column weights")
+    assert col_weight.numel() >= n
+    l = _hip.lib()
+    nb = l.strotss_selfsim_workspace_bytes(n, pred.shape[1])
+    ws = workspaces.get("selfsim", nb, pred.device)
+    check(l.strotss_selfsim_weighted_fwd_bwd(ptr(pred), ptr(content), ptr(col_weight), n, d, pred.shape[1], gscale, ptr(gpred),
+                                             ptr(loss_out), ptr(ws), nb, stream_ptr()), "selfsim_weighted_fwd_bwd")
+    global _selfsim_record
+    _selfsim_record = (ws.data_ptr(), nb, ptr(pred), n, int(pred.shape[1]), stream_ptr())
+
+
 _selfsim_record = None
 remd_borrow_stats = {"borrowed": 0, "plain": 0}      # which path remd_cos_fwd_bwd_after_selfsim took (tests read it)
 
@@ -614,6 +631,25 @@ def step_losses_blend_fwd_bwd(pred, content, n, d, style_set, g_content, g_momen
                                               float(g_moment), float(g_remd), float(g_palette), ptr(gpred), ptr(loss_content),
                                               ptr(loss_moment), ptr(loss_remd), ptr(loss_palette), ptr(ws), nb, stream_ptr()),
           "step_losses_blend_fwd_bwd")
+
+
+def step_losses_cw_fwd_bwd(pred, content, n, d, col_weight, style_set, g_content, g_moment, g_remd, g_palette, gpred,
+                           loss_content, loss_moment, loss_remd, loss_palette):
+    """step_losses_blend_fwd_bwd (any number of styles, one included) with the content term weighted per sampled column
+    (strotss_step_losses_cw_fwd_bwd; col_weight: float32 device vector of >= n values, finite and >= 0).  One style: the
+    single-style launches; several: the blended ones."""
+    require(col_weight, "column weights")
+    assert col_weight.numel() >= n
+    l = _hip.lib()
+    ld = int(pred.shape[1])
+    nb = l.strotss_step_losses_blend_workspace_bytes(C.byref(style_set), n, ld)
+    if nb == 0:
+        raise _hip.StrotssHipError("step_losses_cw: invalid style set")
+    ws = workspaces.get("step_losses_blend", nb, pred.device)
+    check(l.strotss_step_losses_cw_fwd_bwd(ptr(pred), ptr(content), n, d, ld, ptr(col_weight), C.byref(style_set),
+                                           float(g_content), float(g_moment), float(g_remd), float(g_palette), ptr(gpred),
+                                           ptr(loss_content), ptr(loss_moment), ptr(loss_remd), ptr(loss_palette), ptr(ws), nb,
+                                           stream_ptr()), "step_losses_cw_fwd_bwd")
 
 
 def sinkhorn_cos_fwd_bwd(style, rs, ns, pred, n, d, l, n_iter, gscale, gpred, loss_out):

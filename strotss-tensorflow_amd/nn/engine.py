@@ -115,7 +115,11 @@ class StepEngine:
     index set + loss group per region, loss = mean over regions.  With `dist_group` (a ProcessGroup, or
     `parallel.WORLD` for torch.distributed's default group), regions are dealt round-robin to the ranks and the
     pixel gradient is all-reduced (sum) before the fold adjoint, so every rank applies the identical update.
-    The logged scalars ride in the tail of the same buffer: ONE all-reduce per step."""
+    The logged scalars ride in the tail of the same buffer: ONE all-reduce per step.
+
+    `content_weight`: an (h, w) or (1, h, w, 1) map at this scale's size, finite and >= 0 (strotss_utils.content_weight_at_scale
+    builds it from a user's map): the content term of every region weights sample j's column of the self-similarity
+    matrices by the map at sample j.  One GPU only: not with `strips` or `dist_group`."""
 
     N_SCALARS = 4   # loss_c, l_moment, l_remd, l_palette per region
 
@@ -123,7 +127,7 @@ class StepEngine:
                  style_targets: Sequence[StyleTarget], stylized: torch.Tensor, alpha: float,
                  loss_denom: float, lr: float, sample_size: int = 1024, levels: int = 5,
                  dist_group=None, rho: float = 0.99, eps: float = 1e-8, strips: Optional["parallel.StripPlan"] = None,
-                 deterministic: Optional[bool] = None):
+                 deterministic: Optional[bool] = None, content_weight: Optional[torch.Tensor] = None):
         dev = stylized.device
         self.params = params
         self.alpha, self.loss_denom, self.lr, self.rho, self.eps = float(alpha), float(loss_denom), float(lr), rho, eps
@@ -138,6 +142,13 @@ class StepEngine:
                              "supported with several styles")
         h, w = int(stylized.shape[1]), int(stylized.shape[2])
         self.h, self.w = h, w
+        self._cw_map = None
+        if content_weight is not None:
+            if strips is not None or dist_group is not None:
+                raise ValueError("a content-weight map runs on one GPU: image strips and region sharding are not supported "
+                                 "with it")
+            from .strotss_utils import check_content_weight
+            self._cw_map = check_content_weight(content_weight, h, w).to(dev).clone()     # the engine's own copy
         # --- variables = make_laplacian_pyramid(stylized) (run_strotss.py:89), rms slots start at 0
         from .strotss_utils import make_laplacian_pyramid
         self.variables = [v.contiguous() for v in make_laplacian_pyramid(stylized.contiguous(), levels)]
@@ -182,6 +193,14 @@ class StepEngine:
                                else None)
         self._style_sets = [_ops.make_style_set(t.targets, t.weights) if isinstance(t, StyleBlend) else None
                             for t in self.style_targets]
+        # content-weight map: every region's weights of its samples (rows >= n zero), gathered with its features; the grouped
+        # loss call takes a style set, a one-style set of weight 1 for a plain StyleTarget (the single-style launches)
+        self._cw = self._cw_sets = self._mt_cw = None
+        if self._cw_map is not None:
+            self._cw = [torch.zeros(rows, dtype=torch.float32, device=dev) for _ in range(self.R)]
+            self._cw_sets = [self._style_sets[r] if self._style_sets[r] is not None else
+                             (_ops.make_style_set([t], [1.0]) if t.panels is not None else None)
+                             for r, t in enumerate(self.style_targets)]
         # gradient of the variables: level 0 aliases the pixel gradient
         if strips is not None:
             # full-size pixel gradient, zero outside the window; the trunk writes its window rows in place
@@ -208,6 +227,8 @@ class StepEngine:
         # (halo-exchange strips: the adjoint scatters ALL samples and drops the taps outside the window)
         self._mt_pred = _hip.make_maps(self.pred_maps, self.divs, gmaps, windows, window_drop=self._halo is not None)
         self._mt_content = _hip.make_maps(self.content_feat, self.divs)
+        if self._cw_map is not None:
+            self._mt_cw = _hip.make_maps([self._cw_map], [[]])        # level 0: the image's own coordinates, no divisors
         self._layer_to_map = {li: k + 1 for k, li in enumerate(self.trunk.taps)}
         self._layer_to_map[-1] = 0
         if strips is not None:            # strips shard the IMAGE: every rank runs every region's (replicated) losses
@@ -270,8 +291,15 @@ class StepEngine:
                                                       self.ld, _hip.stream_ptr()), "hypercol_gather")
 
     def _gather_both(self, maps_pred, idx, r: int) -> None:
-        """content rows, prediction rows and the zero fill of the gradient rows of region r in ONE launch"""
+        """content rows, prediction rows and the zero fill of the gradient rows of region r in ONE launch (with a content-weight
+        map also the weights of the samples)"""
         n = idx.shape[0]
+        if self._cw is not None:
+            _hip.check(_hip.lib().strotss_hypercol_gather2_cw(
+                _hip.C.byref(self._mt_content), _hip.C.byref(maps_pred), _hip.C.byref(self._mt_cw), idx.data_ptr(), n, 1,
+                self.cf[r].data_ptr(), self.pf[r].data_ptr(), self.ld, self.gp[r].data_ptr(), int(self.gp[r].shape[0]),
+                self._cw[r].data_ptr(), int(self._cw[r].shape[0]), _hip.stream_ptr()), "hypercol_gather2_cw")
+            return
         _hip.check(_hip.lib().strotss_hypercol_gather2(_hip.C.byref(self._mt_content), _hip.C.byref(maps_pred), idx.data_ptr(), n,
                                                        1, self.cf[r].data_ptr(), self.pf[r].data_ptr(), self.ld,
                                                        self.gp[r].data_ptr(), int(self.gp[r].shape[0]), _hip.stream_ptr()),
@@ -287,30 +315,40 @@ class StepEngine:
         if not zeroed:
             gp.zero_()
         base = 1.0 / (self.loss_denom * self.R)
+        cw = self._cw[r] if self._cw is not None else None
         if isinstance(st, StyleBlend):
-            self._losses_blend(r, st, n, base)
+            self._losses_blend(r, st, n, base, cw)
             return
         if st.panels is not None and _ops.step_losses_available():
+            if cw is not None:        # the same launches with the content term weighted per sample
+                _ops.step_losses_cw_fwd_bwd(pf, cf, n, self.d, cw, self._cw_sets[r], self.alpha * base, base, base,
+                                            self.inv_alpha * base, gp, sc[0:], sc[1:], sc[2:], sc[3:])
+                return
             # one call: 13 launches instead of 21, the three forward GEMMs in one of them (bit for bit the four calls below)
             _ops.step_losses_fwd_bwd(pf, cf, n, self.d, st.feats, st.inv_norm, st.panels, st.ns, st.mean, st.cov,
                                      self.alpha * base, base, base, self.inv_alpha * base, gp, sc[0:], sc[1:], sc[2:], sc[3:])
             return
-        _ops.selfsim_fwd_bwd(pf, cf, n, self.d, self.alpha * base, gp, sc[0:])
+        _ops.selfsim_weighted_fwd_bwd(pf, cf, cw, n, self.d, self.alpha * base, gp, sc[0:])
         _ops.moment_fwd_bwd(st.mean, st.cov, pf, n, self.d, base, gp, sc[1:])
         # the relaxed EMD borrows the prediction rows' norms and x3 panels from the content loss's workspace (the moment
         # term has its own) and the style rows' panels from the StyleTarget
         _ops.remd_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, base, gp, sc[2:])
         _ops.palette_remd_fwd_bwd(st.feats, st.ns, pf, n, self.inv_alpha * base, gp, sc[3:])
 
-    def _losses_blend(self, r: int, blend: StyleBlend, n: int, base: float) -> None:
+    def _losses_blend(self, r: int, blend: StyleBlend, n: int, base: float, cw: Optional[torch.Tensor] = None) -> None:
         """_losses for a blend of K > 1 styles: ONE call (the launches of the single-style call), or -- with the grouped loss
-        section switched off -- the content term once and each style's three separate entries with gscale w_k * base."""
+        section switched off -- the content term once and each style's three separate entries with gscale w_k * base.
+        cw: the samples' content weights (content-weight map) or None."""
         pf, cf, gp, sc, ss = self.pf[r], self.cf[r], self.gp[r], self.scalars[r], self._style_scalars[r]
         if _ops.step_losses_available():
+            if cw is not None:
+                _ops.step_losses_cw_fwd_bwd(pf, cf, n, self.d, cw, self._style_sets[r], self.alpha * base, base, base,
+                                            self.inv_alpha * base, gp, sc[0:], ss[0], ss[1], ss[2])
+                return
             _ops.step_losses_blend_fwd_bwd(pf, cf, n, self.d, self._style_sets[r], self.alpha * base, base, base,
                                            self.inv_alpha * base, gp, sc[0:], ss[0], ss[1], ss[2])
             return
-        _ops.selfsim_fwd_bwd(pf, cf, n, self.d, self.alpha * base, gp, sc[0:])
+        _ops.selfsim_weighted_fwd_bwd(pf, cf, cw, n, self.d, self.alpha * base, gp, sc[0:])
         for k, (st, w) in enumerate(zip(blend.targets, blend.weights)):
             _ops.moment_fwd_bwd(st.mean, st.cov, pf, n, self.d, base * w, gp, ss[0, k:])
             _ops.remd_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, base * w, gp, ss[1, k:])

@@ -206,6 +206,26 @@ def self_similarity(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     return _TwoSidedLoss.apply(x, y, run, True)
 
 
+def weighted_self_similarity(x: torch.Tensor, y: torch.Tensor, weight) -> torch.Tensor:
+    """self_similarity with a content weight per sampled column:
+    (1/n) sum_j weight[j] sum_i |A[i,j] - B[i,j]|, A and B the column-normalised cosine matrices of x and y.  weight: n finite
+    values >= 0 (ValueError otherwise); all ones is self_similarity.  x = prediction, y = target (WeightedContentLoss swaps
+    them); differentiable in both -- the loss is symmetric in (x, y) for fixed weights."""
+    n = int(reshape_2d(x).shape[0])
+    wt = weight if torch.is_tensor(weight) else torch.as_tensor(weight)
+    wt = wt.detach().reshape(-1)
+    if wt.numel() != n or int(reshape_2d(y).shape[0]) != n:
+        raise ValueError(f"weighted_self_similarity: {wt.numel()} weights for {n} and {int(reshape_2d(y).shape[0])} rows")
+    if not bool(torch.isfinite(wt).all()) or bool((wt < 0).any()):
+        raise ValueError("weighted_self_similarity: weights must be finite and >= 0")
+    buf = torch.zeros(_ops.pad32(n), dtype=torch.float32, device=x.device)
+    buf[:n] = wt.to(device=x.device, dtype=torch.float32)
+
+    def run(other, n_other, pred, n_, d, g, loss, swapped):
+        _ops.selfsim_weighted_fwd_bwd(pred, other, buf, n_, d, 1.0, g, loss)
+    return _TwoSidedLoss.apply(x, y, run, True)
+
+
 def relaxed_emd(x: torch.Tensor, y: torch.Tensor, distance: str = 'cosine') -> torch.Tensor:
     """max(mean_i min_j C, mean_j min_i C)  (reference losses.py:69-80); x = target, y = prediction in run_strotss.py,
     differentiable in both.  Every entry of `dist_metrics` at any width, as the reference (losses.py:27-28, 74): 'cosine' on

@@ -7,6 +7,7 @@ the functions here are the reference's operator surface, differentiable where th
 from __future__ import annotations
 
 import math
+import os
 from functools import partialmethod
 from typing import List, Optional, Sequence, Tuple, Union
 
@@ -105,6 +106,47 @@ def mask_at_scale(mask: torch.Tensor, h: int, w: int) -> np.ndarray:
     else:
         keep = m > 0.5
     return keep.cpu().numpy()
+
+
+def check_content_weight(weight, h: int, w: int) -> torch.Tensor:
+    """A content-weight map at a scale of (h, w): an (h, w) or (1, h, w, 1) array, every value finite and >= 0 -> the
+    (1, h, w, 1) float32 tensor on the map's device (ValueError otherwise).  Values above 1 are allowed."""
+    t = weight if torch.is_tensor(weight) else torch.as_tensor(np.asarray(weight))
+    if tuple(t.shape) not in ((h, w), (1, h, w, 1)):
+        raise ValueError(f"content-weight map of shape {tuple(t.shape)}: expected ({h}, {w}) or (1, {h}, {w}, 1)")
+    t = t.float()
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError("content-weight map: values must be finite")
+    if bool((t < 0).any()):
+        raise ValueError("content-weight map: values must be >= 0")
+    return t.reshape(1, h, w, 1).contiguous()
+
+
+def content_weight_at_scale(weight_map, h: int, w: int) -> torch.Tensor:
+    """W_s of a scale: the user's (H, W), (H, W, 1) or (1, H, W, 1) weight map, checked (finite,
+    >= 0; ValueError otherwise, before anything runs on the device), resized bilinearly to (h, w) the way mask_at_scale
+    resizes a mask, without its threshold.  -> (1, h, w, 1) float32 on the device, checked again."""
+    m = weight_map if torch.is_tensor(weight_map) else torch.as_tensor(np.asarray(weight_map))
+    if m.dim() == 4 and m.shape[0] == 1 and m.shape[-1] == 1:
+        m = m[0, ..., 0]
+    elif m.dim() == 3 and m.shape[-1] == 1:
+        m = m[..., 0]
+    if m.dim() != 2 or m.shape[0] < 1 or m.shape[1] < 1:
+        raise ValueError(f"content-weight map of shape {tuple(weight_map.shape)}: expected (H, W), (H, W, 1) or (1, H, W, 1)")
+    big_h, big_w = int(m.shape[0]), int(m.shape[1])
+    m = check_content_weight(m, big_h, big_w)
+    m = _ops.resize_bilinear(m.to(utils.device()).contiguous(), int(h), int(w))
+    return check_content_weight(m, int(h), int(w))
+
+
+def load_content_weight_map(path: str) -> torch.Tensor:
+    """--content_weight_map: the image read as greyscale, divided by 255 -> (H, W) float32 host tensor in [0, 1]."""
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"File not found: {path}")
+    from PIL import Image
+    with Image.open(path) as im:
+        grey = np.asarray(im.convert("L"), dtype=np.float32)
+    return torch.from_numpy(grey / np.float32(255.0))
 
 
 class Sampling:

@@ -15,6 +15,10 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
                     style blending: stylise toward a weighted mix of style_path and the --style_mix images (1 + len(mix)
                     weights, default equal; normalised to sum to 1; zero-weight styles are dropped before they are loaded).
                     Not combined with masks or --strips.
+  --content_weight_map PATH
+                    per-pixel content strength: a greyscale image (white = keep the content, black = let it go), divided
+                    by 255 and resized to every scale; weights each sample's column of the content term (DESIGN.md
+                    section 11).  Combines with masks and --style_mix; not with --strips or a multi-process run.
   --strips          under torchrun (one process per GPU): ONE image on all GPUs -- every rank runs the trunk on its strip
                     of the image (+ halo) at the scales where that pays, two all-reduces per step (nn/parallel.py);
                     rank 0 writes the output
@@ -31,7 +35,7 @@ import torch
 from nn import engine as strotss_engine
 from nn import rand, utils
 from nn import strotss_utils as strotss
-from nn.losses import moment_matching, relaxed_emd, self_similarity
+from nn.losses import moment_matching, relaxed_emd, self_similarity, weighted_self_similarity
 from nn.model import VGG
 
 utils.make_logger('STROTSS')
@@ -45,6 +49,17 @@ class ContentLoss:
 
     def __call__(self, target: torch.Tensor, prediction: torch.Tensor) -> torch.Tensor:
         return self_similarity(prediction, target)
+
+
+class WeightedContentLoss:
+    """WeightedContentLoss(weight)(target, prediction) = weighted_self_similarity(prediction, target, weight): the content
+    loss with one weight per sample (the content-weight map at the samples); all ones is ContentLoss"""
+
+    def __init__(self, weight):
+        self.weight = weight
+
+    def __call__(self, target: torch.Tensor, prediction: torch.Tensor) -> torch.Tensor:
+        return weighted_self_similarity(prediction, target, self.weight)
 
 
 class StyleLoss:
@@ -102,6 +117,19 @@ def _style_inputs(args):
     kept = [(p, w) for p, w in zip(paths, weights) if w > 0]
     paths, weights = [p for p, _ in kept], [w for _, w in kept]
     return paths, strotss_engine.normalise_style_weights(weights)
+
+
+def _content_weight_input(args):
+    """--content_weight_map: its path, or None.  One GPU only: with --strips or under torchrun with WORLD_SIZE > 1 a
+    ValueError (checked before anything is loaded)."""
+    path = getattr(args, "content_weight_map", None)
+    if not path:
+        return None
+    if getattr(args, "strips", False):
+        raise ValueError("--content_weight_map cannot be combined with --strips")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("--content_weight_map runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    return path
 
 
 def _load_masks(args):
@@ -231,6 +259,7 @@ def run(args: argparse.Namespace, trace=None):
     timer = utils.Timer()
     timer.start()
 
+    cw_path = _content_weight_input(args)
     seed = int(getattr(args, "seed", 0))
     rand.seed_everything(seed)
     from nn import parallel
@@ -247,6 +276,7 @@ def run(args: argparse.Namespace, trace=None):
     style_paths, style_weights = _style_inputs(args)
     styles = [utils.load_image(p, max_size=args.max_size) for p in style_paths]
     content_masks, style_masks = _load_masks(args)
+    cw_map = strotss.load_content_weight_map(cw_path) if cw_path else None
     sampling = strotss.Sampling(SAMPLE_SIZE)
 
     # alpha = 16 (x3500 with Keras weights), halved after every scale -- also after skipped ones
@@ -268,7 +298,9 @@ def run(args: argparse.Namespace, trace=None):
             vgg.params, strotss_engine.extract_features(vgg.params, scl_content),
             _style_targets(vgg.params, scl_style, style_masks, sampling, style_weights), stylized, alpha,
             loss_denom=2. + alpha + 1. / max(alpha, 1.), lr=lr, sample_size=SAMPLE_SIZE, strips=plan,
-            dist_group=parallel.WORLD if (world > 1 and masked and plan is None) else None)
+            dist_group=parallel.WORLD if (world > 1 and masked and plan is None) else None,
+            content_weight=(None if cw_map is None else
+                            strotss.content_weight_at_scale(cw_map, int(scl_content.shape[1]), int(scl_content.shape[2]))))
         rec = None
         if trace is not None:
             rec = dict(i=i, scl=scl, lr=lr, alpha=alpha, loss_denom=eng.loss_denom, init=stylized.clone(), steps=[],
@@ -308,6 +340,9 @@ _FLAGS = (
                             help="style blending: further style images mixed with style_path")),
     (("--style_weights",), dict(type=float, nargs='+', default=None, metavar='W',
                                 help="style blending: one weight per style (style_path first), default equal")),
+    (("--content_weight_map",), dict(type=str, default=None, metavar='PATH',
+                                     help="greyscale image: per-pixel content strength (white keeps the content, black lets "
+                                          "it go), resized to every scale")),
     (("--strips",), dict(action='store_true', help="under torchrun: shard ONE image over the GPUs by image strips")),
     (("--halo",), dict(action='store_true', help="with --strips: per-layer halo EXCHANGE with the neighbouring ranks (16-row "
                                                  "windows margins, one row per layer and direction) instead of a 128-row recompute margin")),
