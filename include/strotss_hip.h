@@ -473,6 +473,29 @@ int strotss_moment_fwd_bwd(const float* style_mean, const float* style_cov, cons
                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Temporal consistency of frame sequences: the short-term temporal loss of Ruder et al. (2016)
+ * --------------------------------------------------------------------------------------- */
+/* Once per frame, in ONE launch: the previous stylised frame prev(h, w, c) warped along the backward flow and its
+ * certainty.  flow_b, flow_f: (h, w, 2) = (u, v) displacements in pixels (frame t -> t-1 and t-1 -> t); flow_f may be NULL.
+ *   warped(y, x, :) = prev sampled at (x + u_b, y + v_b): pixel centres at integer coordinates, bilinear over the 4
+ *                     neighbours, indices clamped to the edge;
+ *   certainty(y, x) = 0 where the sample point lies outside [0, w-1] x [0, h-1], where it is disoccluded (flow_f given:
+ *                     |f_b + f_f(p + f_b)|^2 > 0.01 (|f_b|^2 + |f_f(p + f_b)|^2) + 0.5, f_f sampled by the same rule) or on
+ *                     a motion boundary (|grad u_b|^2 + |grad v_b|^2 > 0.01 |f_b|^2 + 0.002, central differences with
+ *                     clamped indices); 1 elsewhere.  Coordinates and tests in float64. */
+int strotss_flow_warp(const float* prev, int h, int w, int c, const float* flow_b, const float* flow_f, float* warped,
+                      float* certainty, void* stream);
+/* bytes of the workspace of strotss_temporal_fwd_bwd (0 for h, w <= 0) */
+size_t strotss_temporal_workspace_bytes(int h, int w);
+/* The temporal term of one step, in ONE launch (img, target, gimg: (h, w, 3); certainty: (h, w); all 16-byte aligned):
+ *   loss_out[0] = (1 / (3 h w)) sum_p certainty(p) sum_ch (img - target)^2,   gimg += gscale * dloss/dimg.
+ * gscale == 0 or certainty(p) == 0 leaves gimg (at p) bit for bit.  The scalar is a fixed-order reduction (block partials,
+ * summed in a fixed order by the last block to finish; no float atomics).  workspace: strotss_temporal_workspace_bytes(h, w)
+ * bytes, 16-byte aligned, ZEROED before its first use; every call leaves it ready for the next (one call at a time). */
+int strotss_temporal_fwd_bwd(const float* img, const float* target, const float* certainty, int h, int w, float gscale,
+                             float* gimg, float* loss_out, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Optimiser + output
  * --------------------------------------------------------------------------------------- */
 typedef struct {

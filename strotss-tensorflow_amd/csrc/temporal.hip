@@ -1,0 +1,181 @@
+// Temporal consistency of frame sequences: the short-term temporal loss of Ruder et al. (2016).
+//   - flow_warp_kernel: once per frame, the previous stylised frame warped along the backward flow + its {0, 1} certainty;
+//   - temporal_fwd_bwd_kernel: once per step (inside the captured graph), L_t = (1/(3hw)) sum_p c(p) |x(p) - w(p)|^2 and
+//     gimg += gscale * dL_t/dx, between the trunk's pixel gradient and the fold adjoint.
+#include "internal.h"
+
+namespace {
+
+// Bilinear taps along one axis, pixel centres at integer coordinates, both neighbours clamped to [0, n-1].  Beyond
+// [-2, n+1] every tap is the edge pixel already: clamping there first keeps floor() in int range (a NaN lands on -2).
+struct Tap64 { int lo, hi; double f; };
+__device__ __forceinline__ Tap64 tap64(double s, int n) {
+  s = fmin(fmax(s, -2.0), (double)n + 1.0);
+  const double fl = floor(s);
+  const int i = (int)fl;
+  Tap64 t;
+  t.lo = min(max(i, 0), n - 1);
+  t.hi = min(max(i + 1, 0), n - 1);
+  t.f = s - fl;
+  return t;
+}
+
+__device__ __forceinline__ double bilerp64(const float* __restrict__ p, int w, int c, int ch, const Tap64& ty,
+                                           const Tap64& tx) {
+  const double a = p[((size_t)ty.lo * w + tx.lo) * c + ch], b = p[((size_t)ty.lo * w + tx.hi) * c + ch];
+  const double d = p[((size_t)ty.hi * w + tx.lo) * c + ch], e = p[((size_t)ty.hi * w + tx.hi) * c + ch];
+  return (1.0 - ty.f) * ((1.0 - tx.f) * a + tx.f * b) + ty.f * ((1.0 - tx.f) * d + tx.f * e);
+}
+
+// One thread per pixel.  Coordinates, samples and the three certainty tests in float64: the tests compare sums of squares
+// against thresholds, and float64 keeps them the tests of the float64 statement (an integer shift warps exactly).
+__global__ __launch_bounds__(256) void flow_warp_kernel(const float* __restrict__ prev, int h, int w, int c,
+                                                        const float* __restrict__ fb, const float* __restrict__ ff,
+                                                        float* __restrict__ warped, float* __restrict__ certainty) {
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= (long long)h * w) return;
+  const int y = (int)(p / w), x = (int)(p - (long long)y * w);
+  const double u = fb[2 * p], v = fb[2 * p + 1];
+  const double sx = x + u, sy = y + v;
+  const Tap64 tx = tap64(sx, w), ty = tap64(sy, h);
+  for (int ch = 0; ch < c; ++ch) warped[p * c + ch] = (float)bilerp64(prev, w, c, ch, ty, tx);
+  // out of frame (a NaN coordinate fails both comparisons: out)
+  bool ok = sx >= 0.0 && sx <= (double)(w - 1) && sy >= 0.0 && sy <= (double)(h - 1);
+  const double fb2 = u * u + v * v;
+  // disoccluded: the forward flow at the warped point does not bring the pixel back
+  if (ok && ff) {
+    const double wu = bilerp64(ff, w, 2, 0, ty, tx), wv = bilerp64(ff, w, 2, 1, ty, tx);
+    const double su = u + wu, sv = v + wv;
+    if (su * su + sv * sv > 0.01 * (fb2 + wu * wu + wv * wv) + 0.5) ok = false;
+  }
+  // motion boundary: central differences of the backward flow, indices clamped
+  if (ok) {
+    const int xm = max(x - 1, 0), xp = min(x + 1, w - 1), ym = max(y - 1, 0), yp = min(y + 1, h - 1);
+    const size_t rm = (size_t)y * w, ra = (size_t)ym * w, rb = (size_t)yp * w;
+    const double ux = ((double)fb[2 * (rm + xp)] - (double)fb[2 * (rm + xm)]) * 0.5;
+    const double vx = ((double)fb[2 * (rm + xp) + 1] - (double)fb[2 * (rm + xm) + 1]) * 0.5;
+    const double uy = ((double)fb[2 * (rb + x)] - (double)fb[2 * (ra + x)]) * 0.5;
+    const double vy = ((double)fb[2 * (rb + x) + 1] - (double)fb[2 * (ra + x) + 1]) * 0.5;
+    if ((ux * ux + uy * uy) + (vx * vx + vy * vy) > 0.01 * fb2 + 0.002) ok = false;
+  }
+  certainty[p] = ok ? 1.f : 0.f;
+}
+
+// One workgroup per 1024 pixels = 3072 floats = 768 float4 of x, of the target and of the gradient: thread t takes float4 t,
+// t + 256 and t + 512 of each (coalesced), the block's 1024 certainties staged in LDS first (element e of the block belongs
+// to pixel e / 3).  The last block, if partial, goes element by element.  c(p) == 0 or gscale == 0 leaves gimg bit for bit
+// (the unchanged value is stored back, or nothing at all).  The scalar: per-thread sums in a fixed element order, a fixed
+// tree per block, the partials of the blocks summed in a fixed order by whichever block arrives last (integer ticket, no
+// float atomics).
+#define TEMPORAL_PIX_PER_BLOCK 1024
+__global__ __launch_bounds__(256) void temporal_fwd_bwd_kernel(const float* __restrict__ img, const float* __restrict__ tgt,
+                                                               const float* __restrict__ cert, int npix, float coef,
+                                                               float inv_n, float* __restrict__ gimg,
+                                                               float* __restrict__ loss_out, unsigned* __restrict__ ticket,
+                                                               float* __restrict__ partials) {
+  __shared__ float cs[TEMPORAL_PIX_PER_BLOCK];
+  __shared__ float red[4];
+  __shared__ int is_last;
+  const int t = threadIdx.x;
+  const int base = blockIdx.x * TEMPORAL_PIX_PER_BLOCK;
+  const int count = min(TEMPORAL_PIX_PER_BLOCK, npix - base);
+  const bool full = count == TEMPORAL_PIX_PER_BLOCK;
+  const size_t f0 = 3 * (size_t)base;
+  float acc = 0.f;
+  if (full) {
+    // every global load of the thread in flight at once (a grid of a few waves per SIMD: latency, not bandwidth, bounds it)
+    const f32x4* x4 = reinterpret_cast<const f32x4*>(img + f0);
+    const f32x4* y4 = reinterpret_cast<const f32x4*>(tgt + f0);
+    f32x4* g4 = reinterpret_cast<f32x4*>(gimg + f0);
+    const f32x4 c4 = reinterpret_cast<const f32x4*>(cert + base)[t];
+    f32x4 xv[3], yv[3], gv[3] = {};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      xv[k] = x4[t + 256 * k];
+      yv[k] = y4[t + 256 * k];
+    }
+    if (coef != 0.f) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) gv[k] = g4[t + 256 * k];
+    }
+    reinterpret_cast<f32x4*>(cs)[t] = c4;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const f32x4 d = xv[k] - yv[k];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float ce = cs[(4 * (t + 256 * k) + e) / 3];
+        acc += ce * (d[e] * d[e]);
+        gv[k][e] = ce != 0.f ? gv[k][e] + (coef * ce) * d[e] : gv[k][e];
+      }
+    }
+    if (coef != 0.f) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) g4[t + 256 * k] = gv[k];
+    }
+  } else {
+    for (int p = t; p < count; p += 256) cs[p] = cert[base + p];
+    __syncthreads();
+    for (int i = t; i < 3 * count; i += 256) {
+      const float ce = cs[i / 3], d = img[f0 + i] - tgt[f0 + i];
+      acc += ce * (d * d);
+      if (coef != 0.f && ce != 0.f) gimg[f0 + i] += (coef * ce) * d;
+    }
+  }
+  const float s = block_sum_256(acc, red);
+  if (threadIdx.x == 0) {
+    partials[blockIdx.x] = s;
+    __threadfence();                                  // the partial is visible before the ticket is taken
+    is_last = atomicAdd(ticket, 1u) == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!is_last) return;
+  __threadfence();
+  float a = 0.f;
+  for (int i = threadIdx.x; i < (int)gridDim.x; i += 256)
+    a += __hip_atomic_load(&partials[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  a = block_sum_256(a, red);
+  if (threadIdx.x == 0) {
+    loss_out[0] = a * inv_n;
+    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next call
+  }
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+inline long long temporal_blocks(int h, int w) {
+  return ((long long)h * w + TEMPORAL_PIX_PER_BLOCK - 1) / TEMPORAL_PIX_PER_BLOCK;
+}
+
+}  // namespace
+
+int strotss_flow_warp(const float* prev, int h, int w, int c, const float* flow_b, const float* flow_f, float* warped,
+                      float* certainty, void* stream) {
+  ST_CHECK_ARG(prev && flow_b && warped && certainty && h > 0 && w > 0 && c > 0, STROTSS_EINVAL);
+  const long long npix = (long long)h * w;
+  ST_CHECK_ARG(npix * c <= (1LL << 40), STROTSS_EINVAL);
+  hipLaunchKernelGGL(flow_warp_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, prev, h, w,
+                     c, flow_b, flow_f, warped, certainty);
+  ST_LAUNCH_RET();
+}
+
+size_t strotss_temporal_workspace_bytes(int h, int w) {
+  if (h <= 0 || w <= 0) return 0;
+  return 16 + 4 * (size_t)temporal_blocks(h, w);
+}
+
+int strotss_temporal_fwd_bwd(const float* img, const float* target, const float* certainty, int h, int w, float gscale,
+                             float* gimg, float* loss_out, void* workspace, void* stream) {
+  ST_CHECK_ARG(img && target && certainty && gimg && loss_out && workspace && h > 0 && w > 0, STROTSS_EINVAL);
+  const long long npix = (long long)h * w;
+  ST_CHECK_ARG(3 * npix <= 0x7fffffffLL, STROTSS_EINVAL);
+  ST_CHECK_ARG(aligned16(img) && aligned16(target) && aligned16(certainty) && aligned16(gimg) && aligned16(workspace),
+               STROTSS_EALIGN);
+  const double n = 3.0 * (double)npix;
+  const float coef = (float)(2.0 * (double)gscale / n), inv_n = (float)(1.0 / n);
+  unsigned* ticket = (unsigned*)workspace;
+  float* partials = (float*)((char*)workspace + 16);
+  hipLaunchKernelGGL(temporal_fwd_bwd_kernel, dim3((unsigned)temporal_blocks(h, w)), dim3(256), 0, (hipStream_t)stream, img,
+                     target, certainty, (int)npix, coef, inv_n, gimg, loss_out, ticket, partials);
+  ST_LAUNCH_RET();
+}

@@ -140,6 +140,9 @@ SIGNATURES = {
     "strotss_moment_workspace_bytes": (_Z, [_I, _I]),
     "strotss_moment_stats": (_I, [_P, _I, _I, _I, _P, _P, _P, _Z, _P]),
     "strotss_moment_fwd_bwd": (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _Z, _P]),
+    "strotss_flow_warp": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "strotss_temporal_workspace_bytes": (_Z, [_I, _I]),
+    "strotss_temporal_fwd_bwd": (_I, [_P, _P, _P, _I, _I, _F, _P, _P, _P, _P]),
     "strotss_rmsprop_step": (_I, [C.POINTER(TensorsT), _F, _F, _F, _P]),
     "strotss_postprocess": (_I, [_P, _L, _P, _P, _P]),
 }

@@ -81,6 +81,58 @@ def fold_pyramid_adjoint(gvars: Sequence[torch.Tensor]) -> bool:
     return True
 
 
+def flow_warp(prev: torch.Tensor, flow_b: torch.Tensor, flow_f: Optional[torch.Tensor] = None,
+              warped: Optional[torch.Tensor] = None, certainty: Optional[torch.Tensor] = None):
+    """(warped, certainty) of the temporal term (strotss_flow_warp): prev (1, h, w, c) or (h, w, c)
+    warped along the backward flow (h, w, 2), certainty (h, w) in {0, 1}; flow_f (h, w, 2) or None (no disocclusion test)."""
+    require(prev, "previous frame")
+    require(flow_b, "backward flow")
+    h, w, c = hwc(prev)
+    assert tuple(flow_b.shape[-3:]) == (h, w, 2) and flow_b.numel() == 2 * h * w
+    if flow_f is not None:
+        require(flow_f, "forward flow")
+        assert tuple(flow_f.shape[-3:]) == (h, w, 2) and flow_f.numel() == 2 * h * w
+    if warped is None:
+        warped = torch.empty_like(prev)
+    if certainty is None:
+        certainty = torch.empty((h, w), dtype=torch.float32, device=prev.device)
+    require(warped, "warped frame")
+    require(certainty, "certainty")
+    assert warped.numel() == h * w * c and certainty.numel() == h * w
+    check(_hip.lib().strotss_flow_warp(ptr(prev), h, w, c, ptr(flow_b), ptr(flow_f), ptr(warped), ptr(certainty),
+                                       stream_ptr()), "flow_warp")
+    return warped, certainty
+
+
+def temporal_workspace(h: int, w: int, device) -> torch.Tensor:
+    """a zeroed workspace of strotss_temporal_fwd_bwd for (h, w): the call's ticket counter starts at 0 and every call
+    leaves it there.  One per caller that may run concurrently (an engine owns its own)."""
+    nb = int(_hip.lib().strotss_temporal_workspace_bytes(int(h), int(w)))
+    return torch.zeros(max(nb, 16), dtype=torch.uint8, device=device)
+
+
+_temporal_ws = {}
+
+
+def temporal_fwd_bwd(img: torch.Tensor, target: torch.Tensor, certainty: torch.Tensor, gscale: float, gimg: torch.Tensor,
+                     loss_out: torch.Tensor, workspace: Optional[torch.Tensor] = None) -> None:
+    """loss_out[0] = (1/(3hw)) sum_p certainty(p) |img(p) - target(p)|^2, gimg += gscale * dloss/dimg
+    (strotss_temporal_fwd_bwd; img, target, gimg (h, w, 3) or (1, h, w, 3), certainty (h, w)).  workspace: from
+    temporal_workspace, or None for a module-level one per device and size."""
+    for t, name in ((img, "image"), (target, "temporal target"), (certainty, "certainty"), (gimg, "pixel gradient"),
+                    (loss_out, "temporal loss")):
+        require(t, name)
+    h, w, c = hwc(img)
+    assert c == 3 and target.numel() == gimg.numel() == 3 * h * w and certainty.numel() == h * w
+    if workspace is None:
+        key = (str(img.device), h, w)
+        workspace = _temporal_ws.get(key)
+        if workspace is None:
+            workspace = _temporal_ws[key] = temporal_workspace(h, w, img.device)
+    check(_hip.lib().strotss_temporal_fwd_bwd(ptr(img), ptr(target), ptr(certainty), h, w, float(gscale), ptr(gimg),
+                                              ptr(loss_out), ptr(workspace), stream_ptr()), "temporal_fwd_bwd")
+
+
 def resize_bilinear_adjoint(gout: torch.Tensor, ih: int, iw: int,
                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
     require(gout, "resize adjoint input")

@@ -69,6 +69,17 @@ class StyleBlend:
         self.weights = normalise_style_weights(self.weights)
 
 
+@dataclass
+class TemporalTarget:
+    """The temporal term of a frame sequence at one scale: `target` (h, w, 3) the warped previous
+    frame, `certainty` (h, w) its certainty, `weight` lambda >= 0.  The step adds
+    lambda * L_t = lambda / (3 h w) * sum_p c(p) |x(p) - target(p)|^2 to its loss (strotss_utils.temporal_target_at_scale
+    builds the two arrays)."""
+    target: torch.Tensor
+    certainty: torch.Tensor
+    weight: float
+
+
 def extract_features(params: VGGParams, image: torch.Tensor) -> List[torch.Tensor]:
     """[image] + vgg(image)  (run_strotss.py:95-96), taps cloned out of a temporary trunk."""
     h, w = int(image.shape[1]), int(image.shape[2])
@@ -119,7 +130,10 @@ class StepEngine:
 
     `content_weight`: an (h, w) or (1, h, w, 1) map at this scale's size, finite and >= 0 (strotss_utils.content_weight_at_scale
     builds it from a user's map): the content term of every region weights sample j's column of the self-similarity
-    matrices by the map at sample j.  One GPU only: not with `strips` or `dist_group`."""
+    matrices by the map at sample j.  One GPU only: not with `strips` or `dist_group`.
+
+    `temporal`: a TemporalTarget at this scale's size: the pixel gradient gets lambda * dL_t/dx after the trunk (and the
+    all-reduce) and before the fold adjoint, in ONE launch.  One GPU only, as the map above."""
 
     N_SCALARS = 4   # loss_c, l_moment, l_remd, l_palette per region
 
@@ -127,7 +141,8 @@ class StepEngine:
                  style_targets: Sequence[StyleTarget], stylized: torch.Tensor, alpha: float,
                  loss_denom: float, lr: float, sample_size: int = 1024, levels: int = 5,
                  dist_group=None, rho: float = 0.99, eps: float = 1e-8, strips: Optional["parallel.StripPlan"] = None,
-                 deterministic: Optional[bool] = None, content_weight: Optional[torch.Tensor] = None):
+                 deterministic: Optional[bool] = None, content_weight: Optional[torch.Tensor] = None,
+                 temporal: Optional[TemporalTarget] = None):
         dev = stylized.device
         self.params = params
         self.alpha, self.loss_denom, self.lr, self.rho, self.eps = float(alpha), float(loss_denom), float(lr), rho, eps
@@ -149,6 +164,24 @@ class StepEngine:
                                  "with it")
             from .strotss_utils import check_content_weight
             self._cw_map = check_content_weight(content_weight, h, w).to(dev).clone()     # the engine's own copy
+        self._temporal = None
+        if temporal is not None:
+            if strips is not None or dist_group is not None:
+                raise ValueError("the temporal term runs on one GPU: image strips and region sharding are not supported "
+                                 "with it")
+            lam = float(temporal.weight)
+            if not np.isfinite(lam) or lam < 0:
+                raise ValueError(f"temporal weight must be finite and >= 0, got {temporal.weight}")
+            tgt, cert = temporal.target, temporal.certainty
+            if tgt.numel() != 3 * h * w or tuple(tgt.shape[-3:]) != (h, w, 3):
+                raise ValueError(f"temporal target of shape {tuple(tgt.shape)}: expected ({h}, {w}, 3)")
+            if cert.numel() != h * w or tuple(cert.shape[-2:]) != (h, w):
+                raise ValueError(f"temporal certainty of shape {tuple(cert.shape)}: expected ({h}, {w})")
+            # the engine's own fixed buffers (a captured graph reads them at replay) + the scalar and the reduction's workspace
+            self._temporal = dict(weight=lam, target=tgt.float().to(dev).reshape(h, w, 3).contiguous().clone(),
+                                  certainty=cert.float().to(dev).reshape(h, w).contiguous().clone(),
+                                  loss=torch.zeros(1, dtype=torch.float32, device=dev),
+                                  ws=_ops.temporal_workspace(h, w, dev))
         # --- variables = make_laplacian_pyramid(stylized) (run_strotss.py:89), rms slots start at 0
         from .strotss_utils import make_laplacian_pyramid
         self.variables = [v.contiguous() for v in make_laplacian_pyramid(stylized.contiguous(), levels)]
@@ -393,6 +426,7 @@ class StepEngine:
             return
         self._pixel_gradient(indices)
         self._reduce()
+        self._temporal_term()
         self._fold_adjoint()
 
     def _pixel_gradient(self, indices: Sequence[torch.Tensor]) -> None:
@@ -419,6 +453,12 @@ class StepEngine:
         """sharded regions: ONE all-reduce(sum) over [pixel gradient | scalars] (RCCL over xGMI; 12 MiB at 1024^2)"""
         if self._reduce_buf is not None:
             parallel.allreduce_sum_(self._reduce_buf, self.group)
+
+    def _temporal_term(self) -> None:
+        """gvars[0] += lambda * dL_t/dx and the scalar L_t, x the folded image of this step (no temporal target: nothing)"""
+        t = self._temporal
+        if t is not None:
+            _ops.temporal_fwd_bwd(self.fold[0], t["target"], t["certainty"], t["weight"], self.gvars[0], t["loss"], t["ws"])
 
     def _fold_adjoint(self) -> None:
         """gvars[k] = up^T(gvars[k-1]): adjoint of the fold"""
@@ -593,6 +633,7 @@ class StepEngine:
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):              # warm-up on the side stream (workspace allocation)
             head()
+            self._temporal_term()
             self._fold_adjoint()
             self.apply_gradients()
         torch.cuda.current_stream().wait_stream(side)
@@ -603,11 +644,13 @@ class StepEngine:
                 head()
             post = torch.cuda.CUDAGraph()
             with _Capture(post, side):
+                self._temporal_term()
                 self._fold_adjoint()
                 self.apply_gradients()
         else:
             with _Capture(g, side):
                 head()
+                self._temporal_term()
                 self._fold_adjoint()
                 self.apply_gradients()
         for t, s0 in zip(state, snap):
@@ -665,6 +708,10 @@ class StepEngine:
                "l_palette": float(s[:, 3].mean())}
         if per_style is not None:
             out["per_style"] = per_style         # one dict per style of the blend: its weight and unweighted terms
+        if self._temporal is not None:           # added once per step, not averaged over the regions
+            lt = float(self._temporal["loss"].item())
+            out["loss_t"] = lt
+            out["loss"] = float(loss) + self._temporal["weight"] * lt
         return out
 
     def stylized(self) -> torch.Tensor:

@@ -149,6 +149,53 @@ def load_content_weight_map(path: str) -> torch.Tensor:
     return torch.from_numpy(grey / np.float32(255.0))
 
 
+# ----------------------------------------------------------------------------- frame sequences
+FLO_MAGIC = 202021.25
+
+
+def read_flo(path: str) -> torch.Tensor:
+    """A Middlebury .flo file -> (h, w, 2) float32 host tensor, (u, v) = (x, y) displacement in pixels.  ValueError on a bad
+    magic number or a file whose size is not that of its header's (w, h)."""
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"File not found: {path}")
+    with open(path, "rb") as f:
+        raw = f.read()
+    if len(raw) < 12 or float(np.frombuffer(raw[:4], dtype="<f4")[0]) != FLO_MAGIC:
+        raise ValueError(f"{path}: not a .flo file (magic number {FLO_MAGIC} missing)")
+    w, h = (int(v) for v in np.frombuffer(raw[4:12], dtype="<i4"))
+    if w <= 0 or h <= 0 or len(raw) != 12 + 8 * w * h:
+        raise ValueError(f"{path}: a {w} x {h} flow needs {12 + 8 * max(w, 0) * max(h, 0)} bytes, the file has {len(raw)}")
+    return torch.from_numpy(np.frombuffer(raw[12:], dtype="<f4").astype(np.float32).reshape(h, w, 2))
+
+
+def resize_flow(flow: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    """A (H, W, 2) flow field at the size (h, w) of resized frames: both components resized bilinearly (the kernel of
+    utils.resize), u multiplied by w / W and v by h / H.  The same size: an unchanged copy.  -> (h, w, 2) float32 on the
+    flow's device (a host flow is resized on the device and comes back to the host)."""
+    if flow.dim() != 3 or flow.shape[-1] != 2:
+        raise ValueError(f"flow of shape {tuple(flow.shape)}: expected (H, W, 2)")
+    big_h, big_w = int(flow.shape[0]), int(flow.shape[1])
+    if (big_h, big_w) == (int(h), int(w)):
+        return flow.float().clone()
+    out = _ops.resize_bilinear(flow.float().to(utils.device()).contiguous(), int(h), int(w))
+    out = out * torch.tensor([w / big_w, h / big_h], dtype=torch.float32, device=out.device)
+    return out.to(flow.device)
+
+
+def temporal_target_at_scale(warped: torch.Tensor, certainty: torch.Tensor, h: int, w: int):
+    """(omega_s, c_s) of a scale: the warped previous frame (1, H, W, 3) and its certainty (H, W), resized bilinearly to
+    (h, w) as content_weight_at_scale resizes its map (no threshold) -> ((h, w, 3), (h, w)) float32 on the device."""
+    big_h, big_w = int(warped.shape[-3]), int(warped.shape[-2])
+    if tuple(certainty.shape[-2:]) != (big_h, big_w) or int(warped.shape[-1]) != 3 or certainty.numel() != big_h * big_w:
+        raise ValueError(f"warped frame {tuple(warped.shape)} and certainty {tuple(certainty.shape)} do not match")
+    dev = utils.device()
+    x = warped.float().to(dev).reshape(big_h, big_w, 3).contiguous()
+    c = certainty.float().to(dev).reshape(big_h, big_w, 1).contiguous()
+    if (big_h, big_w) == (int(h), int(w)):
+        return x.clone(), c.reshape(h, w).clone()
+    return _ops.resize_bilinear(x, int(h), int(w)), _ops.resize_bilinear(c, int(h), int(w)).reshape(int(h), int(w))
+
+
 class Sampling:
     """reference strotss_utils.py:20-136.  `rng` defaults to nn.rand.index_rng."""
 

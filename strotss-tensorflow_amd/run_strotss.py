@@ -19,6 +19,12 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
                     per-pixel content strength: a greyscale image (white = keep the content, black = let it go), divided
                     by 255 and resized to every scale; weights each sample's column of the content term (DESIGN.md
                     section 11).  Combines with masks and --style_mix; not with --strips or a multi-process run.
+  --video           content_path is a directory of frames (sorted by name, all of one size) and -o an output directory:
+                    frame <stem> is written as <stem>.jpg.  With --flow_dir DIR (backward_{t}_{t-1}.flo, optional
+                    forward_{t-1}_{t}.flo and reliable_{t}_{t-1}.pgm, t the 1-based position of the frame: the naming of
+                    the artistic-videos tools) every frame after the first is pulled toward the previous result warped
+                    along the flow, weight --temporal_weight; --temporal_init starts a frame's
+                    first executed scale from that warped result.  One GPU; not with --strips.
   --strips          under torchrun (one process per GPU): ONE image on all GPUs -- every rank runs the trunk on its strip
                     of the image (+ halo) at the scales where that pays, two all-reduces per step (nn/parallel.py);
                     rank 0 writes the output
@@ -30,6 +36,7 @@ all-reduce sums the pixel gradient, every rank applies the identical update; ran
 import argparse
 import os
 
+import numpy as np
 import torch
 
 from nn import engine as strotss_engine
@@ -130,6 +137,82 @@ def _content_weight_input(args):
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise ValueError("--content_weight_map runs on one GPU: not under torchrun with WORLD_SIZE > 1")
     return path
+
+
+DEFAULT_TEMPORAL_WEIGHT = 1000.0          # chosen on the MI355X with the consistency error
+IMAGE_SUFFIXES = (".jpg", ".jpeg", ".png", ".bmp", ".ppm", ".pgm", ".tif", ".tiff", ".webp")
+
+
+def _video_inputs(args):
+    """--video: (sorted frame paths, temporal weight); None without --video.  Refused with a ValueError before anything is
+    optimised: --temporal_weight / --flow_dir / --temporal_init without --video, a negative weight, --video with --strips or
+    under torchrun with WORLD_SIZE > 1, no --flow_dir, a content_path that is not a directory of frames, frames of different
+    sizes, a missing backward flow."""
+    video = bool(getattr(args, "video", False))
+    lam = getattr(args, "temporal_weight", None)
+    flow_dir = getattr(args, "flow_dir", None)
+    if not video:
+        for flag, val in (("--temporal_weight", lam), ("--flow_dir", flow_dir),
+                          ("--temporal_init", getattr(args, "temporal_init", False) or None)):
+            if val is not None:
+                raise ValueError(f"{flag} needs --video")
+        return None
+    lam = DEFAULT_TEMPORAL_WEIGHT if lam is None else float(lam)
+    if not np.isfinite(lam) or lam < 0:
+        raise ValueError(f"--temporal_weight must be finite and >= 0, got {lam}")
+    if getattr(args, "strips", False):
+        raise ValueError("--video cannot be combined with --strips")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("--video runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    if not flow_dir:
+        raise ValueError("--video needs --flow_dir (the optical flow between consecutive frames)")
+    if not os.path.isdir(args.content_path):
+        raise ValueError(f"--video: content_path {args.content_path} is not a directory of frames")
+    frames = sorted(os.path.join(args.content_path, f) for f in os.listdir(args.content_path)
+                    if f.lower().endswith(IMAGE_SUFFIXES) and os.path.isfile(os.path.join(args.content_path, f)))
+    if not frames:
+        raise ValueError(f"--video: no frames in {args.content_path}")
+    from PIL import Image
+    sizes = set()
+    for f in frames:
+        with Image.open(f) as im:
+            sizes.add(im.size)
+    if len(sizes) != 1:
+        raise ValueError(f"--video: the frames differ in size: {sorted(sizes)}")
+    for t in range(2, len(frames) + 1):
+        path = os.path.join(flow_dir, f"backward_{t}_{t - 1}.flo")
+        if not os.path.exists(path):
+            raise ValueError(f"--video: backward flow {path} of frame {t} is missing")
+    return frames, lam
+
+
+def _temporal_for_frame(args, t: int, previous: torch.Tensor):
+    """(warped previous result, certainty) of frame t (1-based, t >= 2) at the previous result's size: the flows of
+    --flow_dir resized to that size (strotss_utils.resize_flow), the warp and certainty in one launch; a
+    reliable_{t}_{t-1}.pgm, when there is one, replaces the certainty (its value / 255, resized)."""
+    h, w = int(previous.shape[1]), int(previous.shape[2])
+    dev = previous.device
+    flow_b = strotss.read_flo(os.path.join(args.flow_dir, f"backward_{t}_{t - 1}.flo"))
+    big = tuple(flow_b.shape[:2])
+    fwd_path = os.path.join(args.flow_dir, f"forward_{t - 1}_{t}.flo")
+    flow_f = strotss.read_flo(fwd_path) if os.path.exists(fwd_path) else None
+    if flow_f is not None and tuple(flow_f.shape[:2]) != big:
+        raise ValueError(f"{fwd_path}: a {tuple(flow_f.shape[:2])} flow, the backward one is {big}")
+    fb = strotss.resize_flow(flow_b.to(dev), h, w).contiguous()
+    ff = None if flow_f is None else strotss.resize_flow(flow_f.to(dev), h, w).contiguous()
+    warped, certainty = strotss_engine._ops.flow_warp(previous.contiguous(), fb, ff)
+    rel = os.path.join(args.flow_dir, f"reliable_{t}_{t - 1}.pgm")
+    if os.path.exists(rel):
+        certainty = _resized_reliable(rel, h, w)
+    return warped, certainty
+
+
+def _resized_reliable(path: str, h: int, w: int) -> torch.Tensor:
+    """reliable_{t}_{t-1}.pgm / 255 at (h, w) on the device (bilinear, no threshold): read as a content-weight map is"""
+    c = strotss.load_content_weight_map(path).to(utils.device())
+    if tuple(c.shape) != (h, w):
+        c = strotss_engine._ops.resize_bilinear(c[:, :, None].contiguous(), h, w).reshape(h, w)
+    return c.contiguous()
 
 
 def _load_masks(args):
@@ -255,11 +338,14 @@ def _optimise_scale(eng, scl: int, content_masks, args, dev, quiet: bool = False
 def run(args: argparse.Namespace, trace=None):
     """The reference's run(args) (run_strotss.py:43-161).  `trace` (a list) receives one dict per executed scale:
     scale index and size, lr, alpha, loss_denom, the image the scale starts from, every step's losses and the
-    result -- what the parity test of the schedule compares with the oracle's run_scales."""
+    result -- what the parity test of the schedule compares with the oracle's run_scales.  --video: run_video."""
+    if getattr(args, "video", False):
+        return run_video(args, trace)
     timer = utils.Timer()
     timer.start()
 
     cw_path = _content_weight_input(args)
+    _video_inputs(args)                                      # the sequence flags without --video: ValueError
     seed = int(getattr(args, "seed", 0))
     rand.seed_everything(seed)
     from nn import parallel
@@ -269,15 +355,33 @@ def run(args: argparse.Namespace, trace=None):
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
         rank, world = parallel.init_from_env(torch.cuda.current_device())
     dev = utils.device()
-    level, first = int(args.level), int(getattr(args, "start_level", 0))
 
     vgg = VGG(use_keras_weight=args.use_keras_weight, weights=getattr(args, "weights", None), seed=seed, device=dev)
-    content = utils.load_image(args.content_path, max_size=args.max_size)
+    stylized = _stylise(args, vgg, args.content_path, cw_path, dev, rank, world, trace)
+    final = strotss.postprocess(stylized)
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    timer.stop()
+    if rank == 0:
+        utils.logger.info(f"Done in {timer.elapsed_time:.2f}s.")
+        utils.write_image(final, args.output_path)
+    return final
+
+
+def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: int = 1, trace=None, temporal=None,
+             temporal_weight: float = 0.0):
+    """The coarse-to-fine schedule on one content image -> the final image of the finest scale (1, h, w, 3).
+    temporal: (warped previous result, certainty) at that result's size, or None; every scale then carries the temporal
+    term with weight temporal_weight, and --temporal_init starts the first executed scale from the warped result."""
+    from nn import parallel
+    level, first = int(args.level), int(getattr(args, "start_level", 0))
+    content = utils.load_image(content_path, max_size=args.max_size)
     style_paths, style_weights = _style_inputs(args)
     styles = [utils.load_image(p, max_size=args.max_size) for p in style_paths]
     content_masks, style_masks = _load_masks(args)
     cw_map = strotss.load_content_weight_map(cw_path) if cw_path else None
     sampling = strotss.Sampling(SAMPLE_SIZE)
+    masked = bool(getattr(args, "content_mask", None))
 
     # alpha = 16 (x3500 with Keras weights), halved after every scale -- also after skipped ones
     alpha = args.alpha * 16.0 * (3500 if args.use_keras_weight else 1) / 2.0 ** first
@@ -290,6 +394,13 @@ def run(args: argparse.Namespace, trace=None):
             scl_style = scl_style[0]
         stylized, lr = _initial_image(position, position > 0 and i == level - 1, stylized, scl_content, scl_style,
                                       args.lr, style_weights)
+        hs, ws = int(scl_content.shape[1]), int(scl_content.shape[2])
+        tt = None
+        if temporal is not None:
+            target, cert = strotss.temporal_target_at_scale(temporal[0], temporal[1], hs, ws)
+            tt = strotss_engine.TemporalTarget(target, cert, temporal_weight)
+            if position == 0 and getattr(args, "temporal_init", False):
+                stylized = target[None].contiguous()         # resize(omega) instead of Laplacian + mean style colour
         # --strips: ONE image sharded by rows (the only sharding that cuts trunk work), with or without mask regions; where
         # a scale is too small for strips to pay (strip_plan -> None) a masked run falls back to dealing its regions out
         plan = (parallel.strip_plan(int(scl_content.shape[1]), world, rank, halo=bool(getattr(args, "halo", False)))
@@ -299,8 +410,7 @@ def run(args: argparse.Namespace, trace=None):
             _style_targets(vgg.params, scl_style, style_masks, sampling, style_weights), stylized, alpha,
             loss_denom=2. + alpha + 1. / max(alpha, 1.), lr=lr, sample_size=SAMPLE_SIZE, strips=plan,
             dist_group=parallel.WORLD if (world > 1 and masked and plan is None) else None,
-            content_weight=(None if cw_map is None else
-                            strotss.content_weight_at_scale(cw_map, int(scl_content.shape[1]), int(scl_content.shape[2]))))
+            content_weight=(None if cw_map is None else strotss.content_weight_at_scale(cw_map, hs, ws)), temporal=tt)
         rec = None
         if trace is not None:
             rec = dict(i=i, scl=scl, lr=lr, alpha=alpha, loss_denom=eng.loss_denom, init=stylized.clone(), steps=[],
@@ -312,15 +422,40 @@ def run(args: argparse.Namespace, trace=None):
             rec["final"] = stylized.clone()
         del eng
         alpha /= 2.
+    return stylized
 
-    final = strotss.postprocess(stylized)
-    if torch.cuda.is_available():
-        torch.cuda.synchronize()
-    timer.stop()
-    if rank == 0:
-        utils.logger.info(f"Done in {timer.elapsed_time:.2f}s.")
-        utils.write_image(final, args.output_path)
-    return final
+
+def run_video(args: argparse.Namespace, trace=None):
+    """--video: every frame of the directory content_path through the schedule of run(), one VGG for the sequence, the
+    seeds reset for every frame (each frame draws the index stream a single-image run draws).  Frame t > 1 carries the
+    temporal term toward the previous result warped along the backward flow.  Writes
+    <output dir>/<frame stem>.jpg; returns the list of the frames' uint8 results.  `trace`: one list per frame."""
+    frames, lam = _video_inputs(args)
+    cw_path = _content_weight_input(args)
+    seed = int(getattr(args, "seed", 0))
+    dev = utils.device()
+    os.makedirs(args.output_path, exist_ok=True)
+    vgg = VGG(use_keras_weight=args.use_keras_weight, weights=getattr(args, "weights", None), seed=seed, device=dev)
+    previous, outs = None, []
+    for t, frame in enumerate(frames, start=1):
+        timer = utils.Timer()
+        timer.start()
+        rand.seed_everything(seed)
+        temporal = _temporal_for_frame(args, t, previous) if previous is not None else None
+        rec = None
+        if trace is not None:
+            rec = []
+            trace.append(rec)
+        previous = _stylise(args, vgg, frame, cw_path, dev, trace=rec, temporal=temporal, temporal_weight=lam)
+        final = strotss.postprocess(previous)
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()
+        timer.stop()
+        out = os.path.join(args.output_path, os.path.splitext(os.path.basename(frame))[0] + ".jpg")
+        utils.logger.info(f"Frame {t}/{len(frames)} done in {timer.elapsed_time:.2f}s.")
+        utils.write_image(final, out)
+        outs.append(final)
+    return outs
 
 
 # (flag, kwargs): the reference's flags first, then this build's additions
@@ -343,6 +478,13 @@ _FLAGS = (
     (("--content_weight_map",), dict(type=str, default=None, metavar='PATH',
                                      help="greyscale image: per-pixel content strength (white keeps the content, black lets "
                                           "it go), resized to every scale")),
+    (("--video",), dict(action='store_true', help="content_path is a directory of frames, -o an output directory")),
+    (("--flow_dir",), dict(type=str, default=None, metavar='DIR',
+                           help="with --video: backward_{t}_{t-1}.flo, forward_{t-1}_{t}.flo, reliable_{t}_{t-1}.pgm")),
+    (("--temporal_weight",), dict(type=float, default=None, metavar='LAMBDA',
+                                  help=f"with --video: weight of the temporal term (default {DEFAULT_TEMPORAL_WEIGHT:g})")),
+    (("--temporal_init",), dict(action='store_true', help="with --video: frames after the first start their first executed "
+                                                          "scale from the warped previous result")),
     (("--strips",), dict(action='store_true', help="under torchrun: shard ONE image over the GPUs by image strips")),
     (("--halo",), dict(action='store_true', help="with --strips: per-layer halo EXCHANGE with the neighbouring ranks (16-row "
                                                  "windows margins, one row per layer and direction) instead of a 128-row recompute margin")),
