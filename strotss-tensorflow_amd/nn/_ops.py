@@ -264,25 +264,31 @@ def winograd_packed(u: torch.Tensor):
 _x3 = {}           # id(u) -> (weakref(u), panels): bf16x3 "x3 panels" of frozen F(4x4,3x3) weights
 
 
-def _x3_min_tiles() -> int:
+def env_int(name: str, default: int) -> int:
+    """A switch the library reads too, parsed as its getenv + atoi / atol do: `default` when unset, otherwise the leading
+    integer (after white space, with an optional sign), 0 when there is none -- so "", "00" and "false" are 0 on both sides."""
     import os
-    return int(os.environ.get("STROTSS_X3_MIN_TILES", "1024"))
+    import re
+    v = os.environ.get(name)
+    if v is None:
+        return default
+    m = re.match(r"[ \t\n\v\f\r]*([+-]?[0-9]+)", v)
+    return int(m.group(1)) if m else 0
 
 
 def winograd_x3_wanted(p: int, rows: int, k: int, h: int, w: int) -> bool:
     """Whether the library would run an (h, w) layer with (p, rows, k) Winograd weights on the bf16x3 GEMM core: same policy
     as csrc/winograd.hip x3_enabled (at least STROTSS_X3_MIN_TILES 64 x 64 GEMM tiles) on the layers the fused kernel
     does not take.  Pure host arithmetic (tests/test_route_table.py pins it without a GPU)."""
-    import os
     tiles = -(-(-(-h // 4) * -(-w // 4)) // 64) * -(-rows // 64) * 36       # 64 x 64 tiles (csrc/winograd.hip x3_enabled)
-    if p != 36 or k % 32 or os.environ.get("STROTSS_X3", "1") == "0" \
-            or os.environ.get("STROTSS_X3_CONV", "1") == "0":           # default on, see csrc/winograd.hip x3_enabled
+    if p != 36 or k % 32 or env_int("STROTSS_X3", 1) == 0 or env_int("STROTSS_X3_CONV", 1) == 0:
         return False
+    min_tiles = env_int("STROTSS_X3_MIN_TILES", 1024)
     tiles128 = -(-(-(-h // 4) * -(-w // 4)) // 128) * -(-rows // 128) * 36
-    fused_takes_it = (rows <= int(os.environ.get("STROTSS_WINO_FUSED_MAX_COUT", "256"))
-                      and (rows < int(os.environ.get("STROTSS_X3_MIN_COUT", "256")) or tiles128 < _x3_min_tiles())
-                      and os.environ.get("STROTSS_WINO_FUSED", "1") != "0")
-    return not (tiles < _x3_min_tiles() or fused_takes_it)
+    fused_takes_it = (rows <= env_int("STROTSS_WINO_FUSED_MAX_COUT", 256)
+                      and (rows < env_int("STROTSS_X3_MIN_COUT", 256) or tiles128 < min_tiles)
+                      and env_int("STROTSS_WINO_FUSED", 1) != 0)
+    return not (tiles < min_tiles or fused_takes_it)
 
 
 def winograd_packed_wanted(p: int, rows: int, k: int) -> bool:
@@ -634,9 +640,9 @@ def remd_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, gsca
 
 
 def step_losses_available() -> bool:
-    import os
-    return all(os.environ.get(k, "1") != "0" for k in ("STROTSS_X3", "STROTSS_X3_COST", "STROTSS_X3_MOMENT")) \
-        and os.environ.get("STROTSS_GROUPED_LOSSES", "1") != "0"
+    """the grouped loss entries run (bf16x3 cost and moment products: csrc/losses.hip cost_x3, moment_x3), and
+    STROTSS_GROUPED_LOSSES does not switch them off"""
+    return all(env_int(k, 1) != 0 for k in ("STROTSS_X3", "STROTSS_X3_COST", "STROTSS_X3_MOMENT", "STROTSS_GROUPED_LOSSES"))
 
 
 def step_losses_fwd_bwd(pred, content, n, d, style, rs, style_panels, ns, style_mean, style_cov, g_content, g_moment, g_remd,
@@ -688,10 +694,12 @@ def step_losses_blend_fwd_bwd(pred, content, n, d, style_set, g_content, g_momen
 def step_losses_cw_fwd_bwd(pred, content, n, d, col_weight, style_set, g_content, g_moment, g_remd, g_palette, gpred,
                            loss_content, loss_moment, loss_remd, loss_palette):
     """step_losses_blend_fwd_bwd (any number of styles, one included) with the content term weighted per sampled column
-    (strotss_step_losses_cw_fwd_bwd; col_weight: float32 device vector of >= n values, finite and >= 0).  One style: the
-    single-style launches; several: the blended ones."""
-    require(col_weight, "column weights")
-    assert col_weight.numel() >= n
+    (strotss_step_losses_cw_fwd_bwd; col_weight: float32 device vector of >= n values, finite and >= 0, or None: the
+    unweighted term).  One style: the single-style launches (of weight 1: bit for bit step_losses_fwd_bwd); several: the
+    blended ones."""
+    if col_weight is not None:
+        require(col_weight, "column weights")
+        assert col_weight.numel() >= n
     l = _hip.lib()
     ld = int(pred.shape[1])
     nb = l.strotss_step_losses_blend_workspace_bytes(C.byref(style_set), n, ld)

@@ -58,7 +58,7 @@ def normalise_style_weights(weights: Sequence[float]) -> List[float]:
 class StyleBlend:
     """Style blending: a weighted set of StyleTargets, loss_s = sum_k w_k * style_loss(T_k, P).  The weights are normalised
     to sum to 1 here.  StepEngine runs a one-target blend exactly as its StyleTarget, a larger one in one call
-    (strotss_step_losses_blend_fwd_bwd)."""
+    (strotss_step_losses_cw_fwd_bwd)."""
     targets: List[StyleTarget]
     weights: List[float]
 
@@ -224,16 +224,16 @@ class StepEngine:
         # blended regions: the UNWEIGHTED moment / REMD / palette terms of every style (rows), losses() weighs them
         self._style_scalars = (torch.zeros((self.R, 3, _hip.MAX_STYLES), dtype=torch.float32, device=dev) if self._blended
                                else None)
-        self._style_sets = [_ops.make_style_set(t.targets, t.weights) if isinstance(t, StyleBlend) else None
-                            for t in self.style_targets]
-        # content-weight map: every region's weights of its samples (rows >= n zero), gathered with its features; the grouped
-        # loss call takes a style set, a one-style set of weight 1 for a plain StyleTarget (the single-style launches)
-        self._cw = self._cw_sets = self._mt_cw = None
+        # every region's styles and weights, a StyleTarget as a one-style set of weight 1 (its own single-style launches in
+        # the grouped call, its own floats in the separate entries); the grouped call's style set, None for a target
+        # without x3 panels (separate entries only)
+        self._styles = [(t.targets, t.weights) if isinstance(t, StyleBlend) else ([t], [1.0]) for t in self.style_targets]
+        self._style_sets = [_ops.make_style_set(ts, ws) if len(ts) > 1 or ts[0].panels is not None else None
+                            for ts, ws in self._styles]
+        # content-weight map: every region's weights of its samples (rows >= n zero), gathered with its features
+        self._cw = self._mt_cw = None
         if self._cw_map is not None:
             self._cw = [torch.zeros(rows, dtype=torch.float32, device=dev) for _ in range(self.R)]
-            self._cw_sets = [self._style_sets[r] if self._style_sets[r] is not None else
-                             (_ops.make_style_set([t], [1.0]) if t.panels is not None else None)
-                             for r, t in enumerate(self.style_targets)]
         # gradient of the variables: level 0 aliases the pixel gradient
         if strips is not None:
             # full-size pixel gradient, zero outside the window; the trunk writes its window rows in place
@@ -295,10 +295,11 @@ class StepEngine:
             raise _hip.StrotssHipError("strotss_debug_winograd_stages was left at a partial mask (a timing pass did not "
                                        "restore it): results since then are meaningless")
         self.steps_done = 0
+        self._drawn_steps = 0             # the steps whose index sets the draw kernel made (draws_done)
         self._draw = None                 # device-side index draw (enable_device_draw): counters, masks, output buffers
         self._graph = None
         self._graph_post = None           # sharded regions: the part of the step after the all-reduce
-        self._strip_graphs = None         # image strips: the three stages between the two all-reduces
+        self._strip_graphs = None         # image strips: the three segments around the two all-reduces
         self._graph_drawn = False         # the captured graph starts with the draw kernel (no per-step upload)
         self._graph_idx: List[torch.Tensor] = []
         self._graph_n: List[int] = []
@@ -341,51 +342,30 @@ class StepEngine:
     def _losses(self, r: int, n: int, zeroed: bool = False):
         """(alpha*loss_c + loss_s)/loss_denom/R and its gradient w.r.t. the sampled prediction.  zeroed: the gradient rows
         were cleared by _gather_both already."""
-        st = self.style_targets[r]
+        targets, weights = self._styles[r]
         pf, cf, gp, sc = self.pf[r], self.cf[r], self.gp[r], self.scalars[r]
         if n < pf.shape[0]:
             pf[n:].zero_(); cf[n:].zero_()
         if not zeroed:
             gp.zero_()
         base = 1.0 / (self.loss_denom * self.R)
-        cw = self._cw[r] if self._cw is not None else None
-        if isinstance(st, StyleBlend):
-            self._losses_blend(r, st, n, base, cw)
-            return
-        if st.panels is not None and _ops.step_losses_available():
-            if cw is not None:        # the same launches with the content term weighted per sample
-                _ops.step_losses_cw_fwd_bwd(pf, cf, n, self.d, cw, self._cw_sets[r], self.alpha * base, base, base,
-                                            self.inv_alpha * base, gp, sc[0:], sc[1:], sc[2:], sc[3:])
-                return
-            # one call: 13 launches instead of 21, the three forward GEMMs in one of them (bit for bit the four calls below)
-            _ops.step_losses_fwd_bwd(pf, cf, n, self.d, st.feats, st.inv_norm, st.panels, st.ns, st.mean, st.cov,
-                                     self.alpha * base, base, base, self.inv_alpha * base, gp, sc[0:], sc[1:], sc[2:], sc[3:])
+        cw = self._cw[r] if self._cw is not None else None     # the samples' content weights (content-weight map)
+        # moment / REMD / palette: the region's own scalars for one style, one unweighted value per style of a blend
+        outs = (sc[1:], sc[2:], sc[3:]) if len(targets) == 1 else tuple(self._style_scalars[r])
+        if self._style_sets[r] is not None and _ops.step_losses_available():
+            # one call: 13 launches instead of 21, the three forward GEMMs in one of them (bit for bit the separate entries
+            # below for one style); a blend in as many launches
+            _ops.step_losses_cw_fwd_bwd(pf, cf, n, self.d, cw, self._style_sets[r], self.alpha * base, base, base,
+                                        self.inv_alpha * base, gp, sc[0:], *outs)
             return
         _ops.selfsim_weighted_fwd_bwd(pf, cf, cw, n, self.d, self.alpha * base, gp, sc[0:])
-        _ops.moment_fwd_bwd(st.mean, st.cov, pf, n, self.d, base, gp, sc[1:])
-        # the relaxed EMD borrows the prediction rows' norms and x3 panels from the content loss's workspace (the moment
-        # term has its own) and the style rows' panels from the StyleTarget
-        _ops.remd_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, base, gp, sc[2:])
-        _ops.palette_remd_fwd_bwd(st.feats, st.ns, pf, n, self.inv_alpha * base, gp, sc[3:])
-
-    def _losses_blend(self, r: int, blend: StyleBlend, n: int, base: float, cw: Optional[torch.Tensor] = None) -> None:
-        """_losses for a blend of K > 1 styles: ONE call (the launches of the single-style call), or -- with the grouped loss
-        section switched off -- the content term once and each style's three separate entries with gscale w_k * base.
-        cw: the samples' content weights (content-weight map) or None."""
-        pf, cf, gp, sc, ss = self.pf[r], self.cf[r], self.gp[r], self.scalars[r], self._style_scalars[r]
-        if _ops.step_losses_available():
-            if cw is not None:
-                _ops.step_losses_cw_fwd_bwd(pf, cf, n, self.d, cw, self._style_sets[r], self.alpha * base, base, base,
-                                            self.inv_alpha * base, gp, sc[0:], ss[0], ss[1], ss[2])
-                return
-            _ops.step_losses_blend_fwd_bwd(pf, cf, n, self.d, self._style_sets[r], self.alpha * base, base, base,
-                                           self.inv_alpha * base, gp, sc[0:], ss[0], ss[1], ss[2])
-            return
-        _ops.selfsim_weighted_fwd_bwd(pf, cf, cw, n, self.d, self.alpha * base, gp, sc[0:])
-        for k, (st, w) in enumerate(zip(blend.targets, blend.weights)):
-            _ops.moment_fwd_bwd(st.mean, st.cov, pf, n, self.d, base * w, gp, ss[0, k:])
-            _ops.remd_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, base * w, gp, ss[1, k:])
-            _ops.palette_remd_fwd_bwd(st.feats, st.ns, pf, n, self.inv_alpha * base * w, gp, ss[2, k:])
+        for k, (st, w) in enumerate(zip(targets, weights)):
+            _ops.moment_fwd_bwd(st.mean, st.cov, pf, n, self.d, base * w, gp, outs[0][k:])
+            # the relaxed EMD borrows the prediction rows' norms and x3 panels from the content loss's workspace (the moment
+            # term has its own) and the style rows' panels from the StyleTarget
+            _ops.remd_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, base * w, gp,
+                                                outs[1][k:])
+            _ops.palette_remd_fwd_bwd(st.feats, st.ns, pf, n, self.inv_alpha * base * w, gp, outs[2][k:])
 
     def _scatter_maps(self, r: int):
         """descriptor + sample count of region r's tap adjoint: strips (recompute margin) = this rank's block of the samples
@@ -411,23 +391,52 @@ class StepEngine:
         """every map's taps in one launch per region (pre-scatter backward of the small scales, nn/model.py)"""
         self._scatter(-1, len(self.pred_maps))
 
+    # ------------------------------------------------------------------ the step as one stage list
+    def _stages(self, indices: Optional[Sequence[torch.Tensor]], apply: bool = True):
+        """The step as [(device segment, host collective after it or None)], a segment a list of calls: what the eager step
+        runs, capture_graph captures (one graph per segment) and a replay interleaves with the same collectives.
+            plain            [pixel gradient, temporal, fold adjoint]
+            region-sharded   [pixel gradient] | all-reduce _reduce_buf | [temporal, fold adjoint]
+            image strips     [_strip_stage_a] | all-reduce _pf_all | [_strip_stage_b] | all-reduce gimg_full | [fold adjoint]
+        apply: apply_gradients ends the last segment.  indices: the index sets of the pixel gradient, None = the draw kernel
+        at the head of the step (image strips: the sets _strip_inputs has put in place)."""
+        end = [self._fold_adjoint] + ([self.apply_gradients] if apply else [])
+        if self.strips is not None:
+            # the rows of the other ranks' samples arrive in _pf_all; the windows overlap by the margins: sum gimg_full
+            return [([self._strip_stage_a], lambda: parallel.allreduce_sum_(self._pf_all, self.group)),
+                    ([self._strip_stage_b], lambda: parallel.allreduce_sum_(self.gimg_full, self.group)),
+                    (end, None)]
+        head = [lambda: self._pixel_gradient(self._draw_indices() if indices is None else indices)]
+        tail = [self._temporal_term] + end
+        return [(head, self._reduce), (tail, None)] if self.sharded else [(head + tail, None)]
+
+    @staticmethod
+    def _run(stages) -> None:
+        for segment, collective in stages:
+            for call in segment:
+                call()
+            if collective is not None:
+                collective()
+
+    def _inputs(self, indices: Optional[Sequence[torch.Tensor]], strip_offsets, static: bool):
+        """The host side of a step, ahead of its stage list: the index sets copied into the captured graphs' static buffers
+        (static) and, with image strips, this rank's block of every set (_strip_inputs).  Returns the sets the stages read."""
+        if indices is None:                  # drawn on the device, inside the step
+            return None
+        assert len(indices) == self.R
+        if static:
+            for dst, src in zip(self._graph_idx, indices):
+                dst.copy_(src, non_blocking=True)
+            indices = self._graph_idx
+        if self.strips is not None:
+            self._strip_inputs(indices, strip_offsets)
+        return indices
+
     def forward_backward(self, indices: Sequence[torch.Tensor], strip_offsets: Optional[Sequence[int]] = None) -> None:
         """train_step (run_strotss.py:131-142 / 104-125): fills self.gvars and self.scalars.
         With image strips every region's `indices[r]` must be ordered by owning rank and `strip_offsets[r]` be its world + 1
         block offsets (parallel.sort_indices_by_strip); one region: the offsets list itself is accepted too."""
-        assert len(indices) == self.R
-        if self.strips is not None:
-            self._strip_inputs(indices, strip_offsets)
-            self._strip_stage_a()
-            parallel.allreduce_sum_(self._pf_all, self.group)     # rows of the other ranks' samples arrive here: ONE collective
-            self._strip_stage_b()
-            parallel.allreduce_sum_(self.gimg_full, self.group)   # windows overlap by the margins: sum
-            self._fold_adjoint()
-            return
-        self._pixel_gradient(indices)
-        self._reduce()
-        self._temporal_term()
-        self._fold_adjoint()
+        self._run(self._stages(self._inputs(indices, strip_offsets, static=False), apply=False))
 
     def _pixel_gradient(self, indices: Sequence[torch.Tensor]) -> None:
         """fold, trunk forward, this rank's regions' samples + losses, trunk data-gradient -> trunk.gimg, scalars"""
@@ -547,7 +556,7 @@ class StepEngine:
 
     def draws_done(self) -> int:
         """draws consumed so far by the device stream (to advance the host twin: rand.PhiloxStream.skip)"""
-        return 0 if self._draw is None else self.steps_done * self.R
+        return self._drawn_steps * self.R
 
     def _draw_indices(self) -> List[torch.Tensor]:
         dr = self._draw
@@ -561,61 +570,42 @@ class StepEngine:
     def step(self, indices: Optional[Sequence[torch.Tensor]] = None, strip_offsets: Optional[Sequence[int]] = None) -> None:
         """One optimisation step.  indices None: the index sets are drawn on the device at the head of the step
         (enable_device_draw first); otherwise they are the caller's (injected: tests, fixtures, strips)."""
-        if indices is None:
-            assert self._draw is not None, "step() without indices needs enable_device_draw()"
-            if self._graph is not None and self._graph_drawn:
-                self._graph.replay()
-                if self._graph_post is not None:
-                    self._reduce()
-                    self._graph_post.replay()
-            else:
-                self.forward_backward(self._draw_indices())
-                self.apply_gradients()
-            self.steps_done += 1
-            return
-        if self.strips is not None:
-            if self._strip_graphs is not None and all(int(i.shape[0]) == self._graph_n[r] for r, i in enumerate(indices)):
-                for dst, src in zip(self._graph_idx, indices):
-                    dst.copy_(src, non_blocking=True)
-                self._strip_inputs(self._graph_idx, strip_offsets)
-                ga, gb, gc = self._strip_graphs                       # graph | all-reduce | graph | all-reduce | graph
-                ga.replay()
-                parallel.allreduce_sum_(self._pf_all, self.group)
-                gb.replay()
-                parallel.allreduce_sum_(self.gimg_full, self.group)
-                gc.replay()
-            else:
-                self.forward_backward(indices, strip_offsets)
-                self.apply_gradients()
-            self.steps_done += 1
-            return
-        if self._graph is not None and not self._graph_drawn and all(int(i.shape[0]) == self._graph_n[r] for r, i in enumerate(indices)):
-            for dst, src in zip(self._graph_idx, indices):
-                dst.copy_(src, non_blocking=True)
-            self._graph.replay()
-            if self._graph_post is not None:       # sharded regions: graph | all-reduce | graph
-                self._reduce()
-                self._graph_post.replay()
-        else:
-            self.forward_backward(indices)
-            self.apply_gradients()
+        drawn = indices is None
+        assert not drawn or self._draw is not None, "step() without indices needs enable_device_draw()"
+        graphs = self._captured()
+        if graphs is not None and drawn == self._graph_drawn and \
+                (drawn or all(int(i.shape[0]) == n for i, n in zip(indices, self._graph_n))):
+            self._inputs(indices, strip_offsets, static=True)
+            for g, (_, collective) in zip(graphs, self._stages(None)):
+                g.replay()
+                if collective is not None:
+                    collective()
+        else:                                # eager (also a step whose index counts differ from the captured ones)
+            self._run(self._stages(self._inputs(indices, strip_offsets, static=False)))
         self.steps_done += 1
+        self._drawn_steps += drawn
+
+    def _captured(self):
+        """the captured graphs, one per segment of _stages, or None: the step runs eagerly"""
+        if self.strips is not None:
+            return self._strip_graphs
+        if self._graph is None:
+            return None
+        return (self._graph,) if self._graph_post is None else (self._graph, self._graph_post)
 
     def capture_graph(self, example_indices: Optional[Sequence[torch.Tensor]] = None, example_offsets=None) -> None:
-        """Capture forward_backward + apply_gradients into ONE hipGraph (the ~100 launches of a step
-        replay as one submission; the 64-256 px scales are otherwise bound by host launch rate).  Index
-        sets are copied into static buffers before each replay; a step whose index counts differ from
-        the captured ones runs eagerly.  The captured step does not advance the optimisation: the
-        variables / RMSprop slots are snapshotted around the warm-up and capture passes.
-        Sharded regions (world > 1): the all-reduce stays outside -- TWO graphs, [fold .. pixel gradient] and
-        [fold adjoint + RMSprop], with the collective launched between their replays.  Image strips run eagerly
-        (recompute margin; example_offsets = the block offsets of example_indices): THREE graphs, [fold .. gathers],
-        [losses .. pixel gradient of the window], [fold adjoint + RMSprop], the two all-reduces between their replays; the
-        block of samples a rank owns changes every step and is read from device memory (strotss_maps_t.sample_range).
-        Halo-exchange strips run eagerly (their trunk exchanges rows from Python after every layer)."""
-        if self.strips is not None:
-            if self._halo is None and example_offsets is not None:
-                self._capture_strip_graphs(example_indices, example_offsets)
+        """Capture the step (_stages: forward_backward + apply_gradients) into hipGraphs, one per device segment (the ~100
+        launches of a step replay as one submission; the 64-256 px scales are otherwise bound by host launch rate).  Index
+        sets are copied into static buffers before each replay; a step whose index counts differ from the captured ones runs
+        eagerly.  The captured step does not advance the optimisation: the variables / RMSprop slots (and the draw counters)
+        are snapshotted around the warm-up and capture passes; the warm-up is one whole eager step, collectives included.
+        Sharded regions (world > 1): TWO graphs, [fold .. pixel gradient] and [temporal + fold adjoint + RMSprop], the
+        all-reduce launched between their replays.  Image strips (recompute margin; example_offsets = the block offsets of
+        example_indices): THREE graphs, [fold .. gathers], [losses .. pixel gradient of the window], [fold adjoint + RMSprop],
+        the two all-reduces between their replays; the block of samples a rank owns changes every step and is read from
+        device memory (strotss_maps_t.sample_range).  Halo-exchange strips run eagerly (their trunk exchanges rows from Python
+        after every layer)."""
+        if self.strips is not None and (self._halo is not None or example_offsets is None):
             return
         drawn = example_indices is None        # the draw kernel is the first node of the graph: nothing to upload per step
         state = self.variables + self.rms
@@ -628,61 +618,27 @@ class StepEngine:
             self._graph_idx = [i.clone() for i in example_indices]
             self._graph_n = [int(i.shape[0]) for i in example_indices]
         snap = [t.clone() for t in state]
-        head = (lambda: self._pixel_gradient(self._draw_indices())) if drawn else (lambda: self._pixel_gradient(self._graph_idx))
+        stages = self._stages(None if drawn else self._inputs(self._graph_idx, example_offsets, static=False))
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):              # warm-up on the side stream (workspace allocation)
-            head()
-            self._temporal_term()
-            self._fold_adjoint()
-            self.apply_gradients()
+        with torch.cuda.stream(side):              # warm-up on the side stream: workspaces, collectives, library state
+            self._run(stages)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
-        g, post = torch.cuda.CUDAGraph(), None
-        if self.sharded:
-            with _Capture(g, side):
-                head()
-            post = torch.cuda.CUDAGraph()
-            with _Capture(post, side):
-                self._temporal_term()
-                self._fold_adjoint()
-                self.apply_gradients()
-        else:
-            with _Capture(g, side):
-                head()
-                self._temporal_term()
-                self._fold_adjoint()
-                self.apply_gradients()
+        graphs = []
+        for segment, _ in stages:
+            graphs.append(torch.cuda.CUDAGraph())
+            with _Capture(graphs[-1], side):
+                for call in segment:
+                    call()
         for t, s0 in zip(state, snap):
             t.copy_(s0)
-        self._graph, self._graph_post, self._graph_drawn = g, post, drawn
+        if self.strips is not None:
+            self._strip_graphs = tuple(graphs)
+        else:
+            self._graph, self._graph_post, self._graph_drawn = graphs[0], (graphs[1] if len(graphs) > 1 else None), drawn
 
     # ------------------------------------------------------------------ read-outs (host sync)
-    def _capture_strip_graphs(self, example_indices, example_offsets) -> None:
-        snap = [t.clone() for t in self.variables + self.rms]
-        self._graph_idx = [i.clone() for i in example_indices]
-        self._graph_n = [int(i.shape[0]) for i in example_indices]
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):              # one whole eager step first: workspaces, collectives, library state
-            self.forward_backward(self._graph_idx, example_offsets)
-            self.apply_gradients()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self._strip_inputs(self._graph_idx, example_offsets)
-        torch.cuda.synchronize()
-        graphs = [torch.cuda.CUDAGraph() for _ in range(3)]
-        with _Capture(graphs[0], side):
-            self._strip_stage_a()
-        with _Capture(graphs[1], side):
-            self._strip_stage_b()
-        with _Capture(graphs[2], side):
-            self._fold_adjoint()
-            self.apply_gradients()
-        for t, s0 in zip(self.variables + self.rms, snap):
-            t.copy_(s0)
-        self._strip_graphs = tuple(graphs)
-
     def losses(self) -> dict:
         s = self.scalars.detach().cpu().numpy().astype(np.float64)
         per_style = None

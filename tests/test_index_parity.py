@@ -157,7 +157,8 @@ def test_device_index_draw_equals_the_oracle_draw_element_for_element(h, w):
 def test_engine_device_draw_steps_equal_injected_host_draws():
     """StepEngine.step() with the draw kernel at its head (eager and replayed from a graph whose first node it is) ==
     StepEngine.step(indices) with the host twin's draws injected: the same index sets, hence (deterministic tap adjoint) the
-    same bits after three steps; the host twin advanced by draws_done() continues the same stream."""
+    same bits after three steps; the host twin advanced by draws_done() continues the same stream, also after injected steps
+    (which draw nothing on the device)."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import _region_worker as W
     dev = torch.device("cuda", 0)
@@ -188,3 +189,17 @@ def test_engine_device_draw_steps_equal_injected_host_draws():
     for mode in ("device_eager", "device_graph"):
         assert res[mode][1] == res["host"][1], (mode, res[mode][1], res["host"][1])
         assert all(torch.equal(a, b) for a, b in zip(res[mode][0], res["host"][0])), mode
+    # injected steps draw nothing on the device: after one of them and two drawn steps, the host twin advanced by
+    # draws_done() continues the device's stream
+    eng, _ = W.problem(dev, None)
+    assert eng.enable_device_draw(11, 100, masks)
+    other = RAND.PhiloxStream(5, 0)
+    eng.step([torch.from_numpy(SU.make_indices_np(h, w, True, eng.sample_size, other, m)).to(dev) for m in masks])
+    eng.step()
+    eng.step()
+    assert eng.steps_done == 3 and eng.draws_done() == 2 * R
+    twin = RAND.PhiloxStream(11, 100)
+    twin.skip(eng.draws_done())
+    want = [SU.make_indices_np(h, w, True, eng.sample_size, twin, m) for m in masks]
+    got = [i.cpu().numpy() for i in eng._draw_indices()]
+    assert all(np.array_equal(a, b) for a, b in zip(got, want))

@@ -9,6 +9,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -44,3 +46,33 @@ def test_route_switches_move_the_table():
     assert all(r[5].startswith("direct") and r[6].startswith("direct") for rows in nowino.values() for r in rows)
     nofused = _table({"STROTSS_WINO_FUSED": "0"})
     assert not any("fused" in r[5] or "fused" in r[6] for rows in nofused.values() for r in rows)
+
+
+LIBRARY_SWITCHES = ("STROTSS_X3", "STROTSS_X3_COST", "STROTSS_X3_MOMENT", "STROTSS_X3_CONV", "STROTSS_X3_MIN_TILES",
+                    "STROTSS_X3_MIN_COUT", "STROTSS_WINO_FUSED", "STROTSS_WINO_FUSED_MAX_COUT")
+
+
+@pytest.mark.parametrize("value", ["", "0", "00", "1", " 1", "2", "false", "1x"])
+def test_host_reads_the_library_switches_as_atoi_does(value, monkeypatch):
+    """The switches the library reads with getenv + atoi / atol mean the same on the host: "", "00" and "false" are 0 on
+    both sides (a host that took them for "on" would make the grouped loss call, which the library refuses with EINVAL)."""
+    import ctypes
+    from nn import _ops
+    libc = ctypes.CDLL(None)
+    libc.atoi.argtypes, libc.atoi.restype = [ctypes.c_char_p], ctypes.c_int
+    c = libc.atoi(value.encode())
+    for name in LIBRARY_SWITCHES + ("STROTSS_GROUPED_LOSSES",):
+        monkeypatch.delenv(name, raising=False)
+    assert _ops.step_losses_available() and _ops.winograd_x3_wanted(36, 512, 512, 64, 64)   # block5 at 1024 px: bf16x3
+    for name in ("STROTSS_X3", "STROTSS_X3_COST", "STROTSS_X3_MOMENT"):
+        monkeypatch.setenv(name, value)
+        assert _ops.step_losses_available() == (c != 0), name
+        monkeypatch.delenv(name)
+    for name in ("STROTSS_X3", "STROTSS_X3_CONV"):
+        monkeypatch.setenv(name, value)
+        assert _ops.winograd_x3_wanted(36, 512, 512, 64, 64) == (c != 0), name
+        monkeypatch.delenv(name)
+    for name in LIBRARY_SWITCHES:
+        assert _ops.env_int(name, 7) == 7
+        monkeypatch.setenv(name, value)
+        assert _ops.env_int(name, 7) == c, name
