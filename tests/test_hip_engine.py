@@ -10,6 +10,8 @@ import torch
 
 from oracle import strotss_oracle as O
 
+from _masked_oracle import mask_report, vgg_with_masks_of
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -58,6 +60,30 @@ def _setup(h, w, n_samples, masks=None, seed=0):
     return dict(vgg=vgg, cf=cf, s_samples=s_samples, init=init, eng=eng, idx_sets=idx_sets, alpha=alpha, denom=denom)
 
 
+class _EngineMaskedVGG:
+    """The oracle's VGG with the ReLU masks and pool selections of the engine's last trunk forward (`vgg_with_masks_of`,
+    which checks every disagreement against MASK_FLIP_TOL and records it in `report`)."""
+
+    def __init__(self, vgg, eng):
+        self.vgg, self.acts, self.report = vgg, [a.cpu() for a in eng.trunk.acts], []
+
+    def __call__(self, x):
+        self.report = []
+        return vgg_with_masks_of(self.vgg, x, self.acts, self.report)
+
+
+def _oracle_vgg(S, eng):
+    """The float64 network a step is compared with.  Where a layer runs in Winograd form, its float32 rounding (~1e-5 of the
+    output range) flips the ReLU mask of every pre-activation that close to zero -- measured 9 ... 50 per trunk at 341 x 512
+    and 683 x 1024, each within 1e-6 of its layer's max |pre| -- and each flip moves a whole gradient entry: measured 4.6e-3 relative L2 on the pixel gradient of the linear probe at
+    341 x 512 with the float64 network's own masks, 5.9e-6 with the engine's (test_engine_backward_chain_at_production_
+    routing); the whole steps at 256 px and up then reach 5.2e-3, above GRAD_TOL.  So on any trunk with a Winograd layer
+    the masks and pool selections of ALL layers (the first layer's and split-K direct layers' too: they inherit the
+    Winograd layers' rounding) are taken from the engine's forward, and every place where they disagree with float64 is
+    checked to lie within MASK_FLIP_TOL of zero (`vgg_with_masks_of`).  All-direct trunks keep the oracle's own masks."""
+    return S["vgg"] if _trunk_routes(eng) <= {"direct", "direct_splitk"} else _EngineMaskedVGG(S["vgg"], eng)
+
+
 def _check_step(S, masked):
     eng = S["eng"]
     variables = [v.clone().requires_grad_(True) for v in O.make_laplacian_pyramid(S["init"])]
@@ -66,12 +92,15 @@ def _check_step(S, masked):
         assert (a.cpu().double() - b.detach()).abs().max() < 2e-6
     rms = [torch.zeros_like(v) for v in variables]
     idx0 = [s[0] for s in S["idx_sets"]]
-    if masked:
-        ref = O.train_step_masked(variables, S["vgg"], S["cf"], S["s_samples"], idx0, S["alpha"], S["denom"])
-    else:
-        ref = O.train_step(variables, S["vgg"], S["cf"], S["s_samples"][0], idx0[0], S["alpha"], S["denom"])
     eng.forward_backward([torch.from_numpy(i).to(DEV) for i in idx0])
     torch.cuda.synchronize()
+    vgg = _oracle_vgg(S, eng)
+    if masked:
+        ref = O.train_step_masked(variables, vgg, S["cf"], S["s_samples"], idx0, S["alpha"], S["denom"])
+    else:
+        ref = O.train_step(variables, vgg, S["cf"], S["s_samples"][0], idx0[0], S["alpha"], S["denom"])
+    if isinstance(vgg, _EngineMaskedVGG):
+        print("step %dx%d: %s" % (eng.h, eng.w, mask_report(vgg.report)))
     got = eng.losses()
     for k in ("loss", "loss_c", "loss_s"):
         assert abs(got[k] - float(ref[k])) < 5e-5 * max(1.0, abs(float(ref[k]))), (k, got[k], float(ref[k]))
@@ -79,6 +108,7 @@ def _check_step(S, masked):
     assert (eng.fold[0].cpu().double() - ref["img"]).abs().max() < 5e-6
     for k, (g, gr) in enumerate(zip(eng.gvars, ref["grads"])):
         rel = float((g.cpu().double() - gr).norm() / gr.norm())
+        print("step %dx%d gradient level %d: rel L2 %.2e" % (eng.h, eng.w, k, rel))
         assert rel < GRAD_TOL, (k, rel)
     # one RMSprop update applied to the same gradients must agree tightly
     gsnap = [g.clone() for g in eng.gvars]
@@ -108,6 +138,57 @@ def test_engine_step_matches_oracle_masked():
     _check_step(_setup(h, w, 256, masks=[(cm1, sm1), (cm2, sm2)], seed=5), masked=True)
 
 
+def _trunk_routes(eng):
+    """The convolution routes (forward and data-gradient) the engine's trunk takes on its generic layers."""
+    from nn import model as M
+    out = set()
+    for L, a in zip(eng.trunk.p.layers, eng.trunk.acts):
+        if L["cin"] != 3:
+            h, w = int(a.shape[1]), int(a.shape[2])
+            out.update(M.conv_route(h, w, L["cin"], L["cout"], dgrad=d) for d in (False, True))
+    return out
+
+
+# Default routing at the sizes the product runs (content_im.jpg's scales, DESIGN.md 4): the same tolerances as the
+# small steps above, whose layers all take the split-K direct kernel.
+PRODUCTION_STEPS = {
+    (170, 256): {"F4_fused_f32", "F4_gemm_f32", "F2_gemm_f32", "direct_splitk"},
+    (341, 512): {"F4_fused_f32", "F4_gemm_f32", "F2_gemm_f32"},
+    (683, 1024): {"F4_fused_f32", "F4_gemm_f32", "F4_x3_gemm_128", "F4_x3_gemm_64"},
+}
+
+
+@pytest.mark.parametrize("hw", sorted(PRODUCTION_STEPS), ids=lambda hw: "%dx%d" % hw)
+def test_engine_step_at_production_routing_vs_oracle(hw):
+    h, w = hw
+    S = _setup(h, w, 1024, seed=21)
+    assert _trunk_routes(S["eng"]) == PRODUCTION_STEPS[hw], sorted(_trunk_routes(S["eng"]))
+    _check_step(S, masked=False)
+
+
+def test_engine_masked_step_at_production_routing_vs_oracle():
+    h, w = 256, 256
+    cm1 = np.zeros((h, w, 1), np.float32); cm1[:, :110] = 1
+    sm1 = np.zeros((h + 8, w - 4, 1), np.float32); sm1[:150] = 1
+    S = _setup(h, w, 1024, masks=[(cm1, sm1), (1 - cm1, 1 - sm1)], seed=22)
+    assert _trunk_routes(S["eng"]) == {"F4_fused_f32", "F4_gemm_f32", "direct_splitk"}, sorted(_trunk_routes(S["eng"]))
+    _check_step(S, masked=True)
+
+
+def test_engine_backward_chain_at_production_routing():
+    """test_engine_backward_chain_without_sign_flips at 341 x 512 (fused, F(4x4,3x3) f32 GEMMs and F(2x2,3x3) layers).
+    At this size the float64 network's own ReLU masks are not enough: among 10^7 activations per layer a few lie within
+    float32 rounding of zero (measured 16 flipped masks over the trunk), and each flipped mask moves a whole gradient
+    entry (measured 1.6e-3 ... 4.6e-3 relative L2).  So the float64 side takes the engine's masks and pool selections,
+    every disagreement checked to lie within rounding (`_masked_oracle.py`), and what is left is the linear chain's
+    rounding alone."""
+    eng, rels = _chain_probe(341, 512, 1024, 23, engine_masks=True)
+    assert _trunk_routes(eng) == PRODUCTION_STEPS[(341, 512)], sorted(_trunk_routes(eng))
+    print("341 x 512 backward chain, engine masks, rel L2 per level:", ["%.2e" % r for r in rels])
+    for k, rel in enumerate(rels):
+        assert rel < 3e-4, (k, rel)
+
+
 def test_engine_multi_step_resynchronised():
     """Three consecutive steps (non-zero RMSprop slots, moved variables).  Before each step the
     oracle is re-synchronised to the engine's state so that fp32-vs-fp64 sign flips of near-zero
@@ -119,8 +200,8 @@ def test_engine_multi_step_resynchronised():
         variables = [v.cpu().double().requires_grad_(True) for v in eng.variables]
         rms = [r.cpu().double() for r in eng.rms]
         idx = S["idx_sets"][0][it]
-        ref = O.train_step(variables, S["vgg"], S["cf"], S["s_samples"][0], idx, S["alpha"], S["denom"])
         eng.forward_backward([torch.from_numpy(idx).to(DEV)])
+        ref = O.train_step(variables, _oracle_vgg(S, eng), S["cf"], S["s_samples"][0], idx, S["alpha"], S["denom"])
         got = eng.losses()
         for k in ("loss", "loss_c", "loss_s"):
             assert abs(got[k] - float(ref[k])) < 5e-5 * max(1.0, abs(float(ref[k]))), (it, k, got[k], float(ref[k]))
@@ -183,34 +264,49 @@ def test_graph_replay_equals_eager():
         assert (a - b).abs().mean() < 5e-3
 
 
+def _chain_probe(h, w, n, seed, engine_masks=False):
+    """The engine's backward path driven by a fixed linear functional sum(W * p_feat) instead of the losses, against float64
+    autograd of the same functional: the six variable gradients' relative L2 errors.  engine_masks: the float64 side takes
+    its ReLU masks and pool selections from the engine's activations (`vgg_with_masks_of`)."""
+    S = _setup(h, w, n, seed=seed)
+    eng = S["eng"]
+    idx = S["idx_sets"][0][0]
+    ti = torch.from_numpy(idx).to(DEV)
+    eng.trunk.forward(eng.fold_forward())
+    torch.cuda.synchronize()
+    variables = [v.clone().requires_grad_(True) for v in O.make_laplacian_pyramid(S["init"])]
+    img = O.fold_laplacian_pyramid(variables)
+    if engine_masks:
+        report = []
+        maps = vgg_with_masks_of(S["vgg"], img, [a.cpu() for a in eng.trunk.acts], report)
+        print("%d x %d backward chain: %s" % (h, w, mask_report(report)))
+    else:
+        maps = S["vgg"](img)
+    pf = O.sample_features([img] + maps, idx, True)
+    W = torch.randn(pf.shape, generator=torch.Generator().manual_seed(3), dtype=torch.float64)
+    ref = torch.autograd.grad((pf * W).sum(), variables)
+    eng._idx[0] = ti
+    eng.gp[0].zero_()
+    eng.gp[0][:len(idx), :2179] = W.float().to(DEV)
+    if eng.deterministic:
+        from nn import _ops
+        _ops.hypercol_scatter_plan(eng._mt_pred, ti, eng._plans[0])
+    eng.trunk.backward(eng._scatter)
+    eng._fold_adjoint()
+    torch.cuda.synchronize()
+    return eng, [float((g.cpu().double() - gr).norm() / gr.norm()) for g, gr in zip(eng.gvars, ref)]
+
+
 def test_engine_backward_chain_without_sign_flips():
     """How much of the 2e-2 gradient tolerance of `_check_step` is REAL error?  The losses are L1 / hard-min terms whose
     gradients flip sign on fp32 rounding noise; this probe replaces them by a fixed linear functional sum(W * p_feat)
     (dL/dp_feat = W, no flips) and sends it down the engine's own backward path -- tap scatter, 13 data-gradient layers
-    incl. the Winograd forms, pooling, first-layer gradient, fold adjoint -- against float64 autograd of the same
-    functional.  What is left is the linear chain's rounding (and ReLU masks of activations within rounding of zero)."""
+    (at these sizes all on the split-K direct kernel; test_engine_backward_chain_at_production_routing runs the Winograd
+    forms), pooling, first-layer gradient, fold adjoint -- against float64 autograd of the same functional.  What is left
+    is the linear chain's rounding (and ReLU masks of activations within rounding of zero)."""
     for (h, w, n) in ((64, 64, 384), (42, 64, 300)):
-        S = _setup(h, w, n, seed=13)
-        eng = S["eng"]
-        idx = S["idx_sets"][0][0]
-        variables = [v.clone().requires_grad_(True) for v in O.make_laplacian_pyramid(S["init"])]
-        img = O.fold_laplacian_pyramid(variables)
-        pf = O.sample_features([img] + S["vgg"](img), idx, True)
-        W = torch.randn(pf.shape, generator=torch.Generator().manual_seed(3), dtype=torch.float64)
-        ref = torch.autograd.grad((pf * W).sum(), variables)
-        ti = torch.from_numpy(idx).to(DEV)
-        eng.trunk.forward(eng.fold_forward())
-        eng._idx[0] = ti
-        eng.gp[0].zero_()
-        eng.gp[0][:len(idx), :2179] = W.float().to(DEV)
-        if eng.deterministic:
-            from nn import _ops
-            _ops.hypercol_scatter_plan(eng._mt_pred, ti, eng._plans[0])
-        eng.trunk.backward(eng._scatter)
-        eng._fold_adjoint()
-        torch.cuda.synchronize()
-        for k, (g, gr) in enumerate(zip(eng.gvars, ref)):
-            rel = float((g.cpu().double() - gr).norm() / gr.norm())
+        _, rels = _chain_probe(h, w, n, 13)
+        for k, rel in enumerate(rels):
             assert rel < 3e-4, (h, w, k, rel)            # measured: see DESIGN.md 6
 
 
@@ -647,24 +743,43 @@ def test_cli_config1_reference_images(tmp_path):
         assert im.format == "JPEG" and im.size == (256, 170)
 
 
+def _routes_in_child(env, sizes):
+    """The union of the trunk routes at the given image sizes under `env` (the library reads its switches once per process)."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import json, sys; sys.path.insert(0, %r); import _route_cases as RC; "
+            "print(json.dumps(sorted(set().union(*(RC.routes_at(h, w) for h, w in %r)))))" % (os.path.join(root, "tests"), sizes))
+    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    return set(json.loads(out.stdout.strip().splitlines()[-1]))
+
+
 def test_step_parity_with_the_fused_winograd_kernel_forced():
-    """The size policy keeps the fused F(4x4,3x3) kernel away from the small images the float64 oracle can check; force it
-    (STROTSS_WINO_FUSED=2, read once per process) and repeat the step-level oracle parity tests in a child process."""
+    """The size policy keeps the Winograd forms away from the small images of the step-level oracle parity tests (64 x 64,
+    42 x 64: every layer takes the split-K direct kernel).  Repeat those tests in child processes (the switches are read
+    once per process) with STROTSS_DIRECT_MAX_TILES=0, which sends the layers to Winograd: once with the fused kernel
+    forced (STROTSS_WINO_FUSED=2: F(2x2,3x3) + fused), once without it and with the bf16x3 GEMMs on from 100 tiles
+    (F(2x2,3x3) + f32 GEMMs + bf16x3 GEMMs on 64 x 64 tiles).  Each child's routes are asserted first."""
     import subprocess, sys
     if os.environ.get("STROTSS_WINO_FUSED") == "2":
         pytest.skip("already inside the forced run")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_hip_engine.py"), "-q", "-x", "-m", "gpu",
-                          "-k", "matches_oracle or resynchronised"], env=dict(os.environ, STROTSS_WINO_FUSED="2"), cwd=root,
-                         capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
-    assert " passed" in out.stdout
+    for env, want in (({"STROTSS_WINO_FUSED": "2", "STROTSS_DIRECT_MAX_TILES": "0"}, {"F4_fused_f32", "F2_gemm_f32"}),
+                      ({"STROTSS_DIRECT_MAX_TILES": "0", "STROTSS_WINO_FUSED": "0", "STROTSS_X3_MIN_TILES": "100"},
+                       {"F4_x3_gemm_64", "F4_gemm_f32", "F2_gemm_f32"})):
+        routes = _routes_in_child(env, [(64, 64), (42, 64)])
+        assert want <= routes, (env, sorted(routes))
+        out = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_hip_engine.py"), "-q", "-x", "-m",
+                              "gpu", "-k", "matches_oracle or resynchronised"], env=dict(os.environ, **env), cwd=root,
+                             capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, str(env) + out.stdout[-3000:] + out.stderr[-2000:]
+        assert " passed" in out.stdout
 
 
 def test_full_scale_winograd_vs_direct(tmp_path):
-    """SURVEY.md 7's end-to-end criterion for the Winograd forms: a WHOLE scale of the schedule (128 px, 200 steps, the CLI's
-    own loop and index stream) in child processes -- default convolution routing (F(4x4,3x3) / F(2x2,3x3) / split-K direct,
-    whatever the size policy picks) against STROTSS_WINOGRAD=0 (the direct f32-MFMA form everywhere, 16x less rounding
+    """SURVEY.md 7's end-to-end criterion for the Winograd forms: a WHOLE scale of the schedule (256 px, 200 steps, the CLI's
+    own loop and index stream) in child processes -- default convolution routing (at 256 px: the fused F(4x4,3x3) kernel,
+    F(4x4,3x3) on f32 GEMMs and split-K direct; at 128 px it would be direct everywhere) against STROTSS_WINOGRAD=0 (the direct f32-MFMA form everywhere, 16x less rounding
     error).  The optimisation is chaotic at rounding level (RMSprop's first updates are sign-like, the losses are L1 /
     hard-min terms), so the yardstick is a CONTROL: the direct form once more with the learning rate changed by 1e-7
     relative.  The Winograd run must stay as close to the direct run as the control does (loss curves: median deviation
@@ -673,15 +788,18 @@ def test_full_scale_winograd_vs_direct(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     from nn import utils
     for name, seed in (("c.jpg", 11), ("s.jpg", 12)):
-        utils.write_image(_img(128, 128, seed) * 255.0, str(tmp_path / name))
+        utils.write_image(_img(256, 256, seed) * 255.0, str(tmp_path / name))
     outs = {}
     for tag, env, lr in (("wino", {}, "2e-3"), ("direct", {"STROTSS_WINOGRAD": "0"}, "2e-3"),
                          ("control", {"STROTSS_WINOGRAD": "0"}, "2.0000002e-3")):
         r = subprocess.run([sys.executable, os.path.join(root, "tests", "_scale_worker.py"), str(tmp_path / tag),
-                            str(tmp_path / "c.jpg"), str(tmp_path / "s.jpg"), lr], env=dict(os.environ, **env),
+                            str(tmp_path / "c.jpg"), str(tmp_path / "s.jpg"), lr, "256"], env=dict(os.environ, **env),
                            capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-3000:]
         outs[tag] = np.load(str(tmp_path / tag) + ".npz")
+    routes = {k: set(outs[k]["routes"].tolist()) for k in outs}
+    assert routes["wino"] == {"F4_fused_f32", "F4_gemm_f32", "direct_splitk"}, routes     # the forms under test do run
+    assert routes["direct"] == routes["control"] and routes["direct"] <= {"direct", "direct_splitk"}, routes
     lw, ld, lc = (outs[k]["losses"][:, 0] for k in ("wino", "direct", "control"))
     assert lw.shape == ld.shape == lc.shape == (200,)
     dev_w, dev_c = np.abs(lw - ld) / np.abs(ld), np.abs(lc - ld) / np.abs(ld)
@@ -690,7 +808,7 @@ def test_full_scale_winograd_vs_direct(tmp_path):
     def psnr(a, b):
         return 10 * np.log10(1.0 / np.mean((np.clip(a.astype(np.float64), 0, 1) - np.clip(b.astype(np.float64), 0, 1)) ** 2))
     p_w, p_c = psnr(outs["wino"]["final"], outs["direct"]["final"]), psnr(outs["control"]["final"], outs["direct"]["final"])
-    print(f"128 px, 200 steps, against the direct form: Winograd routing median loss deviation {np.median(dev_w):.2e} (worst "
+    print(f"256 px, 200 steps, against the direct form: Winograd routing median loss deviation {np.median(dev_w):.2e} (worst "
           f"{dev_w.max():.2e}), PSNR {p_w:.1f} dB; control (lr x (1 + 1e-7)) {np.median(dev_c):.2e} (worst {dev_c.max():.2e}), "
           f"PSNR {p_c:.1f} dB; loss {ld[0]:.3f} -> {ld[-20:].mean():.3f} / {lw[-20:].mean():.3f}")
     assert np.median(dev_w) <= max(3 * np.median(dev_c), 1e-2) and np.median(dev_w) < 5e-2, (np.median(dev_w), np.median(dev_c))
