@@ -430,11 +430,14 @@ struct X3Mirror {       // writes the transpose of the workgroup's tile through 
 // C[z] (M x N, ldc) = A[z] B[z]^T, both operands as x3 panels of K columns (K % 32 == 0).
 // 128 x 128 tiles (one workgroup per CU) when there are at least `min_tiles128` of them, else 64 x 64 (two per CU): few
 // big tiles leave CUs idle (36 x (256 x 512 x 512): 288 big tiles on 256 CUs = 2 rounds of 1.1, 1152 small ones fill it).
+static bool x3_k16_enabled() {
+  static const bool k16 = [] { const char* v = getenv("STROTSS_X3_K16"); return !v || atoi(v) != 0; }();
+  return k16;
+}
 int st_gemm_x3_batched(const void* A, const void* B, float* C, int ldc, long long strideC, int M, int N, int K,
                        int batch, hipStream_t s, long min_tiles128) {
   EpiScaleStoreX3 e{{C, ldc, M, N, 1.0f, strideC}, {}};
-  static const bool k16 = [] { const char* v = getenv("STROTSS_X3_K16"); return !v || atoi(v) != 0; }();
-  if ((long)cdiv(N, 128) * cdiv(M, 128) * batch >= min_tiles128 && k16) {
+  if ((long)cdiv(N, 128) * cdiv(M, 128) * batch >= min_tiles128 && x3_k16_enabled()) {
     // two co-resident workgroups per CU (K-step 16, 72 KiB ring): one computes while the other fills, stores or waits
     using Cfg = X3CfgK16<3>;
     dim3 grid((unsigned)cdiv(N, 128) * cdiv(M, 128) * batch);
@@ -451,6 +454,21 @@ int st_gemm_x3_batched(const void* A, const void* B, float* C, int ldc, long lon
     hipLaunchKernelGGL((gemm_x3_kernel<Cfg, EpiScaleStoreX3, X3NoMirror>), grid, dim3(Cfg::NT), 0, s, (const __bf16*)A, M,
                        (long long)3 * M * K, (const __bf16*)B, N, (long long)3 * N * K, K, e, X3NoMirror{});
   }
+  ST_LAUNCH_RET();
+}
+
+bool st_gemm_x3_f32a_ok(int M, int N, int batch, long min_tiles128) {
+  return (long)cdiv(N, 128) * cdiv(M, 128) * batch >= min_tiles128 && x3_k16_enabled();
+}
+// A (batch stride M * K f32) split in registers, B as x3 panels: the K16 ring with a 20 KiB stage (mfma_x3.h: X3CfgK16)
+int st_gemm_x3_batched_f32a(const float* A, const void* B, float* C, int ldc, long long strideC, int M, int N, int K,
+                            int batch, hipStream_t s, long min_tiles128) {
+  if (!st_gemm_x3_f32a_ok(M, N, batch, min_tiles128)) return STROTSS_EINVAL;
+  EpiScaleStoreX3 e{{C, ldc, M, N, 1.0f, strideC}, {}};
+  using Cfg = X3CfgK16<3, true>;
+  dim3 grid((unsigned)cdiv(N, 128) * cdiv(M, 128) * batch);
+  hipLaunchKernelGGL((gemm_x3_kernel<Cfg, EpiScaleStoreX3, X3NoMirror>), grid, dim3(Cfg::NT), 0, s, A, M, (long long)M * K,
+                     (const __bf16*)B, N, (long long)3 * N * K, K, e, X3NoMirror{});
   ST_LAUNCH_RET();
 }
 

@@ -53,6 +53,11 @@ int st_moment_bwd_x3(const void* Pc, int n, int ld, const void* Tp, float alpha,
                      float* dY, hipStream_t s);
 int st_gemm_x3_batched(const void* A, const void* B, float* C, int ldc, long long strideC, int M, int N, int K,
                        int batch, hipStream_t s, long min_tiles128 = 0);
+// The same with A as f32 K-blocked panels (mfma_x3.h: x3_f32_store4) split in registers; only on the K16 128 x 128 route,
+// which st_gemm_x3_f32a_ok tells (st_gemm_x3_batched_f32a refuses the other shapes with STROTSS_EINVAL).
+bool st_gemm_x3_f32a_ok(int M, int N, int batch, long min_tiles128);
+int st_gemm_x3_batched_f32a(const float* A, const void* B, float* C, int ldc, long long strideC, int M, int N, int K,
+                            int batch, hipStream_t s, long min_tiles128);
 
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 

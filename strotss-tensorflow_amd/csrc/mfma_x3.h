@@ -15,7 +15,8 @@
 // is contiguous:
 //     element (kb, plane, row, k)  at  base + ((kb * 3 + plane) * rows + row) * 32 + k      (bf16)
 // with kb = K-block of 32, plane in {h, m, l} (an operand whose values are exact in bf16 may carry the h plane only:
-// element (kb, row, k) at base + (kb * rows + row) * 32 + k).  A 128-row tile of one plane and one K-block is 8 KiB of
+// element (kb, row, k) at base + (kb * rows + row) * 32 + k).  The K16 ring also takes A as plain f32 in the same K-blocked
+// order (X3CfgK16<3, true>: 4 bytes per value instead of 6, split in registers after the fragment read).  A 128-row tile of one plane and one K-block is 8 KiB of
 // consecutive bytes: every staging load instruction of a wave reads 1 KiB contiguous, there is no split
 // arithmetic, no zero-select and no address arithmetic in the main loop (rows past the operand's end are
 // clamped at set-up; their products land in accumulator rows the epilogue masks).
@@ -80,7 +81,7 @@ struct X3Cfg {               // square block tile B x B, B = 128 (64 x 64 per wa
   static constexpr int LDS_BYTES = 3 * STAGE;            // 144 KiB (one workgroup per CU) | 72 KiB (two)
   static constexpr int G = B_ / 64;                      // 16-row DMA groups per wave, operand and plane
   static constexpr int NP = (3 + NPB_) * G;              // DMA pieces (1 KiB wave instructions) per wave and K-step
-  static constexpr bool K16 = false;
+  static constexpr bool K16 = false, AF32 = false;
 };
 
 #define X3_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
@@ -232,17 +233,30 @@ __device__ __forceinline__ void x3_mainloop(unsigned char* lds, int steps, X3Ope
 // on the fragment read), so 16 consecutive lanes of a ds_read_b128 (16 rows, one k-half) cover all 64 banks once.
 // Per step s: the 6 DMA pieces of tile s+2 behind the first MFMAs (its stage is free since the barrier of step s-1),
 // MFMAs 0..15 on the fragments of tile s, `s_waitcnt vmcnt(6)` (tile s+1 landed, tile s+2 stays in flight) + barrier,
-// the fragments of tile s+1 into the other register slot, MFMAs 16..23.
-template <int NPB_ = 3>
+// the fragments of tile s+1 into the other register slot, MFMAs 16..23.  f32 A: 5 pieces, the wait + barrier after MFMA 7
+// (vmcnt(5)), then 16 MFMAs to hide the split of tile s+1's 16 A values per lane (~88 vector instructions) -- waiting after
+// MFMA 3 / 7 / 11 measured 154.6 / 143.0 / 147.5 us on 36 x (4096 x 256 x 256), panels 146.6 (profiles/r05_ab_x3_f32a.txt).
+// AF32_: the A operand is plain f32, K-blocked (f32 V of the Winograd input transform: x3_f32_store4 below), and is split
+// into its h, m, l planes in registers after the fragment read (x3_split8: split3's rounding, so the partial products and M
+// are bit for bit those of the panel form).  A's stage image is [128 rows][64 B] (16 f32 per row) = 8 KiB, two DMA pieces per
+// wave instead of three: stage 20 KiB, five pieces per wave and step.  WQ_: after which product group q of a step the wait +
+// barrier + fragment read of tile s+1 happen (panels: 3, the last 8 MFMAs behind the read; f32 A: the split of tile s+1 must
+// also finish before step s+1's first MFMA, so it moves earlier -- DESIGN.md section 4).
+template <int NPB_ = 3, bool AF32_ = false, int WQ_ = AF32_ ? 1 : 3>
 struct X3CfgK16 {
   static_assert(NPB_ == 3, "K16 ring: three B planes");
+  static_assert(WQ_ >= 0 && WQ_ <= 4, "K16 ring: the wait needs at least one product group after it");
   static constexpr int NPB = NPB_, NPROD = 6;
+  static constexpr bool AF32 = AF32_;
+  static constexpr int WQ = WQ_;
   static constexpr int BM = 128, BN = 128, WM = 2, WN = 2, NT = 256;
   static constexpr int T = 2, TM = 2, TN = 2;
   static constexpr int PL = 128 * 32;                    // bytes of one plane image ([128 rows][32 B])
-  static constexpr int STAGE = 6 * PL;                   // 24 KiB
-  static constexpr int LDS_BYTES = 3 * STAGE;            // 72 KiB: two workgroups per CU
-  static constexpr int G = 1, NP = 6;
+  static constexpr int NPA = AF32_ ? 2 : 3;              // A's DMA pieces per wave and step
+  static constexpr int ABYTES = NPA * PL;                // A's stage image: 3 planes | f32 [128 rows][64 B]
+  static constexpr int STAGE = ABYTES + 3 * PL;          // 24 KiB | 20 KiB
+  static constexpr int LDS_BYTES = 3 * STAGE;            // 72 KiB | 60 KiB: two workgroups per CU
+  static constexpr int G = 1, NP = NPA + 3;
   static constexpr bool K16 = true;
 };
 
@@ -269,24 +283,68 @@ struct X3OperandK16 {
   __device__ __forceinline__ void advance(int half) { cur += half ? 3u * plane - 32u : 32u; }
 };
 
+// f32 K-blocked operand (X3CfgK16<.., true>): element (kb, row, k) at base + (kb * rows + row) * 32 + k (f32), 128 B per row
+// and K-block.  A K16 step stages 64 B of each of the wave's 32 rows as two pieces of 16 rows x 64 B (the same 16 cache
+// lines per piece as a panel piece), with the K32 form's swizzle of the four 16-byte slots of a 64-byte row:
+// slot' = slot ^ ((row >> 2) & 3).  Rows past the end are clamped like the panel loader's.
+struct X3OperandK16F32 {
+  const char* base;
+  unsigned off[2];           // this lane's 16-byte chunk in piece g: row * 128 + swizzled slot * 16
+  unsigned kblk;             // bytes per K-block (rows * 128)
+  unsigned cur;              // byte offset of the current K-block (+ 64 in its second half)
+  __device__ __forceinline__ X3OperandK16F32(const float* p, int rows, int row0) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    base = reinterpret_cast<const char*>(p);
+    kblk = (unsigned)rows * 128u;
+    cur = 0;
+    const int chunk = (lane & 3) ^ ((lane >> 4) & 3);      // (row >> 2) & 3 == (lane >> 4) & 3: pieces start at 16-row edges
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      const int row = min(row0 + wave * 32 + g * 16 + (lane >> 2), rows - 1);
+      off[g] = (unsigned)row * 128u + (unsigned)chunk * 16u;
+    }
+  }
+  __device__ __forceinline__ void dma(int g, unsigned char* lds_dst) const {
+    const char* src = base + (size_t)cur + off[g];
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                     (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
+  }
+  __device__ __forceinline__ void advance(int half) { cur += half ? kblk - 64u : 64u; }
+};
+
+// Stores 4 consecutive k (k0 % 4 == 0) of one row of an f32 K-blocked operand.
+__device__ __forceinline__ void x3_f32_store4(float* base, size_t rows, size_t row, int k0, const f32x4 v) {
+  *reinterpret_cast<f32x4*>(base + ((size_t)(k0 >> 5) * rows + row) * 32 + (k0 & 31)) = v;
+}
+
+// 8 consecutive f32 of an A fragment -> its h, m, l bf16x8 (split3 on each half: the panel producers' rounding)
+__device__ __forceinline__ void x3_split8(const f32x4 lo, const f32x4 hi, bf16x8& h, bf16x8& m, bf16x8& l) {
+  const Split3 a = split3(lo), b = split3(hi);
+  h = __builtin_shufflevector(a.h, b.h, 0, 1, 2, 3, 4, 5, 6, 7);
+  m = __builtin_shufflevector(a.m, b.m, 0, 1, 2, 3, 4, 5, 6, 7);
+  l = __builtin_shufflevector(a.l, b.l, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
 template <class Cfg> struct X3Ops {
-  using A = std::conditional_t<Cfg::K16, X3OperandK16, X3Operand<Cfg::G, 3>>;
+  using A = std::conditional_t<Cfg::K16, std::conditional_t<Cfg::AF32, X3OperandK16F32, X3OperandK16>, X3Operand<Cfg::G, 3>>;
   using B = std::conditional_t<Cfg::K16, X3OperandK16, X3Operand<Cfg::G, Cfg::NPB>>;
+  using AT = std::conditional_t<Cfg::AF32, float, __bf16>;    // element type of A's global image
 };
 
 // The first two tiles' DMA of a product (steps >= 2, even).  Separate from the loop: a persistent workgroup can put the NEXT
 // product's first loads in flight before it stores the current one (tools/x3_gemm_ablate.hip; measured: no gain).
-template <class Cfg>
-__device__ __forceinline__ void x3_k16_prologue(unsigned char* lds, X3OperandK16& oa, X3OperandK16& ob) {
+template <class Cfg, class OA>
+__device__ __forceinline__ void x3_k16_prologue(unsigned char* lds, OA& oa, X3OperandK16& ob) {
 #ifndef X3_ABL_NO_DMA
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     unsigned char* stage = lds + h * Cfg::STAGE;
 #pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      unsigned char* dst = stage + j * Cfg::PL + wave * 1024;
-      if (j < 3) oa.dma(j, dst); else ob.dma(j - 3, dst);
+    for (int j = 0; j < Cfg::NP; ++j) {
+      if (j >= Cfg::NPA) ob.dma(j - Cfg::NPA, stage + Cfg::ABYTES + (j - Cfg::NPA) * Cfg::PL + wave * 1024);
+      else if constexpr (Cfg::AF32) oa.dma(j, stage + wave * 2048 + j * 1024);
+      else oa.dma(j, stage + j * Cfg::PL + wave * 1024);
     }
     oa.advance(h); ob.advance(h);
   }
@@ -294,37 +352,59 @@ __device__ __forceinline__ void x3_k16_prologue(unsigned char* lds, X3OperandK16
 }
 
 // After x3_k16_prologue.  Stores issued between the prologue and this loop (a persistent kernel's epilogue) would not
-// break the first wait: loads return in order among themselves, so "at most 6 operations outstanding" still means that
-// at most the 6 youngest LOADS (tile 1's) are, i.e. tile 0 has landed.
-template <class Cfg>
-__device__ __forceinline__ void x3_mainloop_k16(unsigned char* lds, int steps, X3OperandK16& oa, X3OperandK16& ob,
+// break the first wait: loads return in order among themselves, so "at most NP operations outstanding" still means that
+// at most the NP youngest LOADS (tile 1's) are, i.e. tile 0 has landed.
+template <class Cfg, class OA>
+__device__ __forceinline__ void x3_mainloop_k16(unsigned char* lds, int steps, OA& oa, X3OperandK16& ob,
                                                 f32x16 (&acc)[2][2]) {
-  constexpr int PL = Cfg::PL, STAGE = Cfg::STAGE;
+  constexpr int PL = Cfg::PL, STAGE = Cfg::STAGE, NPA = Cfg::NPA, NP = Cfg::NP, WQ = Cfg::WQ;
+  constexpr bool AF32 = Cfg::AF32;
+  static_assert(NP == 5 || NP == 6, "K16 ring: 5 or 6 DMA pieces per wave and step");
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, hh = lane >> 5;
-  auto dma_piece = [&](int j, unsigned char* stage) {        // j 0..2: A planes, 3..5: B planes; this wave's 32 rows
+  auto dma_piece = [&](int j, unsigned char* stage) {        // j < NPA: A pieces, then the B planes; this wave's 32 rows
 #ifdef X3_ABL_NO_DMA
     return;
 #endif
-    unsigned char* dst = stage + j * PL + wave * 1024;
-    if (j < 3) oa.dma(j, dst); else ob.dma(j - 3, dst);
+    if (j >= NPA) ob.dma(j - NPA, stage + Cfg::ABYTES + (j - NPA) * PL + wave * 1024);
+    else if constexpr (AF32) oa.dma(j, stage + wave * 2048 + j * 1024);
+    else oa.dma(j, stage + j * PL + wave * 1024);
+  };
+  // wait for tile s+1 while the pieces of tile s+2 issued before the wait (one behind each of the first NP MFMAs) fly on
+  constexpr int IN_FLIGHT = 4 * (WQ + 1) < NP ? 4 * (WQ + 1) : NP;
+  auto wait_next_tile = [&]() {
+    if constexpr (IN_FLIGHT == 6) X3_WAIT_VM(6); else if constexpr (IN_FLIGHT == 5) X3_WAIT_VM(5); else X3_WAIT_VM(4);
   };
   int half = 0;
   const int sw = (hh ^ ((l31 >> 3) & 1)) << 4;
   const int a_rd = (wm * 64 + l31) * 32 + sw;
-  const int b_rd = 3 * PL + (wn * 64 + l31) * 32 + sw;
+  const int b_rd = Cfg::ABYTES + (wn * 64 + l31) * 32 + sw;
+  // f32 A: [128 rows][64 B] rows, 16-byte slot s of row r at slot s ^ ((r >> 2) & 3); k 8 hh .. 8 hh + 7 = slots 2 hh, 2 hh + 1
+  const int af = (l31 >> 2) & 3;
+  const int a_rd0 = (wm * 64 + l31) * 64 + (((2 * hh) ^ af) << 4), a_rd1 = (wm * 64 + l31) * 64 + (((2 * hh + 1) ^ af) << 4);
   bf16x8 fa[2][3][2], fb[2][3][2];
+  f32x4 ra[2][2];                                             // f32 A: the fragments of the next tile before the split
   auto read_frags = [&](const unsigned char* stage, int slot) {
 #ifdef X3_ABL_NO_FRAG
     if (stage != lds) return;
 #endif
 #pragma unroll
-    for (int p = 0; p < 3; ++p) {
+    for (int i = 0; i < 2; ++i) {
+      if constexpr (AF32) {
+        ra[i][0] = *reinterpret_cast<const f32x4*>(stage + a_rd0 + i * 2048);
+        ra[i][1] = *reinterpret_cast<const f32x4*>(stage + a_rd1 + i * 2048);
+      }
 #pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        fa[slot][p][i] = *reinterpret_cast<const bf16x8*>(stage + a_rd + p * PL + i * 1024);
+      for (int p = 0; p < 3; ++p) {
+        if constexpr (!AF32) fa[slot][p][i] = *reinterpret_cast<const bf16x8*>(stage + a_rd + p * PL + i * 1024);
         fb[slot][p][i] = *reinterpret_cast<const bf16x8*>(stage + b_rd + p * PL + i * 1024);
       }
+    }
+  };
+  auto split_a = [&](int slot) {
+    if constexpr (AF32) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) x3_split8(ra[i][0], ra[i][1], fa[slot][0][i], fa[slot][1][i], fa[slot][2][i]);
     }
   };
   constexpr int PA[6] = {2, 0, 1, 1, 0, 0};
@@ -333,9 +413,10 @@ __device__ __forceinline__ void x3_mainloop_k16(unsigned char* lds, int steps, X
   unsigned char* s_cur = lds;
   unsigned char* s_nxt = lds + STAGE;
   unsigned char* s_nn = lds + 2 * STAGE;
-  X3_WAIT_VM(6);
+  if constexpr (NP == 6) X3_WAIT_VM(6); else X3_WAIT_VM(5);
   __builtin_amdgcn_s_barrier();
   read_frags(s_cur, 0);
+  split_a(0);
 
   // MODE 2: tile s+2 exists; 1: tile s+1 is the last; 0: last step.  SLOT: register slot of this step's fragments
   auto kstep = [&](auto mode_tag, auto slot_tag) {
@@ -352,16 +433,16 @@ __device__ __forceinline__ void x3_mainloop_k16(unsigned char* lds, int steps, X
           acc[im][in_][0] += (float)fa[SLOT][PA[q]][im][0] + (float)fb[SLOT][PB[q]][in_][0];
 #endif
           const int done = (q * 2 + im) * 2 + in_ + 1;
-          if (MODE == 2 && done <= 6) {
+          if (MODE == 2 && done <= NP) {
             __builtin_amdgcn_sched_barrier(0);
             dma_piece(done - 1, s_nn);
             __builtin_amdgcn_sched_barrier(0);
           }
         }
       }
-      if (q == 3 && MODE != 0) {
+      if (q == WQ && MODE != 0) {
         __builtin_amdgcn_sched_barrier(0);
-        if (MODE == 2) X3_WAIT_VM(6); else X3_WAIT_VM(0);
+        if (MODE == 2) wait_next_tile(); else X3_WAIT_VM(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #ifndef X3_ABL_NO_BARRIER
         __builtin_amdgcn_s_barrier();
@@ -369,6 +450,7 @@ __device__ __forceinline__ void x3_mainloop_k16(unsigned char* lds, int steps, X
         asm volatile("" ::: "memory");
         read_frags(s_nxt, SLOT ^ 1);
         __builtin_amdgcn_sched_barrier(0);
+        split_a(SLOT ^ 1);            // f32 A: left to the scheduler among the remaining MFMAs of the step
       }
     }
     if (MODE == 2) { oa.advance(half); ob.advance(half); half ^= 1; }
@@ -402,7 +484,8 @@ struct X3NoPrefetch {
 // One workgroup's tile of such a product: `bid` of `nblk` workgroups (the launch's own, or one problem's share of a grouped
 // launch: gemm_x3_group3_kernel below).  `lds` holds >= Cfg::LDS_BYTES, 1024-byte aligned.
 template <class Cfg, class Epi, class Mirror>
-__device__ __forceinline__ void gemm_x3_tile(unsigned char* lds, unsigned bid, unsigned nblk, const __bf16* __restrict__ A, int M,
+__device__ __forceinline__ void gemm_x3_tile(unsigned char* lds, unsigned bid, unsigned nblk,
+                                             const typename X3Ops<Cfg>::AT* __restrict__ A, int M,
                                              long long strideA, const __bf16* __restrict__ B, int N, long long strideB, int K,
                                              const Epi& epi_in, const Mirror& mirror, int xbh, int xbw) {
   Epi epi = epi_in;                                 // (set_batch moves its pointers)
@@ -477,7 +560,7 @@ __device__ __forceinline__ void gemm_x3_tile(unsigned char* lds, unsigned bid, u
 }
 
 template <class Cfg, class Epi, class Mirror>
-__global__ __launch_bounds__(Cfg::NT) void gemm_x3_kernel(const __bf16* __restrict__ A, int M, long long strideA,
+__global__ __launch_bounds__(Cfg::NT) void gemm_x3_kernel(const typename X3Ops<Cfg>::AT* __restrict__ A, int M, long long strideA,
                                                           const __bf16* __restrict__ B, int N, long long strideB,
                                                           int K, Epi epi, Mirror mirror, int xbh = 0, int xbw = 0) {
   __shared__ __attribute__((aligned(1024))) unsigned char lds[Cfg::LDS_BYTES];

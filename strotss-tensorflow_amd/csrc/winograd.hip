@@ -176,16 +176,16 @@ __global__ __launch_bounds__(256) void winograd43_in_kernel(const float* __restr
   }
 }
 
-// The same transform writing V as x3 panels (mfma_x3.h) for the bf16x3 GEMM core: per position p a panel of
-// T rows x C columns.  Lane order: 8 lanes = the 32 channels of one K-block of one tile (128 B read per pixel),
-// 8 consecutive tiles per wave: 512 contiguous bytes per plane, position and wave store.
-__global__ __launch_bounds__(256) void winograd43_in_x3_kernel(const float* __restrict__ in, int H, int W, int C4,
-                                                               int TH, int TW, __bf16* __restrict__ V, int kb_shift) {
+// The same transform writing V K-blocked for the bf16x3 GEMM core (mfma_x3.h): per position p a panel of T rows x C
+// columns.  Lane order: 8 lanes = the 32 channels of one K-block of one tile (128 B read per pixel), 8 consecutive tiles per
+// wave.  One body, two stores (below), so that both V images hold the same values bit for bit.
+template <class Store>
+__device__ __forceinline__ void winograd43_in_k_blocked(const float* __restrict__ in, int H, int W, int C4, int TH, int TW,
+                                                        int kb_shift, const Store& store) {
   const size_t T = (size_t)TH * TW;
   const int KB = C4 >> 3;
   const unsigned total = (unsigned)(((T + 7) >> 3) * 64 * KB);
   const f32x4* src = reinterpret_cast<const f32x4*>(in);
-  const size_t panel = 3 * T * (size_t)C4 * 4;
   for (unsigned e = blockIdx.x * 256u + threadIdx.x; e < total; e += gridDim.x * 256u) {
     const int c8 = (int)(e & 7), tlo = (int)((e >> 3) & 7);
     unsigned r8; int kb;
@@ -217,9 +217,28 @@ __global__ __launch_bounds__(256) void winograd43_in_x3_kernel(const float* __re
     for (int rr = 0; rr < 6; ++rr) {     // rows: V = t B
       bt6(d[rr]);
 #pragma unroll
-      for (int q = 0; q < 6; ++q) x3_store4(V + (size_t)(rr * 6 + q) * panel, T, tile, 4 * c, d[rr][q]);
+      for (int q = 0; q < 6; ++q) store(rr * 6 + q, tile, 4 * c, d[rr][q]);
     }
   }
+}
+
+// V as x3 panels (three bf16 planes per K-block): 512 contiguous bytes per plane, position and wave store
+__global__ __launch_bounds__(256) void winograd43_in_x3_kernel(const float* __restrict__ in, int H, int W, int C4,
+                                                               int TH, int TW, __bf16* __restrict__ V, int kb_shift) {
+  const size_t T = (size_t)TH * TW, panel = 3 * T * (size_t)C4 * 4;
+  winograd43_in_k_blocked(in, H, W, C4, TH, TW, kb_shift, [&](int p, unsigned tile, int k0, const f32x4 v) {
+    x3_store4(V + (size_t)p * panel, T, tile, k0, v);
+  });
+}
+
+// V as f32, K-blocked (x3_f32_store4: 128 B per tile and K-block): 1 KiB contiguous per position and wave store, two thirds
+// of the panels' bytes; the GEMM (X3CfgK16<3, true>) splits it in registers
+__global__ __launch_bounds__(256) void winograd43_in_f32k_kernel(const float* __restrict__ in, int H, int W, int C4,
+                                                                 int TH, int TW, float* __restrict__ V, int kb_shift) {
+  const size_t T = (size_t)TH * TW, panel = T * (size_t)C4 * 4;
+  winograd43_in_k_blocked(in, H, W, C4, TH, TW, kb_shift, [&](int p, unsigned tile, int k0, const f32x4 v) {
+    x3_f32_store4(V + (size_t)p * panel, T, tile, k0, v);
+  });
 }
 
 // Y = A^T M A (4x4 outputs per tile);  out = relu(Y + bias)  or  (mask > 0 ? Y : 0)
@@ -348,6 +367,15 @@ static bool x3_enabled(size_t T, int cout) {
   return on != 0 && (long)((T + 63) / 64) * ((cout + 63) / 64) * 36 >= x3_min_tiles();
 }
 
+// F4_x3_gemm_128 route: V as f32 (two thirds of the panels' bytes through the input transform's writes and the GEMM's DMA)
+// and split in the GEMM's registers instead of x3 panels; bit for bit the same M.  STROTSS_X3_CONV_F32A=0: the panel form
+// (A/B baseline and bitwise reference).  The 64 x 64 route (F4_x3_gemm_64) stays on panels.
+static bool x3_f32a_enabled() {
+  static int on = -1;
+  if (on < 0) { const char* e = getenv("STROTSS_X3_CONV_F32A"); on = e ? atoi(e) : 1; }
+  return on != 0;
+}
+
 static int x3_min_cout() {
   static int v = -1;
   if (v < 0) { const char* e = getenv("STROTSS_X3_MIN_COUT"); v = e ? atoi(e) : 256; }
@@ -388,10 +416,16 @@ static int winograd43_run(const float* in, int h, int w, int cin, const float* U
   const int stages = g_wino_stages;
   if (x3) {
     const size_t tin = ((T + 7) / 8) * 8 * (cin / 4);
-    if (stages & 1) hipLaunchKernelGGL(winograd43_in_x3_kernel, dim3((unsigned)min((size_t)16384, (tin + 255) / 256)), dim3(256), 0, st,
-                       in, h, w, cin / 4, TH, TW, reinterpret_cast<__bf16*>(V), log2_or_minus1(cin / 32));
-    if (!(stages & 2)) rc = 0;
-    else rc = st_gemm_x3_batched(V, Ux3, Mw, cout, (long long)T * cout, (int)T, cout, cin, 36, st, x3_min_tiles());
+    const dim3 gin((unsigned)min((size_t)16384, (tin + 255) / 256));
+    if (x3_f32a_enabled() && st_gemm_x3_f32a_ok((int)T, cout, 36, x3_min_tiles())) {      // V as f32, split in the GEMM
+      if (stages & 1) hipLaunchKernelGGL(winograd43_in_f32k_kernel, gin, dim3(256), 0, st, in, h, w, cin / 4, TH, TW, V,
+                                         log2_or_minus1(cin / 32));
+      rc = (stages & 2) ? st_gemm_x3_batched_f32a(V, Ux3, Mw, cout, (long long)T * cout, (int)T, cout, cin, 36, st, x3_min_tiles()) : 0;
+    } else {
+      if (stages & 1) hipLaunchKernelGGL(winograd43_in_x3_kernel, gin, dim3(256), 0, st, in, h, w, cin / 4, TH, TW,
+                                         reinterpret_cast<__bf16*>(V), log2_or_minus1(cin / 32));
+      rc = (stages & 2) ? st_gemm_x3_batched(V, Ux3, Mw, cout, (long long)T * cout, (int)T, cout, cin, 36, st, x3_min_tiles()) : 0;
+    }
   } else {
     const size_t tin = T * (cin / 4);
     if (stages & 1) hipLaunchKernelGGL(winograd43_in_kernel, dim3((unsigned)min((size_t)16384, (tin + 255) / 256)), dim3(256), 0, st, in,

@@ -1,8 +1,11 @@
 // Stand-alone check + timing of the bf16x3-split GEMM core (csrc/mfma_x3.h) against fp64 on the host.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 tools/x3_gemm_bench.hip -o tools/scratch/x3_gemm_bench
 //   x3_gemm_bench [batch M N K [iters]]
+// -DUSE_K16: the K16 ring (X3CfgK16, two workgroups per CU) instead of X3Cfg<TILE>.  -DUSE_K16 -DF32A [-DF32A_WQ=q]: A as f32
+// K-blocked panels split in registers (X3CfgK16<3, true, q>), also checked BITWISE against the K16 panel form.
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include <math.h>
 #include <vector>
 #include <random>
@@ -25,6 +28,10 @@ struct EpiStore : X3NoPrefetch<EpiStore> {
     return 0.f;
   }
   __device__ __forceinline__ void finish(float*, float) const {}
+};
+
+struct NoMirror {
+  template <class P, class Acc, class Map> __device__ void operator()(const EpiStore&, P&, float*, int, int, int, int, Acc&, const Map&) const {}
 };
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e_), __LINE__); exit(1); } } while (0)
@@ -53,17 +60,58 @@ int main(int argc, char** argv) {
 #ifndef TILE
 #define TILE 128
 #endif
+#ifdef USE_K16
+  using Cfg0 = X3CfgK16<3>;
+#ifdef F32A
+#ifndef F32A_WQ
+#define F32A_WQ 1
+#endif
+  using Cfg = X3CfgK16<3, true, F32A_WQ>;
+#else
+  using Cfg = Cfg0;
+#endif
+  constexpr int BT = 128;
+#else
   using Cfg = X3Cfg<TILE>;
-  struct NoMirror {
-    template <class P> __device__ void operator()(const EpiStore&, P&, float*, int, int, int, int, f32x16 (&)[Cfg::T][Cfg::T], const PipeAccMap<Cfg>&) const {}
-  };
+  using Cfg0 = Cfg;
+  constexpr int BT = TILE;
+#endif
   EpiStore e{{}, dC, N, M, N, (long long)M * N};
-  const unsigned gt = (M + TILE - 1) / TILE;
-  dim3 grid(SYMM_SKIP ? gt * (gt + 1) / 2 : (unsigned)(gt * ((N + TILE - 1) / TILE) * batch));
-  auto run = [&]() {
-    hipLaunchKernelGGL((gemm_x3_kernel<Cfg, EpiStore, NoMirror>), grid, dim3(256), 0, st, pA, M, (long long)3 * M * K, pB, N,
+  const unsigned gt = (M + BT - 1) / BT;
+  dim3 grid(SYMM_SKIP ? gt * (gt + 1) / 2 : (unsigned)(gt * ((N + BT - 1) / BT) * batch));
+  auto run_panels = [&]() {
+    hipLaunchKernelGGL((gemm_x3_kernel<Cfg0, EpiStore, NoMirror>), grid, dim3(256), 0, st, pA, M, (long long)3 * M * K, pB, N,
                        (long long)3 * N * K, K, e, NoMirror{});
   };
+#ifdef F32A
+  float* fA;                                       // A K-blocked: (batch, K / 32, M, 32) f32
+  CK(hipMalloc(&fA, hA.size() * 4));
+  {
+    std::vector<float> h(hA.size());
+    for (int z = 0; z < batch; ++z)
+      for (int r = 0; r < M; ++r)
+        for (int k = 0; k < K; ++k) h[(((size_t)z * (K / 32) + k / 32) * M + r) * 32 + k % 32] = hA[((size_t)z * M + r) * K + k];
+    CK(hipMemcpy(fA, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+  }
+  auto run = [&]() {
+    hipLaunchKernelGGL((gemm_x3_kernel<Cfg, EpiStore, NoMirror>), grid, dim3(256), 0, st, fA, M, (long long)M * K, pB, N,
+                       (long long)3 * N * K, K, e, NoMirror{});
+  };
+  {
+    std::vector<float> c0((size_t)batch * M * N), c1(c0.size());
+    run_panels(); CK(hipStreamSynchronize(st)); CK(hipGetLastError());
+    CK(hipMemcpy(c0.data(), dC, c0.size() * 4, hipMemcpyDeviceToHost));
+    CK(hipMemset(dC, 0xff, c0.size() * 4));
+    run(); CK(hipStreamSynchronize(st)); CK(hipGetLastError());
+    CK(hipMemcpy(c1.data(), dC, c1.size() * 4, hipMemcpyDeviceToHost));
+    size_t diff = 0;
+    for (size_t i = 0; i < c0.size(); ++i) diff += memcmp(&c0[i], &c1[i], 4) != 0;
+    printf("f32 A (WQ %d) against panels: %zu of %zu outputs differ bitwise\n", Cfg::WQ, diff, c0.size());
+    if (diff) return 3;
+  }
+#else
+  auto run = run_panels;
+#endif
   run(); CK(hipStreamSynchronize(st)); CK(hipGetLastError());
   std::vector<float> hC((size_t)batch * M * N);
   CK(hipMemcpy(hC.data(), dC, hC.size() * 4, hipMemcpyDeviceToHost));
