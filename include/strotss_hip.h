@@ -495,6 +495,31 @@ size_t strotss_temporal_workspace_bytes(int h, int w);
 int strotss_temporal_fwd_bwd(const float* img, const float* target, const float* certainty, int h, int w, float gscale,
                              float* gimg, float* loss_out, void* workspace, void* stream);
 
+/* Long-term temporal consistency: 1 .. STROTSS_MAX_TEMPORAL warped earlier results at once, nearest
+ * frame first.  Once per frame, in ONE launch, one thread per pixel: raw, out (count, h, w), plane j = certainty of the
+ * j-th nearest frame;  out_j(p) = max(raw_j(p) - sum_{k < j} raw_k(p), 0), the sum in ascending k in float32 (out may equal
+ * raw).  STROTSS_EINVAL: null pointers, h, w <= 0, count outside 1 .. STROTSS_MAX_TEMPORAL, 3 h w > INT_MAX;
+ * STROTSS_EALIGN: a pointer not 16-byte aligned. */
+#define STROTSS_MAX_TEMPORAL 4
+int strotss_temporal_long_certainty(const float* raw, int count, int h, int w, float* out, void* stream);
+typedef struct {
+  int count;                                     /* 1 .. STROTSS_MAX_TEMPORAL */
+  const float* target[STROTSS_MAX_TEMPORAL];     /* (h, w, 3) */
+  const float* certainty[STROTSS_MAX_TEMPORAL];  /* (h, w), already combined */
+  float gscale[STROTSS_MAX_TEMPORAL];
+} strotss_temporal_set_t;
+/* bytes of the workspace of strotss_temporal_multi_fwd_bwd (0 for h, w <= 0 or count outside 1 .. STROTSS_MAX_TEMPORAL) */
+size_t strotss_temporal_multi_workspace_bytes(int h, int w, int count);
+/* The temporal terms of several targets in ONE launch, each read once (img, gimg, every target and certainty 16-byte
+ * aligned):  loss_out[j] = (1 / (3 h w)) sum_p certainty_j(p) sum_ch (img - target_j)^2 for j < count,
+ * gimg += sum_j gscale_j * dloss_j/dimg, added in ascending j per element.  count == 1 is strotss_temporal_fwd_bwd (the
+ * same kernel).  Every gscale_j == 0, or certainty_j(p) == 0 for every j, leaves gimg (at p) bit for bit.  Fixed-order
+ * reductions per j, no float atomics.  workspace: strotss_temporal_multi_workspace_bytes(h, w, set->count) bytes, ZEROED
+ * before its first use (one call at a time).  STROTSS_EINVAL: null pointers, h, w <= 0, count outside
+ * 1 .. STROTSS_MAX_TEMPORAL, 3 h w > INT_MAX; STROTSS_EALIGN: a pointer not 16-byte aligned. */
+int strotss_temporal_multi_fwd_bwd(const float* img, const strotss_temporal_set_t* set, int h, int w, float* gimg,
+                                   float* loss_out, void* workspace, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Optimiser + output
  * --------------------------------------------------------------------------------------- */

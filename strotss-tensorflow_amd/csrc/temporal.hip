@@ -2,6 +2,8 @@
 //   - flow_warp_kernel: once per frame, the previous stylised frame warped along the backward flow + its {0, 1} certainty;
 //   - temporal_fwd_bwd_kernel: once per step (inside the captured graph), L_t = (1/(3hw)) sum_p c(p) |x(p) - w(p)|^2 and
 //     gimg += gscale * dL_t/dx, between the trunk's pixel gradient and the fold adjoint.
+//   - temporal_long_certainty_kernel, temporal_multi_fwd_bwd_kernel: the long-term terms of several earlier frames
+//     (DESIGN.md section 13), once per frame and once per step.
 #include "internal.h"
 
 namespace {
@@ -142,6 +144,139 @@ __global__ __launch_bounds__(256) void temporal_fwd_bwd_kernel(const float* __re
   }
 }
 
+// Long-term certainties, once per frame, one thread per pixel: plane j keeps only what the nearer
+// planes k < j do not already cover, the covered amount summed in ascending k in float32.
+__global__ __launch_bounds__(256) void temporal_long_certainty_kernel(const float* __restrict__ raw, int count, int npix,
+                                                                      float* __restrict__ out) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= npix) return;
+  float c[STROTSS_MAX_TEMPORAL];
+#pragma unroll
+  for (int j = 0; j < STROTSS_MAX_TEMPORAL; ++j) c[j] = j < count ? raw[(size_t)j * npix + p] : 0.f;
+  float covered = 0.f;
+#pragma unroll
+  for (int j = 0; j < STROTSS_MAX_TEMPORAL; ++j) {
+    if (j < count) out[(size_t)j * npix + p] = fmaxf(c[j] - covered, 0.f);
+    covered += c[j];
+  }
+}
+
+// The temporal terms of N >= 2 targets in one launch: temporal_fwd_bwd_kernel's layout (1024 pixels per workgroup, thread t
+// takes float4 t, t + 256, t + 512 of x, gimg and every target, the block's N x 1024 certainties staged in LDS) with x and
+// gimg read once.  Per element the N terms are added to the gradient in ascending j, each exactly as the single-term
+// kernel adds its one (c_j == 0 or gscale_j == 0 adds nothing).  One fixed tree per j per block; the last block by the
+// integer ticket sums partials[j * gridDim.x ..] in a fixed order for every j.
+template <int N>
+struct TemporalSetArgs {
+  const float* tgt[N];
+  const float* cert[N];
+  float coef[N];
+};
+
+template <int N>
+__global__ __launch_bounds__(256) void temporal_multi_fwd_bwd_kernel(const float* __restrict__ img, TemporalSetArgs<N> s,
+                                                                     int npix, float inv_n, float* __restrict__ gimg,
+                                                                     float* __restrict__ loss_out,
+                                                                     unsigned* __restrict__ ticket,
+                                                                     float* __restrict__ partials) {
+  __shared__ float cs[N][TEMPORAL_PIX_PER_BLOCK];
+  __shared__ float red[4];
+  __shared__ int is_last;
+  const int t = threadIdx.x;
+  const int base = blockIdx.x * TEMPORAL_PIX_PER_BLOCK;
+  const int count = min(TEMPORAL_PIX_PER_BLOCK, npix - base);
+  const bool full = count == TEMPORAL_PIX_PER_BLOCK;
+  const size_t f0 = 3 * (size_t)base;
+  bool any_coef = false;
+#pragma unroll
+  for (int j = 0; j < N; ++j) any_coef = any_coef || s.coef[j] != 0.f;
+  float acc[N];
+#pragma unroll
+  for (int j = 0; j < N; ++j) acc[j] = 0.f;
+  if (full) {
+    const f32x4* x4 = reinterpret_cast<const f32x4*>(img + f0);
+    f32x4* g4 = reinterpret_cast<f32x4*>(gimg + f0);
+    f32x4 xv[3], yv[N][3], gv[3] = {}, c4[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) c4[j] = reinterpret_cast<const f32x4*>(s.cert[j] + base)[t];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) xv[k] = x4[t + 256 * k];
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const f32x4* y4 = reinterpret_cast<const f32x4*>(s.tgt[j] + f0);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) yv[j][k] = y4[t + 256 * k];
+    }
+    if (any_coef) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) gv[k] = g4[t + 256 * k];
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) reinterpret_cast<f32x4*>(cs[j])[t] = c4[j];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        const f32x4 d = xv[k] - yv[j][k];
+        const float coef = s.coef[j];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float ce = cs[j][(4 * (t + 256 * k) + e) / 3];
+          acc[j] += ce * (d[e] * d[e]);
+          gv[k][e] = ce != 0.f && coef != 0.f ? gv[k][e] + (coef * ce) * d[e] : gv[k][e];
+        }
+      }
+    }
+    if (any_coef) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) g4[t + 256 * k] = gv[k];
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+      for (int p = t; p < count; p += 256) cs[j][p] = s.cert[j][base + p];
+    __syncthreads();
+    for (int i = t; i < 3 * count; i += 256) {
+      const float x = img[f0 + i];
+      float g = any_coef ? gimg[f0 + i] : 0.f;
+      bool touched = false;
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        const float ce = cs[j][i / 3], d = x - s.tgt[j][f0 + i];
+        acc[j] += ce * (d * d);
+        if (s.coef[j] != 0.f && ce != 0.f) {
+          g += (s.coef[j] * ce) * d;
+          touched = true;
+        }
+      }
+      if (touched) gimg[f0 + i] = g;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    const float b = block_sum_256(acc[j], red);
+    if (threadIdx.x == 0) partials[(size_t)j * gridDim.x + blockIdx.x] = b;
+  }
+  if (threadIdx.x == 0) {
+    __threadfence();                                  // the partials are visible before the ticket is taken
+    is_last = atomicAdd(ticket, 1u) == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!is_last) return;
+  __threadfence();
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    const float* pj = partials + (size_t)j * gridDim.x;
+    float a = 0.f;
+    for (int i = threadIdx.x; i < (int)gridDim.x; i += 256)
+      a += __hip_atomic_load(&pj[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    a = block_sum_256(a, red);
+    if (threadIdx.x == 0) loss_out[j] = a * inv_n;
+  }
+  if (threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next call
+}
+
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 inline long long temporal_blocks(int h, int w) {
   return ((long long)h * w + TEMPORAL_PIX_PER_BLOCK - 1) / TEMPORAL_PIX_PER_BLOCK;
@@ -177,5 +312,59 @@ int strotss_temporal_fwd_bwd(const float* img, const float* target, const float*
   float* partials = (float*)((char*)workspace + 16);
   hipLaunchKernelGGL(temporal_fwd_bwd_kernel, dim3((unsigned)temporal_blocks(h, w)), dim3(256), 0, (hipStream_t)stream, img,
                      target, certainty, (int)npix, coef, inv_n, gimg, loss_out, ticket, partials);
+  ST_LAUNCH_RET();
+}
+
+int strotss_temporal_long_certainty(const float* raw, int count, int h, int w, float* out, void* stream) {
+  ST_CHECK_ARG(raw && out && h > 0 && w > 0 && count >= 1 && count <= STROTSS_MAX_TEMPORAL, STROTSS_EINVAL);
+  const long long npix = (long long)h * w;
+  ST_CHECK_ARG(3 * npix <= 0x7fffffffLL, STROTSS_EINVAL);
+  ST_CHECK_ARG(aligned16(raw) && aligned16(out), STROTSS_EALIGN);
+  hipLaunchKernelGGL(temporal_long_certainty_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, raw, count, (int)npix, out);
+  ST_LAUNCH_RET();
+}
+
+size_t strotss_temporal_multi_workspace_bytes(int h, int w, int count) {
+  if (h <= 0 || w <= 0 || count < 1 || count > STROTSS_MAX_TEMPORAL) return 0;
+  return 16 + 4 * (size_t)count * (size_t)temporal_blocks(h, w);
+}
+
+namespace {
+template <int N>
+void launch_temporal_multi(const float* img, const strotss_temporal_set_t* set, int npix, double n, float* gimg,
+                           float* loss_out, unsigned* ticket, float* partials, hipStream_t stream) {
+  TemporalSetArgs<N> a;
+  for (int j = 0; j < N; ++j) {
+    a.tgt[j] = set->target[j];
+    a.cert[j] = set->certainty[j];
+    a.coef[j] = (float)(2.0 * (double)set->gscale[j] / n);     // as strotss_temporal_fwd_bwd rounds its one coefficient
+  }
+  hipLaunchKernelGGL(temporal_multi_fwd_bwd_kernel<N>, dim3((unsigned)((npix + TEMPORAL_PIX_PER_BLOCK - 1) /
+                                                                       TEMPORAL_PIX_PER_BLOCK)),
+                     dim3(256), 0, stream, img, a, npix, (float)(1.0 / n), gimg, loss_out, ticket, partials);
+}
+}  // namespace
+
+int strotss_temporal_multi_fwd_bwd(const float* img, const strotss_temporal_set_t* set, int h, int w, float* gimg,
+                                   float* loss_out, void* workspace, void* stream) {
+  ST_CHECK_ARG(img && set && gimg && loss_out && workspace && h > 0 && w > 0, STROTSS_EINVAL);
+  const int count = set->count;
+  ST_CHECK_ARG(count >= 1 && count <= STROTSS_MAX_TEMPORAL, STROTSS_EINVAL);
+  for (int j = 0; j < count; ++j) ST_CHECK_ARG(set->target[j] && set->certainty[j], STROTSS_EINVAL);
+  const long long npix = (long long)h * w;
+  ST_CHECK_ARG(3 * npix <= 0x7fffffffLL, STROTSS_EINVAL);
+  ST_CHECK_ARG(aligned16(img) && aligned16(gimg) && aligned16(workspace), STROTSS_EALIGN);
+  for (int j = 0; j < count; ++j) ST_CHECK_ARG(aligned16(set->target[j]) && aligned16(set->certainty[j]), STROTSS_EALIGN);
+  if (count == 1)          // the single-term kernel itself: bit for bit, and its workspace layout is this one's
+    return strotss_temporal_fwd_bwd(img, set->target[0], set->certainty[0], h, w, set->gscale[0], gimg, loss_out,
+                                    workspace, stream);
+  const double n = 3.0 * (double)npix;
+  unsigned* ticket = (unsigned*)workspace;
+  float* partials = (float*)((char*)workspace + 16);
+  const hipStream_t st = (hipStream_t)stream;
+  if (count == 2) launch_temporal_multi<2>(img, set, (int)npix, n, gimg, loss_out, ticket, partials, st);
+  else if (count == 3) launch_temporal_multi<3>(img, set, (int)npix, n, gimg, loss_out, ticket, partials, st);
+  else launch_temporal_multi<4>(img, set, (int)npix, n, gimg, loss_out, ticket, partials, st);
   ST_LAUNCH_RET();
 }

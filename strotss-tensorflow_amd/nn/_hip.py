@@ -68,6 +68,16 @@ class StyleSetT(C.Structure):
                 ("weight", C.c_float * MAX_STYLES)]
 
 
+MAX_TEMPORAL = 4
+
+
+class TemporalSetT(C.Structure):
+    """strotss_temporal_set_t (include/strotss_hip.h): the long-term temporal targets of a step, nearest frame first"""
+    _fields_ = [("count", C.c_int),
+                ("target", C.c_void_p * MAX_TEMPORAL), ("certainty", C.c_void_p * MAX_TEMPORAL),
+                ("gscale", C.c_float * MAX_TEMPORAL)]
+
+
 _P, _I, _F, _Z, _L = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
 # name -> (restype, argtypes); must list EVERY symbol include/strotss_hip.h declares
 SIGNATURES = {
@@ -143,6 +153,9 @@ SIGNATURES = {
     "strotss_flow_warp": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "strotss_temporal_workspace_bytes": (_Z, [_I, _I]),
     "strotss_temporal_fwd_bwd": (_I, [_P, _P, _P, _I, _I, _F, _P, _P, _P, _P]),
+    "strotss_temporal_long_certainty": (_I, [_P, _I, _I, _I, _P, _P]),
+    "strotss_temporal_multi_workspace_bytes": (_Z, [_I, _I, _I]),
+    "strotss_temporal_multi_fwd_bwd": (_I, [_P, C.POINTER(TemporalSetT), _I, _I, _P, _P, _P, _P]),
     "strotss_rmsprop_step": (_I, [C.POINTER(TensorsT), _F, _F, _F, _P]),
     "strotss_postprocess": (_I, [_P, _L, _P, _P, _P]),
 }

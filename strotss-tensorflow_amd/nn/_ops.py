@@ -133,6 +133,53 @@ def temporal_fwd_bwd(img: torch.Tensor, target: torch.Tensor, certainty: torch.T
                                               ptr(loss_out), ptr(workspace), stream_ptr()), "temporal_fwd_bwd")
 
 
+def temporal_long_certainty(stack: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the long-term certainties of one frame (strotss_temporal_long_certainty): stack (count, h, w),
+    plane j the raw certainty of the j-th nearest earlier frame -> (count, h, w), plane j = max(c_j - sum_{k<j} c_k, 0)."""
+    require(stack, "certainty stack")
+    if stack.dim() != 3 or not 1 <= int(stack.shape[0]) <= _hip.MAX_TEMPORAL:
+        raise ValueError(f"certainty stack of shape {tuple(stack.shape)}: expected (1..{_hip.MAX_TEMPORAL}, h, w)")
+    count, h, w = (int(s) for s in stack.shape)
+    if out is None:
+        out = torch.empty_like(stack)
+    require(out, "combined certainties")
+    assert out.numel() == stack.numel()
+    check(_hip.lib().strotss_temporal_long_certainty(ptr(stack), count, h, w, ptr(out), stream_ptr()),
+          "temporal_long_certainty")
+    return out
+
+
+def temporal_multi_workspace(h: int, w: int, count: int, device) -> torch.Tensor:
+    """a zeroed workspace of strotss_temporal_multi_fwd_bwd for (h, w) and `count` targets (as temporal_workspace)"""
+    nb = int(_hip.lib().strotss_temporal_multi_workspace_bytes(int(h), int(w), int(count)))
+    return torch.zeros(max(nb, 16), dtype=torch.uint8, device=device)
+
+
+def temporal_multi_fwd_bwd(img: torch.Tensor, targets: Sequence[torch.Tensor], certainties: Sequence[torch.Tensor],
+                           gscales: Sequence[float], gimg: torch.Tensor, loss_out: torch.Tensor,
+                           workspace: torch.Tensor) -> None:
+    """loss_out[j] = (1/(3hw)) sum_p certainties[j](p) |img(p) - targets[j](p)|^2 for every j, gimg += sum_j gscales[j] *
+    dloss_j/dimg in ONE launch (strotss_temporal_multi_fwd_bwd; img, targets, gimg (h, w, 3) or (1, h, w, 3), certainties
+    (h, w)).  workspace: temporal_multi_workspace(h, w, len(targets))."""
+    count = len(targets)
+    if not 1 <= count <= _hip.MAX_TEMPORAL or len(certainties) != count or len(gscales) != count:
+        raise ValueError(f"{count} temporal targets, {len(certainties)} certainties, {len(gscales)} weights: expected "
+                         f"1..{_hip.MAX_TEMPORAL} of each")
+    for t, name in ((img, "image"), (gimg, "pixel gradient"), (loss_out, "temporal losses")):
+        require(t, name)
+    h, w, c = hwc(img)
+    assert c == 3 and gimg.numel() == 3 * h * w and loss_out.numel() >= count
+    s = _hip.TemporalSetT()
+    s.count = count
+    for j, (tg, ce, g) in enumerate(zip(targets, certainties, gscales)):
+        require(tg, f"temporal target {j}")
+        require(ce, f"certainty {j}")
+        assert tg.numel() == 3 * h * w and ce.numel() == h * w
+        s.target[j], s.certainty[j], s.gscale[j] = tg.data_ptr(), ce.data_ptr(), float(g)
+    check(_hip.lib().strotss_temporal_multi_fwd_bwd(ptr(img), C.byref(s), h, w, ptr(gimg), ptr(loss_out), ptr(workspace),
+                                                    stream_ptr()), "temporal_multi_fwd_bwd")
+
+
 def resize_bilinear_adjoint(gout: torch.Tensor, ih: int, iw: int,
                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
     require(gout, "resize adjoint input")

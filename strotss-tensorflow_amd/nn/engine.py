@@ -14,7 +14,7 @@ strotss_utils.py:83-121), so identical index streams give comparable trajectorie
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -133,7 +133,9 @@ class StepEngine:
     matrices by the map at sample j.  One GPU only: not with `strips` or `dist_group`.
 
     `temporal`: a TemporalTarget at this scale's size: the pixel gradient gets lambda * dL_t/dx after the trunk (and the
-    all-reduce) and before the fold adjoint, in ONE launch.  One GPU only, as the map above."""
+    all-reduce) and before the fold adjoint, in ONE launch.  One GPU only, as the map above.  A
+    sequence of 1..4 TemporalTargets (their certainties already combined, nearest frame first) adds
+    every term in ONE launch as well; one element is the TemporalTarget itself."""
 
     N_SCALARS = 4   # loss_c, l_moment, l_remd, l_palette per region
 
@@ -142,7 +144,7 @@ class StepEngine:
                  loss_denom: float, lr: float, sample_size: int = 1024, levels: int = 5,
                  dist_group=None, rho: float = 0.99, eps: float = 1e-8, strips: Optional["parallel.StripPlan"] = None,
                  deterministic: Optional[bool] = None, content_weight: Optional[torch.Tensor] = None,
-                 temporal: Optional[TemporalTarget] = None):
+                 temporal: Optional[Union[TemporalTarget, Sequence[TemporalTarget]]] = None):
         dev = stylized.device
         self.params = params
         self.alpha, self.loss_denom, self.lr, self.rho, self.eps = float(alpha), float(loss_denom), float(lr), rho, eps
@@ -165,23 +167,40 @@ class StepEngine:
             from .strotss_utils import check_content_weight
             self._cw_map = check_content_weight(content_weight, h, w).to(dev).clone()     # the engine's own copy
         self._temporal = None
+        if temporal is not None and not isinstance(temporal, TemporalTarget):
+            temporal = list(temporal)            # long-term targets, nearest frame first
+            if not 1 <= len(temporal) <= _hip.MAX_TEMPORAL:
+                raise ValueError(f"the temporal term takes 1..{_hip.MAX_TEMPORAL} targets, got {len(temporal)}")
+            if len(temporal) == 1:               # one target IS the TemporalTarget path, bit for bit
+                temporal = temporal[0]
         if temporal is not None:
             if strips is not None or dist_group is not None:
                 raise ValueError("the temporal term runs on one GPU: image strips and region sharding are not supported "
                                  "with it")
-            lam = float(temporal.weight)
-            if not np.isfinite(lam) or lam < 0:
-                raise ValueError(f"temporal weight must be finite and >= 0, got {temporal.weight}")
-            tgt, cert = temporal.target, temporal.certainty
-            if tgt.numel() != 3 * h * w or tuple(tgt.shape[-3:]) != (h, w, 3):
-                raise ValueError(f"temporal target of shape {tuple(tgt.shape)}: expected ({h}, {w}, 3)")
-            if cert.numel() != h * w or tuple(cert.shape[-2:]) != (h, w):
-                raise ValueError(f"temporal certainty of shape {tuple(cert.shape)}: expected ({h}, {w})")
-            # the engine's own fixed buffers (a captured graph reads them at replay) + the scalar and the reduction's workspace
-            self._temporal = dict(weight=lam, target=tgt.float().to(dev).reshape(h, w, 3).contiguous().clone(),
-                                  certainty=cert.float().to(dev).reshape(h, w).contiguous().clone(),
-                                  loss=torch.zeros(1, dtype=torch.float32, device=dev),
-                                  ws=_ops.temporal_workspace(h, w, dev))
+            terms = [temporal] if isinstance(temporal, TemporalTarget) else temporal
+            for tt in terms:
+                if not isinstance(tt, TemporalTarget):
+                    raise ValueError(f"temporal targets must be TemporalTarget, got {type(tt).__name__}")
+                lam = float(tt.weight)
+                if not np.isfinite(lam) or lam < 0:
+                    raise ValueError(f"temporal weight must be finite and >= 0, got {tt.weight}")
+                tgt, cert = tt.target, tt.certainty
+                if tgt.numel() != 3 * h * w or tuple(tgt.shape[-3:]) != (h, w, 3):
+                    raise ValueError(f"temporal target of shape {tuple(tgt.shape)}: expected ({h}, {w}, 3)")
+                if cert.numel() != h * w or tuple(cert.shape[-2:]) != (h, w):
+                    raise ValueError(f"temporal certainty of shape {tuple(cert.shape)}: expected ({h}, {w})")
+            # the engine's own fixed buffers (a captured graph reads them at replay) + the scalars and the reduction's
+            # workspace
+            targets = [tt.target.float().to(dev).reshape(h, w, 3).contiguous().clone() for tt in terms]
+            certainties = [tt.certainty.float().to(dev).reshape(h, w).contiguous().clone() for tt in terms]
+            if isinstance(temporal, TemporalTarget):
+                self._temporal = dict(weight=float(temporal.weight), target=targets[0], certainty=certainties[0],
+                                      loss=torch.zeros(1, dtype=torch.float32, device=dev),
+                                      ws=_ops.temporal_workspace(h, w, dev))
+            else:
+                self._temporal = dict(weights=[float(tt.weight) for tt in terms], targets=targets, certainties=certainties,
+                                      loss=torch.zeros(len(terms), dtype=torch.float32, device=dev),
+                                      ws=_ops.temporal_multi_workspace(h, w, len(terms), dev))
         # --- variables = make_laplacian_pyramid(stylized) (run_strotss.py:89), rms slots start at 0
         from .strotss_utils import make_laplacian_pyramid
         self.variables = [v.contiguous() for v in make_laplacian_pyramid(stylized.contiguous(), levels)]
@@ -466,7 +485,12 @@ class StepEngine:
     def _temporal_term(self) -> None:
         """gvars[0] += lambda * dL_t/dx and the scalar L_t, x the folded image of this step (no temporal target: nothing)"""
         t = self._temporal
-        if t is not None:
+        if t is None:
+            return
+        if "targets" in t:                      # several targets: one launch for all of them
+            _ops.temporal_multi_fwd_bwd(self.fold[0], t["targets"], t["certainties"], t["weights"], self.gvars[0],
+                                        t["loss"], t["ws"])
+        else:
             _ops.temporal_fwd_bwd(self.fold[0], t["target"], t["certainty"], t["weight"], self.gvars[0], t["loss"], t["ws"])
 
     def _fold_adjoint(self) -> None:
@@ -664,10 +688,16 @@ class StepEngine:
                "l_palette": float(s[:, 3].mean())}
         if per_style is not None:
             out["per_style"] = per_style         # one dict per style of the blend: its weight and unweighted terms
-        if self._temporal is not None:           # added once per step, not averaged over the regions
-            lt = float(self._temporal["loss"].item())
+        t = self._temporal
+        if t is not None and "targets" in t:     # several targets: loss_t = sum_j L_j, loss + sum_j lambda_j L_j
+            terms = [float(v) for v in t["loss"].tolist()]
+            out["loss_t"] = float(sum(terms))
+            out["loss_t_terms"] = terms
+            out["loss"] = float(loss) + sum(lam * lt for lam, lt in zip(t["weights"], terms))
+        elif t is not None:                      # added once per step, not averaged over the regions
+            lt = float(t["loss"].item())
             out["loss_t"] = lt
-            out["loss"] = float(loss) + self._temporal["weight"] * lt
+            out["loss"] = float(loss) + t["weight"] * lt
         return out
 
     def stylized(self) -> torch.Tensor:

@@ -196,6 +196,12 @@ def temporal_target_at_scale(warped: torch.Tensor, certainty: torch.Tensor, h: i
     return _ops.resize_bilinear(x, int(h), int(w)), _ops.resize_bilinear(c, int(h), int(w)).reshape(int(h), int(w))
 
 
+
+def temporal_targets_at_scale(temporal, h: int, w: int):
+    """the long-term targets of a scale: [(warped_j, combined certainty_j)] nearest frame first, each
+    resized as temporal_target_at_scale resizes the one target -> [((h, w, 3), (h, w))]"""
+    return [temporal_target_at_scale(warped, certainty, h, w) for warped, certainty in temporal]
+
 class Sampling:
     """reference strotss_utils.py:20-136.  `rng` defaults to nn.rand.index_rng."""
 

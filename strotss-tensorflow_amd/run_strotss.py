@@ -25,6 +25,11 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
                     the artistic-videos tools) every frame after the first is pulled toward the previous result warped
                     along the flow, weight --temporal_weight; --temporal_init starts a frame's
                     first executed scale from that warped result.  One GPU; not with --strips.
+  --temporal_frames J [J ...]
+                    with --video: long-term consistency, 1 to 4 distinct positive frame offsets
+                    (default 1, the short-term term alone; Ruder et al. use 1 10 20 40).  Frame t is also pulled toward the
+                    results of frames t-j, warped along backward_{t}_{t-j}.flo (forward_{t-j}_{t}.flo, reliable_{t}_{t-j}.pgm
+                    as above), each only where no nearer frame covers the pixel; --temporal_init starts from the nearest.
   --strips          under torchrun (one process per GPU): ONE image on all GPUs -- every rank runs the trunk on its strip
                     of the image (+ halo) at the scales where that pays, two all-reduces per step (nn/parallel.py);
                     rank 0 writes the output
@@ -140,23 +145,43 @@ def _content_weight_input(args):
 
 
 DEFAULT_TEMPORAL_WEIGHT = 1000.0          # chosen on the MI355X with the consistency error
+MAX_TEMPORAL_FRAMES = 4                   # STROTSS_MAX_TEMPORAL: the targets of one strotss_temporal_multi_fwd_bwd launch
 IMAGE_SUFFIXES = (".jpg", ".jpeg", ".png", ".bmp", ".ppm", ".pgm", ".tif", ".tiff", ".webp")
+
+
+def _temporal_frames(args):
+    """--temporal_frames as an ascending tuple of 1..4 distinct positive frame offsets ((1,) when not given); ValueError
+    for a non-positive, repeated or fifth offset"""
+    raw = getattr(args, "temporal_frames", None)
+    if raw is None:
+        return (1,)
+    offsets = [int(j) for j in raw]
+    if not offsets or any(j < 1 for j in offsets):
+        raise ValueError(f"--temporal_frames takes positive frame offsets, got {raw}")
+    if len(set(offsets)) != len(offsets):
+        raise ValueError(f"--temporal_frames: repeated offset in {raw}")
+    if len(offsets) > MAX_TEMPORAL_FRAMES:
+        raise ValueError(f"--temporal_frames takes at most {MAX_TEMPORAL_FRAMES} offsets, got {len(offsets)}")
+    return tuple(sorted(offsets))
 
 
 def _video_inputs(args):
     """--video: (sorted frame paths, temporal weight); None without --video.  Refused with a ValueError before anything is
-    optimised: --temporal_weight / --flow_dir / --temporal_init without --video, a negative weight, --video with --strips or
-    under torchrun with WORLD_SIZE > 1, no --flow_dir, a content_path that is not a directory of frames, frames of different
-    sizes, a missing backward flow."""
+    optimised: --temporal_weight / --flow_dir / --temporal_init / --temporal_frames without --video, a negative weight, bad
+    --temporal_frames offsets (_temporal_frames), --video with --strips or under torchrun with WORLD_SIZE > 1, no --flow_dir,
+    a content_path that is not a directory of frames, frames of different sizes, a missing backward flow of any frame and
+    offset."""
     video = bool(getattr(args, "video", False))
     lam = getattr(args, "temporal_weight", None)
     flow_dir = getattr(args, "flow_dir", None)
     if not video:
         for flag, val in (("--temporal_weight", lam), ("--flow_dir", flow_dir),
-                          ("--temporal_init", getattr(args, "temporal_init", False) or None)):
+                          ("--temporal_init", getattr(args, "temporal_init", False) or None),
+                          ("--temporal_frames", getattr(args, "temporal_frames", None))):
             if val is not None:
                 raise ValueError(f"{flag} needs --video")
         return None
+    offsets = _temporal_frames(args)
     lam = DEFAULT_TEMPORAL_WEIGHT if lam is None else float(lam)
     if not np.isfinite(lam) or lam < 0:
         raise ValueError(f"--temporal_weight must be finite and >= 0, got {lam}")
@@ -180,31 +205,46 @@ def _video_inputs(args):
     if len(sizes) != 1:
         raise ValueError(f"--video: the frames differ in size: {sorted(sizes)}")
     for t in range(2, len(frames) + 1):
-        path = os.path.join(flow_dir, f"backward_{t}_{t - 1}.flo")
-        if not os.path.exists(path):
-            raise ValueError(f"--video: backward flow {path} of frame {t} is missing")
+        for j in offsets:
+            if t - j < 1:
+                continue
+            path = os.path.join(flow_dir, f"backward_{t}_{t - j}.flo")
+            if not os.path.exists(path):
+                raise ValueError(f"--video: backward flow {path} of frame {t} is missing")
     return frames, lam
 
 
-def _temporal_for_frame(args, t: int, previous: torch.Tensor):
-    """(warped previous result, certainty) of frame t (1-based, t >= 2) at the previous result's size: the flows of
-    --flow_dir resized to that size (strotss_utils.resize_flow), the warp and certainty in one launch; a
-    reliable_{t}_{t-1}.pgm, when there is one, replaces the certainty (its value / 255, resized)."""
+def _temporal_for_frame(args, t: int, previous: torch.Tensor, j: int = 1):
+    """(warped result of frame t-j, certainty) of frame t (1-based, t > j) at that result's size: the flows of --flow_dir
+    resized to that size (strotss_utils.resize_flow), the warp and certainty in one launch; a reliable_{t}_{t-j}.pgm, when
+    there is one, replaces the certainty (its value / 255, resized).  `previous`: the final result of frame t-j."""
     h, w = int(previous.shape[1]), int(previous.shape[2])
     dev = previous.device
-    flow_b = strotss.read_flo(os.path.join(args.flow_dir, f"backward_{t}_{t - 1}.flo"))
+    flow_b = strotss.read_flo(os.path.join(args.flow_dir, f"backward_{t}_{t - j}.flo"))
     big = tuple(flow_b.shape[:2])
-    fwd_path = os.path.join(args.flow_dir, f"forward_{t - 1}_{t}.flo")
+    fwd_path = os.path.join(args.flow_dir, f"forward_{t - j}_{t}.flo")
     flow_f = strotss.read_flo(fwd_path) if os.path.exists(fwd_path) else None
     if flow_f is not None and tuple(flow_f.shape[:2]) != big:
         raise ValueError(f"{fwd_path}: a {tuple(flow_f.shape[:2])} flow, the backward one is {big}")
     fb = strotss.resize_flow(flow_b.to(dev), h, w).contiguous()
     ff = None if flow_f is None else strotss.resize_flow(flow_f.to(dev), h, w).contiguous()
     warped, certainty = strotss_engine._ops.flow_warp(previous.contiguous(), fb, ff)
-    rel = os.path.join(args.flow_dir, f"reliable_{t}_{t - 1}.pgm")
+    rel = os.path.join(args.flow_dir, f"reliable_{t}_{t - j}.pgm")
     if os.path.exists(rel):
         certainty = _resized_reliable(rel, h, w)
     return warped, certainty
+
+
+def _temporal_targets_for_frame(args, t: int, results, offsets):
+    """[(warped result of frame t-j, combined certainty)] of frame t for the offsets j of `offsets` (ascending) with
+    t - j >= 1, nearest frame first.  results[k]: the final result of frame t-1-k.  Each pair is
+    _temporal_for_frame's; the certainties are combined once, at the frame's size (strotss_temporal_long_certainty), so
+    that a pixel a nearer frame covers does not pull toward an older one.  [] for the first frame."""
+    pairs = [_temporal_for_frame(args, t, results[j - 1], j) for j in offsets if t - j >= 1 and j <= len(results)]
+    if len(pairs) <= 1:                     # nothing nearer to subtract: the raw certainty is the combined one
+        return pairs
+    combined = strotss_engine._ops.temporal_long_certainty(torch.stack([c.float().contiguous() for _, c in pairs]))
+    return [(warped, combined[k]) for k, (warped, _) in enumerate(pairs)]
 
 
 def _resized_reliable(path: str, h: int, w: int) -> torch.Tensor:
@@ -372,7 +412,9 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
              temporal_weight: float = 0.0):
     """The coarse-to-fine schedule on one content image -> the final image of the finest scale (1, h, w, 3).
     temporal: (warped previous result, certainty) at that result's size, or None; every scale then carries the temporal
-    term with weight temporal_weight, and --temporal_init starts the first executed scale from the warped result."""
+    term with weight temporal_weight, and --temporal_init starts the first executed scale from the warped result.  A list
+    of 2..4 such pairs (combined certainties, nearest frame first) carries one term per pair, all
+    with weight temporal_weight; --temporal_init starts from the nearest."""
     from nn import parallel
     level, first = int(args.level), int(getattr(args, "start_level", 0))
     content = utils.load_image(content_path, max_size=args.max_size)
@@ -396,7 +438,12 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
                                       args.lr, style_weights)
         hs, ws = int(scl_content.shape[1]), int(scl_content.shape[2])
         tt = None
-        if temporal is not None:
+        if isinstance(temporal, list):
+            scaled = strotss.temporal_targets_at_scale(temporal, hs, ws)
+            tt = [strotss_engine.TemporalTarget(target, cert, temporal_weight) for target, cert in scaled]
+            if position == 0 and getattr(args, "temporal_init", False):
+                stylized = scaled[0][0][None].contiguous()   # the nearest frame's warp
+        elif temporal is not None:
             target, cert = strotss.temporal_target_at_scale(temporal[0], temporal[1], hs, ws)
             tt = strotss_engine.TemporalTarget(target, cert, temporal_weight)
             if position == 0 and getattr(args, "temporal_init", False):
@@ -428,7 +475,9 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
 def run_video(args: argparse.Namespace, trace=None):
     """--video: every frame of the directory content_path through the schedule of run(), one VGG for the sequence, the
     seeds reset for every frame (each frame draws the index stream a single-image run draws).  Frame t > 1 carries the
-    temporal term toward the previous result warped along the backward flow.  Writes
+    temporal term toward the previous result warped along the backward flow and, with
+    --temporal_frames, toward the results of frames t-j (the last max(J) results stay on the device).
+    Writes
     <output dir>/<frame stem>.jpg; returns the list of the frames' uint8 results.  `trace`: one list per frame."""
     frames, lam = _video_inputs(args)
     cw_path = _content_weight_input(args)
@@ -436,17 +485,24 @@ def run_video(args: argparse.Namespace, trace=None):
     dev = utils.device()
     os.makedirs(args.output_path, exist_ok=True)
     vgg = VGG(use_keras_weight=args.use_keras_weight, weights=getattr(args, "weights", None), seed=seed, device=dev)
+    offsets = _temporal_frames(args)
     previous, outs = None, []
+    results = []                            # results[k]: the final image of frame t-1-k, the last max(offsets) of them
     for t, frame in enumerate(frames, start=1):
         timer = utils.Timer()
         timer.start()
         rand.seed_everything(seed)
-        temporal = _temporal_for_frame(args, t, previous) if previous is not None else None
+        if offsets == (1,):
+            temporal = _temporal_for_frame(args, t, previous) if previous is not None else None
+        else:
+            pairs = _temporal_targets_for_frame(args, t, results, offsets)
+            temporal = None if not pairs else pairs[0] if len(pairs) == 1 else pairs
         rec = None
         if trace is not None:
             rec = []
             trace.append(rec)
         previous = _stylise(args, vgg, frame, cw_path, dev, trace=rec, temporal=temporal, temporal_weight=lam)
+        results = [previous] + results[:offsets[-1] - 1]
         final = strotss.postprocess(previous)
         if torch.cuda.is_available():
             torch.cuda.synchronize()
@@ -485,6 +541,10 @@ _FLAGS = (
                                   help=f"with --video: weight of the temporal term (default {DEFAULT_TEMPORAL_WEIGHT:g})")),
     (("--temporal_init",), dict(action='store_true', help="with --video: frames after the first start their first executed "
                                                           "scale from the warped previous result")),
+    (("--temporal_frames",), dict(type=int, nargs='+', default=None, metavar='J',
+                                  help="with --video: 1 to 4 distinct positive frame offsets of the long-term temporal term "
+                                       "(default 1; Ruder et al. use 1 10 20 40): frame t is also pulled toward frame t-j's "
+                                       "result along backward_{t}_{t-j}.flo where no nearer frame covers the pixel")),
     (("--strips",), dict(action='store_true', help="under torchrun: shard ONE image over the GPUs by image strips")),
     (("--halo",), dict(action='store_true', help="with --strips: per-layer halo EXCHANGE with the neighbouring ranks (16-row "
                                                  "windows margins, one row per layer and direction) instead of a 128-row recompute margin")),
