@@ -521,6 +521,37 @@ int strotss_temporal_multi_fwd_bwd(const float* img, const strotss_temporal_set_
                                    float* loss_out, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Optical flow between two frames: what strotss_flow_warp consumes, computed by the library
+ * --------------------------------------------------------------------------------------- */
+/* Coarse-to-fine Horn-Schunck with warping, solved by Jacobi iterations (Meinhardt-Llopis, Sanchez, Kondermann, IPOL 2013,
+ * Jacobi in place of SOR: no sweep order, no atomics, the same bits on every run).  frame_a, frame_b: (h, w, 3) RGB in
+ * [0, 1]; flow_out: (h, w, 2) = (u, v), x and y displacement in pixels with frame_a(p) ~ frame_b(p + flow(p)) -- flow_b of
+ * strotss_flow_warp for frame t is (frame_t, frame_{t-j}), flow_f is (frame_{t-j}, frame_t).
+ *   1. grey g = 0.299 R + 0.587 G + 0.114 B;  2. level 0 of each pyramid = blur(g), blur = separable [1 4 6 4 1] / 16, along
+ *   the rows then the columns, indices clamped;  3. level k+1 = blur(level k)[::2, ::2] (ceil(h/2) x ceil(w/2)) while
+ *   min(h_k, w_k) / 2 >= min_side and fewer than max_levels levels;  4. u = v = 0 at the coarsest level; to a finer level:
+ *   u'(y, x) = 2 bilinear(u, x/2, y/2), v' likewise (the 4-neighbour, edge-clamped rule of strotss_flow_warp);  5. per level,
+ *   `warps` times: Bw = bilinear(B_k, x + u, y + v), Ix, Iy = central differences of Bw with clamped indices,
+ *   c = Bw - A_k - Ix u - Iy v, inv = 1 / (alpha2 + Ix^2 + Iy^2), then `iters` times for all pixels at once:
+ *   ub = (N + S + W + E of u) / 6 + (the four diagonals of u) / 12 with clamped indices, vb likewise,
+ *   t = (Ix ub + Iy vb + c) inv, u <- ub - Ix t, v <- vb - Iy t;  6. flow = (u, v) of level 0.  float32 throughout.
+ * iters_per_launch: 1 = one sweep per launch; 2, 4, 8 = that many sweeps per launch on LDS-resident tiles with a halo
+ * (bit for bit the results of 1).  alpha2 is the smoothness weight for greys in [0, 1]. */
+typedef struct { float alpha2; int warps, iters, min_side, max_levels, iters_per_launch; } strotss_flow_params_t;
+/* the defaults: alpha2 0.01, warps 5, iters 32, min_side 12, max_levels 8, iters_per_launch 8 */
+void strotss_flow_default_params(strotss_flow_params_t* out);
+/* bytes of the workspace of strotss_optical_flow (both pyramids, the (u, v) ping-pong, the coefficients); 0 on bad
+ * arguments (see below).  params == NULL: the defaults. */
+size_t strotss_flow_workspace_bytes(int h, int w, const strotss_flow_params_t* params);
+/* The whole flow on `stream` from this one call.  params == NULL: the defaults, with iters_per_launch = 1 above 4096
+ * pixels, where the one-sweep form measured faster (the same bits either way).  STROTSS_EINVAL (nothing is launched or
+ * written): a null pointer, h or w < 2, h w > 2^28, alpha2 not finite or <= 0, warps or iters < 1, min_side < 1, max_levels
+ * outside 1 .. STROTSS_MAX_LEVELS, iters_per_launch not in {1, 2, 4, 8} or not dividing iters, workspace_bytes below
+ * strotss_flow_workspace_bytes(h, w, params); STROTSS_EALIGN: frame_a, frame_b, flow_out or workspace not 16-byte aligned. */
+int strotss_optical_flow(const float* frame_a, const float* frame_b, int h, int w, const strotss_flow_params_t* params,
+                         float* flow_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Optimiser + output
  * --------------------------------------------------------------------------------------- */
 typedef struct {

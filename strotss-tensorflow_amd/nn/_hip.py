@@ -78,6 +78,12 @@ class TemporalSetT(C.Structure):
                 ("gscale", C.c_float * MAX_TEMPORAL)]
 
 
+class FlowParamsT(C.Structure):
+    """strotss_flow_params_t (include/strotss_hip.h): the parameters of strotss_optical_flow"""
+    _fields_ = [("alpha2", C.c_float), ("warps", C.c_int), ("iters", C.c_int), ("min_side", C.c_int),
+                ("max_levels", C.c_int), ("iters_per_launch", C.c_int)]
+
+
 _P, _I, _F, _Z, _L = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
 # name -> (restype, argtypes); must list EVERY symbol include/strotss_hip.h declares
 SIGNATURES = {
@@ -156,6 +162,9 @@ SIGNATURES = {
     "strotss_temporal_long_certainty": (_I, [_P, _I, _I, _I, _P, _P]),
     "strotss_temporal_multi_workspace_bytes": (_Z, [_I, _I, _I]),
     "strotss_temporal_multi_fwd_bwd": (_I, [_P, C.POINTER(TemporalSetT), _I, _I, _P, _P, _P, _P]),
+    "strotss_flow_default_params": (None, [C.POINTER(FlowParamsT)]),
+    "strotss_flow_workspace_bytes": (_Z, [_I, _I, C.POINTER(FlowParamsT)]),
+    "strotss_optical_flow": (_I, [_P, _P, _I, _I, C.POINTER(FlowParamsT), _P, _P, _Z, _P]),
     "strotss_rmsprop_step": (_I, [C.POINTER(TensorsT), _F, _F, _F, _P]),
     "strotss_postprocess": (_I, [_P, _L, _P, _P, _P]),
 }

@@ -180,6 +180,46 @@ def temporal_multi_fwd_bwd(img: torch.Tensor, targets: Sequence[torch.Tensor], c
                                                     stream_ptr()), "temporal_multi_fwd_bwd")
 
 
+def flow_params(**overrides) -> "_hip.FlowParamsT":
+    """strotss_flow_params_t with the library's defaults (strotss_flow_default_params; needs no GPU), fields overridden by
+    name: alpha2, warps, iters, min_side, max_levels, iters_per_launch"""
+    p = _hip.FlowParamsT()
+    _hip.load_library().strotss_flow_default_params(C.byref(p))
+    names = {f[0] for f in _hip.FlowParamsT._fields_}
+    for key, val in overrides.items():
+        if key not in names:
+            raise ValueError(f"unknown flow parameter {key!r}: expected one of {sorted(names)}")
+        setattr(p, key, val)
+    return p
+
+
+def optical_flow(frame_a: torch.Tensor, frame_b: torch.Tensor, params: Optional["_hip.FlowParamsT"] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the dense optical flow (h, w, 2) = (u, v) with frame_a(p) ~ frame_b(p + flow(p)) (strotss_optical_flow, DESIGN.md
+    section 14): frames (h, w, 3) or (1, h, w, 3) RGB in [0, 1]; params from flow_params(), None = the defaults.  The
+    backward flow of frame t for strotss_flow_warp is optical_flow(frame_t, frame_{t-j}), the forward one
+    optical_flow(frame_{t-j}, frame_t)."""
+    require(frame_a, "frame a")
+    require(frame_b, "frame b")
+    h, w, c = hwc(frame_a)
+    if c != 3 or frame_a.numel() != 3 * h * w or tuple(frame_b.shape[-3:]) != (h, w, 3) or frame_b.numel() != 3 * h * w:
+        raise ValueError(f"frames of shape {tuple(frame_a.shape)} and {tuple(frame_b.shape)}: expected two (h, w, 3) images "
+                         f"of one size")
+    lib = _hip.lib()
+    pp = None if params is None else C.byref(params)
+    nb = int(lib.strotss_flow_workspace_bytes(h, w, pp))
+    if nb == 0:
+        raise _hip.StrotssHipError(f"optical_flow: bad size {h} x {w} or parameters")
+    if out is None:
+        out = torch.empty((h, w, 2), dtype=torch.float32, device=frame_a.device)
+    require(out, "flow")
+    assert out.numel() == 2 * h * w
+    workspace = torch.empty(nb, dtype=torch.uint8, device=frame_a.device)
+    check(lib.strotss_optical_flow(ptr(frame_a), ptr(frame_b), h, w, pp, ptr(out), ptr(workspace), nb, stream_ptr()),
+          "optical_flow")
+    return out
+
+
 def resize_bilinear_adjoint(gout: torch.Tensor, ih: int, iw: int,
                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
     require(gout, "resize adjoint input")

@@ -168,6 +168,21 @@ def read_flo(path: str) -> torch.Tensor:
     return torch.from_numpy(np.frombuffer(raw[12:], dtype="<f4").astype(np.float32).reshape(h, w, 2))
 
 
+def write_flo(path: str, flow) -> None:
+    """The inverse of read_flo: a (h, w, 2) flow (tensor on any device, or array) as a Middlebury .flo file -- the magic
+    number as float32, (w, h) as little-endian int32, then the (u, v) pairs row by row as little-endian float32."""
+    if isinstance(flow, torch.Tensor):
+        flow = flow.detach().cpu().numpy()
+    flow = np.asarray(flow, dtype=np.float32)
+    if flow.ndim != 3 or flow.shape[-1] != 2:
+        raise ValueError(f"flow of shape {tuple(flow.shape)}: expected (h, w, 2)")
+    h, w = flow.shape[:2]
+    with open(path, "wb") as f:
+        f.write(np.array([FLO_MAGIC], dtype="<f4").tobytes())
+        f.write(np.array([w, h], dtype="<i4").tobytes())
+        f.write(np.ascontiguousarray(flow).astype("<f4").tobytes())
+
+
 def resize_flow(flow: torch.Tensor, h: int, w: int) -> torch.Tensor:
     """A (H, W, 2) flow field at the size (h, w) of resized frames: both components resized bilinearly (the kernel of
     utils.resize), u multiplied by w / W and v by h / H.  The same size: an unchanged copy.  -> (h, w, 2) float32 on the

@@ -30,6 +30,12 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
                     (default 1, the short-term term alone; Ruder et al. use 1 10 20 40).  Frame t is also pulled toward the
                     results of frames t-j, warped along backward_{t}_{t-j}.flo (forward_{t-j}_{t}.flo, reliable_{t}_{t-j}.pgm
                     as above), each only where no nearer frame covers the pixel; --temporal_init starts from the nearest.
+  --compute_flow    with --video, instead of --flow_dir: the flows are computed on the GPU from the content frames at the
+                    results' size (strotss_optical_flow, coarse-to-fine Horn-Schunck), backward and
+                    forward for every --temporal_frames offset; no reliable_*.pgm is involved.  --flow_dir stays the way to
+                    bring better flow from elsewhere.
+  --save_flow DIR   with --compute_flow: also write the computed flows to DIR as backward_{t}_{t-j}.flo and
+                    forward_{t-j}_{t}.flo (a later run with --flow_dir DIR reads the same floats back)
   --strips          under torchrun (one process per GPU): ONE image on all GPUs -- every rank runs the trunk on its strip
                     of the image (+ halo) at the scales where that pays, two all-reduces per step (nn/parallel.py);
                     rank 0 writes the output
@@ -168,18 +174,26 @@ def _temporal_frames(args):
 def _video_inputs(args):
     """--video: (sorted frame paths, temporal weight); None without --video.  Refused with a ValueError before anything is
     optimised: --temporal_weight / --flow_dir / --temporal_init / --temporal_frames without --video, a negative weight, bad
-    --temporal_frames offsets (_temporal_frames), --video with --strips or under torchrun with WORLD_SIZE > 1, no --flow_dir,
-    a content_path that is not a directory of frames, frames of different sizes, a missing backward flow of any frame and
-    offset."""
+    --temporal_frames offsets (_temporal_frames), --video with --strips or under torchrun with WORLD_SIZE > 1, neither
+    --flow_dir nor --compute_flow, a content_path that is not a directory of frames, frames of different sizes, a missing
+    backward flow of any frame and offset (--flow_dir only); --compute_flow without --video or together with --flow_dir,
+    --save_flow without --compute_flow."""
     video = bool(getattr(args, "video", False))
     lam = getattr(args, "temporal_weight", None)
     flow_dir = getattr(args, "flow_dir", None)
+    compute_flow = bool(getattr(args, "compute_flow", False))
     if not video:
         for flag, val in (("--temporal_weight", lam), ("--flow_dir", flow_dir),
                           ("--temporal_init", getattr(args, "temporal_init", False) or None),
-                          ("--temporal_frames", getattr(args, "temporal_frames", None))):
+                          ("--temporal_frames", getattr(args, "temporal_frames", None)),
+                          ("--compute_flow", compute_flow or None)):
             if val is not None:
                 raise ValueError(f"{flag} needs --video")
+    if getattr(args, "save_flow", None) and not compute_flow:
+        raise ValueError("--save_flow needs --compute_flow (it writes the flows the run computes)")
+    if compute_flow and flow_dir:
+        raise ValueError("--compute_flow and --flow_dir exclude each other: the flows are computed or read, not both")
+    if not video:
         return None
     offsets = _temporal_frames(args)
     lam = DEFAULT_TEMPORAL_WEIGHT if lam is None else float(lam)
@@ -189,7 +203,7 @@ def _video_inputs(args):
         raise ValueError("--video cannot be combined with --strips")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise ValueError("--video runs on one GPU: not under torchrun with WORLD_SIZE > 1")
-    if not flow_dir:
+    if not flow_dir and not compute_flow:
         raise ValueError("--video needs --flow_dir (the optical flow between consecutive frames)")
     if not os.path.isdir(args.content_path):
         raise ValueError(f"--video: content_path {args.content_path} is not a directory of frames")
@@ -206,7 +220,7 @@ def _video_inputs(args):
         raise ValueError(f"--video: the frames differ in size: {sorted(sizes)}")
     for t in range(2, len(frames) + 1):
         for j in offsets:
-            if t - j < 1:
+            if t - j < 1 or compute_flow:               # computed flows: no file to look for
                 continue
             path = os.path.join(flow_dir, f"backward_{t}_{t - j}.flo")
             if not os.path.exists(path):
@@ -214,12 +228,40 @@ def _video_inputs(args):
     return frames, lam
 
 
-def _temporal_for_frame(args, t: int, previous: torch.Tensor, j: int = 1):
+def _frame_at_result_size(args, path: str) -> torch.Tensor:
+    """a content frame (h, w, 3) on the device at the size of a frame's final result: resized as _stylise makes the content
+    of its last executed scale"""
+    scl = 2 << (5 + int(args.level) - 1)
+    return utils.resize(utils.load_image(path, max_size=args.max_size), scl)[0].contiguous()
+
+
+def _computed_flows(args, t: int, j: int, frames, h: int, w: int):
+    """--compute_flow: (backward, forward) flow of frame t against frame t-j, both (h, w, 2), by strotss_optical_flow on the
+    content frames at the results' size.  frames: {1-based position: (h, w, 3) frame on the device}.  --save_flow DIR
+    writes them as backward_{t}_{t-j}.flo and forward_{t-j}_{t}.flo."""
+    cur, old = frames[t], frames[t - j]
+    if tuple(cur.shape) != (h, w, 3) or tuple(old.shape) != (h, w, 3):
+        raise ValueError(f"--compute_flow: frames of {tuple(cur.shape)} and {tuple(old.shape)}, the results are {h} x {w}")
+    fb = strotss_engine._ops.optical_flow(cur, old)
+    ff = strotss_engine._ops.optical_flow(old, cur)
+    save = getattr(args, "save_flow", None)
+    if save:
+        os.makedirs(save, exist_ok=True)
+        strotss.write_flo(os.path.join(save, f"backward_{t}_{t - j}.flo"), fb)
+        strotss.write_flo(os.path.join(save, f"forward_{t - j}_{t}.flo"), ff)
+    return fb, ff
+
+
+def _temporal_for_frame(args, t: int, previous: torch.Tensor, j: int = 1, frames=None):
     """(warped result of frame t-j, certainty) of frame t (1-based, t > j) at that result's size: the flows of --flow_dir
     resized to that size (strotss_utils.resize_flow), the warp and certainty in one launch; a reliable_{t}_{t-j}.pgm, when
-    there is one, replaces the certainty (its value / 255, resized).  `previous`: the final result of frame t-j."""
+    there is one, replaces the certainty (its value / 255, resized).  `previous`: the final result of frame t-j.
+    --compute_flow: both flows come from _computed_flows(frames) at that size instead; no file is read."""
     h, w = int(previous.shape[1]), int(previous.shape[2])
     dev = previous.device
+    if getattr(args, "compute_flow", False):
+        fb, ff = _computed_flows(args, t, j, frames, h, w)
+        return strotss_engine._ops.flow_warp(previous.contiguous(), fb, ff)
     flow_b = strotss.read_flo(os.path.join(args.flow_dir, f"backward_{t}_{t - j}.flo"))
     big = tuple(flow_b.shape[:2])
     fwd_path = os.path.join(args.flow_dir, f"forward_{t - j}_{t}.flo")
@@ -235,12 +277,12 @@ def _temporal_for_frame(args, t: int, previous: torch.Tensor, j: int = 1):
     return warped, certainty
 
 
-def _temporal_targets_for_frame(args, t: int, results, offsets):
+def _temporal_targets_for_frame(args, t: int, results, offsets, frames=None):
     """[(warped result of frame t-j, combined certainty)] of frame t for the offsets j of `offsets` (ascending) with
     t - j >= 1, nearest frame first.  results[k]: the final result of frame t-1-k.  Each pair is
     _temporal_for_frame's; the certainties are combined once, at the frame's size (strotss_temporal_long_certainty), so
     that a pixel a nearer frame covers does not pull toward an older one.  [] for the first frame."""
-    pairs = [_temporal_for_frame(args, t, results[j - 1], j) for j in offsets if t - j >= 1 and j <= len(results)]
+    pairs = [_temporal_for_frame(args, t, results[j - 1], j, frames) for j in offsets if t - j >= 1 and j <= len(results)]
     if len(pairs) <= 1:                     # nothing nearer to subtract: the raw certainty is the combined one
         return pairs
     combined = strotss_engine._ops.temporal_long_certainty(torch.stack([c.float().contiguous() for _, c in pairs]))
@@ -477,7 +519,8 @@ def run_video(args: argparse.Namespace, trace=None):
     seeds reset for every frame (each frame draws the index stream a single-image run draws).  Frame t > 1 carries the
     temporal term toward the previous result warped along the backward flow and, with
     --temporal_frames, toward the results of frames t-j (the last max(J) results stay on the device).
-    Writes
+    With --compute_flow the flows come from strotss_optical_flow on the content frames at the results' size (DESIGN.md
+    section 14; the last max(J) + 1 of those frames stay on the device as well).  Writes
     <output dir>/<frame stem>.jpg; returns the list of the frames' uint8 results.  `trace`: one list per frame."""
     frames, lam = _video_inputs(args)
     cw_path = _content_weight_input(args)
@@ -488,14 +531,18 @@ def run_video(args: argparse.Namespace, trace=None):
     offsets = _temporal_frames(args)
     previous, outs = None, []
     results = []                            # results[k]: the final image of frame t-1-k, the last max(offsets) of them
+    flow_frames = {} if getattr(args, "compute_flow", False) else None      # --compute_flow: the last max(offsets) + 1 frames
     for t, frame in enumerate(frames, start=1):
         timer = utils.Timer()
         timer.start()
         rand.seed_everything(seed)
+        if flow_frames is not None:
+            flow_frames[t] = _frame_at_result_size(args, frame)
+            flow_frames.pop(t - offsets[-1] - 1, None)
         if offsets == (1,):
-            temporal = _temporal_for_frame(args, t, previous) if previous is not None else None
+            temporal = _temporal_for_frame(args, t, previous, frames=flow_frames) if previous is not None else None
         else:
-            pairs = _temporal_targets_for_frame(args, t, results, offsets)
+            pairs = _temporal_targets_for_frame(args, t, results, offsets, flow_frames)
             temporal = None if not pairs else pairs[0] if len(pairs) == 1 else pairs
         rec = None
         if trace is not None:
@@ -545,6 +592,11 @@ _FLAGS = (
                                   help="with --video: 1 to 4 distinct positive frame offsets of the long-term temporal term "
                                        "(default 1; Ruder et al. use 1 10 20 40): frame t is also pulled toward frame t-j's "
                                        "result along backward_{t}_{t-j}.flo where no nearer frame covers the pixel")),
+    (("--compute_flow",), dict(action='store_true', help="with --video, instead of --flow_dir: compute the optical flows between "
+                                                         "the frames on the GPU (both directions, every --temporal_frames offset)")),
+    (("--save_flow",), dict(type=str, default=None, metavar='DIR',
+                            help="with --compute_flow: write the computed flows there as backward_{t}_{t-j}.flo and "
+                                 "forward_{t-j}_{t}.flo")),
     (("--strips",), dict(action='store_true', help="under torchrun: shard ONE image over the GPUs by image strips")),
     (("--halo",), dict(action='store_true', help="with --strips: per-layer halo EXCHANGE with the neighbouring ranks (16-row "
                                                  "windows margins, one row per layer and direction) instead of a 128-row recompute margin")),
