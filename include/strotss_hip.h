@@ -552,6 +552,32 @@ int strotss_optical_flow(const float* frame_a, const float* frame_b, int h, int 
                          float* flow_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Colour preservation: keep the content's colours, after Gatys et al. (2016)
+ * --------------------------------------------------------------------------------------- */
+/* Images are (h, w, 3) float32 RGB, a weight plane is (h, w) float32 >= 0 (NULL = all ones); every pointer 16-byte aligned.
+ * The three entries refuse, before anything is launched: STROTSS_EINVAL for a null required pointer, h or w <= 0,
+ * 3 h w > INT_MAX; STROTSS_EALIGN for a pointer that is not 16-byte aligned. */
+/* bytes of the workspace of strotss_color_stats (0 for h, w <= 0 or 3 h w > INT_MAX) */
+size_t strotss_color_stats_workspace_bytes(int h, int w);
+/* The colour statistics of an image, in ONE launch:  out[0] = W = sum_p m(p),  out[1..3] = S_i = sum_p m(p) x_i(p),
+ * out[4..9] = S_ij = sum_p m(p) x_i(p) x_j(p) for (i, j) = (0,0) (0,1) (0,2) (1,1) (1,2) (2,2), m = weight (NULL: 1).
+ * Accumulated in float64 (the products of two float32 values are exact there): per-thread sums in element order, a fixed
+ * tree per block, the block partials summed in a fixed order by the last block to finish (integer ticket, no float
+ * atomics) -- the same ten doubles, bit for bit, on every run.  out: ten doubles in DEVICE memory.  workspace:
+ * strotss_color_stats_workspace_bytes(h, w) bytes, ZEROED before its first use; every call leaves it ready for the next
+ * (one call at a time).  Mean and covariance are formed by the caller: mu = S / W, Sigma = S_ij / W - mu mu^T. */
+int strotss_color_stats(const float* img, const float* weight, int h, int w, double* out, void* workspace, void* stream);
+/* out(p) = A img(p) + b where weight(p) != 0 (NULL: everywhere), img(p) bit for bit elsewhere.  A (row-major 3 x 3) and
+ * b (3) are HOST arrays, read during the call; a value that is not finite: STROTSS_EINVAL.  Per output channel
+ * b_i + A_i0 x_0 + A_i1 x_1 + A_i2 x_2 in float32, evaluated left to right, NOT clamped to [0, 1].  out may equal img. */
+int strotss_color_affine(const float* img, const float* weight, int h, int w, const float* A, const float* b, float* out,
+                         void* stream);
+/* "The luma of the result on the chroma of the content":  out_ch(p) = content_ch(p) + (Y(result(p)) - Y(content(p))),
+ * Y = 0.299 R + 0.587 G + 0.114 B in float32 (the inverse of the RGB -> YUV matrix sends Y to (1, 1, 1)).  result == content
+ * returns the content bit for bit.  out may equal result or content. */
+int strotss_luma_merge(const float* result, const float* content, int h, int w, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Optimiser + output
  * --------------------------------------------------------------------------------------- */
 typedef struct {

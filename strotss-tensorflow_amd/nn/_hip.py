@@ -165,6 +165,10 @@ SIGNATURES = {
     "strotss_flow_default_params": (None, [C.POINTER(FlowParamsT)]),
     "strotss_flow_workspace_bytes": (_Z, [_I, _I, C.POINTER(FlowParamsT)]),
     "strotss_optical_flow": (_I, [_P, _P, _I, _I, C.POINTER(FlowParamsT), _P, _P, _Z, _P]),
+    "strotss_color_stats_workspace_bytes": (_Z, [_I, _I]),
+    "strotss_color_stats": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    "strotss_color_affine": (_I, [_P, _P, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _P]),
+    "strotss_luma_merge": (_I, [_P, _P, _I, _I, _P, _P]),
     "strotss_rmsprop_step": (_I, [C.POINTER(TensorsT), _F, _F, _F, _P]),
     "strotss_postprocess": (_I, [_P, _L, _P, _P, _P]),
 }

@@ -5,6 +5,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _hip
@@ -217,6 +218,75 @@ def optical_flow(frame_a: torch.Tensor, frame_b: torch.Tensor, params: Optional[
     workspace = torch.empty(nb, dtype=torch.uint8, device=frame_a.device)
     check(lib.strotss_optical_flow(ptr(frame_a), ptr(frame_b), h, w, pp, ptr(out), ptr(workspace), nb, stream_ptr()),
           "optical_flow")
+    return out
+
+
+# ------------------------------------------------------------------ colour preservation
+_color_ws = {}
+
+
+def _rgb_image(t: torch.Tensor, name: str) -> Tuple[int, int]:
+    """(h, w) of an (h, w, 3) or (1, h, w, 3) image on the device; ValueError for another shape"""
+    require(t, name)
+    if t.dim() not in (3, 4) or int(t.shape[-1]) != 3 or t.numel() != 3 * int(t.shape[-3]) * int(t.shape[-2]):
+        raise ValueError(f"{name} of shape {tuple(t.shape)}: expected (h, w, 3) or (1, h, w, 3)")
+    return int(t.shape[-3]), int(t.shape[-2])
+
+
+def _weight_plane(weight: Optional[torch.Tensor], h: int, w: int, name: str) -> Optional[torch.Tensor]:
+    if weight is None:
+        return None
+    require(weight, name)
+    if weight.numel() != h * w or tuple(weight.shape[:2]) != (h, w):
+        raise ValueError(f"{name} of shape {tuple(weight.shape)}: expected ({h}, {w}) or ({h}, {w}, 1)")
+    return weight
+
+
+def color_stats(img: torch.Tensor, weight: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the ten float64 sums (W, S_0, S_1, S_2, S_00, S_01, S_02, S_11, S_12, S_22) of an (h, w, 3) image under an optional
+    (h, w) weight plane, on the device (strotss_color_stats; one launch, the same bits on every run).  The workspace is a
+    module-level one per device and size, zeroed when it is made."""
+    h, w = _rgb_image(img, "image")
+    weight = _weight_plane(weight, h, w, "weight plane")
+    lib = _hip.lib()
+    key = (str(img.device), h, w)
+    workspace = _color_ws.get(key)
+    if workspace is None:
+        nb = int(lib.strotss_color_stats_workspace_bytes(h, w))
+        if nb == 0:
+            raise _hip.StrotssHipError(f"color_stats: bad size {h} x {w}")
+        workspace = _color_ws[key] = torch.zeros(nb, dtype=torch.uint8, device=img.device)
+    out = torch.empty(10, dtype=torch.float64, device=img.device)
+    check(lib.strotss_color_stats(ptr(img), ptr(weight), h, w, ptr(out), ptr(workspace), stream_ptr()), "color_stats")
+    return out
+
+
+def color_affine(img: torch.Tensor, A, b, weight: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out(p) = A img(p) + b where weight(p) != 0 (None: everywhere), img(p) elsewhere (strotss_color_affine): A nine and b
+    three host values, rounded to float32 here; out may be img."""
+    h, w = _rgb_image(img, "image")
+    weight = _weight_plane(weight, h, w, "weight plane")
+    a9 = (C.c_float * 9)(*np.asarray(A, dtype=np.float64).reshape(9).astype(np.float32).tolist())
+    b3 = (C.c_float * 3)(*np.asarray(b, dtype=np.float64).reshape(3).astype(np.float32).tolist())
+    if out is None:
+        out = torch.empty_like(img)
+    require(out, "recoloured image")
+    assert out.numel() == img.numel()
+    check(_hip.lib().strotss_color_affine(ptr(img), ptr(weight), h, w, a9, b3, ptr(out), stream_ptr()), "color_affine")
+    return out
+
+
+def luma_merge(result: torch.Tensor, content: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out_ch = content_ch + (Y(result) - Y(content)) (strotss_luma_merge): two images of one size; out may be result."""
+    h, w = _rgb_image(result, "result")
+    if _rgb_image(content, "content") != (h, w):
+        raise ValueError(f"result of shape {tuple(result.shape)} and content of shape {tuple(content.shape)} differ in size")
+    if out is None:
+        out = torch.empty_like(result)
+    require(out, "merged image")
+    assert out.numel() == result.numel()
+    check(_hip.lib().strotss_luma_merge(ptr(result), ptr(content), h, w, ptr(out), stream_ptr()), "luma_merge")
     return out
 
 

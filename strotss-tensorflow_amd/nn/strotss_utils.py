@@ -306,6 +306,105 @@ def postprocess(final: torch.Tensor) -> torch.Tensor:
     return _ops.postprocess(final.detach().float().contiguous())[0]
 
 
+# ----------------------------------------------------------------------------- colour preservation
+COLOUR_EPS = (1.0 / 255.0) ** 2          # a channel whose spread is below one 8-bit step counts as flat
+
+
+def _rgb(image, name: str) -> torch.Tensor:
+    """an (h, w, 3) or (1, h, w, 3) image -> the (h, w, 3) float32 view on the device; ValueError for another shape"""
+    if not torch.is_tensor(image):
+        image = torch.as_tensor(np.asarray(image))
+    if image.dim() == 4 and image.shape[0] == 1:
+        image = image[0]
+    if image.dim() != 3 or image.shape[-1] != 3 or image.shape[0] < 1 or image.shape[1] < 1:
+        raise ValueError(f"{name} of shape {tuple(image.shape)}: expected (h, w, 3) or (1, h, w, 3)")
+    return image.float().to(utils.device()).contiguous()
+
+
+def _plane(mask, h: int, w: int, name: str) -> Optional[torch.Tensor]:
+    """an (h, w), (h, w, 1) or (1, h, w, 1) weight plane -> (h, w) float32 on the device; ValueError for another shape"""
+    if mask is None:
+        return None
+    if not torch.is_tensor(mask):
+        mask = torch.as_tensor(np.asarray(mask))
+    if tuple(mask.shape) not in ((h, w), (h, w, 1), (1, h, w, 1)):
+        raise ValueError(f"{name} of shape {tuple(mask.shape)}: expected ({h}, {w}) for an image of that size")
+    return mask.float().to(utils.device()).reshape(h, w).contiguous()
+
+
+def colour_statistics(image, mask=None) -> Tuple[np.ndarray, np.ndarray]:
+    """(mu, Sigma) of an (h, w, 3) image, float64 numpy: the weighted mean colour and the biased covariance under the
+    optional weight plane `mask` ((h, w), >= 0; None = all ones).  The ten sums come from strotss_color_stats in float64;
+    mu = S / W and Sigma = S_ij / W - mu mu^T are formed here.  ValueError: shapes that do not match, W == 0 (an empty
+    mask region), statistics that are not finite."""
+    x = _rgb(image, "image")
+    h, w = int(x.shape[0]), int(x.shape[1])
+    sums = _ops.color_stats(x, _plane(mask, h, w, "mask")).cpu().numpy()
+    if not np.isfinite(sums).all():
+        raise ValueError("colour statistics: the image or the mask holds values that are not finite")
+    if sums[0] == 0:
+        raise ValueError("colour statistics: the mask selects no pixel (W == 0)")
+    if sums[0] < 0:
+        raise ValueError("colour statistics: the mask's weights must be >= 0")
+    mu = sums[1:4] / sums[0]
+    second = np.empty((3, 3))
+    second[np.triu_indices(3)] = sums[4:10]
+    second = np.triu(second) + np.triu(second, 1).T
+    return mu, second / sums[0] - np.outer(mu, mu)
+
+
+def _sym_power(sigma: np.ndarray, power: float) -> np.ndarray:
+    """(sigma + eps I)^power of a symmetric 3 x 3 matrix through its float64 eigendecomposition"""
+    lam, vec = np.linalg.eigh(sigma)
+    lam = lam + COLOUR_EPS
+    if not (lam > 0).all():
+        raise ValueError(f"colour covariance is not positive semi-definite (eigenvalues {lam - COLOUR_EPS})")
+    return (vec * lam ** power) @ vec.T
+
+
+def colour_transform(mu_s, sigma_s, mu_c, sigma_c) -> Tuple[np.ndarray, np.ndarray]:
+    """(A, b), float64, of the affine map that gives the style's colours the content's mean and covariance (Gatys et al.
+    2016): A = (Sigma_c + eps I)^(1/2) (Sigma_s + eps I)^(-1/2), b = mu_c - A mu_s, eps = (1/255)^2, symmetric roots.
+    Then mean(A s + b) = mu_c and cov(A s + b) = Sigma_c + eps (I - A A^T) exactly.  Pure host.  ValueError: shapes other
+    than (3,) and (3, 3), values that are not finite."""
+    mu_s, mu_c = np.asarray(mu_s, dtype=np.float64), np.asarray(mu_c, dtype=np.float64)
+    sigma_s, sigma_c = np.asarray(sigma_s, dtype=np.float64), np.asarray(sigma_c, dtype=np.float64)
+    if mu_s.shape != (3,) or mu_c.shape != (3,) or sigma_s.shape != (3, 3) or sigma_c.shape != (3, 3):
+        raise ValueError(f"colour statistics of shapes {mu_s.shape}, {sigma_s.shape}, {mu_c.shape}, {sigma_c.shape}: "
+                         f"expected (3,), (3, 3), (3,), (3, 3)")
+    if not all(np.isfinite(v).all() for v in (mu_s, mu_c, sigma_s, sigma_c)):
+        raise ValueError("colour statistics must be finite")
+    A = _sym_power((sigma_c + sigma_c.T) / 2, 0.5) @ _sym_power((sigma_s + sigma_s.T) / 2, -0.5)
+    b = mu_c - A @ mu_s
+    if not (np.isfinite(A).all() and np.isfinite(b).all()):
+        raise ValueError("colour transform is not finite")
+    return A, b
+
+
+def match_colour(style, content, style_mask=None, content_mask=None) -> torch.Tensor:
+    """--preserve_color match: the style image recoloured with the affine map of colour_transform, so that its colour mean
+    and covariance are the content's (strotss_color_stats on both, strotss_color_affine on the style; not clamped).  With
+    masks ((h, w) planes at each image's size): the statistics of the style pixels in style_mask and of the content pixels
+    in content_mask, the map applied where style_mask != 0, the other pixels copied.  -> an image of the style's shape."""
+    s = _rgb(style, "style image")
+    h, w = int(s.shape[0]), int(s.shape[1])
+    sm = _plane(style_mask, h, w, "style mask")
+    A, b = colour_transform(*colour_statistics(s, sm), *colour_statistics(content, content_mask))
+    out = _ops.color_affine(s, A, b, sm)
+    return out.reshape(tuple(style.shape)) if torch.is_tensor(style) else out
+
+
+def luminance_merge(result, content) -> torch.Tensor:
+    """--preserve_color luminance: the luma of `result` on the chroma of `content`, out = content + (Y(result) - Y(content))
+    on every channel with Y = 0.299 R + 0.587 G + 0.114 B (strotss_luma_merge).  Two images of one size -> the result's
+    shape.  ValueError when the sizes differ."""
+    r, c = _rgb(result, "result"), _rgb(content, "content")
+    if tuple(r.shape) != tuple(c.shape):
+        raise ValueError(f"result of shape {tuple(r.shape)} and content of shape {tuple(c.shape)} differ in size")
+    out = _ops.luma_merge(r, c)
+    return out.reshape(tuple(result.shape)) if torch.is_tensor(result) else out
+
+
 def _colour_keys(path: str, max_size: Optional[int], pixel_threth: int) -> np.ndarray:
     """(H, W) int64 key per pixel of a colour-coded region image: its channels floored to multiples of `pixel_threth`
     (uint8 as decoded, or float32 when `max_size` made load_image resize it) and packed so that ascending keys are

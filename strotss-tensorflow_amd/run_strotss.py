@@ -36,6 +36,13 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
                     bring better flow from elsewhere.
   --save_flow DIR   with --compute_flow: also write the computed flows to DIR as backward_{t}_{t-j}.flo and
                     forward_{t-j}_{t}.flo (a later run with --flow_dir DIR reads the same floats back)
+  --preserve_color {match,luminance}
+                    keep the content's colours (Gatys et al. 2016).  match: every style image is
+                    recoloured, before anything is sampled from it, with the affine map that gives it the content's colour
+                    mean and covariance (each --style_mix image on its own; with masks region by region; with --video
+                    against every frame's own colours).  luminance: the written image keeps the luma of the result and takes
+                    the chroma of the content; with --video the temporal targets stay the unmerged results.  One GPU; not
+                    with --strips.
   --strips          under torchrun (one process per GPU): ONE image on all GPUs -- every rank runs the trunk on its strip
                     of the image (+ halo) at the scales where that pays, two all-reduces per step (nn/parallel.py);
                     rank 0 writes the output
@@ -148,6 +155,43 @@ def _content_weight_input(args):
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise ValueError("--content_weight_map runs on one GPU: not under torchrun with WORLD_SIZE > 1")
     return path
+
+
+PRESERVE_COLOR_MODES = ("match", "luminance")
+
+
+def _preserve_color_input(args):
+    """--preserve_color: "match", "luminance" or None.  One GPU only: with --strips or under torchrun with WORLD_SIZE > 1 a
+    ValueError (checked before anything is loaded)."""
+    mode = getattr(args, "preserve_color", None)
+    if mode is None:
+        return None
+    if mode not in PRESERVE_COLOR_MODES:
+        raise ValueError(f"--preserve_color takes one of {PRESERVE_COLOR_MODES}, got {mode!r}")
+    if getattr(args, "strips", False):
+        raise ValueError("--preserve_color cannot be combined with --strips")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("--preserve_color runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    return mode
+
+
+def _match_styles(styles, content, content_masks, style_masks):
+    """--preserve_color match: every style image recoloured toward the content's colour mean and covariance
+    (strotss_utils.match_colour), each style on its own.  With masks region by region: the statistics of the style pixels
+    in style mask r and of the content pixels in content mask r, the map applied to style mask r's pixels only (the masks
+    resized to the images as mask_at_scale resizes them to a scale); pixels in no region stay."""
+    if list(content_masks) == [None]:
+        return [strotss.match_colour(s_k, content) for s_k in styles]
+    ch, cw = int(content.shape[1]), int(content.shape[2])
+    out = []
+    for s_k in styles:
+        sh, sw = int(s_k.shape[1]), int(s_k.shape[2])
+        for c_mask, s_mask in zip(content_masks, style_masks):
+            cm = torch.from_numpy(strotss.mask_at_scale(c_mask, ch, cw).astype(np.float32))
+            sm = torch.from_numpy(strotss.mask_at_scale(s_mask, sh, sw).astype(np.float32))
+            s_k = strotss.match_colour(s_k, content, sm, cm)
+        out.append(s_k)
+    return out
 
 
 DEFAULT_TEMPORAL_WEIGHT = 1000.0          # DESIGN.md section 12: chosen on the MI355X with the consistency error
@@ -427,6 +471,7 @@ def run(args: argparse.Namespace, trace=None):
     timer.start()
 
     cw_path = _content_weight_input(args)
+    preserve = _preserve_color_input(args)
     _video_inputs(args)                                      # the sequence flags without --video: ValueError
     seed = int(getattr(args, "seed", 0))
     rand.seed_everything(seed)
@@ -440,6 +485,8 @@ def run(args: argparse.Namespace, trace=None):
 
     vgg = VGG(use_keras_weight=args.use_keras_weight, weights=getattr(args, "weights", None), seed=seed, device=dev)
     stylized = _stylise(args, vgg, args.content_path, cw_path, dev, rank, world, trace)
+    if preserve == "luminance":                              # the result's luma on the content's chroma, at the result's size
+        stylized = strotss.luminance_merge(stylized, _frame_at_result_size(args, args.content_path))
     final = strotss.postprocess(stylized)
     if torch.cuda.is_available():
         torch.cuda.synchronize()
@@ -463,6 +510,8 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
     style_paths, style_weights = _style_inputs(args)
     styles = [utils.load_image(p, max_size=args.max_size) for p in style_paths]
     content_masks, style_masks = _load_masks(args)
+    if _preserve_color_input(args) == "match":               # before any resize: every scale samples the recoloured styles
+        styles = _match_styles(styles, content, content_masks, style_masks)
     cw_map = strotss.load_content_weight_map(cw_path) if cw_path else None
     sampling = strotss.Sampling(SAMPLE_SIZE)
     masked = bool(getattr(args, "content_mask", None))
@@ -520,8 +569,11 @@ def run_video(args: argparse.Namespace, trace=None):
     temporal term toward the previous result warped along the backward flow and, with
     --temporal_frames, toward the results of frames t-j (the last max(J) results stay on the device).
     With --compute_flow the flows come from strotss_optical_flow on the content frames at the results' size (DESIGN.md
-    section 14; the last max(J) + 1 of those frames stay on the device as well).  Writes
+    section 14; the last max(J) + 1 of those frames stay on the device as well).  --preserve_color match recolours the
+    styles against every frame's own colours (in _stylise); luminance merges only what is written, the temporal targets
+    keep the unmerged results.  Writes
     <output dir>/<frame stem>.jpg; returns the list of the frames' uint8 results.  `trace`: one list per frame."""
+    preserve = _preserve_color_input(args)
     frames, lam = _video_inputs(args)
     cw_path = _content_weight_input(args)
     seed = int(getattr(args, "seed", 0))
@@ -550,7 +602,11 @@ def run_video(args: argparse.Namespace, trace=None):
             trace.append(rec)
         previous = _stylise(args, vgg, frame, cw_path, dev, trace=rec, temporal=temporal, temporal_weight=lam)
         results = [previous] + results[:offsets[-1] - 1]
-        final = strotss.postprocess(previous)
+        written = previous
+        if preserve == "luminance":         # only what is written: the temporal targets stay the optimiser's own results
+            written = strotss.luminance_merge(previous, flow_frames[t] if flow_frames is not None
+                                              else _frame_at_result_size(args, frame))
+        final = strotss.postprocess(written)
         if torch.cuda.is_available():
             torch.cuda.synchronize()
         timer.stop()
@@ -597,6 +653,10 @@ _FLAGS = (
     (("--save_flow",), dict(type=str, default=None, metavar='DIR',
                             help="with --compute_flow: write the computed flows there as backward_{t}_{t-j}.flo and "
                                  "forward_{t-j}_{t}.flo")),
+    (("--preserve_color",), dict(type=str, default=None, choices=PRESERVE_COLOR_MODES,
+                                 help="keep the content's colours: 'match' recolours the style images to the content's colour "
+                                      "mean and covariance before anything is sampled, 'luminance' writes the result's luma on "
+                                      "the content's chroma")),
     (("--strips",), dict(action='store_true', help="under torchrun: shard ONE image over the GPUs by image strips")),
     (("--halo",), dict(action='store_true', help="with --strips: per-layer halo EXCHANGE with the neighbouring ranks (16-row "
                                                  "windows margins, one row per layer and direction) instead of a 128-row recompute margin")),
