@@ -484,13 +484,20 @@ int winograd_run(const float* in, int h, int w, int cin, const float* U, const f
 
 }  // namespace
 
-// U[a * (m + 2) + b][n][k] = (G g[n][k] G^T)[a][b] in float64, rounded once to float32 (one thread per (n, k) pair)
+// U[a * (m + 2) + b][n][k] = (G g[n][k] G^T)[a][b] in float64, rounded once to float32 (one thread per (n, k) pair).
+// G's fractions 1/6, 1/12, 1/24 are not exact as doubles and the sums are contracted (-ffp-contract=on), so terms that cancel
+// exactly -- fma(1/6, 576, -96) -- used to leave 1e-14 where the exact U is 0, and that survives the conversion to float32
+// (tests/test_hip_exact_conv.py, condition 1).  The numerator of (24 G) g (24 G)^T / 576 with the integer matrices 24 G has
+// exact products and, for taps of like magnitude, exact sums in float64: where IT is 0 the entry is stored as 0.  Every other
+// entry keeps the value computed as before, bit for bit (its error of ~1e-16 relative is far below float32's rounding).
 __global__ __launch_bounds__(256) void winograd_weights_kernel(const float* __restrict__ g, long long nk, int tile_m,
                                                               float* __restrict__ U) {
   // Lavin & Gray: F(2x2,3x3) and F(4x4,3x3) (points 0, +-1, +-2, inf)
   const double G2[4][3] = {{1.0, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1.0}};
   const double G4[6][3] = {{1.0 / 4, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
                            {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1.0}};
+  const double N2[4][3] = {{24, 0, 0}, {12, 12, 12}, {12, -12, 12}, {0, 0, 24}};                    // 24 G
+  const double N4[6][3] = {{6, 0, 0}, {-4, -4, -4}, {-4, 4, -4}, {1, 2, 4}, {1, -2, 4}, {0, 0, 24}};
   const int P = tile_m + 2;
   for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < nk; e += (long long)gridDim.x * 256) {
     double w[3][3];
@@ -506,11 +513,21 @@ __global__ __launch_bounds__(256) void winograd_weights_kernel(const float* __re
 #pragma unroll
         for (int r = 0; r < 3; ++r) t[q] += (tile_m == 2 ? G2[a][r] : G4[a][r]) * w[r][q];
       }
+      double tn[3];                                   // (24 G g)[a][q]
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        tn[q] = 0.0;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) tn[q] += (tile_m == 2 ? N2[a][r] : N4[a][r]) * w[r][q];
+      }
       for (int b = 0; b < P; ++b) {
         double u = 0.0;
 #pragma unroll
         for (int q = 0; q < 3; ++q) u += t[q] * (tile_m == 2 ? G2[b][q] : G4[b][q]);
-        U[(size_t)(a * P + b) * nk + e] = (float)u;
+        double un = 0.0;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) un += tn[q] * (tile_m == 2 ? N2[b][q] : N4[b][q]);
+        U[(size_t)(a * P + b) * nk + e] = un == 0.0 ? 0.f : (float)u;
       }
     }
   }
