@@ -578,6 +578,28 @@ int strotss_color_affine(const float* img, const float* weight, int h, int w, co
 int strotss_luma_merge(const float* result, const float* content, int h, int w, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Photo smoothing: the guided filter of He, Sun and Tang (2013), the content as colour guide
+ * --------------------------------------------------------------------------------------- */
+#define STROTSS_SMOOTH_MAX_RADIUS 64
+/* bytes of the workspace of strotss_guided_smooth: 216 per pixel (21 float64 planes of window sums + 12 float32 planes of
+ * a, b); 0 for h, w <= 0, 3 h w > INT_MAX or a radius outside 1..STROTSS_SMOOTH_MAX_RADIUS */
+size_t strotss_guided_smooth_workspace_bytes(int h, int w, int radius);
+/* out = the guided filter of img with guide as colour guide, both (h, w, 3) float32.  The window of a pixel is the
+ * (2 radius + 1)^2 box around it CLIPPED to the image and divided by its own pixel count (no padding).  Per window k:
+ * mu = mean(I), Sigma = mean(I I^T) - mu mu^T + eps Id, and per channel c  a_c = Sigma^{-1} (mean(I p_c) - mu mean(p_c)),
+ * b_c = mean(p_c) - a_c . mu;  out_c(i) = mean_i(a_c) . I(i) + mean_i(b_c), the means over the clipped window around i.
+ * Window sums and the 3 x 3 solves in float64 (direct sums, a column pass and a row pass: no running sums), a and b stored
+ * as float32, the output pixel in float32; NOT clamped.  eps is used at its float32 value.  No atomics: the same bits on
+ * every run.  Four launches on `stream`; the workspace needs no initialisation and is the only scratch.  out may equal
+ * img; it may not equal guide.
+ * Refused before anything is launched: STROTSS_EINVAL for a null pointer, h or w <= 0, 3 h w > INT_MAX, a radius outside
+ * 1..STROTSS_SMOOTH_MAX_RADIUS, eps not finite or outside [1e-4, 1], workspace_bytes below
+ * strotss_guided_smooth_workspace_bytes(h, w, radius), out == guide; STROTSS_EALIGN for a pointer that is not 16-byte
+ * aligned. */
+int strotss_guided_smooth(const float* img, const float* guide, int h, int w, int radius, float eps, float* out,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Optimiser + output
  * --------------------------------------------------------------------------------------- */
 typedef struct {

@@ -169,6 +169,8 @@ SIGNATURES = {
     "strotss_color_stats": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "strotss_color_affine": (_I, [_P, _P, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _P]),
     "strotss_luma_merge": (_I, [_P, _P, _I, _I, _P, _P]),
+    "strotss_guided_smooth_workspace_bytes": (_Z, [_I, _I, _I]),
+    "strotss_guided_smooth": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _Z, _P]),
     "strotss_rmsprop_step": (_I, [C.POINTER(TensorsT), _F, _F, _F, _P]),
     "strotss_postprocess": (_I, [_P, _L, _P, _P, _P]),
 }

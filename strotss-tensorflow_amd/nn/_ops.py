@@ -290,6 +290,36 @@ def luma_merge(result: torch.Tensor, content: torch.Tensor, out: Optional[torch.
     return out
 
 
+# ------------------------------------------------------------------ photo smoothing
+_smooth_ws = {}
+
+
+def guided_smooth(img: torch.Tensor, guide: torch.Tensor, radius: int, eps: float,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the guided filter of an (h, w, 3) image with `guide` (the same size) as colour guide, windows of radius `radius`
+    clipped to the image, regulariser `eps` at its float32 value (strotss_guided_smooth; four launches on the current
+    stream, the same bits on every run).  out may be img, not guide.  The workspace (216 bytes per pixel) is a module-level
+    one per device and size; the library refuses a radius outside 1..64 and an eps outside [1e-4, 1]."""
+    h, w = _rgb_image(img, "image")
+    if _rgb_image(guide, "guide") != (h, w):
+        raise ValueError(f"image of shape {tuple(img.shape)} and guide of shape {tuple(guide.shape)} differ in size")
+    lib = _hip.lib()
+    key = (str(img.device), h, w)
+    workspace = _smooth_ws.get(key)
+    if workspace is None:
+        nb = int(lib.strotss_guided_smooth_workspace_bytes(h, w, 1))        # the size does not depend on the radius
+        if nb == 0:
+            raise _hip.StrotssHipError(f"guided_smooth: bad size {h} x {w}")
+        workspace = _smooth_ws[key] = torch.empty(nb, dtype=torch.uint8, device=img.device)
+    if out is None:
+        out = torch.empty_like(img)
+    require(out, "smoothed image")
+    assert out.numel() == img.numel()
+    check(lib.strotss_guided_smooth(ptr(img), ptr(guide), h, w, int(radius), float(eps), ptr(out), ptr(workspace),
+                                    workspace.numel(), stream_ptr()), "guided_smooth")
+    return out
+
+
 def resize_bilinear_adjoint(gout: torch.Tensor, ih: int, iw: int,
                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
     require(gout, "resize adjoint input")

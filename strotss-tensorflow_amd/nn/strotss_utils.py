@@ -405,6 +405,40 @@ def luminance_merge(result, content) -> torch.Tensor:
     return out.reshape(tuple(result.shape)) if torch.is_tensor(result) else out
 
 
+# ----------------------------------------------------------------------------- photo smoothing
+SMOOTH_MAX_RADIUS = 64                   # STROTSS_SMOOTH_MAX_RADIUS
+SMOOTH_EPS_RANGE = (1e-4, 1.0)
+DEFAULT_SMOOTH_EPS = 1e-2                # 0.1^2 on [0, 1] images: the middle of He's usual range; a documented choice
+
+
+def default_smooth_radius(h: int, w: int) -> int:
+    """1/64 of the longer side, within 1..64 (a documented choice, not a tuned value)"""
+    return max(1, min(SMOOTH_MAX_RADIUS, round(max(int(h), int(w)) / 64)))
+
+
+def check_smooth_parameters(radius, eps) -> None:
+    """ValueError for a radius that is not an integer in 1..64 or an eps that is not finite in [1e-4, 1] (None: not given)"""
+    if radius is not None and (int(radius) != radius or not 1 <= int(radius) <= SMOOTH_MAX_RADIUS):
+        raise ValueError(f"smoothing radius {radius!r}: expected an integer in 1..{SMOOTH_MAX_RADIUS}")
+    if eps is not None and not (math.isfinite(eps) and SMOOTH_EPS_RANGE[0] <= eps <= SMOOTH_EPS_RANGE[1]):
+        raise ValueError(f"smoothing eps {eps!r}: expected a finite value in [{SMOOTH_EPS_RANGE[0]}, {SMOOTH_EPS_RANGE[1]}]")
+
+
+def guided_smooth(result, content, radius=None, eps=DEFAULT_SMOOTH_EPS) -> torch.Tensor:
+    """--photo_smooth: the guided filter (He, Sun, Tang 2013) of `result` with `content` as colour guide, which puts the
+    content's edges back into the result (strotss_guided_smooth; not clamped).  Two images of one size, (h, w, 3) or
+    (1, h, w, 3) -> the result's shape.  radius None: default_smooth_radius(h, w).  ValueError when the sizes differ, for a
+    radius outside 1..64, for an eps that is not finite or outside [1e-4, 1]."""
+    check_smooth_parameters(radius, eps)
+    r, c = _rgb(result, "result"), _rgb(content, "content")
+    if tuple(r.shape) != tuple(c.shape):
+        raise ValueError(f"result of shape {tuple(r.shape)} and content of shape {tuple(c.shape)} differ in size")
+    if radius is None:
+        radius = default_smooth_radius(int(r.shape[0]), int(r.shape[1]))
+    out = _ops.guided_smooth(r, c, int(radius), float(eps))
+    return out.reshape(tuple(result.shape)) if torch.is_tensor(result) else out
+
+
 def _colour_keys(path: str, max_size: Optional[int], pixel_threth: int) -> np.ndarray:
     """(H, W) int64 key per pixel of a colour-coded region image: its channels floored to multiples of `pixel_threth`
     (uint8 as decoded, or float32 when `max_size` made load_image resize it) and packed so that ascending keys are

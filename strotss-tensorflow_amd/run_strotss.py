@@ -43,6 +43,12 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
                     against every frame's own colours).  luminance: the written image keeps the luma of the result and takes
                     the chroma of the content; with --video the temporal targets stay the unmerged results.  One GPU; not
                     with --strips.
+  --photo_smooth    keep the content's edges: the result is passed through the guided filter of He, Sun and Tang (2013) with
+                    the content at the result's size as colour guide before --preserve_color
+                    luminance's merge and before it is written; with --video the temporal targets stay the unfiltered
+                    results.  One GPU; not with --strips.
+  --smooth_radius R with --photo_smooth: the window radius in pixels, 1..64 (default: 1/64 of the result's longer side)
+  --smooth_eps E    with --photo_smooth: the regulariser on [0, 1] colours, 1e-4..1 (default 1e-2); smaller keeps weaker edges
   --strips          under torchrun (one process per GPU): ONE image on all GPUs -- every rank runs the trunk on its strip
                     of the image (+ halo) at the scales where that pays, two all-reduces per step (nn/parallel.py);
                     rank 0 writes the output
@@ -173,6 +179,22 @@ def _preserve_color_input(args):
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise ValueError("--preserve_color runs on one GPU: not under torchrun with WORLD_SIZE > 1")
     return mode
+
+
+def _photo_smooth_input(args):
+    """--photo_smooth: (radius or None, eps) or None when the flag is absent.  ValueError, before anything is loaded: a
+    radius or an eps without the flag, a radius outside 1..64, an eps outside [1e-4, 1], --strips, WORLD_SIZE > 1."""
+    radius, eps = getattr(args, "smooth_radius", None), getattr(args, "smooth_eps", None)
+    if not getattr(args, "photo_smooth", False):
+        if radius is not None or eps is not None:
+            raise ValueError("--smooth_radius and --smooth_eps need --photo_smooth")
+        return None
+    strotss.check_smooth_parameters(radius, eps)
+    if getattr(args, "strips", False):
+        raise ValueError("--photo_smooth cannot be combined with --strips")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("--photo_smooth runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    return (None if radius is None else int(radius)), (strotss.DEFAULT_SMOOTH_EPS if eps is None else float(eps))
 
 
 def _match_styles(styles, content, content_masks, style_masks):
@@ -472,6 +494,7 @@ def run(args: argparse.Namespace, trace=None):
 
     cw_path = _content_weight_input(args)
     preserve = _preserve_color_input(args)
+    smooth = _photo_smooth_input(args)
     _video_inputs(args)                                      # the sequence flags without --video: ValueError
     seed = int(getattr(args, "seed", 0))
     rand.seed_everything(seed)
@@ -485,8 +508,11 @@ def run(args: argparse.Namespace, trace=None):
 
     vgg = VGG(use_keras_weight=args.use_keras_weight, weights=getattr(args, "weights", None), seed=seed, device=dev)
     stylized = _stylise(args, vgg, args.content_path, cw_path, dev, rank, world, trace)
+    guide = _frame_at_result_size(args, args.content_path) if smooth or preserve == "luminance" else None
+    if smooth:                                               # the content's edges back into the result, then its colours
+        stylized = strotss.guided_smooth(stylized, guide, *smooth)
     if preserve == "luminance":                              # the result's luma on the content's chroma, at the result's size
-        stylized = strotss.luminance_merge(stylized, _frame_at_result_size(args, args.content_path))
+        stylized = strotss.luminance_merge(stylized, guide)
     final = strotss.postprocess(stylized)
     if torch.cuda.is_available():
         torch.cuda.synchronize()
@@ -571,9 +597,11 @@ def run_video(args: argparse.Namespace, trace=None):
     With --compute_flow the flows come from strotss_optical_flow on the content frames at the results' size (DESIGN.md
     section 14; the last max(J) + 1 of those frames stay on the device as well).  --preserve_color match recolours the
     styles against every frame's own colours (in _stylise); luminance merges only what is written, the temporal targets
-    keep the unmerged results.  Writes
+    keep the unmerged results.  --photo_smooth filters only what is written as well, before that
+    merge.  Writes
     <output dir>/<frame stem>.jpg; returns the list of the frames' uint8 results.  `trace`: one list per frame."""
     preserve = _preserve_color_input(args)
+    smooth = _photo_smooth_input(args)
     frames, lam = _video_inputs(args)
     cw_path = _content_weight_input(args)
     seed = int(getattr(args, "seed", 0))
@@ -602,10 +630,13 @@ def run_video(args: argparse.Namespace, trace=None):
             trace.append(rec)
         previous = _stylise(args, vgg, frame, cw_path, dev, trace=rec, temporal=temporal, temporal_weight=lam)
         results = [previous] + results[:offsets[-1] - 1]
-        written = previous
-        if preserve == "luminance":         # only what is written: the temporal targets stay the optimiser's own results
-            written = strotss.luminance_merge(previous, flow_frames[t] if flow_frames is not None
-                                              else _frame_at_result_size(args, frame))
+        written = previous                  # only what is written is filtered or merged: the temporal targets and
+        if smooth or preserve == "luminance":                    # --temporal_init keep the optimiser's own results
+            guide = flow_frames[t] if flow_frames is not None else _frame_at_result_size(args, frame)
+        if smooth:
+            written = strotss.guided_smooth(written, guide, *smooth)
+        if preserve == "luminance":
+            written = strotss.luminance_merge(written, guide)
         final = strotss.postprocess(written)
         if torch.cuda.is_available():
             torch.cuda.synchronize()
@@ -657,6 +688,12 @@ _FLAGS = (
                                  help="keep the content's colours: 'match' recolours the style images to the content's colour "
                                       "mean and covariance before anything is sampled, 'luminance' writes the result's luma on "
                                       "the content's chroma")),
+    (("--photo_smooth",), dict(action='store_true', help="keep the content's edges: pass the result through the guided filter "
+                                                         "with the content as colour guide before it is written")),
+    (("--smooth_radius",), dict(type=int, default=None, metavar='R',
+                                help="with --photo_smooth: window radius in pixels, 1..64 (default: 1/64 of the longer side)")),
+    (("--smooth_eps",), dict(type=float, default=None, metavar='E',
+                             help="with --photo_smooth: regulariser on [0, 1] colours, 1e-4..1 (default 1e-2)")),
     (("--strips",), dict(action='store_true', help="under torchrun: shard ONE image over the GPUs by image strips")),
     (("--halo",), dict(action='store_true', help="with --strips: per-layer halo EXCHANGE with the neighbouring ranks (16-row "
                                                  "windows margins, one row per layer and direction) instead of a 128-row recompute margin")),
