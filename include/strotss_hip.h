@@ -600,6 +600,35 @@ int strotss_guided_smooth(const float* img, const float* guide, int h, int w, in
                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Region clustering: spherical k-means on sampled feature rows, the kernels of --auto_masks
+ * --------------------------------------------------------------------------------------- */
+#define STROTSS_KMEANS_MAX_K 16
+/* x: a zero-padded (rows, ld) float32 feature matrix (strotss_hypercol_gather's layout, ld % 32 == 0), n rows of d columns
+ * in use; inv_norm: strotss_row_inv_norm(x); centres: (k, ld) float32, every row of unit length or all zero (an empty
+ * cluster), columns d..ld-1 zero; 1 <= k <= STROTSS_KMEANS_MAX_K.  Both entries refuse, before anything is launched and with
+ * their outputs untouched: STROTSS_EINVAL for a null pointer, n <= 0, d <= 0, d > ld, n ld > INT_MAX, k outside
+ * 1..STROTSS_KMEANS_MAX_K, a workspace below strotss_kmeans_update_workspace_bytes(n, ld, k); STROTSS_EALIGN for
+ * ld % 32 != 0 or a pointer that is not 16-byte aligned. */
+/* For every row i < n:  s_ij = (x_i . c_j) inv_norm_i, the dot product accumulated in float32 over the d columns;
+ * label[i] (int32) = the j with the largest s_ij, the lowest j on equal values; best[i] = that value; second[i] = the largest
+ * of the other k - 1 values (-inf for k == 1).  A row with inv_norm_i == 0 gets label 0 and best = second = 0.  One launch;
+ * x is read once, the centres stay in LDS a 512-column chunk at a time.  The same bits on every run and stream. */
+int strotss_kmeans_assign(const float* x, const float* inv_norm, int n, int d, int ld, const float* centres, int k, int* label,
+                          float* best, float* second, void* stream);
+/* bytes of the workspace of strotss_kmeans_update (the row blocks' float64 partial sums: at most 32 k ld doubles); 0 for
+ * n <= 0, ld <= 0, ld % 32 != 0, n ld > INT_MAX or k outside 1..STROTSS_KMEANS_MAX_K */
+size_t strotss_kmeans_update_workspace_bytes(int n, int ld, int k);
+/* count[j] (int32) = the number of rows i < n with label[i] == j;  centres[j] = S_j / |S_j| with
+ * S_j = sum_{label[i] == j} x_i inv_norm_i: the products (exact) and the sums in float64, in an order fixed by (n, d, k)
+ * alone (rows ascending inside a row block, row blocks ascending, a fixed tree for the norm; no float atomics), the norm
+ * and the division in float64, ONE rounding to float32 at the store; columns d..ld-1 are written as zero.  A cluster with
+ * count[j] == 0 keeps its centre bit for bit; one whose S_j is all zero becomes the zero centre.  Labels outside 0..k-1
+ * are skipped (counted nowhere, never used as an index).  Two launches; x is read once; the workspace needs no
+ * initialisation.  The same bits on every run and stream. */
+int strotss_kmeans_update(const float* x, const float* inv_norm, const int* label, int n, int d, int ld, int k, float* centres,
+                          int* count, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Optimiser + output
  * --------------------------------------------------------------------------------------- */
 typedef struct {

@@ -36,6 +36,7 @@ class MapsT(C.Structure):
 
 
 MAX_DRAW_REGIONS = 16
+KMEANS_MAX_K = 16          # STROTSS_KMEANS_MAX_K
 
 
 class DrawT(C.Structure):
@@ -171,6 +172,9 @@ SIGNATURES = {
     "strotss_luma_merge": (_I, [_P, _P, _I, _I, _P, _P]),
     "strotss_guided_smooth_workspace_bytes": (_Z, [_I, _I, _I]),
     "strotss_guided_smooth": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _Z, _P]),
+    "strotss_kmeans_assign": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
+    "strotss_kmeans_update_workspace_bytes": (_Z, [_I, _I, _I]),
+    "strotss_kmeans_update": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
     "strotss_rmsprop_step": (_I, [C.POINTER(TensorsT), _F, _F, _F, _P]),
     "strotss_postprocess": (_I, [_P, _L, _P, _P, _P]),
 }

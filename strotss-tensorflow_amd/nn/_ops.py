@@ -721,6 +721,50 @@ def row_inv_norm(x: torch.Tensor, n: int) -> torch.Tensor:
     return r
 
 
+# ------------------------------------------------------------------ region clustering
+def _kmeans_rows(x: torch.Tensor, inv_norm: torch.Tensor, n: int, d: int, centres: torch.Tensor, k: int) -> int:
+    """checks of the two k-means wrappers -> ld"""
+    require(x, "feature rows")
+    require(inv_norm, "inverse norms")
+    require(centres, "centres")
+    ld = int(x.shape[1])
+    if not (x.dim() == 2 and 0 < n <= int(x.shape[0]) and 0 < d <= ld and inv_norm.numel() >= n):
+        raise ValueError(f"{n} rows of {d} columns in a feature buffer of shape {tuple(x.shape)} with {inv_norm.numel()} norms")
+    if not 1 <= k <= _hip.KMEANS_MAX_K or centres.dim() != 2 or int(centres.shape[0]) < k or int(centres.shape[1]) != ld:
+        raise ValueError(f"{k} centres in a buffer of shape {tuple(centres.shape)}: expected 1..{_hip.KMEANS_MAX_K} rows of {ld}")
+    return ld
+
+
+def kmeans_assign(x: torch.Tensor, inv_norm: torch.Tensor, n: int, d: int, centres: torch.Tensor, k: int):
+    """(label, best, second) of strotss_kmeans_assign: per row i < n of the zero-padded (rows, ld) buffer x the first arg-max j
+    of (x_i . centres_j) inv_norm_i (int32), that value and the largest of the others (-inf for k == 1); three (n,) tensors."""
+    ld = _kmeans_rows(x, inv_norm, n, d, centres, k)
+    label = torch.empty(n, dtype=torch.int32, device=x.device)
+    best = torch.empty(n, dtype=torch.float32, device=x.device)
+    second = torch.empty(n, dtype=torch.float32, device=x.device)
+    check(_hip.lib().strotss_kmeans_assign(ptr(x), ptr(inv_norm), n, d, ld, ptr(centres), k, ptr(label), ptr(best), ptr(second),
+                                           stream_ptr()), "kmeans_assign")
+    return label, best, second
+
+
+def kmeans_update(x: torch.Tensor, inv_norm: torch.Tensor, label: torch.Tensor, n: int, d: int, k: int,
+                  centres: torch.Tensor) -> torch.Tensor:
+    """strotss_kmeans_update: centres[j] <- the normalised float64 sum of the unit rows with label j, in place (an empty
+    cluster keeps its centre); -> count (k,) int32.  label: (>= n,) int32; values outside 0..k-1 are skipped."""
+    ld = _kmeans_rows(x, inv_norm, n, d, centres, k)
+    if not (label.is_cuda and label.dtype == torch.int32 and label.is_contiguous() and label.numel() >= n):
+        raise _hip.StrotssHipError(f"labels must be a contiguous int32 CUDA/HIP tensor of >= {n} values")
+    lib = _hip.lib()
+    nb = int(lib.strotss_kmeans_update_workspace_bytes(n, ld, k))
+    if nb == 0:
+        raise _hip.StrotssHipError(f"kmeans_update: bad sizes n {n}, ld {ld}, k {k}")
+    ws = workspaces.get("kmeans", nb, x.device)
+    count = torch.empty(k, dtype=torch.int32, device=x.device)
+    check(lib.strotss_kmeans_update(ptr(x), ptr(inv_norm), ptr(label), n, d, ld, k, ptr(centres), ptr(count), ptr(ws), nb,
+                                    stream_ptr()), "kmeans_update")
+    return count
+
+
 def cosine_distance(x, rx, nx, y, ry, ny) -> torch.Tensor:
     ldc = pad32(ny)
     Cm = torch.empty((nx, ldc), dtype=torch.float32, device=x.device)

@@ -439,6 +439,146 @@ def guided_smooth(result, content, radius=None, eps=DEFAULT_SMOOTH_EPS) -> torch
     return out.reshape(tuple(result.shape)) if torch.is_tensor(result) else out
 
 
+# ----------------------------------------------------------------------------- automatic region masks
+AUTO_MASK_ITERS = 16                     # k-means iterations, fixed (no convergence test: no host synchronisation)
+AUTO_MASK_SIZE = 256                     # long side at which the two images are clustered
+AUTO_MASK_GRID = 64                      # grid points per image along its long side at most
+AUTO_MASK_MIN_SHARE = 1.0 / 32.0         # a cluster is a region when it holds this share of BOTH images' grid points
+AUTO_MASK_RANGE = (2, 8)                 # --auto_masks K: the colour-coded mask format tells eight colours apart
+MASK_COLOURS = tuple((r, g, b) for r in (0, 255) for g in (0, 255) for b in (0, 255))      # ascending (r, g, b)
+
+
+def farthest_first(x: torch.Tensor, inv_norm: torch.Tensor, n: int, d: int, k: int) -> torch.Tensor:
+    """(k, ld) initial centres, deterministic, on the device: centre 0 is the unit row with the largest cosine to the
+    normalised sum of all unit rows (strotss_kmeans_update with one cluster, strotss_kmeans_assign against it), centre j the
+    unit row whose largest cosine to centres 0..j-1 (the `best` of strotss_kmeans_assign) is smallest.  torch.argmax /
+    argmin return the lowest index among equal values (tests/test_hip_cluster.py asserts it on the device)."""
+    centres = torch.zeros((k, int(x.shape[1])), dtype=torch.float32, device=x.device)
+    everyone = torch.zeros(n, dtype=torch.int32, device=x.device)
+    _ops.kmeans_update(x, inv_norm, everyone, n, d, 1, centres)
+    _, best, _ = _ops.kmeans_assign(x, inv_norm, n, d, centres, 1)
+    row = torch.argmax(best).reshape(1)
+    for j in range(k):                                       # index_select: the row number never leaves the device
+        centres[j] = (x.index_select(0, row) * inv_norm.index_select(0, row))[0]
+        if j + 1 < k:
+            _, best, _ = _ops.kmeans_assign(x, inv_norm, n, d, centres, j + 1)
+            row = torch.argmin(best).reshape(1)
+    return centres
+
+
+def label_counts(label: torch.Tensor, k: int) -> torch.Tensor:
+    """(k,) int32 on the device: how many labels equal 0, 1, .., k-1 (torch.bincount would read the largest label back)"""
+    return (label[:, None] == torch.arange(k, dtype=label.dtype, device=label.device)).sum(dim=0).to(torch.int32)
+
+
+def spherical_kmeans(x: torch.Tensor, n: int, d: int, k: int, iters: int = AUTO_MASK_ITERS,
+                     inv_norm: Optional[torch.Tensor] = None):
+    """Spherical k-means of the first n rows (d columns) of a zero-padded (rows, ld) feature buffer, in the cosine metric of
+    the style term: farthest_first centres, one assignment, then `iters` times (centre update, assignment) -- a fixed
+    count, nothing is read back.  -> (label (n,) int32, centres (k, ld) unit or zero rows, count (k,) int32 of the labels
+    returned, objective (iters,) = the mean of each assignment's best cosine, never decreasing), all on the device.  The
+    labels are the assignment against the centres returned."""
+    if not 1 <= int(k) <= _ops._hip.KMEANS_MAX_K:
+        raise ValueError(f"{k} clusters: expected 1..{_ops._hip.KMEANS_MAX_K}")
+    if inv_norm is None:
+        inv_norm = _ops.row_inv_norm(x, n)
+    centres = farthest_first(x, inv_norm, n, d, k)
+    label, best, _ = _ops.kmeans_assign(x, inv_norm, n, d, centres, k)
+    objective = torch.empty(iters, dtype=torch.float32, device=x.device)
+    for it in range(iters):
+        _ops.kmeans_update(x, inv_norm, label, n, d, k, centres)
+        label, best, _ = _ops.kmeans_assign(x, inv_norm, n, d, centres, k)
+        objective[it] = best.mean()
+    count = label_counts(label, k)
+    return label, centres, count, objective
+
+
+def auto_mask_grid(h: int, w: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(rows, columns) of the clustering grid of an (h, w) image: stride g = ceil(long side / 64), from g // 2"""
+    g = -(-max(int(h), int(w)) // AUTO_MASK_GRID)
+    return np.arange(g // 2, int(h), g), np.arange(g // 2, int(w), g)
+
+
+def upsample_labels(grid: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """a (gh, gw) label grid at (H, W) by nearest neighbour: pixel (y, x) takes cell (min(y gh // H, gh-1), min(x gw // W, gw-1))"""
+    gh, gw = int(grid.shape[0]), int(grid.shape[1])
+    ys = torch.clamp(torch.arange(H, device=grid.device) * gh // H, max=gh - 1)
+    xs = torch.clamp(torch.arange(W, device=grid.device) * gw // W, max=gw - 1)
+    return grid[ys][:, xs]
+
+
+def auto_mask_regions(params, content: torch.Tensor, style: torch.Tensor, k: int, min_share: float = AUTO_MASK_MIN_SHARE):
+    """The clustering behind auto_masks, with everything the tests look at: dict(kept = number of regions (0: fewer than
+    two clusters hold min_share of both images' grid points), content_grid / style_grid = (gh, gw) int32 label grids over the
+    kept clusters, centres (kept, ld), rows = the (n_c + n_s, ld) hypercolumn buffer (content rows first), inv_norm, n_c,
+    n_s, d, shares (kept, 2) of the two images' points per region).  One device-to-host read: the (2, k) counts."""
+    lo, hi = 1, _ops._hip.KMEANS_MAX_K
+    if not lo <= int(k) <= hi:
+        raise ValueError(f"{k} clusters: expected {lo}..{hi}")
+    from . import engine
+    grids, blocks, d = [], [], 0
+    for image in (content, style):
+        small = utils.resize(image, min(AUTO_MASK_SIZE, max(int(image.shape[-3]), int(image.shape[-2]))))
+        if small.dim() == 3:
+            small = small[None]
+        feats = engine.extract_features(params, small.contiguous())
+        ys, xs = auto_mask_grid(int(small.shape[1]), int(small.shape[2]))
+        idx = np.stack(np.meshgrid(ys, xs, indexing="ij"), axis=-1).reshape(-1, 2).astype(np.float32)      # (row, col), row-major
+        grids.append((len(ys), len(xs)))
+        blocks.append((feats, torch.from_numpy(idx).to(small.device)))
+        d = sum(int(m.shape[-1]) for m in feats)
+    n_c, n_s = (g[0] * g[1] for g in grids)
+    rows = torch.zeros((_ops.pad32(n_c + n_s), _ops.pad32(d)), dtype=torch.float32, device=blocks[0][1].device)
+    _ops.hypercol_gather(blocks[0][0], blocks[0][1], False, out=rows)
+    _ops.hypercol_gather(blocks[1][0], blocks[1][1], False, out=rows[n_c:])
+    n = n_c + n_s
+    inv_norm = _ops.row_inv_norm(rows, n)
+    label, centres, _, _ = spherical_kmeans(rows, n, d, int(k), inv_norm=inv_norm)
+    counts = torch.stack([label_counts(label[:n_c], k), label_counts(label[n_c:], k)]).cpu().numpy()
+    keep = np.flatnonzero((counts[0] >= min_share * n_c) & (counts[1] >= min_share * n_s))
+    out = dict(kept=0, rows=rows, inv_norm=inv_norm, n_c=n_c, n_s=n_s, d=d, counts=counts)
+    if keep.size < 2:
+        return out
+    if keep.size < k:                                        # every point into a kept cluster (ascending cluster order)
+        centres = centres[torch.from_numpy(keep).to(centres.device)].contiguous()
+        label, _, _ = _ops.kmeans_assign(rows, inv_norm, n, d, centres, int(keep.size))
+    out.update(kept=int(keep.size), centres=centres, content_grid=label[:n_c].reshape(grids[0]),
+               style_grid=label[n_c:].reshape(grids[1]))
+    return out
+
+
+def auto_masks(params, content: torch.Tensor, style: torch.Tensor, k: int, min_share: float = AUTO_MASK_MIN_SHARE):
+    """--auto_masks K: (content_masks, style_masks) as load_mask returns them -- lists of (H, W, 1) float 0/1 tensors at the
+    two images' own sizes, one pair per region, each list a partition of its image -- from a joint spherical k-means of both
+    images' hypercolumns (auto_mask_regions): cluster j is content region j and the style region it draws from.  Fewer than
+    two clusters with min_share of both images: ([None], [None]) and a warning (the run proceeds unmasked)."""
+    found = auto_mask_regions(params, content, style, k, min_share)
+    if not found["kept"]:
+        utils.logger.warning(f"--auto_masks {k}: fewer than two clusters hold {min_share:.3f} of both images "
+                             f"(content {found['counts'][0].tolist()}, style {found['counts'][1].tolist()} of "
+                             f"{found['n_c']}, {found['n_s']} points); running unmasked")
+        return [None], [None]
+    out = []
+    for image, grid in ((content, found["content_grid"]), (style, found["style_grid"])):
+        labels = upsample_labels(grid, int(image.shape[-3]), int(image.shape[-2]))
+        out.append([(labels == j).float()[..., None] for j in range(found["kept"])])
+    return out[0], out[1]
+
+
+def save_masks(directory: str, content_masks, style_masks) -> None:
+    """--save_masks: content_mask.png and style_mask.png in `directory`, region r painted in MASK_COLOURS[r] -- the format
+    load_mask reads, in the order it returns them (ascending (r, g, b)).  The masks of auto_masks are a partition, so every
+    pixel gets the colour of its one region."""
+    from PIL import Image
+    if len(content_masks) > len(MASK_COLOURS):
+        raise ValueError(f"{len(content_masks)} regions: the colour-coded format tells {len(MASK_COLOURS)} apart")
+    os.makedirs(directory, exist_ok=True)
+    palette = torch.tensor(MASK_COLOURS, dtype=torch.uint8)
+    for name, masks in (("content_mask.png", content_masks), ("style_mask.png", style_masks)):
+        region = torch.stack([m.reshape(m.shape[0], m.shape[1]) for m in masks]).argmax(dim=0).cpu()
+        Image.fromarray(palette[region].numpy(), "RGB").save(os.path.join(directory, name), format="PNG")
+
+
 def _colour_keys(path: str, max_size: Optional[int], pixel_threth: int) -> np.ndarray:
     """(H, W) int64 key per pixel of a colour-coded region image: its channels floored to multiples of `pixel_threth`
     (uint8 as decoded, or float32 when `max_size` made load_image resize it) and packed so that ascending keys are

@@ -49,6 +49,17 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
                     results.  One GPU; not with --strips.
   --smooth_radius R with --photo_smooth: the window radius in pixels, 1..64 (default: 1/64 of the result's longer side)
   --smooth_eps E    with --photo_smooth: the regulariser on [0, 1] colours, 1e-4..1 (default 1e-2); smaller keeps weaker edges
+  --auto_masks K    region guidance without painted masks: the hypercolumns of the content and of
+                    style_path on a regular grid are clustered jointly into K groups (2..8) by spherical k-means on the GPU;
+                    every cluster that holds 1/32 of both images' grid points is a content region and the style region it
+                    draws from, exactly as a pair of --content_mask / --style_mask colours is.  Computed on the images as
+                    loaded (before --preserve_color match recolours the style, which then runs region by region).  Fewer
+                    than two such clusters: a warning and an unmasked run.  Combines with --content_weight_map,
+                    --preserve_color and --photo_smooth; not with --content_mask / --style_mask, --style_mix, --video,
+                    --strips or a multi-process run.
+  --save_masks DIR  with --auto_masks: write the regions to DIR as content_mask.png and style_mask.png in the colour-coded
+                    format of --content_mask / --style_mask (region r in the r-th of the eight colours with channels in
+                    {0, 255}, ascending (r, g, b)), to be edited and handed back through those two flags
   --strips          under torchrun (one process per GPU): ONE image on all GPUs -- every rank runs the trunk on its strip
                     of the image (+ halo) at the scales where that pays, two all-reduces per step (nn/parallel.py);
                     rank 0 writes the output
@@ -195,6 +206,31 @@ def _photo_smooth_input(args):
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise ValueError("--photo_smooth runs on one GPU: not under torchrun with WORLD_SIZE > 1")
     return (None if radius is None else int(radius)), (strotss.DEFAULT_SMOOTH_EPS if eps is None else float(eps))
+
+
+def _auto_masks_input(args):
+    """--auto_masks K, --save_masks DIR: (K, DIR or None), or None without --auto_masks.  ValueError, before anything is
+    loaded: K outside 2..8, --save_masks without --auto_masks, --auto_masks with --content_mask / --style_mask, --style_mix,
+    --video, --strips or under torchrun with WORLD_SIZE > 1."""
+    k, save = getattr(args, "auto_masks", None), getattr(args, "save_masks", None)
+    if k is None:
+        if save:
+            raise ValueError("--save_masks needs --auto_masks (it writes the regions the run finds)")
+        return None
+    lo, hi = strotss.AUTO_MASK_RANGE
+    if int(k) != k or not lo <= int(k) <= hi:
+        raise ValueError(f"--auto_masks takes a number of clusters in {lo}..{hi}, got {k!r}")
+    if getattr(args, "content_mask", None) or getattr(args, "style_mask", None):
+        raise ValueError("--auto_masks cannot be combined with --content_mask / --style_mask: the regions are found or given")
+    if getattr(args, "style_mix", None):
+        raise ValueError("--auto_masks cannot be combined with --style_mix: masks and blends exclude each other")
+    if getattr(args, "video", False):
+        raise ValueError("--auto_masks cannot be combined with --video: clustering every frame on its own would flicker")
+    if getattr(args, "strips", False):
+        raise ValueError("--auto_masks cannot be combined with --strips")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("--auto_masks runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    return int(k), (save or None)
 
 
 def _match_styles(styles, content, content_masks, style_masks):
@@ -487,6 +523,7 @@ def run(args: argparse.Namespace, trace=None):
     """The reference's run(args) (run_strotss.py:43-161).  `trace` (a list) receives one dict per executed scale:
     scale index and size, lr, alpha, loss_denom, the image the scale starts from, every step's losses and the
     result -- what the parity test of the schedule compares with the oracle's run_scales.  --video: run_video."""
+    _auto_masks_input(args)                                  # refusals first, --video among them
     if getattr(args, "video", False):
         return run_video(args, trace)
     timer = utils.Timer()
@@ -535,7 +572,15 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
     content = utils.load_image(content_path, max_size=args.max_size)
     style_paths, style_weights = _style_inputs(args)
     styles = [utils.load_image(p, max_size=args.max_size) for p in style_paths]
-    content_masks, style_masks = _load_masks(args)
+    auto = _auto_masks_input(args)
+    if auto:                                                 # regions found on the images as loaded, in place of painted masks
+        content_masks, style_masks = strotss.auto_masks(vgg.params, content, styles[0], auto[0])
+        if content_masks[0] is not None:
+            utils.logger.info(f'Found {len(content_masks)} regions.')
+            if auto[1]:
+                strotss.save_masks(auto[1], content_masks, style_masks)
+    else:
+        content_masks, style_masks = _load_masks(args)
     if _preserve_color_input(args) == "match":               # before any resize: every scale samples the recoloured styles
         styles = _match_styles(styles, content, content_masks, style_masks)
     cw_map = strotss.load_content_weight_map(cw_path) if cw_path else None
@@ -694,6 +739,12 @@ _FLAGS = (
                                 help="with --photo_smooth: window radius in pixels, 1..64 (default: 1/64 of the longer side)")),
     (("--smooth_eps",), dict(type=float, default=None, metavar='E',
                              help="with --photo_smooth: regulariser on [0, 1] colours, 1e-4..1 (default 1e-2)")),
+    (("--auto_masks",), dict(type=int, default=None, metavar='K',
+                             help="region guidance without painted masks: cluster the hypercolumns of content and style "
+                                  "jointly into K groups (2..8); every cluster found in both images is a region")),
+    (("--save_masks",), dict(type=str, default=None, metavar='DIR',
+                             help="with --auto_masks: write content_mask.png and style_mask.png there, in the colour-coded "
+                                  "format of --content_mask / --style_mask")),
     (("--strips",), dict(action='store_true', help="under torchrun: shard ONE image over the GPUs by image strips")),
     (("--halo",), dict(action='store_true', help="with --strips: per-layer halo EXCHANGE with the neighbouring ranks (16-row "
                                                  "windows margins, one row per layer and direction) instead of a 128-row recompute margin")),
