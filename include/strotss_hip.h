@@ -629,6 +629,34 @@ int strotss_kmeans_update(const float* x, const float* inv_norm, const int* labe
                           int* count, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Mask refinement: joint bilateral upsampling of a label grid, the kernels of --refine_masks
+ * --------------------------------------------------------------------------------------- */
+#define STROTSS_REFINE_MAX_RADIUS 4
+/* bytes of the workspace of strotss_refine_labels (the (gh, gw, 3) float32 cell colours); 0 for h, w, gh or gw <= 0,
+ * gh > h, gw > w or 3 h w > INT_MAX */
+size_t strotss_refine_labels_workspace_bytes(int h, int w, int gh, int gw);
+/* img: an (h, w, 3) float32 image; grid_label: its (gh, gw) int32 label grid over the labels 0..k-1, gh <= h, gw <= w,
+ * 1 <= k <= STROTSS_KMEANS_MAX_K.  Cell (i, j) owns the pixels (y, x) with y gh / h == i and x gw / w == j (integer
+ * division); m(i, j) is the mean of img over them, summed and divided in float64 in a fixed order and rounded once to
+ * float32.  For every pixel, with u = (y + 0.5) gh / h - 0.5, v = (x + 0.5) gw / w - 0.5 and (i0, j0) its own cell, over the
+ * cells |i - i0| <= radius, |j - j0| <= radius inside the grid (no padding), row by row, in float64:
+ *   vote[l] = sum over the cells with label l of
+ *             exp(-(((u - i)^2 + (v - j)^2) / (2 sigma_s^2) + |img(y, x) - m(i, j)|^2 / (2 sigma_r^2)))
+ * label[y w + x] (int32) = the l with the largest vote among the labels that occur in the window, the lowest l on equal
+ * votes; best / second (float64, each may be NULL) = that vote and the largest of the other occurring labels' votes
+ * (-inf when only one occurs).  A cell whose label lies outside 0..k-1 casts no vote (compared, never used as an index);
+ * a window without any label in 0..k-1 gives label 0 and best = second = -inf.  count[l] (int32, l < k) = the number of
+ * pixels with label l, by integer atomics.  Two launches; the image is read once per launch; the workspace needs no
+ * initialisation; no float atomics: the same bits on every run and stream.
+ * Refused before anything is launched: STROTSS_EINVAL for a null img, grid_label, label, count or workspace, a size <= 0,
+ * gh > h, gw > w, 3 h w > INT_MAX, k outside 1..STROTSS_KMEANS_MAX_K, a radius outside 1..STROTSS_REFINE_MAX_RADIUS, a sigma
+ * that is not finite or not positive (or so small that 1 / (2 sigma^2) overflows), workspace_bytes below
+ * strotss_refine_labels_workspace_bytes(h, w, gh, gw); STROTSS_EALIGN for a pointer that is not 16-byte aligned. */
+int strotss_refine_labels(const float* img, int h, int w, const int* grid_label, int gh, int gw, int k, int radius,
+                          double sigma_s, double sigma_r, int* label, double* best, double* second, int* count,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Optimiser + output
  * --------------------------------------------------------------------------------------- */
 typedef struct {

@@ -37,6 +37,7 @@ class MapsT(C.Structure):
 
 MAX_DRAW_REGIONS = 16
 KMEANS_MAX_K = 16          # STROTSS_KMEANS_MAX_K
+REFINE_MAX_RADIUS = 4      # STROTSS_REFINE_MAX_RADIUS
 
 
 class DrawT(C.Structure):
@@ -175,6 +176,8 @@ SIGNATURES = {
     "strotss_kmeans_assign": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
     "strotss_kmeans_update_workspace_bytes": (_Z, [_I, _I, _I]),
     "strotss_kmeans_update": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "strotss_refine_labels_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "strotss_refine_labels": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, C.c_double, C.c_double, _P, _P, _P, _P, _P, _Z, _P]),
     "strotss_rmsprop_step": (_I, [C.POINTER(TensorsT), _F, _F, _F, _P]),
     "strotss_postprocess": (_I, [_P, _L, _P, _P, _P]),
 }

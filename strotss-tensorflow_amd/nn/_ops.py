@@ -765,6 +765,32 @@ def kmeans_update(x: torch.Tensor, inv_norm: torch.Tensor, label: torch.Tensor, 
     return count
 
 
+# ------------------------------------------------------------------ mask refinement
+def refine_labels(img: torch.Tensor, grid: torch.Tensor, k: int, radius: int, sigma_s: float, sigma_r: float,
+                  votes: bool = False, means: bool = False):
+    """strotss_refine_labels: the (gh, gw) int32 label grid of an (h, w, 3) image brought to (h, w) by a joint bilateral vote
+    among the (2 radius + 1)^2 cells around each pixel's own.  -> (label (h, w) int32, count (k,) int32, best, second, mean):
+    best / second (h, w) float64 with votes=True, mean the (gh, gw, 3) float32 cell colours with means=True, else None.  Two
+    launches on the current stream; the library refuses gh > h, gw > w, k outside 1..16, a radius outside 1..4, a sigma <= 0."""
+    h, w = _rgb_image(img, "image")
+    if not (grid.is_cuda and grid.dtype == torch.int32 and grid.is_contiguous() and grid.dim() == 2):
+        raise _hip.StrotssHipError("the label grid must be a contiguous (gh, gw) int32 CUDA/HIP tensor")
+    gh, gw = int(grid.shape[0]), int(grid.shape[1])
+    lib = _hip.lib()
+    nb = int(lib.strotss_refine_labels_workspace_bytes(h, w, gh, gw))
+    if nb == 0:
+        raise ValueError(f"refine_labels: a {gh} x {gw} label grid for an image of {h} x {w} (the grid may not be larger)")
+    ws = workspaces.get("refine", nb, img.device)
+    label = torch.empty((h, w), dtype=torch.int32, device=img.device)
+    count = torch.empty(int(k), dtype=torch.int32, device=img.device) if 1 <= int(k) <= _hip.KMEANS_MAX_K else None
+    best = torch.empty((h, w), dtype=torch.float64, device=img.device) if votes else None
+    second = torch.empty((h, w), dtype=torch.float64, device=img.device) if votes else None
+    check(lib.strotss_refine_labels(ptr(img), h, w, ptr(grid), gh, gw, int(k), int(radius), float(sigma_s), float(sigma_r),
+                                    ptr(label), ptr(best), ptr(second), ptr(count), ptr(ws), nb, stream_ptr()), "refine_labels")
+    mean = ws[:gh * gw * 12].view(torch.float32).reshape(gh, gw, 3).clone() if means else None
+    return label, count, best, second, mean
+
+
 def cosine_distance(x, rx, nx, y, ry, ny) -> torch.Tensor:
     ldc = pad32(ny)
     Cm = torch.empty((nx, ldc), dtype=torch.float32, device=x.device)

@@ -547,22 +547,77 @@ def auto_mask_regions(params, content: torch.Tensor, style: torch.Tensor, k: int
     return out
 
 
-def auto_masks(params, content: torch.Tensor, style: torch.Tensor, k: int, min_share: float = AUTO_MASK_MIN_SHARE):
+# mask refinement: three documented choices, none tuned
+REFINE_RADIUS = 2                        # a 5 x 5 window of cells around the pixel's own
+REFINE_SIGMA_S = 1.0                     # in cells
+REFINE_SIGMA_R = 0.1                     # on [0, 1] colours: the 0.1 behind DEFAULT_SMOOTH_EPS = 0.1^2
+REFINE_SIGMA_RANGE = (0.01, 1.0)         # --refine_sigma
+
+
+def check_refine_sigma(sigma_r) -> None:
+    """ValueError for a colour sigma that is not finite or outside [0.01, 1] (None: not given)"""
+    lo, hi = REFINE_SIGMA_RANGE
+    if sigma_r is not None and not (math.isfinite(sigma_r) and lo <= sigma_r <= hi):
+        raise ValueError(f"refinement sigma {sigma_r!r}: expected a finite value in [{lo}, {hi}]")
+
+
+def refine_labels(image, grid: torch.Tensor, k: int, sigma_r: float = REFINE_SIGMA_R):
+    """--refine_masks for one image: its (gh, gw) int32 label grid over the regions 0..k-1 brought to the image's size by
+    joint bilateral upsampling with the image itself as guide (strotss_refine_labels at REFINE_RADIUS and REFINE_SIGMA_S):
+    every pixel takes the label with the largest vote among the 5 x 5 cells around its own, a cell counting for more when
+    it is near and when its mean colour is like the pixel's.  image: (H, W, 3) or (1, H, W, 3) in [0, 1] -> (labels (H, W)
+    int32, count (k,) int32 pixels per label), both on the device.  ValueError: a sigma outside [0.01, 1], k outside 1..16,
+    a grid that is not two-dimensional or larger than the image."""
+    check_refine_sigma(sigma_r)
+    if not 1 <= int(k) <= _ops._hip.KMEANS_MAX_K:
+        raise ValueError(f"{k} regions: expected 1..{_ops._hip.KMEANS_MAX_K}")
+    x = _rgb(image, "image")
+    if grid.dim() != 2 or int(grid.shape[0]) > int(x.shape[0]) or int(grid.shape[1]) > int(x.shape[1]):
+        raise ValueError(f"a label grid of shape {tuple(grid.shape)} for an image of {tuple(x.shape[:2])}: expected (gh, gw), "
+                         f"not larger than the image")
+    label, count, _, _, _ = _ops.refine_labels(x, grid.to(device=x.device, dtype=torch.int32).contiguous(), int(k),
+                                               REFINE_RADIUS, REFINE_SIGMA_S, float(sigma_r))
+    return label, count
+
+
+def masks_from_grids(content, style, content_grid: torch.Tensor, style_grid: torch.Tensor, kept: int, refine=None,
+                     min_share: float = AUTO_MASK_MIN_SHARE):
+    """(content_masks, style_masks): `kept` (H, W, 1) float 0/1 masks per image in ascending region order, a partition of
+    each image, from the two label grids.  refine None: nearest neighbour (upsample_labels).  refine = sigma_r: each grid is
+    refined against its own image (refine_labels) and the two (kept,) pixel counts are read back; when a region then holds
+    fewer than min_share of either image's pixels -- an emptied region must never reach the masked draw -- a warning is
+    logged and both images keep their unrefined masks."""
+    pairs = ((content, content_grid), (style, style_grid))
+    labels = [upsample_labels(grid, int(image.shape[-3]), int(image.shape[-2])) for image, grid in pairs]
+    if refine is not None:
+        refined = [refine_labels(image, grid, kept, refine) for image, grid in pairs]
+        counts = torch.stack([count for _, count in refined]).cpu().numpy()
+        pixels = [int(image.shape[-3]) * int(image.shape[-2]) for image, _ in pairs]
+        if all((counts[i] >= min_share * pixels[i]).all() for i in range(2)):
+            labels = [label for label, _ in refined]
+        else:
+            utils.logger.warning(f"--refine_masks: a region would hold fewer than {min_share:.3f} of an image's pixels "
+                                 f"(content {counts[0].tolist()} of {pixels[0]}, style {counts[1].tolist()} of {pixels[1]}); "
+                                 f"keeping the unrefined masks")
+    return tuple([(lab == j).float()[..., None] for j in range(kept)] for lab in labels)
+
+
+def auto_masks(params, content: torch.Tensor, style: torch.Tensor, k: int, min_share: float = AUTO_MASK_MIN_SHARE,
+               refine=None):
     """--auto_masks K: (content_masks, style_masks) as load_mask returns them -- lists of (H, W, 1) float 0/1 tensors at the
     two images' own sizes, one pair per region, each list a partition of its image -- from a joint spherical k-means of both
     images' hypercolumns (auto_mask_regions): cluster j is content region j and the style region it draws from.  Fewer than
-    two clusters with min_share of both images: ([None], [None]) and a warning (the run proceeds unmasked)."""
+    two clusters with min_share of both images: ([None], [None]) and a warning (the run proceeds unmasked).  refine: None
+    brings the label grids to the images by nearest neighbour; a colour sigma (--refine_masks) by
+    joint bilateral upsampling against each image itself (masks_from_grids)."""
+    check_refine_sigma(refine)
     found = auto_mask_regions(params, content, style, k, min_share)
     if not found["kept"]:
         utils.logger.warning(f"--auto_masks {k}: fewer than two clusters hold {min_share:.3f} of both images "
                              f"(content {found['counts'][0].tolist()}, style {found['counts'][1].tolist()} of "
                              f"{found['n_c']}, {found['n_s']} points); running unmasked")
         return [None], [None]
-    out = []
-    for image, grid in ((content, found["content_grid"]), (style, found["style_grid"])):
-        labels = upsample_labels(grid, int(image.shape[-3]), int(image.shape[-2]))
-        out.append([(labels == j).float()[..., None] for j in range(found["kept"])])
-    return out[0], out[1]
+    return masks_from_grids(content, style, found["content_grid"], found["style_grid"], found["kept"], refine, min_share)
 
 
 def save_masks(directory: str, content_masks, style_masks) -> None:

@@ -57,6 +57,13 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
                     than two such clusters: a warning and an unmasked run.  Combines with --content_weight_map,
                     --preserve_color and --photo_smooth; not with --content_mask / --style_mask, --style_mix, --video,
                     --strips or a multi-process run.
+  --refine_masks    with --auto_masks: edge-aligned regions.  The label grid of each image is brought to
+                    the image by joint bilateral upsampling with the image itself as guide instead of by nearest neighbour:
+                    every pixel votes among the 5 x 5 grid cells around its own, a cell counting for more when it is near
+                    and when its mean colour is like the pixel's.  The borders then follow the image's edges, not the
+                    grid's blocks.  A region left with less than 1/32 of either image: a warning and the unrefined masks.
+  --refine_sigma S  with --refine_masks: the colour scale of the vote on [0, 1] colours, 0.01..1 (default 0.1); smaller
+                    follows weaker edges
   --save_masks DIR  with --auto_masks: write the regions to DIR as content_mask.png and style_mask.png in the colour-coded
                     format of --content_mask / --style_mask (region r in the r-th of the eight colours with channels in
                     {0, 255}, ascending (r, g, b)), to be edited and handed back through those two flags
@@ -208,11 +215,34 @@ def _photo_smooth_input(args):
     return (None if radius is None else int(radius)), (strotss.DEFAULT_SMOOTH_EPS if eps is None else float(eps))
 
 
+def _refine_masks_input(args):
+    """--refine_masks, --refine_sigma S: the colour sigma of the refinement (S, or the default), or None without
+    --refine_masks.  ValueError: --refine_masks without --auto_masks, --refine_sigma without --refine_masks or outside
+    0.01..1."""
+    refine, sigma = getattr(args, "refine_masks", False), getattr(args, "refine_sigma", None)
+    if sigma is not None and not refine:
+        raise ValueError("--refine_sigma needs --refine_masks")
+    if not refine:
+        return None
+    if getattr(args, "auto_masks", None) is None:
+        raise ValueError("--refine_masks needs --auto_masks (it refines the regions the run finds)")
+    if sigma is None:
+        return strotss.REFINE_SIGMA_R
+    try:
+        strotss.check_refine_sigma(float(sigma))
+    except ValueError:
+        lo, hi = strotss.REFINE_SIGMA_RANGE
+        raise ValueError(f"--refine_sigma takes a colour scale in {lo}..{hi}, got {sigma!r}") from None
+    return float(sigma)
+
+
 def _auto_masks_input(args):
     """--auto_masks K, --save_masks DIR: (K, DIR or None), or None without --auto_masks.  ValueError, before anything is
     loaded: K outside 2..8, --save_masks without --auto_masks, --auto_masks with --content_mask / --style_mask, --style_mix,
-    --video, --strips or under torchrun with WORLD_SIZE > 1."""
+    --video, --strips or under torchrun with WORLD_SIZE > 1, and the refusals of --refine_masks / --refine_sigma
+    (_refine_masks_input)."""
     k, save = getattr(args, "auto_masks", None), getattr(args, "save_masks", None)
+    _refine_masks_input(args)
     if k is None:
         if save:
             raise ValueError("--save_masks needs --auto_masks (it writes the regions the run finds)")
@@ -574,7 +604,11 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
     styles = [utils.load_image(p, max_size=args.max_size) for p in style_paths]
     auto = _auto_masks_input(args)
     if auto:                                                 # regions found on the images as loaded, in place of painted masks
-        content_masks, style_masks = strotss.auto_masks(vgg.params, content, styles[0], auto[0])
+        refine = _refine_masks_input(args)
+        if refine is None:                                   # without --refine_masks the call is what it was
+            content_masks, style_masks = strotss.auto_masks(vgg.params, content, styles[0], auto[0])
+        else:
+            content_masks, style_masks = strotss.auto_masks(vgg.params, content, styles[0], auto[0], refine=refine)
         if content_masks[0] is not None:
             utils.logger.info(f'Found {len(content_masks)} regions.')
             if auto[1]:
@@ -742,6 +776,10 @@ _FLAGS = (
     (("--auto_masks",), dict(type=int, default=None, metavar='K',
                              help="region guidance without painted masks: cluster the hypercolumns of content and style "
                                   "jointly into K groups (2..8); every cluster found in both images is a region")),
+    (("--refine_masks",), dict(action='store_true', help="with --auto_masks: bring the label grids to the images by joint "
+                                                         "bilateral upsampling, so that the regions follow the images' edges")),
+    (("--refine_sigma",), dict(type=float, default=None, metavar='S',
+                               help="with --refine_masks: colour scale of the vote on [0, 1] colours, 0.01..1 (default 0.1)")),
     (("--save_masks",), dict(type=str, default=None, metavar='DIR',
                              help="with --auto_masks: write content_mask.png and style_mask.png there, in the colour-coded "
                                   "format of --content_mask / --style_mask")),
