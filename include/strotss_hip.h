@@ -125,6 +125,10 @@ int strotss_conv3x3_dgrad_unpool(const float* gout, int h, int w, int cout, cons
 int strotss_conv3x3_dgrad(const float* gout, int h, int w, int cout, const float* w_tik, int cin,
                           const float* act_in, float* gin, int accumulate, void* workspace, size_t workspace_bytes,
                           void* stream);
+/* 1 when strotss_conv3x3_dgrad(..., accumulate = 1, ...) launches for this shape (given its
+ * strotss_conv3x3_workspace_bytes(h, w, cout, cin) workspace), 0 where it answers STROTSS_EINVAL or _EALIGN: the one-pass
+ * kernel of STROTSS_CONV_VARIANT=1 overwrites, the split-K form adds under every variant.  Host arithmetic, no launch. */
+int strotss_conv3x3_dgrad_can_accumulate(int h, int w, int cout, int cin);
 /* Data gradient of the first layer down to the pixels, preprocess adjoint fused:
  *   gimg(h,w,3) (+)= conv3x3^T(gout(h,w,cout)) / std.   w_tic: (9, 3, cout) flipped kernel.
  *   accumulate != 0 adds to gimg (the hypercolumn scatter of map 0 lands there first).
@@ -177,8 +181,10 @@ int strotss_conv3x3_winograd_dgrad(const float* gout, int h, int w, int cout, co
                                    const float* act_in, const unsigned int* relu_bits, float* gin, int accumulate,
                                    void* workspace, size_t workspace_bytes, void* stream);
 /* Which kernels strotss_conv3x3_winograd_fwd / _dgrad run for a layer shape (the routing is a size policy with
- * environment switches, read once per process): what bench.py names in its roofline.  has_packed / has_x3: whether the
- * caller passes u_packed / u_x3 for this layer. */
+ * environment switches, read once per process): the very function those two entries dispatch on (csrc/winograd.hip
+ * winograd43_route), so the answer cannot differ from what launches.  has_packed / has_x3: whether the caller passes
+ * u_packed / u_x3 for this layer; a caller that wants to know whether making the x3 panels is worth it asks with
+ * has_x3 = 1 and makes them where the answer is one of the two X3 routes.  Host arithmetic, no GPU needed. */
 #define STROTSS_ROUTE_F2_GEMM_F32 0     /* F(2x2,3x3): input transform, 16 f32-MFMA GEMMs, output transform            */
 #define STROTSS_ROUTE_F4_FUSED_F32 1    /* F(4x4,3x3), one persistent kernel, f32 MFMA (csrc/winograd_fused.hip)       */
 #define STROTSS_ROUTE_F4_GEMM_F32 2     /* F(4x4,3x3), three kernels, 36 f32-MFMA GEMMs                                 */
@@ -420,7 +426,10 @@ int strotss_remd_metric_fwd_bwd(const float* style, int ns, const float* pred, i
  * launch, the prologues of all four terms another, every statistic of the forward products (self-similarity rows, moment
  * scalars, REMD and palette minima) a third, the two branch selections + the self-similarity gradient matrix a fourth:
  * 9 launches instead of 21.
- * bf16x3 core only: STROTSS_EINVAL when STROTSS_X3 / _COST / _MOMENT switch it off (take the separate entry points). */
+ * bf16x3 core only: STROTSS_EINVAL when STROTSS_X3 / _COST / _MOMENT switch it off (take the separate entry points).
+ * strotss_step_losses_available() is 1 exactly when the switches (read once per process) do NOT make this entry and the
+ * blend / cw entries below refuse that way: the caller asks instead of parsing the switches itself. */
+int strotss_step_losses_available(void);
 size_t strotss_step_losses_workspace_bytes(int ns, int n, int ld);
 int strotss_step_losses_fwd_bwd(const float* pred, const float* content, int n, int d, int ld, const float* style,
                                 const float* style_inv_norm, const void* style_panels, int ns, const float* style_mean,

@@ -435,6 +435,8 @@ static int conv_variant() {
   }
   return v;
 }
+// the one-pass kernels add to their output on request, except the two-barrier A/B kernel: it overwrites
+static bool conv_one_pass_accumulates() { return conv_variant() != 1; }
 
 static int conv_waves() {
   static int v = -1;
@@ -449,8 +451,8 @@ template <int BM, int BN>
 int launch_conv(const float* in, int H, int W, int Cin, const float* wt, const float* bias, int Cout,
                 const float* mask, float* out, int relu, hipStream_t s, int accumulate) {
   dim3 grid(Cout / BN, cdiv((int64_t)H * W, BM));
+  if (accumulate && !conv_one_pass_accumulates()) return STROTSS_EINVAL;
   if (conv_variant() == 1) {
-    if (accumulate) return STROTSS_EINVAL;             // (the two-barrier A/B kernel overwrites)
     hipLaunchKernelGGL((conv3x3_mfma_kernel<BM, BN>), grid, dim3(256), 0, s, in, H, W, Cin, wt, bias, Cout,
                        mask, out, relu);
     ST_LAUNCH_RET();
@@ -1019,6 +1021,12 @@ int strotss_conv3x3_dgrad_unpool(const float* gout, int h, int w, int cout, cons
   fp.ucode = pool_code; fp.ugin = gin_full; fp.uH = full_h; fp.uW = full_w;
   return conv_dispatch(gout, h, w, cout, w_tik, nullptr, cin, nullptr, nullptr, 0, (hipStream_t)stream, workspace, workspace_bytes,
                        accumulate, &fp);
+}
+
+int strotss_conv3x3_dgrad_can_accumulate(int h, int w, int cout, int cin) {
+  if (h <= 0 || w <= 0 || cout <= 0 || cout % 32 || cin <= 0 || cin % 64) return 0;
+  // conv_dispatch: the split-K finish kernel adds under every variant, the one-pass kernels as launch_conv says
+  return conv_splits(h, w, cout, cin) != 0 || conv_one_pass_accumulates();
 }
 
 int strotss_conv3x3_c3_dgrad(const float* gout, int h, int w, int cout, const float* w_tic,

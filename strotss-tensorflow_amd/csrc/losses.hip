@@ -1794,6 +1794,8 @@ int strotss_moment_fwd_bwd(const float* style_mean, const float* style_cov, cons
 // (strotss_selfsim_fwd_bwd, strotss_moment_fwd_bwd, strotss_remd_cos_fwd_bwd_panels, strotss_palette_remd_fwd_bwd): bit for bit the
 // same losses and gradient rows; 13 launches instead of 21 (one prologue launch, one for row statistics + moment scalars).  bf16x3 core only (STROTSS_X3 / _COST /
 // _MOMENT = 0: STROTSS_EINVAL, the caller takes the separate entry points).
+int strotss_step_losses_available(void) { return cost_x3() && moment_x3(); }
+
 size_t strotss_step_losses_workspace_bytes(int ns, int n, int ld) {
   Workspace w = Workspace::planner();
   SelfsimWs a; MomentWs b; RemdWs c, p;
@@ -1810,7 +1812,7 @@ static int step_losses_impl(const float* pred, const float* content, const float
                loss_moment && loss_remd && loss_palette && workspace && ns > 0 && feat_ok(n, d, ld), STROTSS_EINVAL);
   ST_CHECK_ARG(ld % 32 == 0, STROTSS_EALIGN);
   ST_CHECK_ARG(ns <= REMD_MAX_LIST, STROTSS_ERANGE);
-  ST_CHECK_ARG(cost_x3() && moment_x3(), STROTSS_EINVAL);
+  ST_CHECK_ARG(strotss_step_losses_available(), STROTSS_EINVAL);
   Workspace w(workspace, workspace_bytes);
   SelfsimWs s; MomentWs m; RemdWs r, pl;
   ST_CHECK_ARG(s.plan(w, n, ld) && m.plan(w, n, ld) && r.plan(w, ns, n, ld) && pl.plan(w, ns, n, 0), STROTSS_EINVAL);
@@ -1907,7 +1909,7 @@ static int blend_impl(const float* pred, const float* content, const float* cw, 
   const strotss_style_set_t& ss = *styles;
   const int K = ss.n_styles;
   for (int k = 0; k < K; ++k) ST_CHECK_ARG(ss.ns[k] <= REMD_MAX_LIST, STROTSS_ERANGE);
-  ST_CHECK_ARG(cost_x3() && moment_x3(), STROTSS_EINVAL);
+  ST_CHECK_ARG(strotss_step_losses_available(), STROTSS_EINVAL);
   if (K == 1) {
     const float w = ss.weight[0];
     return step_losses_impl(pred, content, cw, n, d, ld, ss.feats[0], ss.inv_norm[0], ss.panels[0], ss.ns[0], ss.mean[0],

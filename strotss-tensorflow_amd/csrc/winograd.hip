@@ -381,11 +381,20 @@ static int x3_min_cout() {
   if (v < 0) { const char* e = getenv("STROTSS_X3_MIN_COUT"); v = e ? atoi(e) : 256; }
   return v;
 }
-// layers the fused kernel could take but the three-kernel form with bf16x3 GEMMs runs faster: 256 output channels with
-// enough 128 x 128 GEMM tiles (block3 at 1024 px: step 5.06 -> 4.99 ms; at 512 px the fused kernel wins, 1.99 vs 2.03 ms)
-static bool winograd43_prefers_x3(int h, int w, int cout) {
+
+// THE route policy of the F(4x4,3x3) form, given the weight forms the caller hands over: winograd43_run dispatches on it,
+// strotss_conv3x3_winograd_route returns it, nothing else decides.  In order: bf16x3 GEMMs on 128 x 128 tiles ahead of the
+// fused kernel from STROTSS_X3_MIN_COUT (256) output channels (block3 at 1024 px: step 5.06 -> 4.99 ms, 5.102 -> 5.039 ms in
+// three alternating runs each; at 512 px the fused kernel wins, 1.99 vs 2.03 ms); the fused kernel (everything on chip) where
+// it accepts the layer; bf16x3 GEMMs on 128 x 128 or 64 x 64 tiles (gemm.hip splits alike); f32 GEMMs.
+static int winograd43_route(int h, int w, int cin, int cout, bool has_packed, bool has_x3) {
   const size_t T = (size_t)((h + 3) / 4) * ((w + 3) / 4);
-  return cout >= x3_min_cout() && x3_enabled(T, cout) && (long)((T + 127) / 128) * ((cout + 127) / 128) * 36 >= x3_min_tiles();
+  const bool x3 = has_x3 && cin % 32 == 0 && x3_enabled(T, cout);
+  const bool x3_128 = x3 && (long)((T + 127) / 128) * ((cout + 127) / 128) * 36 >= x3_min_tiles();
+  if (x3_128 && cout >= x3_min_cout()) return STROTSS_ROUTE_F4_X3_GEMM_128;
+  if (has_packed && cin % 32 == 0 && st_winograd43_fused_enabled(h, w, cout)) return STROTSS_ROUTE_F4_FUSED_F32;
+  if (!x3) return STROTSS_ROUTE_F4_GEMM_F32;
+  return x3_128 ? STROTSS_ROUTE_F4_X3_GEMM_128 : STROTSS_ROUTE_F4_X3_GEMM_64;
 }
 
 // Measurement hook (strotss_debug_winograd_stages): which stages of the F(4x4,3x3) three-kernel form are launched.
@@ -396,15 +405,13 @@ static int winograd43_run(const float* in, int h, int w, int cin, const float* U
                           const void* Ux3, const float* bias, int cout, const float* mask, int relu, float* out,
                           float* pool_out, unsigned char* pool_code, void* workspace, size_t workspace_bytes,
                           hipStream_t st, const unsigned* bits_in = nullptr, unsigned* bits_out = nullptr, int accumulate = 0) {
-  // 256 output channels and enough tiles for the bf16x3 GEMMs: the three-kernel form wins (1024-px step 5.102 -> 5.039 ms,
-  // three alternating runs each); STROTSS_X3_MIN_COUT (default 256) moves the border
-  const bool prefer_x3 = Ux3 && cin % 32 == 0 && winograd43_prefers_x3(h, w, cout);
-  if (!prefer_x3 && Upacked && cin % 32 == 0 && st_winograd43_fused_enabled(h, w, cout))      // everything on chip
+  const int route = winograd43_route(h, w, cin, cout, Upacked != nullptr, Ux3 != nullptr);
+  if (route == STROTSS_ROUTE_F4_FUSED_F32)
     return st_winograd43_fused(in, h, w, cin, Upacked, bias, cout, mask, relu, out, pool_out, pool_code, bits_in, bits_out, st,
                                accumulate);
   const int TH = (h + 3) / 4, TW = (w + 3) / 4;
   const size_t T = (size_t)TH * TW;
-  const bool x3 = Ux3 && cin % 32 == 0 && x3_enabled(T, cout);
+  const bool x3 = route != STROTSS_ROUTE_F4_GEMM_F32;
   if (T * (size_t)(max(cin, cout) / 4 + 8) >= (1ull << 32)) return STROTSS_ERANGE;     // 32-bit element indices in the transforms
   Workspace ws(workspace, workspace_bytes);
   float* V = ws.take<float>(36 * T * cin * 3 / 2);           // f32 V, or its x3 panels (3 bf16 per value)
@@ -602,12 +609,7 @@ int strotss_debug_winograd_stages(int mask) {
 int strotss_conv3x3_winograd_route(int h, int w, int cin, int cout, int tile_m, int has_packed, int has_x3) {
   if (h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || (tile_m != 2 && tile_m != 4)) return STROTSS_EINVAL;
   if (tile_m == 2) return STROTSS_ROUTE_F2_GEMM_F32;
-  const size_t T = (size_t)((h + 3) / 4) * ((w + 3) / 4);
-  const bool prefer_x3 = has_x3 && cin % 32 == 0 && winograd43_prefers_x3(h, w, cout);
-  if (!prefer_x3 && has_packed && cin % 32 == 0 && st_winograd43_fused_enabled(h, w, cout)) return STROTSS_ROUTE_F4_FUSED_F32;
-  if (!(has_x3 && cin % 32 == 0 && x3_enabled(T, cout))) return STROTSS_ROUTE_F4_GEMM_F32;
-  return (long)((T + 127) / 128) * ((cout + 127) / 128) * 36 >= x3_min_tiles() ? STROTSS_ROUTE_F4_X3_GEMM_128
-                                                                             : STROTSS_ROUTE_F4_X3_GEMM_64;
+  return winograd43_route(h, w, cin, cout, has_packed != 0, has_x3 != 0);
 }
 
 size_t strotss_conv3x3_winograd_x3_bytes(int rows, int k) { return (size_t)36 * 3 * rows * k * sizeof(unsigned short); }

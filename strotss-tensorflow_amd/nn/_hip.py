@@ -101,6 +101,7 @@ SIGNATURES = {
     "strotss_conv3x3_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "strotss_conv3x3_relu_fwd": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _Z, _P]),
     "strotss_conv3x3_dgrad": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _I, _P, _Z, _P]),
+    "strotss_conv3x3_dgrad_can_accumulate": (_I, [_I, _I, _I, _I]),
     "strotss_conv3x3_relu_pool_fwd": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _Z, _P]),
     "strotss_conv3x3_dgrad_unpool": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _I, _I, _I, _P, _Z, _P]),
     "strotss_conv3x3_c3_dgrad": (_I, [_P, _I, _I, _I, _P, C.POINTER(_F), _P, _I, _P]),
@@ -148,6 +149,7 @@ SIGNATURES = {
     "strotss_palette_remd_fwd_bwd": (_I, [_P, _I, _P, _I, _I, _I, _F, _P, _P, _I, _P, _Z, _P]),
     "strotss_remd_metric_workspace_bytes": (_Z, [_I, _I]),
     "strotss_remd_metric_fwd_bwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _F, _P, _P, _I, _P, _Z, _P]),
+    "strotss_step_losses_available": (_I, []),
     "strotss_step_losses_workspace_bytes": (_Z, [_I, _I, _I]),
     "strotss_step_losses_fwd_bwd": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "strotss_step_losses_blend_workspace_bytes": (_Z, [C.POINTER(StyleSetT), _I, _I]),

@@ -383,6 +383,12 @@ def conv3x3_direct_splits(h: int, w: int, cin: int, cout: int) -> bool:
     return _hip.load_library().strotss_conv3x3_workspace_bytes(h, w, cin, cout) > 0
 
 
+def conv3x3_dgrad_accumulates(h: int, w: int, cout: int, cin: int) -> bool:
+    """True when conv3x3_dgrad(accumulate=True) launches for a (h, w, cout) gradient of a cin-channel input (the library's
+    answer: its one-pass kernel of STROTSS_CONV_VARIANT=1 only overwrites).  No GPU needed."""
+    return bool(_hip.load_library().strotss_conv3x3_dgrad_can_accumulate(h, w, cout, cin))
+
+
 def conv3x3_dgrad(gout, w_tik, cin, act_in=None, out=None, accumulate=False):
     require(gout, "conv grad"); h, w, cout = hwc(gout)
     if out is None:
@@ -452,8 +458,8 @@ _x3 = {}           # id(u) -> (weakref(u), panels): bf16x3 "x3 panels" of frozen
 
 
 def env_int(name: str, default: int) -> int:
-    """A switch the library reads too, parsed as its getenv + atoi / atol do: `default` when unset, otherwise the leading
-    integer (after white space, with an optional sign), 0 when there is none -- so "", "00" and "false" are 0 on both sides."""
+    """A host-only switch, parsed as the library's getenv + atoi / atol parse theirs: `default` when unset, otherwise the
+    leading integer (after white space, with an optional sign), 0 when there is none -- so "", "00" and "false" are 0."""
     import os
     import re
     v = os.environ.get(name)
@@ -464,18 +470,11 @@ def env_int(name: str, default: int) -> int:
 
 
 def winograd_x3_wanted(p: int, rows: int, k: int, h: int, w: int) -> bool:
-    """Whether the library would run an (h, w) layer with (p, rows, k) Winograd weights on the bf16x3 GEMM core: same policy
-    as csrc/winograd.hip x3_enabled (at least STROTSS_X3_MIN_TILES 64 x 64 GEMM tiles) on the layers the fused kernel
-    does not take.  Pure host arithmetic (tests/test_route_table.py pins it without a GPU)."""
-    tiles = -(-(-(-h // 4) * -(-w // 4)) // 64) * -(-rows // 64) * 36       # 64 x 64 tiles (csrc/winograd.hip x3_enabled)
-    if p != 36 or k % 32 or env_int("STROTSS_X3", 1) == 0 or env_int("STROTSS_X3_CONV", 1) == 0:
-        return False
-    min_tiles = env_int("STROTSS_X3_MIN_TILES", 1024)
-    tiles128 = -(-(-(-h // 4) * -(-w // 4)) // 128) * -(-rows // 128) * 36
-    fused_takes_it = (rows <= env_int("STROTSS_WINO_FUSED_MAX_COUT", 256)
-                      and (rows < env_int("STROTSS_X3_MIN_COUT", 256) or tiles128 < min_tiles)
-                      and env_int("STROTSS_WINO_FUSED", 1) != 0)
-    return not (tiles < min_tiles or fused_takes_it)
+    """Whether an (h, w) layer with (p, rows, k) Winograd weights gets x3 panels: exactly where the library, offered them
+    next to the packed copy it would also be offered, answers with a bf16x3 GEMM route (csrc/winograd.hip winograd43_route,
+    the function its launches dispatch on).  A question to the library, no policy of the host's; needs no GPU."""
+    return p == 36 and _hip.load_library().strotss_conv3x3_winograd_route(
+        h, w, k, rows, 4, int(winograd_packed_wanted(p, rows, k)), 1) in (3, 4)      # STROTSS_ROUTE_F4_X3_GEMM_128 / _64
 
 
 def winograd_packed_wanted(p: int, rows: int, k: int) -> bool:
@@ -897,9 +896,9 @@ def remd_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, gsca
 
 
 def step_losses_available() -> bool:
-    """the grouped loss entries run (bf16x3 cost and moment products: csrc/losses.hip cost_x3, moment_x3), and
-    STROTSS_GROUPED_LOSSES does not switch them off"""
-    return all(env_int(k, 1) != 0 for k in ("STROTSS_X3", "STROTSS_X3_COST", "STROTSS_X3_MOMENT", "STROTSS_GROUPED_LOSSES"))
+    """the library's grouped loss entries would not refuse on account of its switches (strotss_step_losses_available), and
+    the host-only STROTSS_GROUPED_LOSSES does not switch them off"""
+    return bool(_hip.load_library().strotss_step_losses_available()) and env_int("STROTSS_GROUPED_LOSSES", 1) != 0
 
 
 def step_losses_fwd_bwd(pred, content, n, d, style, rs, style_panels, ns, style_mean, style_cov, g_content, g_moment, g_remd,

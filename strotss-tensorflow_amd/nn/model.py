@@ -124,20 +124,22 @@ ROUTE_NAMES = {0: "F2_gemm_f32", 1: "F4_fused_f32", 2: "F4_gemm_f32", 3: "F4_x3_
 
 
 def conv_route(h: int, w: int, cin: int, cout: int, dgrad: bool = False) -> str:
-    """Which kernels the generic 3x3 layer `cin` -> `cout` runs at (h, w), forward or data-gradient: the host policy above
-    (`winograd_tile`, one decision per layer for both directions, as VGGTrunk takes it) followed by the library's
-    (`strotss_conv3x3_winograd_route` / `strotss_conv3x3_workspace_bytes`, include/strotss_hip.h; the data-gradient is the
-    same kernel with the channel roles swapped).  No GPU needed: tests/test_route_table.py pins the default table of the
-    five BASELINE scales so that a policy regression cannot pass unnoticed."""
+    """Which kernels the generic 3x3 layer `cin` -> `cout` runs at (h, w), forward or data-gradient.  The host policy is only
+    `use_winograd` / `winograd_tile` / `direct_splitk` above (one decision per layer for both directions, as VGGTrunk takes
+    it); everything behind it the library decides and is asked for: `strotss_conv3x3_workspace_bytes` for the direct forms,
+    `strotss_conv3x3_winograd_route` for the Winograd forms -- csrc/winograd.hip winograd43_route, the one statement of that
+    policy, on which the launches dispatch (the data-gradient is the same kernel with the channel roles swapped).  Asked with
+    has_x3 = 1, because the host makes the x3 panels exactly where that answer is a bf16x3 route (`_ops.winograd_x3_wanted`)
+    and a route that is no bf16x3 route does not depend on has_x3.  No GPU needed: tests/test_route_table.py pins the
+    default table of the five BASELINE scales so that a policy regression cannot pass unnoticed."""
     from . import _hip
     t = winograd_tile(h, w, cin, cout) if use_winograd(cin, cout) else 0
     ci, co = (cout, cin) if dgrad else (cin, cout)
     if t == 0:
         return "direct_splitk" if _ops.conv3x3_direct_splits(h, w, ci, co) else "direct"
     p = 16 if t == 2 else 36
-    r = int(_hip.load_library().strotss_conv3x3_winograd_route(h, w, ci, co, t, int(_ops.winograd_packed_wanted(p, co, ci)),
-                                                               int(_ops.winograd_x3_wanted(p, co, ci, h, w))))
-    return ROUTE_NAMES[r]
+    return ROUTE_NAMES[int(_hip.load_library().strotss_conv3x3_winograd_route(
+        h, w, ci, co, t, int(_ops.winograd_packed_wanted(p, co, ci)), 1))]
 
 
 class _LazyWinograd:
@@ -321,8 +323,10 @@ class VGGTrunk:
                 a = self.acts[li]
                 if self.wtile[li] == 4:
                     continue                              # winograd_dgrad(accumulate=1): any F(4x4,3x3) route
-                if self.wtile[li] != 0:                   # (F(2x2,3x3) overwrites; the direct kernels add, split-K or not)
+                if self.wtile[li] != 0:                   # F(2x2,3x3) overwrites
                     return False
+                if not _ops.conv3x3_dgrad_accumulates(int(a.shape[1]), int(a.shape[2]), L["cout"], L["cin"]):
+                    return False                          # the direct kernels add, as far as the library says so
         return n - 1 in tapped                            # (the deepest layer is scattered into a zeroed buffer anyway)
 
     def _src(self, src):

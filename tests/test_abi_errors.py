@@ -35,6 +35,10 @@ def test_convolutions_refuse_bad_shapes_and_missing_buffers(lib):
     assert lib.strotss_conv3x3_relu_fwd(P, 8, 8, 64, P, P, 96, P, P, WS, NULL) == EALIGN
     assert lib.strotss_conv3x3_relu_fwd(P, 0, 8, 64, P, P, 64, P, P, WS, NULL) == EINVAL
     assert lib.strotss_conv3x3_dgrad(P, 8, 8, 64, P, 65, NULL, P, 0, P, WS, NULL) == EALIGN
+    # ... and the query whether its accumulate form would launch answers 0 for what that entry refuses, never an error code
+    assert lib.strotss_conv3x3_dgrad_can_accumulate(8, 8, 64, 65) == 0
+    assert lib.strotss_conv3x3_dgrad_can_accumulate(0, 8, 64, 64) == 0
+    assert lib.strotss_conv3x3_dgrad_can_accumulate(8, 8, 64, 64) in (0, 1)
     # pooled finish (ABI 8): needs the pooled output and a workspace; the gradient in front of the pool must be 2x the map
     assert lib.strotss_conv3x3_relu_pool_fwd(P, 8, 8, 64, P, P, 64, P, NULL, NULL, P, WS, NULL) == EINVAL
     assert lib.strotss_conv3x3_relu_pool_fwd(P, 8, 8, 64, P, P, 64, P, P, NULL, NULL, 0, NULL) == EINVAL
@@ -60,6 +64,7 @@ def test_losses_refuse_unpadded_rows_and_oversized_lists(lib):
     assert lib.strotss_step_losses_fwd_bwd(*args(0, 2179, 2208, 1024)) == EINVAL
     bad = list(args(1024, 2179, 2208, 1024)); bad[15] = NULL                                   # no gradient buffer
     assert lib.strotss_step_losses_fwd_bwd(*bad) == EINVAL
+    assert lib.strotss_step_losses_available() in (0, 1)                                       # (a query: no error codes)
 
 
 def test_sampling_entries_refuse_bad_descriptors(lib):

@@ -20,7 +20,8 @@ def test_header_declares_the_hot_path():
     syms = declared_symbols()
     for must in ("strotss_selfsim_fwd_bwd", "strotss_remd_cos_fwd_bwd", "strotss_moment_fwd_bwd",
                  "strotss_conv3x3_relu_fwd", "strotss_conv3x3_dgrad", "strotss_hypercol_gather",
-                 "strotss_hypercol_scatter", "strotss_rmsprop_step", "strotss_resize_bilinear"):
+                 "strotss_hypercol_scatter", "strotss_rmsprop_step", "strotss_resize_bilinear",
+                 "strotss_conv3x3_winograd_route", "strotss_conv3x3_dgrad_can_accumulate", "strotss_step_losses_available"):
         assert must in syms
 
 

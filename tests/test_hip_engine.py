@@ -386,6 +386,41 @@ def test_prescatter_backward_equals_the_interleaved_one():
         assert float((a - b).norm() / b.norm()) < 1e-5
 
 
+_VARIANT1_CHILD = """
+import sys; sys.path[:0] = %r
+import torch, test_hip_engine as T
+# 96 px: block1_conv2's data-gradient (64 -> 64 at 96 x 96) is a one-pass direct kernel and writes a tapped buffer
+S = T._setup(96, 96, 384, seed=5); eng = S["eng"]
+assert not eng.trunk.prescatter, "the library's one-pass kernel overwrites under this variant"
+eng.forward_backward([torch.from_numpy(S["idx_sets"][0][0]).to(T.DEV)])
+assert all(bool(torch.isfinite(g).all()) and float(g.norm()) > 0 for g in eng.gvars)
+# 64 px: every tapped gradient comes from a split-K data-gradient or a pool backward, which add under every variant
+S = T._setup(64, 64, 384, seed=5); eng = S["eng"]
+assert eng.trunk.prescatter
+i0 = torch.from_numpy(S["idx_sets"][0][0]).to(T.DEV)
+eng.forward_backward([i0]); pre = [g.clone() for g in eng.gvars]
+eng.trunk.prescatter = False
+eng.forward_backward([i0])
+for a, b in zip(pre, eng.gvars):
+    assert float((a - b).norm() / b.norm()) < 1e-5
+print("variant 1 ok")
+"""
+
+
+def test_prescatter_asks_the_library_whether_the_direct_data_gradient_adds():
+    """STROTSS_CONV_VARIANT=1 (read once per process, hence a child): the one-pass direct kernel of that variant only
+    overwrites, so strotss_conv3x3_dgrad refuses `accumulate` there.  The trunk asks the library before it pre-scatters
+    (strotss_conv3x3_dgrad_can_accumulate): the step runs at a size with such a layer, interleaved, and where every
+    producer still adds the pre-scattered backward equals the interleaved one as in the test above."""
+    import subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    paths = [os.path.join(root, "tests"), os.path.join(root, "strotss-tensorflow_amd"), root]
+    env = {k: v for k, v in os.environ.items() if not k.startswith("STROTSS_")}
+    out = subprocess.run([sys.executable, "-c", _VARIANT1_CHILD % (paths,)], env=dict(env, STROTSS_CONV_VARIANT="1"), cwd=root,
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "variant 1 ok" in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]
+
+
 # ------------------------------------------------------------------ operator surface (autograd)
 def test_losses_api_autograd():
     from nn import losses as L
