@@ -491,7 +491,14 @@ int strotss_moment_fwd_bwd(const float* style_mean, const float* style_cov, cons
  *   certainty(y, x) = 0 where the sample point lies outside [0, w-1] x [0, h-1], where it is disoccluded (flow_f given:
  *                     |f_b + f_f(p + f_b)|^2 > 0.01 (|f_b|^2 + |f_f(p + f_b)|^2) + 0.5, f_f sampled by the same rule) or on
  *                     a motion boundary (|grad u_b|^2 + |grad v_b|^2 > 0.01 |f_b|^2 + 0.002, central differences with
- *                     clamped indices); 1 elsewhere.  Coordinates and tests in float64. */
+ *                     clamped indices); 1 elsewhere.  Coordinates and tests in float64.
+ * Out-of-range and non-finite coordinates, per axis (n = w or h): the coordinate s = x + u is clamped to [-2, n + 1] before
+ * its floor, a NaN taken as -2; both taps are then clamped to [0, n - 1].  So s < 0, -inf and NaN sample the edge pixel 0,
+ * s > n - 1 and +inf the edge pixel n - 1: warped is finite wherever prev is, whatever the flows hold.  s == n - 1 is inside
+ * the frame (certainty by the other tests, the sample exact); the next float32 u beyond it, +-inf and NaN are outside:
+ * certainty 0, and flow_f is not consulted.  The threshold tests are IEEE `>` comparisons: a NaN on the left (a NaN in a
+ * neighbour's flow_b or in a tap of flow_f, zero-weight taps included, or inf - inf) removes nothing, +inf against a finite
+ * right side removes the pixel.  Pixels whose own tests read only finite values are unaffected by non-finite ones elsewhere. */
 int strotss_flow_warp(const float* prev, int h, int w, int c, const float* flow_b, const float* flow_f, float* warped,
                       float* certainty, void* stream);
 /* bytes of the workspace of strotss_temporal_fwd_bwd (0 for h, w <= 0) */

@@ -1,7 +1,9 @@
 """Optical flow of --video sequences without a GPU: the numpy restatement of strotss_optical_flow on
 known motion (the acceptance table's two conditions), the .flo writer, the --compute_flow / --save_flow command line and
 its refusals, the header's declarations, and the status codes of refused strotss_optical_flow calls (checked before
-anything launches)."""
+anything launches).  And the conditions of the device tests' cases (_flow_cases.py): the restatement runs on each, its
+level count is the expected one, the float32 yardstick is positive and below the cap, degenerate frames give exactly 0, and
+strotss_flow_workspace_bytes is the total the restatement's levels imply."""
 import ctypes as C
 import os
 import re
@@ -17,6 +19,7 @@ for p in (ROOT, PKG, os.path.join(ROOT, "tests")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+import _flow_cases as FC  # noqa: E402
 import _flow_ref as R  # noqa: E402
 import _temporal_ref as T  # noqa: E402
 
@@ -77,6 +80,90 @@ def test_blur_and_sampling_rules():
     ref = T.bilinear(img[..., None], xs + 0.3, ys - 0.6)[..., 0]
     assert np.array_equal(R.bilinear(img, xs + 0.3, ys - 0.6), ref)    # the rule of _temporal_ref.bilinear
     assert np.array_equal(R.upsample(np.full((2, 2), 1.5), 4, 3), np.full((4, 3), 3.0))
+
+
+# ------------------------------------------------------------------ the cases of the device tests meet their conditions
+ALL_CASES = FC.stage_cases() + FC.grid_cases() + [c[:5] for c in FC.threshold_cases()]
+
+
+def test_case_lists_are_the_ones_the_device_tests_need():
+    assert (FC.FLOW_TW, FC.FLOW_TH) == tuple(
+        int(re.search(r"#define\s+%s\s+(\d+)" % n, open(os.path.join(PKG, "csrc", "flow.hip")).read()).group(1))
+        for n in ("FLOW_TW", "FLOW_TH"))
+    shapes = set(FC.STAGE_SHAPES)
+    assert {(2, 2), (2, 300), (300, 2), (3, 5), (42, 63)} <= shapes
+    for d in (-1, 0, 1):                                 # one below, on and above each tile side, the other side odd
+        assert any(h == FC.FLOW_TH + d and w % 2 for h, w in shapes) and any(w == FC.FLOW_TW + d and h % 2 for h, w in shapes)
+    assert any(h % 2 and w % 2 and ((h + 1) // 2) % 2 and ((w + 1) // 2) % 2 for h, w in shapes)
+    assert len(FC.stage_cases()) == len(FC.STAGE_SETS) * len(FC.STAGE_SHAPES)
+    for name, p in FC.STAGE_SETS.items():
+        assert p["min_side"] == 1 and p["iters"] % p["iters_per_launch"] == 0, name
+    assert all(FC.STAGE_SETS[n]["iters_per_launch"] == 1 for n in ("first_sweep", "two_levels", "second_warp", "odd_sweeps"))
+    launches = {n: p["iters"] // p["iters_per_launch"] for n, p in FC.STAGE_SETS.items()}
+    assert launches["odd_sweeps"] % 2 == 1 and launches["one_blocked_launch"] == 1          # odd ping-pong parity per warp
+    # a stage set has the levels it names wherever a side can be halved at all
+    for cid, h, w, _, p in FC.stage_cases():
+        assert FC.n_levels(h, w, p) == p["max_levels"], cid
+    moved = {k: sorted(m[k] for m in FC.GRID_MOVES if k in m) for k in ("alpha2", "warps", "iters", "max_levels", "min_side")}
+    assert moved == dict(alpha2=[1e-3, 0.1], warps=[1, 3], iters=[8, 24], max_levels=[1, 2, 8], min_side=[1, 6, 20])
+    assert len(FC.grid_cases()) == 2 * 12 and {(h, w) for _, h, w, _, _ in FC.grid_cases()} == {(42, 63), (97, 130)}
+
+
+@pytest.mark.parametrize("case", FC.threshold_cases(), ids=[c[0] for c in FC.threshold_cases()])
+def test_threshold_cases_sit_on_the_level_rule(case):
+    cid, h, w, seed, params, levels, other, other_levels = case
+    assert params["min_side"] == 12
+    assert FC.n_levels(h, w, params) == levels and FC.n_levels(h, w, other) == other_levels
+    assert abs(levels - other_levels) == 1
+    f_own, y_own = FC.reference(h, w, seed, params)
+    f_other, y_other = FC.reference(h, w, seed, other)
+    gap = float(np.abs(f_own - f_other).max())
+    print(f"{cid}: {levels} levels against {other_levels}: max |F - F_other| = {gap:.3e}, yardsticks {y_own:.3e} {y_other:.3e}")
+    # the other level count is another flow by far more than the device test's tolerance (4 x yardstick; a flow within it
+    # of one statement is then at least 9 tolerances from the other): the rule decides, not the bound
+    assert gap > 10 * 4.0 * max(y_own, y_other)
+
+
+def test_threshold_pairs_of_the_level_rule():
+    sizes = {(t["h"], t["w"]): t["levels"] for t in FC.THRESHOLDS}
+    assert sizes[(24, 40)] == sizes[(23, 40)] + 1                    # 24 // 2 = 12 >= 12 gains a level, 23 // 2 = 11 does not
+    assert sizes[(48, 50)] == sizes[(47, 50)] == sizes[(46, 50)] + 1  # ceil(47 / 2) = 24 keeps the third level, 23 loses it
+    assert R.level_sizes(47, 50) == [(47, 50), (24, 25), (12, 13)] and R.level_sizes(46, 50) == [(46, 50), (23, 25)]
+
+
+@pytest.mark.parametrize("case", ALL_CASES, ids=[c[0] for c in ALL_CASES])
+def test_case_yardstick_is_positive_and_below_the_cap(case):
+    cid, h, w, seed, params = case
+    f64, yard = FC.reference(h, w, seed, params)
+    assert f64.shape == (h, w, 2) and f64.dtype == np.float64 and np.isfinite(f64).all()
+    print(f"{cid}: {FC.n_levels(h, w, params)} levels, max |F_f32ref - F_f64ref| = {yard:.3e}, max |F| = {np.abs(f64).max():.3f}")
+    assert 0 < yard < FC.YARDSTICK_CAP
+    assert np.abs(f64).max() > 1e3 * yard                # a real flow, far above its own rounding
+
+
+def test_degenerate_frames():
+    for name in FC.ZERO_FLOW:                            # exactly 0 in both number formats
+        f64, f32 = FC.degenerate_reference(name)
+        assert f64.dtype == np.float64 and f32.dtype == np.float32
+        assert (f64 == 0).all() and (f32 == 0).all(), name
+    a, b = FC.degenerate_pair("identical")
+    assert b is a
+    a, b = FC.degenerate_pair("constants")
+    assert len(np.unique(a)) == 1 and len(np.unique(b)) == 1 and a[0, 0, 0] != b[0, 0, 0]
+    a, b = FC.degenerate_pair("blocks")
+    assert set(np.unique(a)) == set(np.unique(b)) == {0.0, 1.0} and np.array_equal(a[:-1, :-1], b[1:, 1:])
+    h, w = FC.DEGENERATE_SHAPE
+    a, b = FC.degenerate_pair("far_translation")
+    assert np.array_equal(b[:, int(round(0.4 * w)):], a[:, :w - int(round(0.4 * w))])
+    for name in FC.FINITE_FLOW:
+        f64, f32 = FC.degenerate_reference(name)
+        yard = float(np.abs(f32.astype(np.float64) - f64).max())
+        print(f"{name}: max |F_f32ref - F_f64ref| = {yard:.3e}, max |F| = {np.abs(f64).max():.3f}")
+        assert np.isfinite(f64).all() and 0 < yard < FC.YARDSTICK_CAP
+    # the far translation does carry the warp's samples outside the frame
+    f64 = FC.degenerate_reference("far_translation")[0]
+    xs = np.arange(w)[None, :] + f64[..., 0]
+    assert (xs > w - 1).any() or (xs < 0).any()
 
 
 # ------------------------------------------------------------------ .flo files
@@ -198,6 +285,22 @@ def test_flow_defaults_and_workspace_bytes(lib):
     for bad in BAD_PARAMS:
         assert lib.strotss_flow_workspace_bytes(48, 64, C.byref(_params(lib, **bad))) == 0, bad
     assert lib.strotss_flow_workspace_bytes(48, 64, C.byref(_params(lib, iters=30, iters_per_launch=2))) == nb
+
+
+@pytest.mark.parametrize("case", ALL_CASES, ids=[c[0] for c in ALL_CASES])
+def test_workspace_bytes_are_what_the_levels_imply(lib, case):
+    cid, h, w, seed, params = case
+    want = FC.workspace_bytes(h, w, params)
+    # every level adds two planes of at least 256 bytes: a level count off by one is another total, without a GPU
+    assert lib.strotss_flow_workspace_bytes(h, w, C.byref(_params(lib, **params))) == want
+
+
+def test_workspace_bytes_of_the_forced_level_counts(lib):
+    for cid, h, w, seed, params, levels, other, other_levels in FC.threshold_cases():
+        own = lib.strotss_flow_workspace_bytes(h, w, C.byref(_params(lib, **params)))
+        forced = lib.strotss_flow_workspace_bytes(h, w, C.byref(_params(lib, **other)))
+        assert own == FC.workspace_bytes(h, w, params) and forced == FC.workspace_bytes(h, w, other), cid
+        assert (own > forced) == (levels > other_levels) and own != forced, cid
 
 
 def test_optical_flow_refuses_before_launching(lib):

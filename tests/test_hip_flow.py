@@ -1,6 +1,9 @@
 """strotss_optical_flow on the MI355X: the temporally blocked solver against the plain one bit for
 bit, the flow against the float64 restatement with the float32 restatement's own distance as the yardstick, accuracy on
-known motion, reproducibility and refusals, and --video --compute_flow end to end.  Every test prints the figures its
+known motion, reproducibility and refusals, and --video --compute_flow end to end.  Then the cases of _flow_cases.py
+(test_flow_cpu.py proves their conditions): the stage sets, which make the flow a few operations of one or two kernels so
+that no later sweep forgets an early error, at the small and tile-edge shapes; the blocked solver at those shapes; every
+parameter moved from its default; the level rule on its threshold; degenerate frames.  Every test prints the figures its
 assertions are judged by; the measured ones are in DESIGN.md section 14."""
 import ctypes as C
 import os
@@ -11,6 +14,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _flow_cases as FC  # noqa: E402
 import _flow_ref as R  # noqa: E402
 import _temporal_ref as T  # noqa: E402
 
@@ -122,7 +126,85 @@ def test_bad_arguments_return_the_codes_and_write_nothing():
     assert bool(torch.isfinite(out).all()) and not bool((out == 7.0).all())
 
 
-# ------------------------------------------------------------------ 5. --video --compute_flow end to end
+# ------------------------------------------------------------------ 5. stage by stage, parameter by parameter
+def _against_float64(cid, got, f64, yard):
+    """print the figures and assert |F_hip - F_f64| <= F32_YARDSTICK x yardstick"""
+    err = np.abs(got.astype(np.float64) - f64)
+    dist = float(err.max())
+    y, x, k = np.unravel_index(int(err.argmax()), err.shape)
+    print(f"{cid}: yardstick max |F_f32ref - F_f64ref| = {yard:.3e}, max |F_hip - F_f64ref| = {dist:.3e} at (y {y}, x {x}, "
+          f"{'uv'[k]}), ratio {dist / yard:.2f}, max |F| = {np.abs(f64).max():.3f}")
+    assert np.isfinite(got).all(), cid
+    assert dist <= F32_YARDSTICK * yard, (cid, dist, yard)
+    return dist
+
+
+@pytest.mark.parametrize("case", FC.stage_cases(), ids=[c[0] for c in FC.stage_cases()])
+def test_stage_sets_match_float64(case):
+    cid, h, w, seed, params = case
+    a, b = FC.frames(h, w, seed)
+    f64, yard = FC.reference(h, w, seed, params)
+    _against_float64(cid, _flow(a, b, **params).cpu().numpy(), f64, yard)
+
+
+@pytest.mark.parametrize("hw", FC.STAGE_SHAPES, ids=[f"{h}x{w}" for h, w in FC.STAGE_SHAPES])
+def test_blocked_sweeps_equal_the_plain_form_at_small_and_tile_edge_shapes(hw):
+    h, w = hw
+    a, b = FC.frames(h, w, 1000 + 7 * h + w)
+    for iters in (8, 24):                                # K = 8: 1 and 3 launches per warp, odd ping-pong parities
+        plain = _flow(a, b, iters=iters, iters_per_launch=1)
+        assert torch.isfinite(plain).all() and float(plain.abs().max()) > 0
+        for k in (8, 4, 2):
+            blocked = _flow(a, b, iters=iters, iters_per_launch=k)
+            d = (blocked - plain).abs()
+            bad = torch.nonzero(d.sum(-1) > 0)
+            print(f"{h} x {w}, {iters} sweeps, {k} per launch ({iters // k} launches per warp): {len(bad)} pixels differ, "
+                  f"max {float(d.max()):.3e}, first at {bad[:5].tolist()}")
+            assert torch.equal(blocked.view(torch.int32), plain.view(torch.int32)), (hw, iters, k)
+
+
+@pytest.mark.parametrize("case", FC.grid_cases(), ids=[c[0] for c in FC.grid_cases()])
+def test_every_parameter_moved_matches_float64(case):
+    cid, h, w, seed, params = case
+    a, b = FC.frames(h, w, seed)
+    f64, yard = FC.reference(h, w, seed, params)
+    _against_float64(cid, _flow(a, b, **params).cpu().numpy(), f64, yard)
+
+
+@pytest.mark.parametrize("case", FC.threshold_cases(), ids=[c[0] for c in FC.threshold_cases()])
+def test_level_rule_on_its_threshold(case):
+    cid, h, w, seed, params, levels, other, other_levels = case
+    a, b = FC.frames(h, w, seed)
+    f64, yard = FC.reference(h, w, seed, params)
+    g64, yard_other = FC.reference(h, w, seed, other)
+    own = _flow(a, b, **params).cpu().numpy()
+    forced = _flow(a, b, **other).cpu().numpy()
+    _against_float64(f"{cid}, {levels} levels", own, f64, yard)
+    _against_float64(f"{cid} forced to {other_levels} levels", forced, g64, yard_other)
+    gap = float(np.abs(own.astype(np.float64) - forced).max())
+    print(f"{cid}: max |F_hip - F_hip forced to {other_levels} levels| = {gap:.3e}")
+    assert gap > F32_YARDSTICK * max(yard, yard_other)    # the level rule, not the tolerance, decides
+
+
+@pytest.mark.parametrize("name", FC.ZERO_FLOW)
+def test_identical_and_constant_frames_give_exactly_zero(name):
+    a, b = FC.degenerate_pair(name)
+    for k in (1, 8):                                     # both solver forms; == 0, so that -0.0 passes
+        got = _flow(a, b, iters_per_launch=k)
+        nonzero = int((got != 0).sum())
+        print(f"{name}, {k} sweeps per launch: {nonzero} non-zero values, max |F| = {float(got.abs().max()):.3e}")
+        assert bool((got == 0).all()), (name, k)
+
+
+@pytest.mark.parametrize("name", FC.FINITE_FLOW)
+def test_block_frames_and_a_far_translation_match_float64(name):
+    a, b = FC.degenerate_pair(name)
+    f64, f32 = FC.degenerate_reference(name)
+    yard = float(np.abs(f32.astype(np.float64) - f64).max())
+    _against_float64(name, _flow(a, b).cpu().numpy(), f64, yard)
+
+
+# ------------------------------------------------------------------ 6. --video --compute_flow end to end
 H, W, SHIFT = 48, 64, (3, 2)
 CONSISTENCY_RATIO = 0.3         # E(default lambda) < ratio * E(0), the criterion of test_video_end_to_end (DESIGN.md section 12)
 

@@ -21,17 +21,6 @@ DEV = "cuda"
 D = 2179
 
 
-def _smooth_flow(h, w, seed, amp=3.0):
-    """a few pixels of displacement, gradients mostly below the motion-boundary threshold"""
-    rng = np.random.default_rng(seed)
-    ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
-    f = np.zeros((h, w, 2))
-    for k in range(2):
-        a, b, p, q = rng.uniform(0.01, 0.06, 4)
-        f[..., k] = amp * (np.sin(a * xs + p * 7) * np.cos(b * ys + q * 5)) + rng.uniform(-2, 2)
-    return f.astype(np.float32)
-
-
 def _dev(a):
     return torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device=DEV)
 
@@ -42,13 +31,9 @@ def _dev(a):
 def test_flow_warp_matches_float64(with_forward, hw):
     from nn import _ops
     h, w = hw
-    rng = np.random.default_rng(h * w)
-    prev = rng.random((h, w, 3)).astype(np.float32)
-    fb = _smooth_flow(h, w, 1)
-    ff = None
-    if with_forward:        # roughly the inverse flow, wrong in a band: some pixels disoccluded, most not
-        ff = (-fb + rng.normal(0, 0.05, fb.shape)).astype(np.float32)
-        ff[h // 3: h // 3 + 5] += 3.0
+    # the inputs of _temporal_ref.random_warp_case: test_temporal_cpu.py proves that every threshold test of theirs is a
+    # margin away from equality, so the array_equal below does not hang on how the device contracts its float64 to FMAs
+    prev, fb, ff = T.random_warp_case(h, w, with_forward)
     warped, cert = _ops.flow_warp(_dev(prev)[None], _dev(fb), None if ff is None else _dev(ff))
     torch.cuda.synchronize()
     ref_w, ref_c = T.warp64(prev, fb), T.certainty64(fb, ff)
@@ -74,6 +59,37 @@ def test_flow_warp_integer_shifts_are_exact(shift):
         assert np.array_equal(cert.cpu().numpy(), T.certainty64(fb, f).astype(np.float32))
         dx, dy = shift
         assert cert.sum().item() == (w - abs(dx)) * (h - abs(dy))
+
+
+@pytest.mark.parametrize("hw", T.WARP_SHAPES, ids=[f"{h}x{w}" for h, w in T.WARP_SHAPES])
+def test_flow_warp_shapes_channels_borders_and_non_finite_flows(hw):
+    """The cases of _temporal_ref.warp_cases (test_temporal_cpu.py proves their conditions) with 1, 3 and 4 channels, with
+    and without the forward flow: warped finite everywhere (the rule of DESIGN.md section 12 for out-of-range, infinite and
+    NaN coordinates), within 2e-6 of the float64 warp and equal to it for whole-pixel shifts; the certainty equal bit for bit."""
+    from nn import _ops
+    h, w = hw
+    prevs = {c: T.warp_prev(h, w, c) for c in T.WARP_CHANNELS}
+    worst, checked = 0.0, 0
+    for name, fb, ff in T.warp_cases(h, w):
+        ref_w = {c: T.warp64(prevs[c], fb) for c in T.WARP_CHANNELS}
+        for f in (None, ff):
+            ref_c = T.certainty64(fb, f).astype(np.float32)
+            for c in T.WARP_CHANNELS:
+                warped, cert = _ops.flow_warp(_dev(prevs[c])[None], _dev(fb), None if f is None else _dev(f))
+                torch.cuda.synchronize()
+                got_w, got_c = warped[0].cpu().numpy(), cert.cpu().numpy()
+                assert got_w.shape == (h, w, c) and np.isfinite(got_w).all(), (name, c)
+                err = float(np.abs(got_w - ref_w[c]).max())
+                worst = max(worst, err)
+                assert err < 2e-6, (name, c, err)
+                if name.startswith("whole") or name == "far":
+                    assert np.array_equal(got_w, ref_w[c].astype(np.float32)), (name, c)
+                wrong = np.argwhere(got_c.view(np.uint32) != ref_c.view(np.uint32))
+                assert len(wrong) == 0, (name, c, f is not None, wrong[:5].tolist())
+                checked += 1
+        print(f"{h} x {w} {name}: certain pixels {int(T.certainty64(fb).sum())} without / {int(T.certainty64(fb, ff).sum())} "
+              f"with the forward flow of {h * w}")
+    print(f"{h} x {w}: {checked} calls, max |warped - warp64| = {worst:.3e}")
 
 
 # ------------------------------------------------------------------ 2. the term of one step
