@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 import _route_cases as RC
+from _conv_ref import conv64, sign_words          # (shared with the float64 route tests)
 
 LIMIT = 2.0 ** 24
 U_RND = 2.0 ** -24
@@ -451,36 +452,6 @@ def make_wide_problem(shape, direction, kind):
 
 
 # ---------------------------------------------------------------------------------------------------------- references
-def conv64(x, w):
-    """float64 3x3 convolution with zero padding 1 as nine shifted GEMMs: x (1, h, w, ci), w (3, 3, ci, co) -> (1, h, w, co)."""
-    h, wd = int(x.shape[1]), int(x.shape[2])
-    xp = torch.nn.functional.pad(x[0].double(), (0, 0, 1, 1, 1, 1))
-    w = w.double()
-    out = torch.zeros(h, wd, int(w.shape[3]), dtype=torch.float64, device=x.device)
-    for r in range(3):
-        for q in range(3):
-            out += torch.matmul(xp[r:r + h, q:q + wd], w[r, q])
-    return out[None]
-
-
-def sign_words(act):
-    """relu_bits of include/strotss_hip.h for a (1, h, w, c) tensor: word (tile, ch), byte r, bit q = act[4ty+r, 4tx+q, ch] > 0;
-    and the mask of the bits that lie inside the image (the others are unspecified)."""
-    _, h, w, c = act.shape
-    th, tw = (h + 3) // 4, (w + 3) // 4
-    pos = torch.zeros(th * 4, tw * 4, c, dtype=torch.bool, device=act.device)
-    inside = torch.zeros_like(pos)
-    pos[:h, :w] = act[0] > 0
-    inside[:h, :w] = True
-    words = torch.zeros(th * tw, c, dtype=torch.int64, device=act.device)
-    valid = torch.zeros_like(words)
-    for r in range(4):
-        for q in range(4):
-            words |= pos[r::4, q::4].reshape(th * tw, c).long() << (8 * r + q)
-            valid |= inside[r::4, q::4].reshape(th * tw, c).long() << (8 * r + q)
-    return words, valid
-
-
 def pool_reference(pre, last=False):
     """strotss_maxpool2_fwd by its header, from the float64 pre-activation (1, h, w, c): (max(window, 0), code) with code the
     FIRST maximum in scan order (0,0), (0,1), (1,0), (1,1), or 4 where the maximum is not positive.  last=True: the planted

@@ -14,9 +14,11 @@ import functools
 
 import numpy as np
 
+import _regime
 from _loss_ref import RGB2YUV, TAU_C
 
-# (label, n, ns, d, kind): kind "plain" | "flat_style" | "flat_pred" | "exact_rows" | "public"
+# (label, n, ns, d, kind): kind "plain" | "flat_style" | "flat_pred" | "exact_rows" | "public" | "regime" (rows of
+# tests/_regime.py loss_rows: mostly zero, heavy-tailed, block scales 1 .. 100, dead columns)
 CASES = [
     ("step", 1024, 1024, 2179, "plain"),
     ("ragged_n1000_ns777", 1000, 777, 2179, "plain"),
@@ -28,6 +30,8 @@ CASES = [
     ("flat_style_1500_of_2048", 1024, 2048, 2179, "flat_style"),
     ("flat_pred_600_of_1024", 1024, 2048, 2179, "flat_pred"),
     ("second_column_trip_d3100", 200, 300, 3100, "public"),
+    ("regime_n1000_ns777", 1000, 777, 2179, "regime"),
+    ("regime_small_n37", 37, 300, 2179, "regime"),
 ]
 LABELS = [c[0] for c in CASES]
 FLAT_STYLE_ROWS = 1500
@@ -139,7 +143,8 @@ def make_case(label):
     _, n, ns, d, kind = spec[0]
     seed = 1000 + LABELS.index(label)
     rng = np.random.default_rng(seed)
-    x, y, c = hyper_rows(rng, ns, d), hyper_rows(rng, n, d), hyper_rows(rng, n, d)
+    rows = _regime.loss_rows if kind == "regime" else hyper_rows
+    x, y, c = rows(rng, ns, d), rows(rng, n, d), rows(rng, n, d)
     gx, gy = np.arange(ns), np.arange(n)
     if kind == "exact_rows":
         y = exact_rows(rng, n, d)
@@ -166,9 +171,9 @@ def make_case(label):
             bad_y = {int(np.flatnonzero(np.bincount(gy)[gy] == 1)[0])}     # R_X == R_Y within TAU_C: move one prediction row
         r2 = np.random.default_rng([seed, attempt + 1])
         for i in sorted(bad_x):
-            x[i] = hyper_rows(r2, 1, d)[0]
+            x[i] = rows(r2, 1, d)[0]
         for j in sorted(bad_y):
-            y[j] = (exact_rows if kind == "exact_rows" else hyper_rows)(r2, 1, d)[0]
+            y[j] = (exact_rows if kind == "exact_rows" else rows)(r2, 1, d)[0]
         redrawn += len(bad_x) + len(bad_y)
     raise AssertionError(f"case {label}: not conditioned after 50 redraws")
 

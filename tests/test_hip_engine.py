@@ -30,10 +30,11 @@ def _img(h, w, seed):
     return torch.nn.functional.avg_pool2d(x.permute(0, 3, 1, 2), 3, 1, 1).permute(0, 2, 3, 1).contiguous()
 
 
-def _setup(h, w, n_samples, masks=None, seed=0):
+def _setup(h, w, n_samples, masks=None, seed=0, weights=None):
     from nn import _ops, engine
     from nn.model import VGGParams, synthetic_weights
-    weights = synthetic_weights('16', 0)
+    if weights is None:
+        weights = synthetic_weights('16', 0)
     content, style = _img(h, w, 1 + seed), _img(h + 8, w - 4, 2 + seed)
     rng = np.random.default_rng(seed)
     alpha = 8.0
@@ -122,6 +123,13 @@ def _check_step(S, masked):
 
 def test_engine_step_matches_oracle_square():
     _check_step(_setup(64, 64, 384), masked=False)
+
+
+def test_engine_step_matches_oracle_regime_weights():
+    """the square step's problem and bounds on weights shaped like a pretrained trunk's (tests/_regime.py trunk_weights:
+    dead channels, mostly-zero maps, channel scales spread over orders of magnitude and growing from block1 to block5)"""
+    import _regime
+    _check_step(_setup(64, 64, 256, weights=_regime.trunk_weights()), masked=False)
 
 
 def test_engine_step_matches_oracle_nonsquare():

@@ -119,6 +119,8 @@ def test_case_meets_its_conditioning(label):
             np.bincount(C.argmin(1)[c.gx == np.bincount(c.gx).argmax()]).max() >= LC.FLAT_STYLE_ROWS
     if c.kind == "flat_pred":
         assert np.bincount(c.gy).max() >= LC.FLAT_PRED_ROWS
+    if c.kind == "regime":
+        assert all(0.6 <= (v[:, 3:] == 0).mean() <= 0.9 and (v[:, 3:].max(0) == 0).mean() >= 0.05 for v in (c.x, c.y, c.c))
     if c.kind == "exact_rows":
         assert (LR.cos_dist(c.y, c.y).diagonal() == 0).all() and (LR.cos_dist(c.c, c.c) == 0).all()
 
