@@ -432,29 +432,19 @@ def _tile_m(u: torch.Tensor) -> int:
     return {16: 2, 36: 4}[int(u.shape[0])]
 
 
-_packed = {}       # id(u) -> (weakref(u), packed): fragment-major copies of frozen F(4x4,3x3) weights
-
-
 def winograd_packed(u: torch.Tensor):
-    """The fragment-major copy of a (36, rows, k) Winograd weight tensor for the fused kernel (made once per
-    tensor object; the weights are frozen), or None where the fused kernel does not apply."""
-    import weakref
+    """The fragment-major copy of a (36, rows, k) Winograd weight tensor for the fused kernel, or None where the fused
+    kernel does not apply.  Made once and kept on `u` itself (the weights are frozen), so it lives as long as they do."""
     if not winograd_packed_wanted(int(u.shape[0]), int(u.shape[1]), int(u.shape[2])):
         return None
-    hit = _packed.get(id(u))
-    if hit is not None and hit[0]() is u:
-        return hit[1]
-    require(u, "winograd weights")
-    up = torch.empty_like(u)
-    check(_hip.lib().strotss_conv3x3_winograd_pack(ptr(u), int(u.shape[1]), int(u.shape[2]), ptr(up), stream_ptr()),
-          "conv3x3_winograd_pack")
-    for k in [k for k, v in _packed.items() if v[0]() is None]:
-        del _packed[k]
-    _packed[id(u)] = (weakref.ref(u), up)
+    up = getattr(u, "_winograd_packed", None)
+    if up is None:
+        require(u, "winograd weights")
+        up = torch.empty_like(u)
+        check(_hip.lib().strotss_conv3x3_winograd_pack(ptr(u), int(u.shape[1]), int(u.shape[2]), ptr(up), stream_ptr()),
+              "conv3x3_winograd_pack")
+        u._winograd_packed = up
     return up
-
-
-_x3 = {}           # id(u) -> (weakref(u), panels): bf16x3 "x3 panels" of frozen F(4x4,3x3) weights
 
 
 def env_int(name: str, default: int) -> int:
@@ -483,22 +473,18 @@ def winograd_packed_wanted(p: int, rows: int, k: int) -> bool:
 
 def winograd_x3(u: torch.Tensor, h: int, w: int):
     """The x3 panels (three bf16 planes per f32 weight, K-blocked; csrc/mfma_x3.h) of a (36, rows, k) Winograd weight
-    tensor for the bf16x3 GEMM core (made once per tensor object; the weights are frozen), or None where the library
-    would not use them for an (h, w) layer (`winograd_x3_wanted`)."""
-    import weakref
+    tensor for the bf16x3 GEMM core, or None where the library would not use them for an (h, w) layer
+    (`winograd_x3_wanted`).  Made once and kept on `u` itself, like the packed copy."""
     if not winograd_x3_wanted(int(u.shape[0]), int(u.shape[1]), int(u.shape[2]), h, w):
         return None
-    hit = _x3.get(id(u))
-    if hit is not None and hit[0]() is u:
-        return hit[1]
-    require(u, "winograd weights")
-    rows, k = int(u.shape[1]), int(u.shape[2])
-    nb = _hip.lib().strotss_conv3x3_winograd_x3_bytes(rows, k)
-    up = torch.empty(nb // 2, dtype=torch.bfloat16, device=u.device)
-    check(_hip.lib().strotss_conv3x3_winograd_x3pack(ptr(u), rows, k, ptr(up), stream_ptr()), "conv3x3_winograd_x3pack")
-    for key in [key for key, v in _x3.items() if v[0]() is None]:
-        del _x3[key]
-    _x3[id(u)] = (weakref.ref(u), up)
+    up = getattr(u, "_winograd_x3", None)
+    if up is None:
+        require(u, "winograd weights")
+        rows, k = int(u.shape[1]), int(u.shape[2])
+        nb = _hip.lib().strotss_conv3x3_winograd_x3_bytes(rows, k)
+        up = torch.empty(nb // 2, dtype=torch.bfloat16, device=u.device)
+        check(_hip.lib().strotss_conv3x3_winograd_x3pack(ptr(u), rows, k, ptr(up), stream_ptr()), "conv3x3_winograd_x3pack")
+        u._winograd_x3 = up
     return up
 
 

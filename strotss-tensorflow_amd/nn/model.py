@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Callable, List, Optional, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -82,12 +82,30 @@ def load_weights(path: str, vgg_type: str = '16') -> List[Tuple[torch.Tensor, to
     return out
 
 
+class Switches(NamedTuple):
+    """Every STROTSS_* variable the host side of the trunk reads; `switches()` is the only reader: the policy functions below
+    call it per question, a VGGTrunk once when it is built."""
+    winograd: bool              # STROTSS_WINOGRAD=0: the direct implicit GEMM everywhere
+    winograd_tile: int          # STROTSS_WINOGRAD_TILE=2 | 4: one tiling for the Cin >= 128 layers (0: by size)
+    direct_max_tiles: int       # STROTSS_DIRECT_MAX_TILES (64): see direct_splitk; 0 switches it off
+    relu_bits: bool             # STROTSS_RELU_BITS=0: F(4x4,3x3) data-gradients mask with the f32 activations
+    prescatter: bool            # STROTSS_PRESCATTER=0: no pre-scatter backward
+    prescatter_max_pixels: int  # STROTSS_PRESCATTER_MAX_PIXELS (160 x 160): see VGGTrunk
+    pool_in_finish: bool        # STROTSS_POOL_IN_FINISH=0: split-K layers leave the max-pool and its adjoint to their own launches
+
+
+def switches() -> Switches:
+    env = os.environ.get
+    tile = env("STROTSS_WINOGRAD_TILE", "auto")
+    return Switches(env("STROTSS_WINOGRAD", "auto") != "0", int(tile) if tile in ("2", "4") else 0,
+                    int(env("STROTSS_DIRECT_MAX_TILES", "64")), env("STROTSS_RELU_BITS", "1") != "0",
+                    env("STROTSS_PRESCATTER", "1") != "0", int(env("STROTSS_PRESCATTER_MAX_PIXELS", str(160 * 160))),
+                    env("STROTSS_POOL_IN_FINISH", "1") != "0")
+
+
 def use_winograd(cin: int, cout: int) -> bool:
-    """Layers that MAY run in Winograd form (their transformed weights are prepared): every generic layer.
-    STROTSS_WINOGRAD=0 disables Winograd altogether (direct implicit GEMM everywhere)."""
-    if os.environ.get("STROTSS_WINOGRAD", "auto") == "0":
-        return False
-    return cin % 32 == 0 and cout % 64 == 0
+    """Layers that MAY run in Winograd form (their transformed weights are prepared): every generic layer."""
+    return switches().winograd and cin % 32 == 0 and cout % 64 == 0
 
 
 def direct_splitk(h: int, w: int, cin: int, cout: int) -> bool:
@@ -98,7 +116,7 @@ def direct_splitk(h: int, w: int, cin: int, cout: int) -> bool:
     A layer takes it with at most STROTSS_DIRECT_MAX_TILES (64) output tiles of 64 x 64, or at most 4x that many when it
     has at most 128 channels on both sides (short K); 0 switches it off."""
     tiles = -(-(h * w) // 64) * (cout // 64)
-    mt = int(os.environ.get("STROTSS_DIRECT_MAX_TILES", "64"))
+    mt = switches().direct_max_tiles
     return 0 < tiles <= mt or (max(cin, cout) <= 128 and 0 < tiles <= 4 * mt)
 
 
@@ -108,11 +126,10 @@ def winograd_tile(h: int, w: int, cin: int = 128, cout: int = 0) -> int:
     activations -- wins from 32x32 pixels up for every channel count (1.2x at 64->64 ... 2.9x at 512->512 over
     the direct kernel); below that F(2x2,3x3) (4 MACs, 4x tensors) wins for Cin >= 128 and the direct kernel
     for Cin = 64.  f32 rounding of the convolution: direct ~2e-7, F(2x2,3x3) ~5e-7, F(4x4,3x3) ~1e-5 of the
-    output range; every step-level parity test holds at unchanged tolerances.
-    STROTSS_WINOGRAD_TILE=2 | 4 forces one tiling for the Cin >= 128 layers."""
-    mode = os.environ.get("STROTSS_WINOGRAD_TILE", "auto")
-    if mode in ("2", "4"):
-        return int(mode) if cin >= 128 else 0
+    output range; every step-level parity test holds at unchanged tolerances."""
+    forced = switches().winograd_tile
+    if forced:
+        return forced if cin >= 128 else 0
     if cout and direct_splitk(h, w, cin, cout):
         return 0
     if h * w >= 1024:
@@ -120,23 +137,30 @@ def winograd_tile(h: int, w: int, cin: int = 128, cout: int = 0) -> int:
     return 2 if cin >= 128 else 0
 
 
+def layer_route(h: int, w: int, cin: int, cout: int, dgrad: bool = False) -> Tuple[int, bool]:
+    """What the generic 3x3 layer `cin` -> `cout` runs at (h, w), forward or data-gradient: (Winograd tile 0 | 2 | 4, whether
+    its direct form splits K).  The one place that turns a layer into a tile: one decision for both directions, of
+    `use_winograd` / `winograd_tile` / `direct_splitk` above; VGGTrunk plans its launches from it and `conv_route` names them.
+    Split-K is the library's answer (the data-gradient is the same kernel with the channel roles swapped); no GPU needed."""
+    t = winograd_tile(h, w, cin, cout) if use_winograd(cin, cout) else 0
+    return t, _ops.conv3x3_direct_splits(h, w, *((cout, cin) if dgrad else (cin, cout)))
+
+
 ROUTE_NAMES = {0: "F2_gemm_f32", 1: "F4_fused_f32", 2: "F4_gemm_f32", 3: "F4_x3_gemm_128", 4: "F4_x3_gemm_64"}
 
 
 def conv_route(h: int, w: int, cin: int, cout: int, dgrad: bool = False) -> str:
-    """Which kernels the generic 3x3 layer `cin` -> `cout` runs at (h, w), forward or data-gradient.  The host policy is only
-    `use_winograd` / `winograd_tile` / `direct_splitk` above (one decision per layer for both directions, as VGGTrunk takes
-    it); everything behind it the library decides and is asked for: `strotss_conv3x3_workspace_bytes` for the direct forms,
-    `strotss_conv3x3_winograd_route` for the Winograd forms -- csrc/winograd.hip winograd43_route, the one statement of that
-    policy, on which the launches dispatch (the data-gradient is the same kernel with the channel roles swapped).  Asked with
-    has_x3 = 1, because the host makes the x3 panels exactly where that answer is a bf16x3 route (`_ops.winograd_x3_wanted`)
-    and a route that is no bf16x3 route does not depend on has_x3.  No GPU needed: tests/test_route_table.py pins the
-    default table of the five BASELINE scales so that a policy regression cannot pass unnoticed."""
+    """Which kernels the generic 3x3 layer `cin` -> `cout` runs at (h, w), forward or data-gradient.  The host policy is
+    `layer_route`, the decision VGGTrunk plans from; behind it the library decides and is asked: `layer_route`'s split-K answer
+    for the direct forms, `strotss_conv3x3_winograd_route` for the Winograd forms -- csrc/winograd.hip winograd43_route, the
+    one statement of that policy, on which the launches dispatch.  Asked with has_x3 = 1: the host makes the x3 panels exactly
+    where that answer is a bf16x3 route (`_ops.winograd_x3_wanted`), and no other route depends on has_x3.  No GPU needed:
+    tests/test_route_table.py pins the default table of the five BASELINE scales against a policy regression."""
     from . import _hip
-    t = winograd_tile(h, w, cin, cout) if use_winograd(cin, cout) else 0
-    ci, co = (cout, cin) if dgrad else (cin, cout)
+    t, splits = layer_route(h, w, cin, cout, dgrad)
     if t == 0:
-        return "direct_splitk" if _ops.conv3x3_direct_splits(h, w, ci, co) else "direct"
+        return "direct_splitk" if splits else "direct"
+    ci, co = (cout, cin) if dgrad else (cin, cout)
     p = 16 if t == 2 else 36
     return ROUTE_NAMES[int(_hip.load_library().strotss_conv3x3_winograd_route(
         h, w, ci, co, t, int(_ops.winograd_packed_wanted(p, co, ci)), 1))]
@@ -221,6 +245,27 @@ class VGGParams:
         return [names.index(t) for t in self.tap_names]
 
 
+class Step(tuple):
+    """One entry of `VGGTrunk.plan`: ('conv', layer_idx, (src_kind, src_idx)) or ('pool', pool_idx, src_layer), and as
+    attributes what its launches are -- decided once, when the trunk is built; forward() and backward() only run them.
+    conv: fwd    'first' (the 3-channel layer) | 'direct' | 'winograd'
+          pool   the pool this layer's forward launch writes as well (+ its codes), or None: in a Winograd layer's output
+                 transform, in a split-K layer's finish kernel (ABI 8)
+          dgrad  'first' | 'direct' | 'unpool' (split-K through the adjoint of the pool in front, ABI 8) | 'winograd'
+          dst    the data-gradient goes to grads[dst] (source a layer; 'unpool': the layer in front of the pool), else gpools[dst]
+          mask   the layer whose activation (or sign words) masks the data-gradient, or None
+          tapped grads[dst] is a tapped layer's: under pre-scatter the data-gradient adds to it
+          adds   its data-gradient CAN add to its output: the first layer's, split-K direct ones, the one-pass direct one as
+                 far as the library says so, F(4x4,3x3) since ABI 7; F(2x2,3x3) overwrites
+    pool: fwd / bwd  whether its own forward / backward launch exists (not when the layer before / behind it does the work)
+          tapped     its source layer is tapped"""
+
+    def __new__(cls, kind, idx, src, **launches):
+        self = super().__new__(cls, (kind, idx, src))
+        self.__dict__.update(launches)
+        return self
+
+
 class VGGTrunk:
     """Pre-allocated forward/backward of the trunk for one image size.
 
@@ -233,20 +278,19 @@ class VGGTrunk:
     def __init__(self, params: VGGParams, h: int, w: int, with_grad: bool = True, halo=None):
         """halo: a parallel.HaloExchange when (h, w) is the window of a halo-exchange strip: after every layer, forward
         and backward, the window's outermost rows are refreshed from the neighbouring ranks."""
-        self.p = params
-        self.halo = halo
+        self.p, self.halo, self.h, self.w = params, halo, h, w
         dev = params.device
-        self.h, self.w = h, w
         self.acts: List[torch.Tensor] = []
         self.pools: List[torch.Tensor] = []
-        self.plan = []     # ('conv', layer_idx, src) | ('pool', pool_idx, src_layer)
+        sw = switches()
+        order = []     # ('conv', layer_idx, src) | ('pool', pool_idx, src_layer)
         ch, cw = h, w
         li = pi = 0
         src = ('img', 0)
         for it in params.cfg:
             if it == 'pool':
                 self.pools.append(torch.empty((1, ch // 2, cw // 2, self.acts[-1].shape[-1]), dtype=torch.float32, device=dev))
-                self.plan.append(('pool', pi, li - 1))
+                order.append(('pool', pi, li - 1))
                 src = ('pool', pi)
                 pi += 1
                 ch, cw = ch // 2, cw // 2
@@ -254,12 +298,12 @@ class VGGTrunk:
                     raise ValueError(f"image {h}x{w} too small for this VGG depth")
             else:
                 self.acts.append(torch.empty((1, ch, cw, it[2]), dtype=torch.float32, device=dev))
-                self.plan.append(('conv', li, src))
+                order.append(('conv', li, src))
                 src = ('conv', li)
                 li += 1
         # pooling level (number of 2x2 pools above) of every layer's output and of every pooled map
         self.layer_level, self.pool_level, lvl = {}, {}, 0
-        for step in self.plan:
+        for step in order:
             if step[0] == 'pool':
                 lvl += 1
                 self.pool_level[step[1]] = lvl
@@ -267,9 +311,37 @@ class VGGTrunk:
                 self.layer_level[step[1]] = lvl
         self.taps = params.tap_layer_indices
         self.with_grad = with_grad
-        # Winograd tile per layer for this image size
-        self.wtile = [winograd_tile(int(a.shape[1]), int(a.shape[2]), L["cin"], L["cout"]) if "u_fwd" in L else 0
-                      for L, a in zip(params.layers, self.acts)]
+        # per layer: the Winograd tile for this image size and whether the direct form splits K, forward / data-gradient
+        self.wtile, splits_fwd, splits_bwd = [], [], []
+        for L, a in zip(params.layers, self.acts):
+            generic, at = L["cin"] != 3, (int(a.shape[1]), int(a.shape[2]), L["cin"], L["cout"])
+            t, splits = layer_route(*at) if generic else (0, False)
+            self.wtile.append(t if "u_fwd" in L else 0)
+            splits_fwd.append(splits)
+            splits_bwd.append(generic and layer_route(*at, dgrad=True)[1])
+        # block ends (Step.pool, 'unpool').  Not with a halo exchange: the pooling launch then reads refreshed rows.
+        pool_in_finish = halo is None and sw.pool_in_finish
+        tapped = set(self.taps)
+        pool_src = {i: src for kind, i, src in order if kind == 'pool'}
+        rides = {pi: halo is None and (self.wtile[li] != 0 or (pool_in_finish and splits_fwd[li])) for pi, li in pool_src.items()}
+        unpools = {src[1]: pool_in_finish and self.wtile[i] == 0 and splits_bwd[i]
+                   for kind, i, src in order if kind == 'conv' and src[0] == 'pool'}
+        self.plan = []
+        for k, (kind, i, src) in enumerate(order):
+            if kind == 'pool':
+                self.plan.append(Step(kind, i, src, fwd=not rides[i], bwd=not unpools.get(i, False), tapped=src in tapped))
+                continue
+            L, a, t = params.layers[i], self.acts[i], self.wtile[i]
+            nxt = order[k + 1] if k + 1 < len(order) else None
+            first, unpool = src[0] == 'img', src[0] == 'pool' and unpools[src[1]]
+            form = 'first' if first else ('winograd' if t else 'direct')
+            dst = None if first else (pool_src[src[1]] if unpool else src[1])
+            self.plan.append(Step(
+                kind, i, src, fwd=form, pool=nxt[1] if nxt is not None and nxt[0] == 'pool' and rides[nxt[1]] else None,
+                dgrad='unpool' if unpool else form, dst=dst, mask=src[1] if src[0] == 'conv' else None,
+                tapped=(src[0] == 'conv' or unpool) and dst in tapped,
+                adds=first or unpool or t == 4 or (t == 0 and _ops.conv3x3_dgrad_accumulates(
+                    int(a.shape[1]), int(a.shape[2]), L["cout"], L["cin"]))))
         self.relu_bits = [None] * len(self.acts)
         if with_grad:
             # argmax codes of the pools (1 byte per pooled element): the backward pass reads them, not the activations
@@ -277,26 +349,22 @@ class VGGTrunk:
             # sign words of the activations whose ReLU mask an F(4x4,3x3) data-gradient applies: 4 bytes per 4x4 tile and
             # channel, written by the producing forward kernel from registers, instead of re-reading the f32 activation
             # (268 MB for block1_conv1 at 1024^2).  Not with a halo exchange: it rewrites border rows of the activations.
-            if halo is None and os.environ.get("STROTSS_RELU_BITS", "1") != "0":
+            if halo is None and sw.relu_bits:
                 for step in self.plan:
-                    if step[0] == 'conv' and step[2][0] == 'conv' and self.wtile[step[1]] == 4:
-                        si = step[2][1]
-                        if self.wtile[si] == 4 or params.layers[si]["cin"] == 3:
-                            a = self.acts[si]
-                            self.relu_bits[si] = _ops.relu_bits_buffer(int(a.shape[1]), int(a.shape[2]), int(a.shape[3]), dev)
+                    si = step.mask if step[0] == 'conv' else None
+                    if si is not None and self.wtile[step[1]] == 4 and (self.wtile[si] == 4 or params.layers[si]["cin"] == 3):
+                        a = self.acts[si]
+                        self.relu_bits[si] = _ops.relu_bits_buffer(int(a.shape[1]), int(a.shape[2]), int(a.shape[3]), dev)
             # "Pre-scatter" backward: when EVERY tapped layer's gradient is produced by a kernel that can add to its
-            # output (the split-K direct data-gradient, the F(4x4,3x3) data-gradients since ABI 7, the pooling backward,
-            # the first layer's pixel gradient), the taps of all maps are scattered in ONE launch into zeroed buffers
+            # output (Step.adds, the pooling backward), the taps of all maps are scattered in ONE launch into zeroed buffers
             # before the backward pass and the producers accumulate -- 9 launches less per step.  It costs ONE fill of
             # every tapped gradient buffer plus the producers' extra read of their output, so it pays only where the maps
             # are tiny: measured (alternating runs on one box) 256 px 1.188 against 1.185 ms per step interleaved, 512 px
             # 1.904 against 1.860 (65 / 262 MB of fill) -- hence up to 160 x 160 pixels, the 64 / 128-px scales, by default
             # (STROTSS_PRESCATTER_MAX_PIXELS).  The tapped layers' gradient buffers are then slices of one allocation.
-            max_px = int(os.environ.get("STROTSS_PRESCATTER_MAX_PIXELS", str(160 * 160)))
-            self.prescatter = (halo is None and h * w <= max_px and self._can_prescatter()
-                               and os.environ.get("STROTSS_PRESCATTER", "1") != "0")
+            self.prescatter = halo is None and h * w <= sw.prescatter_max_pixels and sw.prescatter and self._can_prescatter()
             if self.prescatter:
-                sizes = [a.numel() if i in set(self.taps) else 0 for i, a in enumerate(self.acts)]
+                sizes = [a.numel() if i in tapped else 0 for i, a in enumerate(self.acts)]
                 # (+ the pixel gradient at the end: ONE fill clears everything the single scatter launch adds into)
                 self._tap_flat = torch.zeros(sum(sizes) + 3 * h * w, dtype=torch.float32, device=dev)
                 offs = np.cumsum([0] + sizes)
@@ -308,26 +376,9 @@ class VGGTrunk:
             self.gpools = [torch.empty_like(p) for p in self.pools]
             self.gimg = self._gimg_in_flat if self.prescatter else torch.empty((1, h, w, 3), dtype=torch.float32, device=dev)
         self.img = None
-        # block ends on split-K layers: the max-pool (and its adjoint) inside the layer's finish kernel (ABI 8)
-        self._pool_in_finish = halo is None and os.environ.get("STROTSS_POOL_IN_FINISH", "1") != "0"
 
-    def _can_prescatter(self) -> bool:
-        tapped = set(self.taps)
-        n = len(self.acts)
-        for step in self.plan:
-            if step[0] != 'conv':
-                continue
-            _, li, (kind, si) = step
-            if kind == 'conv' and si in tapped:           # layer li's data-gradient writes the tapped grads[si]
-                L = self.p.layers[li]
-                a = self.acts[li]
-                if self.wtile[li] == 4:
-                    continue                              # winograd_dgrad(accumulate=1): any F(4x4,3x3) route
-                if self.wtile[li] != 0:                   # F(2x2,3x3) overwrites
-                    return False
-                if not _ops.conv3x3_dgrad_accumulates(int(a.shape[1]), int(a.shape[2]), L["cout"], L["cin"]):
-                    return False                          # the direct kernels add, as far as the library says so
-        return n - 1 in tapped                            # (the deepest layer is scattered into a zeroed buffer anyway)
+    def _can_prescatter(self) -> bool:      # (the deepest layer is scattered into a zeroed buffer anyway)
+        return len(self.acts) - 1 in self.taps and all(s.adds for s in self.plan if s[0] == 'conv' and s.tapped)
 
     def _src(self, src):
         kind, i = src
@@ -336,41 +387,25 @@ class VGGTrunk:
     def forward(self, img: torch.Tensor) -> List[torch.Tensor]:
         self.img = img
         P = self.p
-        pooled = set()                  # pools already written by the conv before them
-        for si, step in enumerate(self.plan):
-            if step[0] == 'pool':
-                if step[1] not in pooled:
-                    _ops.maxpool2_fwd(self.acts[step[2]], out=self.pools[step[1]],
-                                      code=self.pool_codes[step[1]] if self.with_grad else None)
+        codes = self.pool_codes if self.with_grad else [None] * len(self.pools)
+        for s in self.plan:
+            kind, li, src = s
+            if kind == 'pool':
+                if s.fwd:
+                    _ops.maxpool2_fwd(self.acts[src], out=self.pools[li], code=codes[li])
+                continue
+            L, x = P.layers[li], self._src(src)
+            pool_out, pool_code = (None, None) if s.pool is None else (self.pools[s.pool], codes[s.pool])
+            if s.fwd == 'first':
+                _ops.conv3x3_c3_fwd(x, L["w_fwd"], L["bias"], out=self.acts[li], mean=P.mean, std=P.std,
+                                    relu_bits_out=self.relu_bits[li])
+            elif s.fwd == 'winograd':
+                _ops.conv3x3_winograd_fwd(x, L["u_fwd"][self.wtile[li]], L["bias"], out=self.acts[li],
+                                          pool_out=pool_out, pool_code=pool_code, relu_bits_out=self.relu_bits[li])
             else:
-                _, li, src = step
-                L = P.layers[li]
-                x = self._src(src)
-                if L["cin"] == 3:
-                    _ops.conv3x3_c3_fwd(x, L["w_fwd"], L["bias"], out=self.acts[li], mean=P.mean, std=P.std,
-                                        relu_bits_out=self.relu_bits[li])
-                elif self.wtile[li]:
-                    nxt = self.plan[si + 1] if si + 1 < len(self.plan) else None
-                    pool_out = pool_code = None
-                    if self.halo is None and nxt is not None and nxt[0] == 'pool' and nxt[2] == li:   # its pool rides along
-                        pool_out = self.pools[nxt[1]]
-                        pool_code = self.pool_codes[nxt[1]] if self.with_grad else None
-                        pooled.add(nxt[1])
-                    _ops.conv3x3_winograd_fwd(x, L["u_fwd"][self.wtile[li]], L["bias"], out=self.acts[li],
-                                              pool_out=pool_out, pool_code=pool_code, relu_bits_out=self.relu_bits[li])
-                else:
-                    nxt = self.plan[si + 1] if si + 1 < len(self.plan) else None
-                    a = self.acts[li]
-                    if (self._pool_in_finish and nxt is not None and nxt[0] == 'pool' and nxt[2] == li
-                            and _ops.conv3x3_direct_splits(int(a.shape[1]), int(a.shape[2]), L["cin"], L["cout"])):
-                        # split-K layer at a block end: its finish kernel pools as well
-                        _ops.conv3x3_relu_fwd(x, L["w_fwd"], L["bias"], out=a, pool_out=self.pools[nxt[1]],
-                                              pool_code=self.pool_codes[nxt[1]] if self.with_grad else None)
-                        pooled.add(nxt[1])
-                    else:
-                        _ops.conv3x3_relu_fwd(x, L["w_fwd"], L["bias"], out=a)
-                if self.halo is not None:     # (the pooling launch that may follow then reads right rows only)
-                    self.halo.refresh(self.acts[li], self.layer_level[li])
+                _ops.conv3x3_relu_fwd(x, L["w_fwd"], L["bias"], out=self.acts[li], pool_out=pool_out, pool_code=pool_code)
+            if self.halo is not None:     # (the pooling launch that may follow then reads right rows only)
+                self.halo.refresh(self.acts[li], self.layer_level[li])
         return [self.acts[i] for i in self.taps]
 
     def backward(self, scatter: Callable[[int], None], scatter_all: Optional[Callable[[], None]] = None) -> torch.Tensor:
@@ -378,11 +413,7 @@ class VGGTrunk:
         one go; given and usable -> the per-layer `scatter` is not called."""
         assert self.with_grad
         P = self.p
-        n_layers = len(self.acts)
-        tapped = set(self.taps)
         pre = self.prescatter and scatter_all is not None
-        # the deepest layer receives gradient from its tap only
-        last = n_layers - 1
         if pre:
             self._tap_flat.zero_()
             if self.gimg.data_ptr() != self._gimg_in_flat.data_ptr():      # (a sharded engine points gimg into its reduce buffer)
@@ -390,57 +421,39 @@ class VGGTrunk:
             scatter_all()
             scatter = lambda li: None
         else:
-            self.grads[last].zero_()
-            scatter(last)
+            self.grads[-1].zero_()              # the deepest layer receives gradient from its tap only
+            scatter(len(self.acts) - 1)
         # walk the plan backwards; grads[li] always holds the ReLU-masked gradient of layer li's output
-        unpooled = set()                # pools whose adjoint the finish kernel of the layer behind them has already applied
-        pool_src = {s_[1]: s_[2] for s_ in self.plan if s_[0] == 'pool'}
-        for step in reversed(self.plan):
-            if step[0] == 'pool':
-                _, pi, src_layer = step
-                if pi not in unpooled:
-                    _ops.maxpool2_bwd(self.acts[src_layer], self.gpools[pi], out=self.grads[src_layer],
-                                      code=self.pool_codes[pi], accumulate=pre and src_layer in tapped)
-                if src_layer in tapped:
-                    scatter(src_layer)
+        for s in reversed(self.plan):
+            kind, li, src = s
+            if kind == 'pool':
+                if s.bwd:
+                    _ops.maxpool2_bwd(self.acts[src], self.gpools[li], out=self.grads[src], code=self.pool_codes[li],
+                                      accumulate=pre and s.tapped)
+                if s.tapped:
+                    scatter(src)
+                continue
+            L, g = P.layers[li], self.grads[li]
+            if s.dgrad == 'first':
+                _ops.conv3x3_c3_dgrad(g, L["w_bwd"], self.gimg, accumulate=pre, std=P.std)
+                scatter(-1)
+            elif s.dgrad == 'unpool':
+                _ops.conv3x3_dgrad_unpool(g, L["w_bwd"], L["cin"], self.pool_codes[src[1]], self.grads[s.dst],
+                                          accumulate=pre and s.tapped)
             else:
-                _, li, src = step
-                L = P.layers[li]
-                kind, si = src
-                if kind == 'img':
-                    _ops.conv3x3_c3_dgrad(self.grads[li], L["w_bwd"], self.gimg, accumulate=pre, std=P.std)
-                    scatter(-1)
+                in_layer = src[0] == 'conv'
+                out = self.grads[s.dst] if in_layer else self.gpools[s.dst]
+                act_in = None if s.mask is None else self.acts[s.mask]
+                if s.dgrad == 'winograd':
+                    _ops.conv3x3_winograd_dgrad(g, L["u_bwd"][self.wtile[li]], L["cin"], act_in=act_in, out=out,
+                                                relu_bits=None if s.mask is None else self.relu_bits[s.mask],
+                                                accumulate=pre and s.tapped)
                 else:
-                    wino = self.wtile[li] != 0
-                    dgrad = _ops.conv3x3_winograd_dgrad if wino else _ops.conv3x3_dgrad
-                    wts = L["u_bwd"][self.wtile[li]] if wino else L["w_bwd"]
-                    if kind == 'conv':
-                        if pre and si in tapped and wino:
-                            dgrad(self.grads[li], wts, L["cin"], act_in=self.acts[si], out=self.grads[si],
-                                  relu_bits=self.relu_bits[si], accumulate=True)
-                        elif pre and si in tapped:
-                            dgrad(self.grads[li], wts, L["cin"], act_in=self.acts[si], out=self.grads[si], accumulate=True)
-                        elif wino and self.relu_bits[si] is not None:
-                            dgrad(self.grads[li], wts, L["cin"], act_in=self.acts[si], out=self.grads[si],
-                                  relu_bits=self.relu_bits[si])
-                        else:
-                            dgrad(self.grads[li], wts, L["cin"], act_in=self.acts[si], out=self.grads[si])
-                        if si in tapped:
-                            scatter(si)
-                        if self.halo is not None:
-                            self.halo.refresh(self.grads[si], self.layer_level[si])
-                    else:
-                        g = self.grads[li]
-                        if (self._pool_in_finish and not wino
-                                and _ops.conv3x3_direct_splits(int(g.shape[1]), int(g.shape[2]), L["cout"], L["cin"])):
-                            src_layer = pool_src[si]
-                            _ops.conv3x3_dgrad_unpool(g, wts, L["cin"], self.pool_codes[si], self.grads[src_layer],
-                                                      accumulate=pre and src_layer in tapped)
-                            unpooled.add(si)
-                        else:
-                            dgrad(g, wts, L["cin"], act_in=None, out=self.gpools[si])
-                        if self.halo is not None:
-                            self.halo.refresh(self.gpools[si], self.pool_level[si])
+                    _ops.conv3x3_dgrad(g, L["w_bwd"], L["cin"], act_in=act_in, out=out, accumulate=pre and s.tapped)
+                if s.tapped:
+                    scatter(s.dst)
+                if self.halo is not None:
+                    self.halo.refresh(out, self.layer_level[s.dst] if in_layer else self.pool_level[s.dst])
         return self.gimg
 
 
