@@ -673,6 +673,39 @@ int strotss_refine_labels(const float* img, int h, int w, const int* grid_label,
                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Region tracking: the regions of --auto_masks through a frame sequence, the kernels of --track_masks
+ * --------------------------------------------------------------------------------------- */
+/* The prior label of every cell of frame t's (gh, gw) label grid, from the grid of an earlier frame, in ONE launch.
+ * prev_grid: (gh, gw) int32, the earlier frame's labels; flow: (h, w, 2) float32 = (dx, dy) per pixel, the backward flow of
+ * frame t against the earlier frame as .flo files and strotss_flow_warp have it; certainty: (h, w) float32 or NULL (no
+ * test); prior: (gh gw) int32; gh <= h, gw <= w, 1 <= k <= STROTSS_KMEANS_MAX_K.  Cell (i, j) owns the pixels (y, x) with
+ * y gh / h == i and x gw / w == j (integer division, the convention of strotss_refine_labels).  Its probe pixel is
+ * y_c = (y_lo + y_hi) / 2, x_c = (x_lo + x_hi) / 2, the integer mean of its first and last owned row and column; the source
+ * pixel is sy = floor(y_c + dy + 0.5f), sx = floor(x_c + dx + 0.5f) with (dx, dy) = flow(y_c, x_c), two float32 additions each.
+ *   prior(i, j) = prev_grid[sy gh / h, sx gw / w],
+ * and -1 where a flow component is not finite, (sy, sx) lies outside the image, certainty(y_c, x_c) < 0.5 (an IEEE `<`: a NaN
+ * removes nothing) or the label found lies outside 0..k-1 (compared, never used as an index).  No atomics: the same bits
+ * on every run and stream.  Refused before anything is launched, prior untouched: STROTSS_EINVAL for a null prev_grid, flow
+ * or prior, a size <= 0, gh > h, gw > w, 3 h w > INT_MAX, k outside 1..STROTSS_KMEANS_MAX_K; STROTSS_EALIGN for a pointer
+ * that is not 16-byte aligned. */
+int strotss_label_warp(const int* prev_grid, int gh, int gw, int k, const float* flow, const float* certainty, int h, int w,
+                       int* prior, void* stream);
+/* strotss_kmeans_assign with a bias toward a prior label.  x, inv_norm, n, d, ld, centres, k as there, and s_ij the same
+ * bits as there (one kernel source); prior: (n) int32; 0 <= beta <= 2.
+ *   score_ij = s_ij + (prior_i == j ? beta : 0), ONE float32 addition; a prior outside 0..k-1 adds nothing and is never used
+ *   as an index;  label[i] = the j with the largest score, the lowest j on equal scores;  best[i] = the raw s of that j;
+ *   second[i] = the largest raw s of the other j (-inf for k == 1; it may exceed best).
+ * A row with inv_norm_i == 0 has every s = 0: it takes its prior when that is valid and beta > 0, else label 0, and
+ * best = second = 0.  With beta == 0, or without a valid prior, label, best and second are strotss_kmeans_assign's bit for
+ * bit.  Cosines lie in [-1, 1], so beta == 2 never changes a label that has a prior.  One launch; x is read once, the centres
+ * stay in LDS a 512-column chunk at a time; no atomics: the same bits on every run and stream.  Refused before anything is
+ * launched, the outputs untouched: STROTSS_EINVAL for a null pointer, n <= 0, d <= 0, d > ld, n ld > INT_MAX, k outside
+ * 1..STROTSS_KMEANS_MAX_K, a beta that is not finite or outside [0, 2]; STROTSS_EALIGN for ld % 32 != 0 or a pointer that
+ * is not 16-byte aligned. */
+int strotss_kmeans_assign_prior(const float* x, const float* inv_norm, int n, int d, int ld, const float* centres, int k,
+                                const int* prior, float beta, int* label, float* best, float* second, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Optimiser + output
  * --------------------------------------------------------------------------------------- */
 typedef struct {

@@ -1,12 +1,9 @@
 // Spherical k-means on sampled feature rows: the two kernels behind --auto_masks.  x is a zero-padded
 // (rows, ld) float32 feature buffer as strotss_hypercol_gather writes it, inv_norm its reciprocal row norms
 // (strotss_row_inv_norm), centres a (k, ld) float32 matrix of unit (or all-zero) rows, k <= STROTSS_KMEANS_MAX_K.
-//   assign   kmeans_assign_kernel<KP>  s_ij = (x_i . c_j) inv_norm_i in float32; label = first arg-max, best, second.  A tile
-//                                      is 32 rows of x, 4 per wave of a 512-thread workgroup: lane l holds columns 4l..4l+3 of
-//                                      each 256-column half of a 512-column chunk of its 4 rows and KP x 4 partial scores; the
-//                                      chunk of the centres lives in LDS (KP x 512 floats, 32 KB at KP = 16: several workgroups
-//                                      per CU; all 16 x 2208 floats = 138 KB would leave room for one) and is read once per
-//                                      4 rows of a wave.  x is read once; the centres come from L2 once per tile and chunk.
+//   assign   kmeans_assign_kernel<KP, false> (kmeans_assign.h, shared with track.hip)  s_ij = (x_i . c_j) inv_norm_i in
+//                                      float32; label = first arg-max, best, second.  x is read once, the centres stay in LDS
+//                                      a 512-column chunk at a time.
 //   update   kmeans_partial_kernel     per (row block, 256-column block): thread t owns column t, walks the rows of its block
 //                                      in ascending order and adds x inv_norm (exact in float64) to acc[label][t] in LDS
 //                                      (float64, 32 KB; a row's label is uniform, so lane t reads double t + const:
@@ -17,103 +14,13 @@
 // kernels (at most 16 centres: 8 flops per byte of x at k = 16, no MFMA shape to fill).
 #include <math.h>
 
-#include "internal.h"
+#include "kmeans_assign.h"
 
 namespace {
 
-#define KM_ASSIGN_THREADS 512
-#define KM_ROWS_PER_WAVE 4
-#define KM_TILE_ROWS ((KM_ASSIGN_THREADS / WAVE) * KM_ROWS_PER_WAVE)       // 32
-#define KM_CHUNK 512                     // columns of the centres in LDS at a time: two float4 per lane
-#define KM_MAX_GRID 2048u                // workgroups of an assign launch at most; a workgroup walks the tiles beyond
 #define KM_COLS 256                      // update: columns per workgroup, one per thread
 #define KM_MAX_ROW_BLOCKS 32             // update: row blocks at most (the partials are row blocks x k x ld doubles)
 #define KM_MIN_BLOCK_ROWS 64             // update: rows per row block at least
-
-template <int KP>
-__global__ __launch_bounds__(KM_ASSIGN_THREADS) void kmeans_assign_kernel(const float* __restrict__ x,
-                                                                          const float* __restrict__ inv_norm, int n, int d,
-                                                                          int ld, const float* __restrict__ centres, int k,
-                                                                          int* __restrict__ label, float* __restrict__ best,
-                                                                          float* __restrict__ second) {
-  __shared__ __attribute__((aligned(16))) float cs[KP][KM_CHUNK];
-  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
-  const unsigned ntiles = ((unsigned)n + KM_TILE_ROWS - 1) / KM_TILE_ROWS;
-  for (unsigned tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int row0 = (int)tile * KM_TILE_ROWS + wave * KM_ROWS_PER_WAVE;
-    float acc[KM_ROWS_PER_WAVE][KP];
-#pragma unroll
-    for (int q = 0; q < KM_ROWS_PER_WAVE; ++q)
-#pragma unroll
-      for (int j = 0; j < KP; ++j) acc[q][j] = 0.f;
-    for (int c0 = 0; c0 < d; c0 += KM_CHUNK) {
-      __syncthreads();                                                  // the chunk (or tile) before is read
-      for (int i = (int)threadIdx.x; i < KP * (KM_CHUNK / 4); i += KM_ASSIGN_THREADS) {
-        const int j = i / (KM_CHUNK / 4), c = c0 + (i % (KM_CHUNK / 4)) * 4;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (j < k && c < ld) {                                          // ld % 4 == 0: a float4 is inside ld or outside
-          v = *reinterpret_cast<const f32x4*>(centres + (size_t)j * ld + c);
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (c + e >= d) v[e] = 0.f;                                 // the sum runs over the d columns
-        }
-        *reinterpret_cast<f32x4*>(&cs[j][(i % (KM_CHUNK / 4)) * 4]) = v;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int half = 0; half < KM_CHUNK / 256; ++half) {
-        const int col = half * 256 + lane * 4;
-        if (c0 + col >= d) continue;
-        f32x4 xv[KM_ROWS_PER_WAVE];
-#pragma unroll
-        for (int q = 0; q < KM_ROWS_PER_WAVE; ++q) {
-          xv[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-          if (row0 + q < n) xv[q] = *reinterpret_cast<const f32x4*>(x + (size_t)(row0 + q) * ld + c0 + col);
-        }
-#pragma unroll
-        for (int j = 0; j < KP; ++j) {
-          const f32x4 cv = *reinterpret_cast<const f32x4*>(&cs[j][col]);
-#pragma unroll
-          for (int q = 0; q < KM_ROWS_PER_WAVE; ++q)
-            acc[q][j] += xv[q][0] * cv[0] + xv[q][1] * cv[1] + xv[q][2] * cv[2] + xv[q][3] * cv[3];
-        }
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < KM_ROWS_PER_WAVE; ++q)
-#pragma unroll
-      for (int j = 0; j < KP; ++j) acc[q][j] = wave_sum(acc[q][j]);
-    if (lane == 0) {
-#pragma unroll
-      for (int q = 0; q < KM_ROWS_PER_WAVE; ++q) {
-        const int row = row0 + q;
-        if (row >= n) continue;
-        const float inv = inv_norm[row];
-        int bj = 0;
-        float b = 0.f, s2 = 0.f;
-        if (inv != 0.f) {
-          b = -INFINITY;
-          s2 = -INFINITY;
-#pragma unroll
-          for (int j = 0; j < KP; ++j) {
-            if (j >= k) continue;
-            const float s = acc[q][j] * inv;
-            if (s > b) {                                                // strictly: the lowest j wins on equal values
-              s2 = b;
-              b = s;
-              bj = j;
-            } else if (s > s2) {
-              s2 = s;
-            }
-          }
-        }
-        label[row] = bj;
-        best[row] = b;
-        second[row] = s2;
-      }
-    }
-  }
-}
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
@@ -173,9 +80,9 @@ __global__ __launch_bounds__(256) void kmeans_finish_kernel(const int* __restric
   for (int c = t; c < ld; c += 256) centres[(size_t)j * ld + c] = (c < d && norm > 0.0) ? (float)(sum[c] / norm) : 0.f;
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-inline bool rows_ok(int n, int d, int ld) { return n > 0 && d > 0 && d <= ld && (long long)n * ld <= 0x7fffffffLL; }
-inline bool k_ok(int k) { return k >= 1 && k <= STROTSS_KMEANS_MAX_K; }
+inline bool aligned16(const void* p) { return km_aligned16(p); }
+inline bool rows_ok(int n, int d, int ld) { return km_rows_ok(n, d, ld); }
+inline bool k_ok(int k) { return km_k_ok(k); }
 inline int row_blocks(int n) { return min(KM_MAX_ROW_BLOCKS, (n + KM_MIN_BLOCK_ROWS - 1) / KM_MIN_BLOCK_ROWS); }
 
 }  // namespace
@@ -187,15 +94,7 @@ int strotss_kmeans_assign(const float* x, const float* inv_norm, int n, int d, i
   ST_CHECK_ARG(aligned16(x) && aligned16(inv_norm) && aligned16(centres) && aligned16(label) && aligned16(best) &&
                    aligned16(second),
                STROTSS_EALIGN);
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned ntiles = ((unsigned)n + KM_TILE_ROWS - 1) / KM_TILE_ROWS;
-  const dim3 grid(min(ntiles, KM_MAX_GRID)), block(KM_ASSIGN_THREADS);
-  if (k <= 4)
-    hipLaunchKernelGGL(kmeans_assign_kernel<4>, grid, block, 0, st, x, inv_norm, n, d, ld, centres, k, label, best, second);
-  else if (k <= 8)
-    hipLaunchKernelGGL(kmeans_assign_kernel<8>, grid, block, 0, st, x, inv_norm, n, d, ld, centres, k, label, best, second);
-  else
-    hipLaunchKernelGGL(kmeans_assign_kernel<16>, grid, block, 0, st, x, inv_norm, n, d, ld, centres, k, label, best, second);
+  km_launch_assign<false>(x, inv_norm, n, d, ld, centres, k, nullptr, 0.f, label, best, second, (hipStream_t)stream);
   ST_LAUNCH_RET();
 }
 

@@ -180,6 +180,8 @@ SIGNATURES = {
     "strotss_kmeans_update": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
     "strotss_refine_labels_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "strotss_refine_labels": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, C.c_double, C.c_double, _P, _P, _P, _P, _P, _Z, _P]),
+    "strotss_label_warp": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
+    "strotss_kmeans_assign_prior": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _F, _P, _P, _P, _P]),
     "strotss_rmsprop_step": (_I, [C.POINTER(TensorsT), _F, _F, _F, _P]),
     "strotss_postprocess": (_I, [_P, _L, _P, _P, _P]),
 }

@@ -776,6 +776,51 @@ def refine_labels(img: torch.Tensor, grid: torch.Tensor, k: int, radius: int, si
     return label, count, best, second, mean
 
 
+# ------------------------------------------------------------------ region tracking
+def _int32_on_device(t: torch.Tensor, n: int, name: str) -> torch.Tensor:
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= n):
+        raise _hip.StrotssHipError(f"{name} must be a contiguous int32 CUDA/HIP tensor of >= {n} values")
+    return t
+
+
+def label_warp(prev_grid: torch.Tensor, k: int, flow: torch.Tensor, certainty: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """strotss_label_warp: the (gh, gw) int32 prior labels of a frame from the (gh, gw) int32 label grid of an earlier one,
+    along the backward flow (h, w, 2) = (dx, dy) between the two; -1 where the flow is not finite, leaves the image, the
+    certainty (h, w) at the cell's probe pixel is below 0.5 (None: no test) or the label found lies outside 0..k-1.  One
+    launch on the current stream; the library refuses gh > h, gw > w and k outside 1..16."""
+    if prev_grid.dim() != 2:
+        raise _hip.StrotssHipError("the label grid must be a contiguous (gh, gw) int32 CUDA/HIP tensor")
+    gh, gw = int(prev_grid.shape[0]), int(prev_grid.shape[1])
+    _int32_on_device(prev_grid, gh * gw, "the label grid")
+    require(flow, "backward flow")
+    if flow.dim() != 3 or int(flow.shape[2]) != 2:
+        raise ValueError(f"a flow of shape {tuple(flow.shape)}: expected (h, w, 2)")
+    h, w = int(flow.shape[0]), int(flow.shape[1])
+    if certainty is not None:
+        require(certainty, "certainty")
+        if certainty.numel() != h * w:
+            raise ValueError(f"a certainty of shape {tuple(certainty.shape)} for a flow of {h} x {w}")
+    prior = torch.empty((gh, gw), dtype=torch.int32, device=flow.device)
+    check(_hip.lib().strotss_label_warp(ptr(prev_grid), gh, gw, int(k), ptr(flow), ptr(certainty), h, w, ptr(prior),
+                                        stream_ptr()), "label_warp")
+    return prior
+
+
+def kmeans_assign_prior(x: torch.Tensor, inv_norm: torch.Tensor, n: int, d: int, centres: torch.Tensor, k: int,
+                        prior: torch.Tensor, beta: float):
+    """(label, best, second) of strotss_kmeans_assign_prior: kmeans_assign with beta added to the score of each row's prior
+    label (int32, (>= n,); a value outside 0..k-1 adds nothing); best and second are raw scores.  The library refuses a beta
+    that is not finite or outside [0, 2]."""
+    ld = _kmeans_rows(x, inv_norm, n, d, centres, k)
+    _int32_on_device(prior, n, "the prior labels")
+    label = torch.empty(n, dtype=torch.int32, device=x.device)
+    best = torch.empty(n, dtype=torch.float32, device=x.device)
+    second = torch.empty(n, dtype=torch.float32, device=x.device)
+    check(_hip.lib().strotss_kmeans_assign_prior(ptr(x), ptr(inv_norm), n, d, ld, ptr(centres), k, ptr(prior), float(beta),
+                                                 ptr(label), ptr(best), ptr(second), stream_ptr()), "kmeans_assign_prior")
+    return label, best, second
+
+
 def cosine_distance(x, rx, nx, y, ry, ny) -> torch.Tensor:
     ldc = pad32(ny)
     Cm = torch.empty((nx, ldc), dtype=torch.float32, device=x.device)

@@ -634,6 +634,122 @@ def save_masks(directory: str, content_masks, style_masks) -> None:
         Image.fromarray(palette[region].numpy(), "RGB").save(os.path.join(directory, name), format="PNG")
 
 
+# ----------------------------------------------------------------------------- region tracking
+MASK_INERTIA = 0.05                      # beta of --track_masks: a documented choice, not tuned
+MASK_INERTIA_RANGE = (0.0, 2.0)          # cosines lie in [-1, 1]: 2 never changes a label that has a prior
+
+
+def check_mask_inertia(beta) -> None:
+    """ValueError for an inertia that is not finite or outside [0, 2] (None: not given)"""
+    lo, hi = MASK_INERTIA_RANGE
+    if beta is not None and not (math.isfinite(beta) and lo <= beta <= hi):
+        raise ValueError(f"mask inertia {beta!r}: expected a finite value in [{lo}, {hi}]")
+
+
+def frame_rows(params, frame: torch.Tensor):
+    """The content half of what auto_mask_regions gathers, for one frame: dict(rows = the zero-padded (pad32(n), ld)
+    hypercolumn buffer of the frame's clustering grid, inv_norm, n, d, grid = (gh, gw), size = (h, w) of the image the grid
+    lies on).  One trunk forward at
+    AUTO_MASK_SIZE; the rows are bit for bit the content rows of auto_mask_regions on the same image."""
+    from . import engine
+    small = utils.resize(frame, min(AUTO_MASK_SIZE, max(int(frame.shape[-3]), int(frame.shape[-2]))))
+    if small.dim() == 3:
+        small = small[None]
+    feats = engine.extract_features(params, small.contiguous())
+    ys, xs = auto_mask_grid(int(small.shape[1]), int(small.shape[2]))
+    idx = np.stack(np.meshgrid(ys, xs, indexing="ij"), axis=-1).reshape(-1, 2).astype(np.float32)          # (row, col), row-major
+    n, d = len(ys) * len(xs), sum(int(m.shape[-1]) for m in feats)
+    rows = torch.zeros((_ops.pad32(n), _ops.pad32(d)), dtype=torch.float32, device=small.device)
+    _ops.hypercol_gather(feats, torch.from_numpy(idx).to(small.device), False, out=rows)
+    return dict(rows=rows, inv_norm=_ops.row_inv_norm(rows, n), n=n, d=d, grid=(len(ys), len(xs)),
+                size=(int(small.shape[1]), int(small.shape[2])))
+
+
+def tracking_state(found) -> dict:
+    """The state of frame 1 from its auto_mask_regions result (kept >= 2): dict(kept, centres (kept, ld), grid = G_1 over all
+    kept regions, present = the regions of this frame (all of them), mask_grid = the grid over the present regions)"""
+    kept = int(found["kept"])
+    grid = found["content_grid"].clone()                     # its own allocation: the library wants it 16-byte aligned
+    return dict(kept=kept, centres=found["centres"], grid=grid, present=list(range(kept)), mask_grid=grid)
+
+
+def track_regions(state: dict, params, frame: torch.Tensor, flow: Optional[torch.Tensor], certainty: Optional[torch.Tensor],
+                  beta: float = MASK_INERTIA, min_share: float = AUTO_MASK_MIN_SHARE) -> dict:
+    """The regions of one frame after the first.  state: the state of the earlier frame the prior is
+    taken from (tracking_state for frame 1, or what this function returned); flow (h, w, 2), certainty (h, w) or None: the
+    backward flow of this frame against that one and its certainty, at the results' size (brought to the clustering
+    image's size when the grid has more points than they have pixels); flow None: no prior (every cell -1).  Every cell of the
+    frame's clustering grid is assigned to one of the fixed centres of frame 1, `beta` added to the cosine of the label its
+    scene point had in the earlier frame (strotss_label_warp, strotss_kmeans_assign_prior) -> grid = G_t over all kept
+    regions.  The counts of G_t are read back (the one device-to-host read): a region below min_share of the grid points
+    is absent from this frame and its cells are reassigned among the present ones (a second biased assignment against the
+    present centres) -> mask_grid over the labels 0..len(present)-1.  Returns the new state; fewer than two present
+    regions: present = [] and mask_grid = None (the frame runs unmasked)."""
+    check_mask_inertia(beta)
+    kept, centres = int(state["kept"]), state["centres"]
+    got = frame_rows(params, frame)
+    shape, n, d = got["grid"], got["n"], got["d"]
+    if shape != tuple(state["grid"].shape):
+        raise ValueError(f"a clustering grid of {shape} after one of {tuple(state['grid'].shape)}: the frames differ in size")
+    if flow is None:
+        prior = torch.full(shape, -1, dtype=torch.int32, device=centres.device)
+    else:
+        if int(flow.shape[0]) < shape[0] or int(flow.shape[1]) < shape[1]:      # results smaller than the clustering image
+            hs, ws = got["size"]                                                # (the coarse levels): the grid fits that one
+            if certainty is not None:
+                certainty = _ops.resize_bilinear(certainty.float().reshape(int(flow.shape[0]), int(flow.shape[1]), 1)
+                                                 .contiguous(), hs, ws).reshape(hs, ws)
+            flow = resize_flow(flow, hs, ws).contiguous()
+        prior = _ops.label_warp(state["grid"].contiguous(), kept, flow, certainty)
+    label, _, _ = _ops.kmeans_assign_prior(got["rows"], got["inv_norm"], n, d, centres, kept, prior.reshape(-1), float(beta))
+    counts = label_counts(label, kept).cpu().numpy()
+    present = [int(r) for r in np.flatnonzero(counts >= min_share * n)]
+    out = dict(kept=kept, centres=centres, grid=label.reshape(shape), present=present, mask_grid=label.reshape(shape),
+               prior=prior, counts=counts)
+    if len(present) < 2:
+        out.update(present=[], mask_grid=None)
+    elif len(present) < kept:                                # the absent regions' cells go to a present one
+        lut = torch.full((kept + 1,), -1, dtype=torch.int32)
+        lut[torch.tensor(present) + 1] = torch.arange(len(present), dtype=torch.int32)
+        sub_prior = lut.to(prior.device)[(prior.reshape(-1) + 1).long()].contiguous()
+        sub_centres = centres[torch.tensor(present, device=centres.device)].contiguous()
+        sub, _, _ = _ops.kmeans_assign_prior(got["rows"], got["inv_norm"], n, d, sub_centres, len(present), sub_prior,
+                                             float(beta))
+        out["mask_grid"] = sub.reshape(shape)
+    return out
+
+
+def masks_from_grid(image, grid: torch.Tensor, kept: int, refine=None, min_share: float = AUTO_MASK_MIN_SHARE):
+    """masks_from_grids for one image: `kept` (H, W, 1) float 0/1 masks in ascending label order from its label grid, by
+    nearest neighbour (refine None) or refined against the image itself (refine = sigma_r) with the same fallback: a
+    region left with fewer than min_share of the pixels logs a warning and the unrefined masks are kept."""
+    H, W = int(image.shape[-3]), int(image.shape[-2])
+    label = upsample_labels(grid, H, W)
+    if refine is not None:
+        refined, count = refine_labels(image, grid, kept, refine)
+        count = count.cpu().numpy()
+        if (count >= min_share * H * W).all():
+            label = refined
+        else:
+            utils.logger.warning(f"--refine_masks: a region would hold fewer than {min_share:.3f} of the frame's pixels "
+                                 f"({count.tolist()} of {H * W}); keeping the unrefined masks")
+    return [(label == j).float()[..., None] for j in range(kept)]
+
+
+def save_region_image(path: str, masks, regions=None) -> None:
+    """One colour-coded region image in the format of save_masks: the pixels of masks[i] painted in MASK_COLOURS[regions[i]]
+    (regions None: 0, 1, ..), so that a region keeps its colour across the frames of a sequence while an absent one's colour
+    does not occur."""
+    from PIL import Image
+    regions = list(range(len(masks))) if regions is None else [int(r) for r in regions]
+    if len(regions) != len(masks) or any(not 0 <= r < len(MASK_COLOURS) for r in regions):
+        raise ValueError(f"{len(masks)} masks for the regions {regions}: the colour-coded format tells {len(MASK_COLOURS)} apart")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    palette = torch.tensor(MASK_COLOURS, dtype=torch.uint8)[torch.tensor(regions)]
+    region = torch.stack([m.reshape(m.shape[0], m.shape[1]) for m in masks]).argmax(dim=0).cpu()
+    Image.fromarray(palette[region].numpy(), "RGB").save(path, format="PNG")
+
+
 def _colour_keys(path: str, max_size: Optional[int], pixel_threth: int) -> np.ndarray:
     """(H, W) int64 key per pixel of a colour-coded region image: its channels floored to multiples of `pixel_threth`
     (uint8 as decoded, or float32 when `max_size` made load_image resize it) and packed so that ascending keys are

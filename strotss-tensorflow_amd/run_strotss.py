@@ -55,8 +55,8 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
                     draws from, exactly as a pair of --content_mask / --style_mask colours is.  Computed on the images as
                     loaded (before --preserve_color match recolours the style, which then runs region by region).  Fewer
                     than two such clusters: a warning and an unmasked run.  Combines with --content_weight_map,
-                    --preserve_color and --photo_smooth; not with --content_mask / --style_mask, --style_mix, --video,
-                    --strips or a multi-process run.
+                    --preserve_color and --photo_smooth; not with --content_mask / --style_mask, --style_mix, --strips or a
+                    multi-process run; with --video only together with --track_masks.
   --refine_masks    with --auto_masks: edge-aligned regions.  The label grid of each image is brought to
                     the image by joint bilateral upsampling with the image itself as guide instead of by nearest neighbour:
                     every pixel votes among the 5 x 5 grid cells around its own, a cell counting for more when it is near
@@ -67,6 +67,16 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
   --save_masks DIR  with --auto_masks: write the regions to DIR as content_mask.png and style_mask.png in the colour-coded
                     format of --content_mask / --style_mask (region r in the r-th of the eight colours with channels in
                     {0, 255}, ascending (r, g, b)), to be edited and handed back through those two flags
+  --track_masks     with --auto_masks K --video: the regions of the first frame followed through the sequence (DESIGN.md
+                    section 19).  Frame 1 is clustered jointly with style_path as a single image is; its regions, their
+                    centres and the style masks then stay.  Every later frame's grid cells are assigned to those centres,
+                    the label that the same scene point had in the nearest earlier frame of --temporal_frames (followed
+                    along the backward flow of --flow_dir / --compute_flow, where that flow is certain) preferred by
+                    --mask_inertia.  A region below 1/32 of a frame's grid points is absent from that frame (its cells go
+                    to the others) and may come back later.  --save_masks DIR then writes style_mask.png once and
+                    content_mask_<frame stem>.png per frame, a region keeping its colour.
+  --mask_inertia B  with --track_masks: what is added to the cosine of the prior label, 0..2 (default 0.05, not tuned); 0 is
+                    the plain assignment to frame 1's centres, 2 never changes a label that has a prior
   --strips          under torchrun (one process per GPU): ONE image on all GPUs -- every rank runs the trunk on its strip
                     of the image (+ halo) at the scales where that pays, two all-reduces per step (nn/parallel.py);
                     rank 0 writes the output
@@ -236,13 +246,37 @@ def _refine_masks_input(args):
     return float(sigma)
 
 
+def _track_masks_input(args):
+    """--track_masks, --mask_inertia B: the inertia of the tracking (B, or the default), or None without --track_masks.
+    ValueError: --track_masks without --auto_masks or without --video, --mask_inertia without --track_masks, not finite or
+    outside 0..2."""
+    track, beta = getattr(args, "track_masks", False), getattr(args, "mask_inertia", None)
+    if beta is not None and not track:
+        raise ValueError("--mask_inertia needs --track_masks")
+    if not track:
+        return None
+    if getattr(args, "auto_masks", None) is None:
+        raise ValueError("--track_masks needs --auto_masks (it follows the regions the run finds)")
+    if not getattr(args, "video", False):
+        raise ValueError("--track_masks needs --video (it follows the regions through a frame sequence)")
+    if beta is None:
+        return strotss.MASK_INERTIA
+    try:
+        strotss.check_mask_inertia(float(beta))
+    except ValueError:
+        lo, hi = strotss.MASK_INERTIA_RANGE
+        raise ValueError(f"--mask_inertia takes a value in {lo:g}..{hi:g}, got {beta!r}") from None
+    return float(beta)
+
+
 def _auto_masks_input(args):
     """--auto_masks K, --save_masks DIR: (K, DIR or None), or None without --auto_masks.  ValueError, before anything is
     loaded: K outside 2..8, --save_masks without --auto_masks, --auto_masks with --content_mask / --style_mask, --style_mix,
-    --video, --strips or under torchrun with WORLD_SIZE > 1, and the refusals of --refine_masks / --refine_sigma
-    (_refine_masks_input)."""
+    --video without --track_masks, --strips or under torchrun with WORLD_SIZE > 1, and the refusals of --refine_masks /
+    --refine_sigma (_refine_masks_input) and of --track_masks / --mask_inertia (_track_masks_input)."""
     k, save = getattr(args, "auto_masks", None), getattr(args, "save_masks", None)
     _refine_masks_input(args)
+    track = _track_masks_input(args)
     if k is None:
         if save:
             raise ValueError("--save_masks needs --auto_masks (it writes the regions the run finds)")
@@ -254,8 +288,9 @@ def _auto_masks_input(args):
         raise ValueError("--auto_masks cannot be combined with --content_mask / --style_mask: the regions are found or given")
     if getattr(args, "style_mix", None):
         raise ValueError("--auto_masks cannot be combined with --style_mix: masks and blends exclude each other")
-    if getattr(args, "video", False):
-        raise ValueError("--auto_masks cannot be combined with --video: clustering every frame on its own would flicker")
+    if getattr(args, "video", False) and track is None:
+        raise ValueError("--auto_masks cannot be combined with --video: clustering every frame on its own would flicker "
+                         "(--track_masks follows the first frame's regions through the sequence)")
     if getattr(args, "strips", False):
         raise ValueError("--auto_masks cannot be combined with --strips")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -384,16 +419,17 @@ def _computed_flows(args, t: int, j: int, frames, h: int, w: int):
     return fb, ff
 
 
-def _temporal_for_frame(args, t: int, previous: torch.Tensor, j: int = 1, frames=None):
-    """(warped result of frame t-j, certainty) of frame t (1-based, t > j) at that result's size: the flows of --flow_dir
-    resized to that size (strotss_utils.resize_flow), the warp and certainty in one launch; a reliable_{t}_{t-j}.pgm, when
-    there is one, replaces the certainty (its value / 255, resized).  `previous`: the final result of frame t-j.
-    --compute_flow: both flows come from _computed_flows(frames) at that size instead; no file is read."""
+def _flow_warp_for_frame(args, t: int, previous: torch.Tensor, j: int = 1, frames=None):
+    """(backward flow (h, w, 2), warped result of frame t-j, certainty) of frame t (1-based, t > j) at that result's size:
+    the flows of --flow_dir resized to that size (strotss_utils.resize_flow), the warp and certainty in one launch; a
+    reliable_{t}_{t-j}.pgm, when there is one, replaces the certainty (its value / 255, resized).  `previous`: the final
+    result of frame t-j.  --compute_flow: both flows come from _computed_flows(frames) at that size instead; no file is
+    read."""
     h, w = int(previous.shape[1]), int(previous.shape[2])
     dev = previous.device
     if getattr(args, "compute_flow", False):
         fb, ff = _computed_flows(args, t, j, frames, h, w)
-        return strotss_engine._ops.flow_warp(previous.contiguous(), fb, ff)
+        return (fb,) + tuple(strotss_engine._ops.flow_warp(previous.contiguous(), fb, ff))
     flow_b = strotss.read_flo(os.path.join(args.flow_dir, f"backward_{t}_{t - j}.flo"))
     big = tuple(flow_b.shape[:2])
     fwd_path = os.path.join(args.flow_dir, f"forward_{t - j}_{t}.flo")
@@ -406,7 +442,13 @@ def _temporal_for_frame(args, t: int, previous: torch.Tensor, j: int = 1, frames
     rel = os.path.join(args.flow_dir, f"reliable_{t}_{t - j}.pgm")
     if os.path.exists(rel):
         certainty = _resized_reliable(rel, h, w)
-    return warped, certainty
+    return fb, warped, certainty
+
+
+def _temporal_for_frame(args, t: int, previous: torch.Tensor, j: int = 1, frames=None):
+    """(warped result of frame t-j, certainty) of frame t (1-based, t > j) at that result's size: _flow_warp_for_frame
+    without the flow"""
+    return _flow_warp_for_frame(args, t, previous, j, frames)[1:]
 
 
 def _temporal_targets_for_frame(args, t: int, results, offsets, frames=None):
@@ -591,19 +633,22 @@ def run(args: argparse.Namespace, trace=None):
 
 
 def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: int = 1, trace=None, temporal=None,
-             temporal_weight: float = 0.0):
+             temporal_weight: float = 0.0, masks=None):
     """The coarse-to-fine schedule on one content image -> the final image of the finest scale (1, h, w, 3).
     temporal: (warped previous result, certainty) at that result's size, or None; every scale then carries the temporal
     term with weight temporal_weight, and --temporal_init starts the first executed scale from the warped result.  A list
     of 2..4 such pairs (combined certainties, nearest frame first) carries one term per pair, all
-    with weight temporal_weight; --temporal_init starts from the nearest."""
+    with weight temporal_weight; --temporal_init starts from the nearest.  masks: (content_masks, style_masks) of this
+    frame from the caller (--track_masks), in place of the regions found or loaded here."""
     from nn import parallel
     level, first = int(args.level), int(getattr(args, "start_level", 0))
     content = utils.load_image(content_path, max_size=args.max_size)
     style_paths, style_weights = _style_inputs(args)
     styles = [utils.load_image(p, max_size=args.max_size) for p in style_paths]
     auto = _auto_masks_input(args)
-    if auto:                                                 # regions found on the images as loaded, in place of painted masks
+    if masks is not None:
+        content_masks, style_masks = masks
+    elif auto:                                               # regions found on the images as loaded, in place of painted masks
         refine = _refine_masks_input(args)
         if refine is None:                                   # without --refine_masks the call is what it was
             content_masks, style_masks = strotss.auto_masks(vgg.params, content, styles[0], auto[0])
@@ -668,6 +713,56 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
     return stylized
 
 
+def _tracked_masks(args, vgg, tracking: dict, t: int, frame: str, j: int, nearest, auto, inertia: float):
+    """--track_masks: (content_masks, style_masks) of frame t.  tracking: {frame position: state} of the
+    last j frames plus the sequence's constants under "style" (the style masks of all kept regions) -- or {"off": True} once
+    frame 1 gave fewer than two regions (the whole sequence then runs unmasked).  Frame 1: auto_mask_regions jointly with
+    style_path, the masks of both images as a single-image run makes them.  Frame t > 1: strotss_utils.track_regions
+    against the state of frame t-j along `nearest` = (backward flow, warped result, certainty) of that pair (None for
+    t <= j: no prior), then the content masks of the present regions with the matching style masks.  --save_masks DIR:
+    style_mask.png once, content_mask_<frame stem>.png per frame (of a frame that runs unmasked: its label grid)."""
+    if tracking.get("off"):
+        return [None], [None]
+    k, save = auto
+    refine = _refine_masks_input(args)
+    content = utils.load_image(frame, max_size=args.max_size)
+    stem = os.path.splitext(os.path.basename(frame))[0]
+    if t == 1:
+        style = utils.load_image(args.style_path, max_size=args.max_size)
+        found = strotss.auto_mask_regions(vgg.params, content, style, k)
+        if not found["kept"]:
+            utils.logger.warning(f"--auto_masks {k}: fewer than two clusters hold {strotss.AUTO_MASK_MIN_SHARE:.3f} of both "
+                                 f"images (content {found['counts'][0].tolist()}, style {found['counts'][1].tolist()} of "
+                                 f"{found['n_c']}, {found['n_s']} points); running the sequence unmasked")
+            tracking["off"] = True
+            return [None], [None]
+        content_masks, style_masks = strotss.masks_from_grids(content, style, found["content_grid"], found["style_grid"],
+                                                              found["kept"], refine)
+        utils.logger.info(f'Found {len(content_masks)} regions.')
+        tracking["style"], tracking[1] = style_masks, strotss.tracking_state(found)
+        if save:
+            strotss.save_region_image(os.path.join(save, "style_mask.png"), style_masks)
+            strotss.save_region_image(os.path.join(save, f"content_mask_{stem}.png"), content_masks)
+        return content_masks, style_masks
+    source = tracking[t - j] if nearest is not None else tracking[1]      # t <= j: frame 1's state is still held
+    flow, certainty = (nearest[0], nearest[2].float().contiguous()) if nearest is not None else (None, None)
+    state = strotss.track_regions(source, vgg.params, content, flow, certainty, inertia)
+    tracking[t] = state
+    tracking.pop(t - j, None)
+    present = state["present"]
+    if not present:
+        utils.logger.warning(f"--track_masks: fewer than two regions hold {strotss.AUTO_MASK_MIN_SHARE:.3f} of frame {t}'s grid "
+                             f"points ({state['counts'].tolist()}); running this frame unmasked")
+        if save:                            # what the frame was given: its grid over all regions, by nearest neighbour
+            strotss.save_region_image(os.path.join(save, f"content_mask_{stem}.png"),
+                                      strotss.masks_from_grid(content, state["grid"], state["kept"]))
+        return [None], [None]
+    content_masks = strotss.masks_from_grid(content, state["mask_grid"], len(present), refine)
+    if save:
+        strotss.save_region_image(os.path.join(save, f"content_mask_{stem}.png"), content_masks, present)
+    return content_masks, [tracking["style"][r] for r in present]
+
+
 def run_video(args: argparse.Namespace, trace=None):
     """--video: every frame of the directory content_path through the schedule of run(), one VGG for the sequence, the
     seeds reset for every frame (each frame draws the index stream a single-image run draws).  Frame t > 1 carries the
@@ -677,7 +772,8 @@ def run_video(args: argparse.Namespace, trace=None):
     section 14; the last max(J) + 1 of those frames stay on the device as well).  --preserve_color match recolours the
     styles against every frame's own colours (in _stylise); luminance merges only what is written, the temporal targets
     keep the unmerged results.  --photo_smooth filters only what is written as well, before that
-    merge.  Writes
+    merge.  --auto_masks K --track_masks: the regions of frame 1 followed through the sequence
+    (_tracked_masks).  Writes
     <output dir>/<frame stem>.jpg; returns the list of the frames' uint8 results.  `trace`: one list per frame."""
     preserve = _preserve_color_input(args)
     smooth = _photo_smooth_input(args)
@@ -688,6 +784,8 @@ def run_video(args: argparse.Namespace, trace=None):
     os.makedirs(args.output_path, exist_ok=True)
     vgg = VGG(use_keras_weight=args.use_keras_weight, weights=getattr(args, "weights", None), seed=seed, device=dev)
     offsets = _temporal_frames(args)
+    auto, inertia = _auto_masks_input(args), _track_masks_input(args)
+    tracking = {} if auto else None         # --track_masks: the states of the last offsets[0] frames, by frame position
     previous, outs = None, []
     results = []                            # results[k]: the final image of frame t-1-k, the last max(offsets) of them
     flow_frames = {} if getattr(args, "compute_flow", False) else None      # --compute_flow: the last max(offsets) + 1 frames
@@ -698,7 +796,12 @@ def run_video(args: argparse.Namespace, trace=None):
         if flow_frames is not None:
             flow_frames[t] = _frame_at_result_size(args, frame)
             flow_frames.pop(t - offsets[-1] - 1, None)
-        if offsets == (1,):
+        nearest = None                      # --track_masks: (flow, warped, certainty) against the nearest earlier frame
+        if tracking is not None and t > offsets[0]:
+            nearest = _flow_warp_for_frame(args, t, results[offsets[0] - 1], offsets[0], flow_frames)
+        if offsets == (1,) and nearest is not None:
+            temporal = nearest[1:]
+        elif offsets == (1,):
             temporal = _temporal_for_frame(args, t, previous, frames=flow_frames) if previous is not None else None
         else:
             pairs = _temporal_targets_for_frame(args, t, results, offsets, flow_frames)
@@ -707,7 +810,10 @@ def run_video(args: argparse.Namespace, trace=None):
         if trace is not None:
             rec = []
             trace.append(rec)
-        previous = _stylise(args, vgg, frame, cw_path, dev, trace=rec, temporal=temporal, temporal_weight=lam)
+        masks = None
+        if tracking is not None:
+            masks = _tracked_masks(args, vgg, tracking, t, frame, offsets[0], nearest, auto, inertia)
+        previous = _stylise(args, vgg, frame, cw_path, dev, trace=rec, temporal=temporal, temporal_weight=lam, masks=masks)
         results = [previous] + results[:offsets[-1] - 1]
         written = previous                  # only what is written is filtered or merged: the temporal targets and
         if smooth or preserve == "luminance":                    # --temporal_init keep the optimiser's own results
@@ -783,6 +889,11 @@ _FLAGS = (
     (("--save_masks",), dict(type=str, default=None, metavar='DIR',
                              help="with --auto_masks: write content_mask.png and style_mask.png there, in the colour-coded "
                                   "format of --content_mask / --style_mask")),
+    (("--track_masks",), dict(action='store_true', help="with --auto_masks K --video: follow the first frame's regions through "
+                                                        "the sequence along the backward flow instead of refusing the pair")),
+    (("--mask_inertia",), dict(type=float, default=None, metavar='B',
+                               help=f"with --track_masks: added to the cosine of a cell's prior label, 0..2 (default "
+                                    f"{strotss.MASK_INERTIA:g})")),
     (("--strips",), dict(action='store_true', help="under torchrun: shard ONE image over the GPUs by image strips")),
     (("--halo",), dict(action='store_true', help="with --strips: per-layer halo EXCHANGE with the neighbouring ranks (16-row "
                                                  "windows margins, one row per layer and direction) instead of a 128-row recompute margin")),
