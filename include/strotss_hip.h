@@ -336,8 +336,10 @@ int strotss_cosine_distance_x3(const void* x_panels, const float* rx, int nx, co
                                int ny, int ld, float* C, int ldc, void* stream);
 /* Backward of a pairwise distance matrix w.r.t. one of its row sets (what tape.gradient does to nn/losses.py:12-24):
  *   dx[i, :] += g * r[i] * ( sum_{j < k} W[i, j] * B[j, :]  -  x[i, :] * r[i] * q[i] ),   i < n,
- * W (n rows, ldw >= k floats per row, ldw % 32 == 0, entries j >= k zero), B (>= ldw rows of ld floats, rows >= k zero or
- * finite), x / dx (n, ld), ld % 32 == 0; r, q: n floats.  cosine_distance(x, y) with upstream gradient G: W = -G * ry[j],
+ * W (n rows, ldw >= k floats per row, ldw % 32 == 0), B (>= ldw rows of ld floats), x / dx (n, ld), ld % 32 == 0; r, q: n
+ * floats.  THE CALLER ZERO-FILLS: the product runs over all ldw columns of W and the first ldw rows of B (k is only
+ * validated, 0 < k <= ldw), so the sum is the one over j < k exactly when W[i, j] = 0 for k <= j < ldw and rows k .. ldw - 1
+ * of B are finite (zero or not); anything else in those columns of W is summed too.  cosine_distance(x, y) with upstream gradient G: W = -G * ry[j],
  * B = y, r = the reciprocal norms of x, q[i] = -sum_j G[i, j] (1 - C[i, j]);  l2_distance: W = -2 G' (G' = G / (2 D C) where
  * the clamp passes), B = y, r = 1, q[i] = -2 sum_j G'[i, j].  f32 MFMA (the loss path's own backward GEMMs run on the
  * bf16x3 core from pre-split panels; this entry is the operator surface's). */

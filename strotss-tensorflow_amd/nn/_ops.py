@@ -1042,7 +1042,9 @@ def remd_metric_fwd_bwd(style, ns, pred, n, d, metric: str, gscale, gpred, loss_
 def rows_gemm_bwd(W, k, B, x, r, q, n, g, dx):
     """dx[i, :] += g * r[i] * (sum_j W[i, j] B[j, :] - x[i, :] * r[i] * q[i])   for i < n, j < k  (strotss_rows_gemm_bwd):
     the backward of a pairwise distance matrix w.r.t. one of its two row sets (reference losses.py:12-24 under
-    tape.gradient) -- W = d(loss)/d(product) scaled by the other side's factors, q = the normalisation's rank-one term."""
+    tape.gradient) -- W = d(loss)/d(product) scaled by the other side's factors, q = the normalisation's rank-one term.
+    The caller zero-fills: the product runs over ALL W.shape[1] columns of W and as many rows of B (k is only validated), so
+    columns k .. W.shape[1] - 1 of W must be zero and those rows of B finite for the sum to be the one over j < k."""
     assert W.is_contiguous() and B.is_contiguous() and x.is_contiguous() and dx.is_contiguous()
     assert int(W.shape[1]) % 32 == 0 and int(B.shape[1]) == int(x.shape[1]) == int(dx.shape[1]) and int(B.shape[0]) >= int(W.shape[1])
     check(_hip.lib().strotss_rows_gemm_bwd(ptr(W), int(W.shape[1]), int(k), ptr(B), ptr(x), ptr(r), ptr(q), n, int(x.shape[1]),

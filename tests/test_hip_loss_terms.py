@@ -1,4 +1,4 @@
-"""Every loss entry of the C ABI, one term at a time, at every case of tests/_loss_cases.py (the step's shape, ragged sample
+"""Every loss entry of the C ABI (but the Sinkhorn entries and strotss_rows_gemm_bwd: tests/test_hip_sinkhorn.py), one term at a time, at every case of tests/_loss_cases.py (the step's shape, ragged sample
 counts, the tie-list limit ns = 2048, n = 1 / 2 / 37, flat regions, d = 3100) against the float64 restatement of
 tests/_loss_ref.py: every scalar within TOL_SCALAR relative, every gradient within TOL_GRAD of max|ref| (the L1 terms
 outside the flip-aware bound).  The grouped entries are called once per term with only that term's g non-zero.  Every call:
@@ -15,12 +15,10 @@ import torch
 
 import _loss_cases as LC
 import _loss_ref as LR
+from _loss_harness import DEV, LC_pad, check_gradient, check_scalar, fbuf, report, run_entry
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-TOL_SCALAR, TOL_GRAD = LR.TOL_SCALAR, LR.TOL_GRAD
-SENTINEL = 7.25
 CASES = [c[0] for c in LC.CASES if c[4] != "public"]
 PUBLIC = [c for c in LC.LABELS if c not in CASES]
 
@@ -34,10 +32,6 @@ def ops():
 @pytest.fixture(scope="module", params=CASES, ids=[f"case_{c}" for c in CASES])
 def R(request):
     return refs_of(request.param)
-
-
-def report(what, case, value):
-    print(f"MEASURE {what} {case} {value}")
 
 
 class Refs:
@@ -82,59 +76,6 @@ def refs_of(label):
         _refs.clear()                       # one case's references at a time (tests are grouped by case)
         _refs[label] = Refs(label)
     return _refs[label]
-
-
-def fbuf(x):
-    n, d = x.shape
-    b = torch.zeros((LC_pad(n), LC_pad(d)), dtype=torch.float32, device=DEV)
-    b[:n, :d] = torch.as_tensor(x, dtype=torch.float32, device=DEV)
-    return b
-
-
-def LC_pad(v):
-    return (v + 31) // 32 * 32
-
-
-def poison(ops):
-    for b in ops.workspaces.bufs.values():
-        b.fill_(255)
-
-
-def gpred_base(n, d, scale, seed):
-    g = torch.full((LC_pad(n), LC_pad(d)), SENTINEL, dtype=torch.float32)
-    g[:n, :d] = torch.as_tensor(np.random.default_rng(seed).standard_normal((n, d)) * scale, dtype=torch.float32)
-    return g.to(DEV)
-
-
-def run_entry(ops, fn, n, d, scale, seed=0):
-    """fn(gpred, loss4) once on a zero buffer (workspaces take their size; its gradient is returned for the duplicate-row
-    check), then on NaN-filled workspaces into a seeded base with sentinel padding: (added gradient float64 [:n, :d],
-    losses float64, gradient of the zero-buffer call)"""
-    g0 = torch.zeros((LC_pad(n), LC_pad(d)), dtype=torch.float32, device=DEV)
-    fn(g0, torch.zeros(4, 4, dtype=torch.float32, device=DEV))
-    torch.cuda.synchronize()
-    poison(ops)
-    g = gpred_base(n, d, scale, seed)
-    base = g.clone()
-    loss = torch.zeros(4, 4, dtype=torch.float32, device=DEV)
-    fn(g, loss)
-    torch.cuda.synchronize()
-    assert torch.equal(g[n:], base[n:]) and torch.equal(g[:, d:], base[:, d:]), "padding of gpred changed"
-    got = (g.double() - base.double())[:n, :d].cpu().numpy()
-    assert np.isfinite(got).all()
-    return got, loss.double().cpu().numpy(), g0[:n, :d].cpu().numpy()
-
-
-def check_scalar(what, label, got, ref):
-    rel = abs(got - ref) / max(abs(ref), 1e-30)
-    report(f"scalar:{what}", label, f"{rel:.3e}")
-    assert abs(got - ref) <= TOL_SCALAR * abs(ref), (what, got, ref)
-
-
-def check_gradient(what, label, got, ref, bound=None, tol=TOL_GRAD):
-    ok, worst, rms = LR.check_grad(got, ref, bound, tol)
-    report(f"grad:{what}", label, f"max {worst:.3e} rms {rms:.3e}")
-    assert ok, (what, worst, rms)
 
 
 def check_dups(what, case, g0):
