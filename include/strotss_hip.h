@@ -370,6 +370,20 @@ size_t strotss_sinkhorn_workspace_bytes(int ns, int n, int n_iter);
 int strotss_sinkhorn_cos_fwd_bwd(const float* style, const float* rs, int ns, const float* pred, int n, int d,
                                  int ld, float l, int n_iter, float gscale, float* gpred, float* loss_out,
                                  void* workspace, size_t workspace_bytes, void* stream);
+/* strotss_sinkhorn_cos_fwd_bwd as the style term of a train step: the same loss and gradient, with the
+ * prologue convention of strotss_remd_cos_fwd_bwd_panels -- pred_inv_norm / pred_panels from the content loss's workspace
+ * (strotss_selfsim_pred_panels), rs / style_panels made once per scale (strotss_row_inv_norm_x3).  The scalings and their
+ * reverse sweep are the entry's above (a fused one-launch-per-scaling form measured 3.5 times slower).
+ * Both panels given: the cost matrix on the bf16x3 core; both NULL (what strotss_selfsim_pred_panels hands out under
+ * STROTSS_X3=0): on the f32 MFMA from the rows; one of the two: STROTSS_EINVAL.  No float atomics: the same bits on every
+ * call and stream.  Refusals before any launch, outputs and workspace untouched: STROTSS_EINVAL (null pointers, sizes, a
+ * workspace below strotss_sinkhorn_step_workspace_bytes), STROTSS_EALIGN (ld % 32 != 0), STROTSS_ERANGE (l not finite or
+ * <= 0, n_iter outside 1..64). */
+size_t strotss_sinkhorn_step_workspace_bytes(int ns, int n, int n_iter);
+int strotss_sinkhorn_cos_fwd_bwd_panels(const float* style, const float* rs, const void* style_panels, int ns, const float* pred,
+                                        const float* pred_inv_norm, const void* pred_panels, int n, int d, int ld, float l,
+                                        int n_iter, float gscale, float* gpred, float* loss_out, void* workspace,
+                                        size_t workspace_bytes, void* stream);
 /* ld = row stride of the feature matrices (strotss_remd_cos_fwd_bwd), 0 for strotss_palette_remd_fwd_bwd */
 /* The same with dist_metrics 'l2' (STROTSS_METRIC_L2) or 'both' (STROTSS_METRIC_BOTH) as the cost (losses.py:27-28): cost matrix
  * on the f32 MFMA with the distance in its epilogue, the scalings and their reverse sweep as above, the clamp of l2_distance

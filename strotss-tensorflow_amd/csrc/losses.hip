@@ -1533,6 +1533,36 @@ int strotss_sinkhorn_cos_fwd_bwd(const float* style, const float* rs, int ns, co
   return st_selfsim_bwd_gemm(s.W, ldm, ldm, style, pred, s.rp, s.q, n, ld, gscale, gpred, st);
 }
 
+// The step's Sinkhorn term takes strotss_sinkhorn_cos_fwd_bwd's workspace less nothing: the reciprocal norms it borrows are
+// 4 n bytes of it.  An entry of its own so that the step's workspace can change without the operator's.
+size_t strotss_sinkhorn_step_workspace_bytes(int ns, int n, int n_iter) {
+  if (ns <= 0 || n <= 0 || n_iter < 1 || n_iter > 64) return 0;
+  return strotss_sinkhorn_workspace_bytes(ns, n, n_iter);
+}
+
+int strotss_sinkhorn_cos_fwd_bwd_panels(const float* style, const float* rs, const void* style_panels, int ns,
+                                        const float* pred, const float* pred_inv_norm, const void* pred_panels, int n, int d,
+                                        int ld, float l, int n_iter, float gscale, float* gpred, float* loss_out,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+  // the panels come as a pair: both (cost matrix on the bf16x3 core) or neither (f32 MFMA from the rows)
+  ST_CHECK_ARG(style && rs && pred && pred_inv_norm && gpred && loss_out && workspace && ns > 0 && feat_ok(n, d, ld) &&
+               (style_panels != nullptr) == (pred_panels != nullptr), STROTSS_EINVAL);
+  ST_CHECK_ARG(ld % 32 == 0, STROTSS_EALIGN);
+  ST_CHECK_ARG(l > 0.f && l <= 3.0e38f && n_iter >= 1 && n_iter <= 64, STROTSS_ERANGE);
+  Workspace w(workspace, workspace_bytes);
+  SinkhornWs s;
+  ST_CHECK_ARG(s.plan(w, ns, n, n_iter), STROTSS_EINVAL);
+  hipStream_t st = (hipStream_t)stream;
+  const int ldm = s.ldm, T = n_iter;
+  if (pred_panels) CHK(st_cosine_distance_x3(pred_panels, pred_inv_norm, n, style_panels, rs, ns, ld, 0, s.Mt, ldm, 1, 0, 0, 0, st));
+  else CHK(st_cosine_distance(pred, pred_inv_norm, n, style, rs, ns, ld, s.Mt, ldm, st));     // Mt[j][i] = 1 - <yhat_j, xhat_i>
+  CHK(sinkhorn_iterate(s, ns, n, l, T, loss_out, st));
+  hipLaunchKernelGGL(sk_assemble_kernel, dim3(n), dim3(256), 0, st, s.Kt, s.Mt, ns, ldm, T, l, s.U, s.DA, s.V, s.DB, n, rs,
+                     s.W, s.q);
+  LAUNCH_OK();
+  return st_selfsim_bwd_gemm(s.W, ldm, ldm, style, pred, pred_inv_norm, s.q, n, ld, gscale, gpred, st);
+}
+
 // sinkhorn_knopp with dist_metrics 'l2' / 'both' (losses.py:27-28, 83-105; build-defined like the cosine form): the cost
 // matrix from st_remd_cost (one f32-MFMA product, the distance in its epilogue), the same scalings and reverse sweep, the
 // metric's chain rule in the assembly, one (l2) or two (both) backward GEMMs against the style rows.

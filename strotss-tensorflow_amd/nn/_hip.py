@@ -140,6 +140,8 @@ SIGNATURES = {
     "strotss_selfsim_weighted_fwd_bwd": (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _Z, _P]),
     "strotss_sinkhorn_workspace_bytes": (_Z, [_I, _I, _I]),
     "strotss_sinkhorn_cos_fwd_bwd": (_I, [_P, _P, _I, _P, _I, _I, _I, _F, _I, _F, _P, _P, _P, _Z, _P]),
+    "strotss_sinkhorn_step_workspace_bytes": (_Z, [_I, _I, _I]),
+    "strotss_sinkhorn_cos_fwd_bwd_panels": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _F, _I, _F, _P, _P, _P, _Z, _P]),
     "strotss_sinkhorn_metric_workspace_bytes": (_Z, [_I, _I, _I]),
     "strotss_sinkhorn_metric_fwd_bwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _F, _I, _F, _P, _P, _P, _Z, _P]),
     "strotss_remd_workspace_bytes": (_Z, [_I, _I, _I]),

@@ -1008,6 +1008,29 @@ def sinkhorn_cos_fwd_bwd(style, rs, ns, pred, n, d, l, n_iter, gscale, gpred, lo
           "sinkhorn_cos_fwd_bwd")
 
 
+def sinkhorn_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, l, n_iter, gscale, gpred, loss_out):
+    """The step's Sinkhorn term (strotss_sinkhorn_cos_fwd_bwd_panels) for the prediction rows that
+    selfsim_fwd_bwd has just processed: their reciprocal norms and x3 panels come from that call's workspace, the style rows'
+    panels from `style_panels`.  Where the cost matrices run on the f32 MFMA (STROTSS_X3=0: the library hands out no panels)
+    or the StyleTarget has none, both panels are passed as NULL.  Unlike the relaxed EMD there is no plain call to fall back
+    to: rows other than those the content loss left its record for are an error."""
+    l_ = _hip.lib()
+    ld = pred.shape[1]
+    nb = l_.strotss_selfsim_workspace_bytes(n, ld)
+    ws = workspaces.get("selfsim", nb, pred.device)
+    if _selfsim_record != (ws.data_ptr(), nb, ptr(pred), n, int(ld), stream_ptr()):
+        raise _hip.StrotssHipError("sinkhorn_cos_fwd_bwd_after_selfsim: selfsim_fwd_bwd has not just run on these rows")
+    rp, xp = C.c_void_p(), C.c_void_p()
+    check(l_.strotss_selfsim_pred_panels(ptr(ws), nb, n, ld, C.byref(rp), C.byref(xp)), "selfsim_pred_panels")
+    both = style_panels is not None and bool(xp.value)
+    nbs = l_.strotss_sinkhorn_step_workspace_bytes(ns, n, int(n_iter))
+    wss = workspaces.get("sinkhorn_step", nbs, pred.device)
+    check(l_.strotss_sinkhorn_cos_fwd_bwd_panels(ptr(style), ptr(rs), ptr(style_panels) if both else None, ns, ptr(pred),
+                                                 rp.value, xp.value if both else None, n, d, ld, float(l), int(n_iter),
+                                                 float(gscale), ptr(gpred), ptr(loss_out), ptr(wss), nbs, stream_ptr()),
+          "sinkhorn_cos_fwd_bwd_panels")
+
+
 def sinkhorn_metric_fwd_bwd(style, ns, pred, n, d, metric: str, l, n_iter, gscale, gpred, loss_out):
     lib = _hip.lib()
     nb = lib.strotss_sinkhorn_metric_workspace_bytes(ns, n, n_iter)

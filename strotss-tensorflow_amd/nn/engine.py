@@ -69,6 +69,24 @@ class StyleBlend:
         self.weights = normalise_style_weights(self.weights)
 
 
+STYLE_TRANSPORTS = ("remd", "sinkhorn")
+SINKHORN_MAX_ITERS = 64
+DEFAULT_SINKHORN_L, DEFAULT_SINKHORN_ITERS = 10.0, 30
+
+
+def check_style_transport(style_transport, sinkhorn_l, sinkhorn_iters) -> None:
+    """ValueError unless the transport is a known one, sinkhorn_l finite and > 0 and sinkhorn_iters a whole number in
+    1..SINKHORN_MAX_ITERS (the library's range)"""
+    if style_transport not in STYLE_TRANSPORTS:
+        raise ValueError(f"style_transport must be one of {STYLE_TRANSPORTS}, got {style_transport!r}")
+    if isinstance(sinkhorn_l, bool) or not isinstance(sinkhorn_l, (int, float, np.integer, np.floating)) or \
+            not np.isfinite(sinkhorn_l) or sinkhorn_l <= 0:
+        raise ValueError(f"sinkhorn_l must be finite and > 0, got {sinkhorn_l!r}")
+    if isinstance(sinkhorn_iters, bool) or not isinstance(sinkhorn_iters, (int, np.integer)) or \
+            not 1 <= sinkhorn_iters <= SINKHORN_MAX_ITERS:
+        raise ValueError(f"sinkhorn_iters must be a whole number in 1..{SINKHORN_MAX_ITERS}, got {sinkhorn_iters!r}")
+
+
 @dataclass
 class TemporalTarget:
     """The temporal term of a frame sequence at one scale: `target` (h, w, 3) the warped previous
@@ -135,7 +153,12 @@ class StepEngine:
     `temporal`: a TemporalTarget at this scale's size: the pixel gradient gets lambda * dL_t/dx after the trunk (and the
     all-reduce) and before the fold adjoint, in ONE launch.  One GPU only, as the map above.  A
     sequence of 1..4 TemporalTargets (their certainties already combined, nearest frame first) adds
-    every term in ONE launch as well; one element is the TemporalTarget itself."""
+    every term in ONE launch as well; one element is the TemporalTarget itself.
+
+    `style_transport`: "remd" (the relaxed EMD) or "sinkhorn" (DESIGN.md section 20): the entropic transport cost
+    sinkhorn_knopp(target, prediction, 'cosine', sinkhorn_l, sinkhorn_iters) takes the place of the cosine relaxed EMD in
+    every region and for every style of a blend, with its weight and in its scalar slot (l_remd); the moment, palette and
+    content terms are unchanged.  One GPU only, as the map above."""
 
     N_SCALARS = 4   # loss_c, l_moment, l_remd, l_palette per region
 
@@ -144,8 +167,15 @@ class StepEngine:
                  loss_denom: float, lr: float, sample_size: int = 1024, levels: int = 5,
                  dist_group=None, rho: float = 0.99, eps: float = 1e-8, strips: Optional["parallel.StripPlan"] = None,
                  deterministic: Optional[bool] = None, content_weight: Optional[torch.Tensor] = None,
-                 temporal: Optional[Union[TemporalTarget, Sequence[TemporalTarget]]] = None):
+                 temporal: Optional[Union[TemporalTarget, Sequence[TemporalTarget]]] = None,
+                 style_transport: str = "remd", sinkhorn_l: float = DEFAULT_SINKHORN_L,
+                 sinkhorn_iters: int = DEFAULT_SINKHORN_ITERS):
         dev = stylized.device
+        check_style_transport(style_transport, sinkhorn_l, sinkhorn_iters)
+        if style_transport == "sinkhorn" and (strips is not None or dist_group is not None):
+            raise ValueError("the Sinkhorn style term runs on one GPU: image strips and region sharding are not supported "
+                             "with it")
+        self.style_transport, self.sinkhorn_l, self.sinkhorn_iters = style_transport, float(sinkhorn_l), int(sinkhorn_iters)
         self.params = params
         self.alpha, self.loss_denom, self.lr, self.rho, self.eps = float(alpha), float(loss_denom), float(lr), rho, eps
         self.inv_alpha = 1.0 / max(self.alpha, 1.0)
@@ -371,7 +401,8 @@ class StepEngine:
         cw = self._cw[r] if self._cw is not None else None     # the samples' content weights (content-weight map)
         # moment / REMD / palette: the region's own scalars for one style, one unweighted value per style of a blend
         outs = (sc[1:], sc[2:], sc[3:]) if len(targets) == 1 else tuple(self._style_scalars[r])
-        if self._style_sets[r] is not None and _ops.step_losses_available():
+        sinkhorn = self.style_transport == "sinkhorn"      # the separate entries, Sinkhorn where the cosine REMD stands
+        if not sinkhorn and self._style_sets[r] is not None and _ops.step_losses_available():
             # one call: 13 launches instead of 21, the three forward GEMMs in one of them (bit for bit the separate entries
             # below for one style); a blend in as many launches
             _ops.step_losses_cw_fwd_bwd(pf, cf, n, self.d, cw, self._style_sets[r], self.alpha * base, base, base,
@@ -381,9 +412,13 @@ class StepEngine:
         for k, (st, w) in enumerate(zip(targets, weights)):
             _ops.moment_fwd_bwd(st.mean, st.cov, pf, n, self.d, base * w, gp, outs[0][k:])
             # the relaxed EMD borrows the prediction rows' norms and x3 panels from the content loss's workspace (the moment
-            # term has its own) and the style rows' panels from the StyleTarget
-            _ops.remd_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, base * w, gp,
-                                                outs[1][k:])
+            # term has its own) and the style rows' panels from the StyleTarget; so does the Sinkhorn term
+            if sinkhorn:
+                _ops.sinkhorn_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, self.sinkhorn_l,
+                                                        self.sinkhorn_iters, base * w, gp, outs[1][k:])
+            else:
+                _ops.remd_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, base * w, gp,
+                                                    outs[1][k:])
             _ops.palette_remd_fwd_bwd(st.feats, st.ns, pf, n, self.inv_alpha * base * w, gp, outs[2][k:])
 
     def _scatter_maps(self, r: int):
@@ -686,6 +721,8 @@ class StepEngine:
         out = {"loss": float(loss), "loss_c": float(lc.mean()), "loss_s": float(ls.mean()),
                "l_moment": float(s[:, 1].mean()), "l_remd": float(s[:, 2].mean()),
                "l_palette": float(s[:, 3].mean())}
+        if self.style_transport == "sinkhorn":    # the slot of l_remd holds the Sinkhorn term: also under its own name
+            out["l_sinkhorn"] = out["l_remd"]
         if per_style is not None:
             out["per_style"] = per_style         # one dict per style of the blend: its weight and unweighted terms
         t = self._temporal

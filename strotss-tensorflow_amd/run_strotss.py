@@ -77,6 +77,17 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
                     content_mask_<frame stem>.png per frame, a region keeping its colour.
   --mask_inertia B  with --track_masks: what is added to the cosine of the prior label, 0..2 (default 0.05, not tuned); 0 is
                     the plain assignment to frame 1's centres, 2 never changes a label that has a prior
+  --style_transport {remd,sinkhorn}
+                    the transport term of the style loss.  remd (default): the relaxed EMD, every
+                    row matched to its nearest neighbour on each side.  sinkhorn: the entropic transport cost between the
+                    style's and the result's hypercolumns (cosine cost, uniform marginals, differentiated through the
+                    scalings), which conserves mass -- the style's features are matched in proportion -- and costs about
+                    60 more kernel launches per region and step.  Combines with masks, --style_mix, --content_weight_map
+                    and --video; one GPU, not with --strips.
+  --sinkhorn_reg L  with --style_transport sinkhorn: K = exp(-L * cost), finite and > 0 (default 10); larger is closer to
+                    the unregularised plan and needs more scalings
+  --sinkhorn_iters T
+                    with --style_transport sinkhorn: the number of scalings, 1..64 (default 30)
   --strips          under torchrun (one process per GPU): ONE image on all GPUs -- every rank runs the trunk on its strip
                     of the image (+ halo) at the scales where that pays, two all-reduces per step (nn/parallel.py);
                     rank 0 writes the output
@@ -207,6 +218,25 @@ def _preserve_color_input(args):
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise ValueError("--preserve_color runs on one GPU: not under torchrun with WORLD_SIZE > 1")
     return mode
+
+
+def _style_transport_input(args) -> dict:
+    """--style_transport, --sinkhorn_reg, --sinkhorn_iters: StepEngine's keywords for them.  ValueError, before anything is
+    loaded: an unknown transport, a regulariser or an iteration count without --style_transport sinkhorn or out of range,
+    and with sinkhorn --strips or WORLD_SIZE > 1."""
+    transport = getattr(args, "style_transport", None) or "remd"
+    reg, iters = getattr(args, "sinkhorn_reg", None), getattr(args, "sinkhorn_iters", None)
+    if transport != "sinkhorn" and (reg is not None or iters is not None):
+        raise ValueError("--sinkhorn_reg and --sinkhorn_iters need --style_transport sinkhorn")
+    reg = strotss_engine.DEFAULT_SINKHORN_L if reg is None else reg
+    iters = strotss_engine.DEFAULT_SINKHORN_ITERS if iters is None else iters
+    strotss_engine.check_style_transport(transport, reg, iters)
+    if transport == "sinkhorn":
+        if getattr(args, "strips", False):
+            raise ValueError("--style_transport sinkhorn cannot be combined with --strips")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise ValueError("--style_transport sinkhorn runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    return dict(style_transport=transport, sinkhorn_l=float(reg), sinkhorn_iters=int(iters))
 
 
 def _photo_smooth_input(args):
@@ -551,7 +581,7 @@ def _optimise_scale(eng, scl: int, content_masks, args, dev, quiet: bool = False
                 if (it + 1) % log_every == 0 or it + 1 == args.max_iter:
                     r = eng.losses()
                     bar.set_description(f"Scale: {scl:4d} - It: {it+1:4d}")
-                    bar.set_postfix({k: f'{r[k]:.3f}' for k in ('loss', 'loss_c', 'loss_s')})
+                    bar.set_postfix({k: f'{r[_LOGGED.get(k, k)]:.3f}' for k in _logged_terms(eng)})
         stream.skip(args.max_iter * len(masks_here))          # the host twin moves past the draws the device made
         return
     ring, slots = 8, {}
@@ -588,7 +618,16 @@ def _optimise_scale(eng, scl: int, content_masks, args, dev, quiet: bool = False
             if (it + 1) % log_every == 0 or it + 1 == args.max_iter:
                 r = eng.losses()
                 bar.set_description(f"Scale: {scl:4d} - It: {it+1:4d}")
-                bar.set_postfix({k: f'{r[k]:.3f}' for k in ('loss', 'loss_c', 'loss_s')})
+                bar.set_postfix({k: f'{r[_LOGGED.get(k, k)]:.3f}' for k in _logged_terms(eng)})
+
+
+_LOGGED = {"sinkhorn": "l_sinkhorn"}      # the log line's name of a term -> its key in StepEngine.losses()
+
+
+def _logged_terms(eng):
+    """the scalars of the log line: with --style_transport sinkhorn also the transport term, under its name"""
+    terms = ('loss', 'loss_c', 'loss_s')
+    return terms + ('sinkhorn',) if eng.style_transport == "sinkhorn" else terms
 
 
 def run(args: argparse.Namespace, trace=None):
@@ -596,6 +635,7 @@ def run(args: argparse.Namespace, trace=None):
     scale index and size, lr, alpha, loss_denom, the image the scale starts from, every step's losses and the
     result -- what the parity test of the schedule compares with the oracle's run_scales.  --video: run_video."""
     _auto_masks_input(args)                                  # refusals first, --video among them
+    _style_transport_input(args)
     if getattr(args, "video", False):
         return run_video(args, trace)
     timer = utils.Timer()
@@ -665,6 +705,7 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
     cw_map = strotss.load_content_weight_map(cw_path) if cw_path else None
     sampling = strotss.Sampling(SAMPLE_SIZE)
     masked = bool(getattr(args, "content_mask", None))
+    transport = _style_transport_input(args)
 
     # alpha = 16 (x3500 with Keras weights), halved after every scale -- also after skipped ones
     alpha = args.alpha * 16.0 * (3500 if args.use_keras_weight else 1) / 2.0 ** first
@@ -698,7 +739,8 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
             _style_targets(vgg.params, scl_style, style_masks, sampling, style_weights), stylized, alpha,
             loss_denom=2. + alpha + 1. / max(alpha, 1.), lr=lr, sample_size=SAMPLE_SIZE, strips=plan,
             dist_group=parallel.WORLD if (world > 1 and masked and plan is None) else None,
-            content_weight=(None if cw_map is None else strotss.content_weight_at_scale(cw_map, hs, ws)), temporal=tt)
+            content_weight=(None if cw_map is None else strotss.content_weight_at_scale(cw_map, hs, ws)), temporal=tt,
+            **transport)
         rec = None
         if trace is not None:
             rec = dict(i=i, scl=scl, lr=lr, alpha=alpha, loss_denom=eng.loss_denom, init=stylized.clone(), steps=[],
@@ -894,6 +936,15 @@ _FLAGS = (
     (("--mask_inertia",), dict(type=float, default=None, metavar='B',
                                help=f"with --track_masks: added to the cosine of a cell's prior label, 0..2 (default "
                                     f"{strotss.MASK_INERTIA:g})")),
+    (("--style_transport",), dict(type=str, default="remd", choices=strotss_engine.STYLE_TRANSPORTS,
+                                  help="the transport term of the style loss: the relaxed EMD, or the Sinkhorn transport cost "
+                                       "(mass-conserving, about 60 more launches per region and step)")),
+    (("--sinkhorn_reg",), dict(type=float, default=None, metavar='L',
+                               help=f"with --style_transport sinkhorn: K = exp(-L cost), > 0 (default "
+                                    f"{strotss_engine.DEFAULT_SINKHORN_L:g})")),
+    (("--sinkhorn_iters",), dict(type=int, default=None, metavar='T',
+                                 help=f"with --style_transport sinkhorn: scalings, 1..{strotss_engine.SINKHORN_MAX_ITERS} (default "
+                                      f"{strotss_engine.DEFAULT_SINKHORN_ITERS})")),
     (("--strips",), dict(action='store_true', help="under torchrun: shard ONE image over the GPUs by image strips")),
     (("--halo",), dict(action='store_true', help="with --strips: per-layer halo EXCHANGE with the neighbouring ranks (16-row "
                                                  "windows margins, one row per layer and direction) instead of a 128-row recompute margin")),
