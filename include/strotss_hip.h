@@ -319,14 +319,19 @@ int strotss_index_draw(const strotss_draw_t* d, void* stream);
  * --------------------------------------------------------------------------------------- */
 /* r[i] = rsqrt(max(sum_k x[i,k]^2, 1e-12)) for i < n  (tf.nn.l2_normalize, losses.py:13-14) */
 int strotss_row_inv_norm(const float* x, int n, int ld, float* r, void* stream);
-/* C[i,j] = 1 - <x_i,y_j> * rx[i]*ry[j], i < nx, j < ny   (losses.py:12-15) */
+/* C[i,j] = 1 - <x_i,y_j> * rx[i]*ry[j], i < nx, j < ny   (losses.py:12-15); C (nx, ldc) row-major, ldc >= ny.
+ * Output contract of this entry and of strotss_cosine_distance_x3, whatever the tile grid: exactly the elements of
+ * [0, nx) x [0, ny) are written, each once per launch (x == y: the entries below the diagonal are the mirrored copies of
+ * those above); the pad columns ny .. ldc - 1 of every row and everything past row nx - 1 are NEVER written -- a caller that
+ * reads them finds what it put there (tests/test_hip_tilegrid.py asserts it at every grid up to 16 x 33 tiles). */
 int strotss_cosine_distance(const float* x, const float* rx, int nx, const float* y,
                             const float* ry, int ny, int ld, float* C, int ldc, void* stream);
 /* The same two entry points on the bf16x3 GEMM core (csrc/mfma_x3.h): every f32 value is split EXACTLY into three
  * bf16 values, six exact partial products, f32 accumulation -- f32-class results at 6/16 of the f32-MFMA cost.
  * strotss_row_inv_norm_x3 also writes the rows as "x3 panels" (3 * n * ld bf16; element (i, k), plane p at
  * ((k/32 * 3 + p) * n + i) * 32 + k%32); r may be NULL.  strotss_cosine_distance_x3 takes the panels of x and y;
- * x == y gives an exactly symmetric matrix.  The loss entry points below use this core unless STROTSS_X3=0. */
+ * x == y gives an exactly symmetric matrix.  Same output contract as strotss_cosine_distance: [0, nx) x [0, ny) only, the
+ * pad columns and further rows untouched.  The loss entry points below use this core unless STROTSS_X3=0. */
 /* C[i][j] = sqrt(max(|x_i|^2 + |y_j|^2 - 2 x_i.y_j, 1e-6) / d)   (nn/losses.py:18-24, l2_distance); x (nx, ld), y (ny, ld)
  * row-major with columns >= d zero, ld % 32 == 0; C (nx, ldc); workspace: nx + ny floats. */
 int strotss_l2_distance(const float* x, int nx, const float* y, int ny, int d, int ld, float* C, int ldc,
