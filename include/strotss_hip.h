@@ -389,6 +389,28 @@ int strotss_sinkhorn_cos_fwd_bwd_panels(const float* style, const float* rs, con
                                         const float* pred_inv_norm, const void* pred_panels, int n, int d, int ld, float l,
                                         int n_iter, float gscale, float* gpred, float* loss_out, void* workspace,
                                         size_t workspace_bytes, void* stream);
+/* The sliced Wasserstein distance as the style term of a train step, with the prologue convention of
+ * strotss_sinkhorn_cos_fwd_bwd_panels (pred_inv_norm / pred_panels from the content loss's workspace, rs / style_panels made
+ * once per scale; both panels: projections on the bf16x3 core, both NULL: on the f32 MFMA from the rows, one of the two:
+ * STROTSS_EINVAL).  With xhat_i, shat_j the L2-normalised rows and n_proj sign directions eps_p in {-1, +1}^d,
+ *     a[p][i] = <eps_p, xhat_i>,  b[p][j] = <eps_p, shat_j>,  both sorted ascending by (value, row; -0 counts as +0),
+ *     W_p = sum_ij len_ij (a_(i) - b_(j))^2,  len_ij = max(0, min((i+1) ns, (j+1) n) - max(i ns, j n)) / (n ns),
+ *     loss_out[0] = sum_p W_p / (2 n_proj),   gpred += gscale * dloss/dpred (through the sort, piecewise constant, and
+ *     through the normalisation); rows >= n of gpred untouched, pad columns d .. ld-1 of rows < n receive +0.
+ * The sign of (direction p, feature k, draw t) is bit k & 31 of word (k >> 5) & 3 of
+ * philox4x32_10(ctr = (k >> 7, 2, t, p), key = (seed_lo, seed_hi)): 1 -> +1, 0 -> -1 (c1 = 2: disjoint from
+ * strotss_index_draw's blocks, c1 = 0, 1); columns k >= d of the direction matrix are zero.  nn/rand.py:sliced_signs is the
+ * host twin.  `counter`: one unsigned in device memory; the entry draws with t = *counter and its last kernel stores t + 1,
+ * so a captured graph draws fresh directions on every replay.  7 launches, no float atomics: the same bits on every call
+ * and stream for the same counter.  Refusals before any launch, outputs, workspace and counter untouched: STROTSS_EINVAL
+ * (null pointers, non-positive sizes, d > ld, one panel of the two, a workspace below strotss_sliced_workspace_bytes),
+ * STROTSS_EALIGN (ld % 32 != 0), STROTSS_ERANGE (n or ns above 1024, n_proj above 1024).  The query returns 0 for
+ * arguments the entry refuses. */
+size_t strotss_sliced_workspace_bytes(int ns, int n, int ld, int n_proj);
+int strotss_sliced_cos_fwd_bwd(const float* style, const float* rs, const void* style_panels, int ns, const float* pred,
+                               const float* pred_inv_norm, const void* pred_panels, int n, int d, int ld, int n_proj,
+                               unsigned seed_lo, unsigned seed_hi, unsigned* counter, float gscale, float* gpred,
+                               float* loss_out, void* workspace, size_t workspace_bytes, void* stream);
 /* ld = row stride of the feature matrices (strotss_remd_cos_fwd_bwd), 0 for strotss_palette_remd_fwd_bwd */
 /* The same with dist_metrics 'l2' (STROTSS_METRIC_L2) or 'both' (STROTSS_METRIC_BOTH) as the cost (losses.py:27-28): cost matrix
  * on the f32 MFMA with the distance in its epilogue, the scalings and their reverse sweep as above, the clamp of l2_distance

@@ -16,25 +16,13 @@
 // a bitonic network.  No global traffic besides the mask bytes and the 8 KB result.  Each wave owns a contiguous segment
 // of the candidate list (lane-consecutive addresses: conflict-free), positions under a mask come from ballots.
 #include "internal.h"
+#include "philox.h"
 
 namespace {
 
 constexpr int DRAW_T = 1024;
 constexpr int DRAW_MAXC = 32768;
 constexpr int DRAW_BINS = 2048;
-
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned out[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    const unsigned n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 
 // exclusive prefix over the 16 waves' values (one value per wave, in lane 0..15 of wave 0 after the first barrier);
 // returns this wave's exclusive prefix, *total = sum.  `sh` holds >= 17 unsigned.

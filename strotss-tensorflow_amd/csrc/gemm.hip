@@ -98,6 +98,16 @@ struct EpiScaleStore {  // C = alpha * acc   (batched: C += z * strideC)
   }
   __device__ __forceinline__ void finish(float*, float) const {}
 };
+struct EpiColScale {  // C = acc * rb[j]: rows of unit directions against rows normalised in the epilogue (sliced transport)
+  static constexpr bool SYMM = false;
+  const float* rb; float* C; int ldc; int M, N;
+  __device__ __forceinline__ void set_batch(int) {}
+  __device__ __forceinline__ float apply(int r, int c, float v) const {
+    if (r < M && c < N) C[(size_t)r * ldc + c] = v * rb[c];
+    return 0.f;
+  }
+  __device__ __forceinline__ void finish(float*, float) const {}
+};
 struct EpiAxpbyBias {  // C = alpha*acc + C + bias[c]
   static constexpr bool SYMM = false;
   float* C; int ldc; int M, N; float alpha; const float* bias; float bias_scale;
@@ -148,6 +158,19 @@ struct EpiSelfsimBwd {
     return 0.f;
   }
   __device__ __forceinline__ void finish(float*, float) const {}
+};
+
+// The same with the added value rounded on its own (no contraction into the sum): a call into a filled buffer gives, bit for
+// bit, the buffer's contents plus what a call into zeros gives
+struct EpiSelfsimBwdAdd : EpiSelfsimBwd {
+  __device__ __forceinline__ float apply(int row, int c, float v) const {
+    if (row < M && c < N) {
+      const size_t o = (size_t)row * ld + c;
+      const float ri = r[row];
+      dx[o] = __fadd_rn(dx[o], __fmul_rn(g * ri, v - x[o] * ri * q[row]));
+    }
+    return 0.f;
+  }
 };
 
 // Writes the transpose of this workgroup's BM x BN tile (values val(r, c)) to (c, r) through LDS so that the mirrored
@@ -346,6 +369,21 @@ int st_selfsim_bwd_gemm(const float* Mq, int ldm, int kpad, const float* bmat, c
                         const float* q, int n, int ld, float g, float* dx, hipStream_t s) {
   EpiSelfsimBwd e{x, r, q, dx, ld, n, ld, g};
   return launch<64, 64, true, false>(Mq, ldm, n, bmat, ld, ld, kpad, e, s);
+}
+
+// st_selfsim_bwd_gemm with the coefficient matrix stored TRANSPOSED, Mt (kpad x ldm, element (i, k) at Mt[k * ldm + i]; columns
+// n .. round_up(n, 4) - 1 and rows up to kpad hold zeros): the sliced transport's coefficients, written one direction a row
+int st_selfsim_bwd_gemm_tn(const float* Mt, int ldm, int kpad, const float* bmat, const float* x, const float* r,
+                           const float* q, int n, int ld, float g, float* dx, hipStream_t s) {
+  EpiSelfsimBwdAdd e{{x, r, q, dx, ld, n, ld, g}};
+  return launch<64, 64, false, false>(Mt, ldm, round_up(n, 4), bmat, ld, ld, kpad, e, s);
+}
+
+// C[p][j] = <e_p, y_j> ry[j] (np x ny, ldc): the projections of the normalised rows y on the rows of e (sliced transport)
+int st_rows_project(const float* e, int np, const float* y, const float* ry, int ny, int ld, float* C, int ldc,
+                    hipStream_t s) {
+  EpiColScale ep{ry, C, ldc, np, ny};
+  return launch_pipe<64, 64>(e, ld, np, 0, y, ld, ny, 0, ld, 1, ep, s);
 }
 
 // Batched C[z] (M x N, ldc) = A[z] (M x K, lda) * B[z]^T (N x K, ldb): the 16 / 36 Winograd-domain GEMMs.
@@ -740,6 +778,21 @@ int st_selfsim_bwd_x3(const void* Mp, int kpad, const void* Xt, const float* x, 
   dim3 grid((unsigned)cdiv(ld, 128) * cdiv(n, 128));
   hipLaunchKernelGGL((gemm_x3_kernel<Cfg, EpiSelfsimBwdX3, X3NoMirror>), grid, dim3(Cfg::NT), 0, s, (const __bf16*)Mp, n, 0LL,
                      (const __bf16*)Xt, ld, 0LL, kpad, e, X3NoMirror{});
+  ST_LAUNCH_RET();
+}
+
+// st_rows_project on x3 panels of e and y (64 x 64 tiles, the configuration of the cost matrices)
+struct EpiColScaleX3 : EpiColScale, X3NoPrefetch<EpiColScaleX3> {
+  using EpiColScale::apply;
+  using X3NoPrefetch<EpiColScaleX3>::apply;
+};
+int st_rows_project_x3(const void* ep, int np, const void* yp, const float* ry, int ny, int K, float* C, int ldc,
+                       hipStream_t s) {
+  using Cfg = X3Cfg<64>;
+  EpiColScaleX3 e{{ry, C, ldc, np, ny}, {}};
+  dim3 grid((unsigned)cdiv(ny, 64) * cdiv(np, 64));
+  hipLaunchKernelGGL((gemm_x3_kernel<Cfg, EpiColScaleX3, X3NoMirror>), grid, dim3(Cfg::NT), 0, s, (const __bf16*)ep, np, 0LL,
+                     (const __bf16*)yp, ny, 0LL, K, e, X3NoMirror{});
   ST_LAUNCH_RET();
 }
 

@@ -17,6 +17,11 @@ int st_moment_bwd_gemm(const float* cy, int n, int ld, const float* T, float alp
 int st_selfsim_bwd_gemm(const float* Mq, int ldm, int kpad, const float* bmat, const float* x, const float* r,
                         const float* q, int n, int ld, float g, float* dx, hipStream_t s);
 
+int st_selfsim_bwd_gemm_tn(const float* Mt, int ldm, int kpad, const float* bmat, const float* x, const float* r,
+                           const float* q, int n, int ld, float g, float* dx, hipStream_t s);
+int st_rows_project(const float* e, int np, const float* y, const float* ry, int ny, int ld, float* C, int ldc,
+                    hipStream_t s);
+
 int st_gemm_nt_batched(const float* A, int lda, long long strideA, const float* B, int ldb, long long strideB,
                        float* C, int ldc, long long strideC, int M, int N, int K, int batch, hipStream_t s);
 
@@ -34,6 +39,8 @@ int st_x3_split_rows(const float* x, int rows, int ld, int K, long long stride_i
 int st_cosine_distance_x3(const void* xp, const float* rx, int nx, const void* yp, const float* ry, int ny, int K,
                           int symm, float* C, int ldc, int batch, long long pstride, long long rstride,
                           long long cstride, hipStream_t s);
+int st_rows_project_x3(const void* ep, int np, const void* yp, const float* ry, int ny, int K, float* C, int ldc,
+                       hipStream_t s);
 int st_selfsim_bwd_x3(const void* Mp, int kpad, const void* Xt, const float* x, const float* r, const float* q, int n,
                       int ld, float g, float* dx, hipStream_t s);
 int st_gram_tn_x3(const void* Pt, int npad, int ld, float alpha, float* C, hipStream_t s);

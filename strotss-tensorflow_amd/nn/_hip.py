@@ -86,7 +86,7 @@ class FlowParamsT(C.Structure):
                 ("max_levels", C.c_int), ("iters_per_launch", C.c_int)]
 
 
-_P, _I, _F, _Z, _L = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
+_P, _I, _F, _Z, _L, _U = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64, C.c_uint
 # name -> (restype, argtypes); must list EVERY symbol include/strotss_hip.h declares
 SIGNATURES = {
     "strotss_abi_version": (_I, []),
@@ -142,6 +142,8 @@ SIGNATURES = {
     "strotss_sinkhorn_cos_fwd_bwd": (_I, [_P, _P, _I, _P, _I, _I, _I, _F, _I, _F, _P, _P, _P, _Z, _P]),
     "strotss_sinkhorn_step_workspace_bytes": (_Z, [_I, _I, _I]),
     "strotss_sinkhorn_cos_fwd_bwd_panels": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _F, _I, _F, _P, _P, _P, _Z, _P]),
+    "strotss_sliced_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "strotss_sliced_cos_fwd_bwd": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _U, _U, _P, _F, _P, _P, _P, _Z, _P]),
     "strotss_sinkhorn_metric_workspace_bytes": (_Z, [_I, _I, _I]),
     "strotss_sinkhorn_metric_fwd_bwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _F, _I, _F, _P, _P, _P, _Z, _P]),
     "strotss_remd_workspace_bytes": (_Z, [_I, _I, _I]),

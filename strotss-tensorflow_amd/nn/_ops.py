@@ -1031,6 +1031,31 @@ def sinkhorn_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, 
           "sinkhorn_cos_fwd_bwd_panels")
 
 
+def sliced_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, n_proj, seed, counter, gscale, gpred, loss_out):
+    """The step's sliced Wasserstein term (strotss_sliced_cos_fwd_bwd) for the prediction rows that
+    selfsim_fwd_bwd has just processed: their reciprocal norms and x3 panels come from that call's workspace, the style rows'
+    panels from `style_panels`; both panels are passed as NULL where the library hands out none (STROTSS_X3=0) or the
+    StyleTarget has none.  `counter`: one int32 on the device, the draw number of the directions; the call leaves it one
+    higher.  As for the Sinkhorn term, rows other than those the content loss left its record for are an error."""
+    l_ = _hip.lib()
+    ld = pred.shape[1]
+    assert counter.dtype == torch.int32 and counter.numel() >= 1 and counter.is_cuda
+    nb = l_.strotss_selfsim_workspace_bytes(n, ld)
+    ws = workspaces.get("selfsim", nb, pred.device)
+    if _selfsim_record != (ws.data_ptr(), nb, ptr(pred), n, int(ld), stream_ptr()):
+        raise _hip.StrotssHipError("sliced_cos_fwd_bwd_after_selfsim: selfsim_fwd_bwd has not just run on these rows")
+    rp, xp = C.c_void_p(), C.c_void_p()
+    check(l_.strotss_selfsim_pred_panels(ptr(ws), nb, n, ld, C.byref(rp), C.byref(xp)), "selfsim_pred_panels")
+    both = style_panels is not None and bool(xp.value)
+    nbs = l_.strotss_sliced_workspace_bytes(ns, n, ld, int(n_proj))
+    wss = workspaces.get("sliced_step", nbs, pred.device)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    check(l_.strotss_sliced_cos_fwd_bwd(ptr(style), ptr(rs), ptr(style_panels) if both else None, ns, ptr(pred), rp.value,
+                                        xp.value if both else None, n, d, ld, int(n_proj), seed & 0xFFFFFFFF, seed >> 32,
+                                        ptr(counter), float(gscale), ptr(gpred), ptr(loss_out), ptr(wss), nbs, stream_ptr()),
+          "sliced_cos_fwd_bwd")
+
+
 def sinkhorn_metric_fwd_bwd(style, ns, pred, n, d, metric: str, l, n_iter, gscale, gpred, loss_out):
     lib = _hip.lib()
     nb = lib.strotss_sinkhorn_metric_workspace_bytes(ns, n, n_iter)

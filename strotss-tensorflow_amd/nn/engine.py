@@ -69,14 +69,16 @@ class StyleBlend:
         self.weights = normalise_style_weights(self.weights)
 
 
-STYLE_TRANSPORTS = ("remd", "sinkhorn")
+STYLE_TRANSPORTS = ("remd", "sinkhorn", "sliced")
 SINKHORN_MAX_ITERS = 64
 DEFAULT_SINKHORN_L, DEFAULT_SINKHORN_ITERS = 10.0, 30
+SLICED_MAX_PROJECTIONS = 1024            # the library's range
+DEFAULT_SLICED_PROJECTIONS = 256         # not tuned for image quality: a quarter of the range, 7 launches whatever the count
 
 
-def check_style_transport(style_transport, sinkhorn_l, sinkhorn_iters) -> None:
-    """ValueError unless the transport is a known one, sinkhorn_l finite and > 0 and sinkhorn_iters a whole number in
-    1..SINKHORN_MAX_ITERS (the library's range)"""
+def check_style_transport(style_transport, sinkhorn_l, sinkhorn_iters, sliced_projections=DEFAULT_SLICED_PROJECTIONS) -> None:
+    """ValueError unless the transport is a known one, sinkhorn_l finite and > 0, sinkhorn_iters a whole number in
+    1..SINKHORN_MAX_ITERS and sliced_projections a whole number in 1..SLICED_MAX_PROJECTIONS (the library's ranges)"""
     if style_transport not in STYLE_TRANSPORTS:
         raise ValueError(f"style_transport must be one of {STYLE_TRANSPORTS}, got {style_transport!r}")
     if isinstance(sinkhorn_l, bool) or not isinstance(sinkhorn_l, (int, float, np.integer, np.floating)) or \
@@ -85,6 +87,10 @@ def check_style_transport(style_transport, sinkhorn_l, sinkhorn_iters) -> None:
     if isinstance(sinkhorn_iters, bool) or not isinstance(sinkhorn_iters, (int, np.integer)) or \
             not 1 <= sinkhorn_iters <= SINKHORN_MAX_ITERS:
         raise ValueError(f"sinkhorn_iters must be a whole number in 1..{SINKHORN_MAX_ITERS}, got {sinkhorn_iters!r}")
+    if isinstance(sliced_projections, bool) or not isinstance(sliced_projections, (int, np.integer)) or \
+            not 1 <= sliced_projections <= SLICED_MAX_PROJECTIONS:
+        raise ValueError(f"sliced_projections must be a whole number in 1..{SLICED_MAX_PROJECTIONS}, "
+                         f"got {sliced_projections!r}")
 
 
 @dataclass
@@ -158,7 +164,11 @@ class StepEngine:
     `style_transport`: "remd" (the relaxed EMD) or "sinkhorn" (DESIGN.md section 20): the entropic transport cost
     sinkhorn_knopp(target, prediction, 'cosine', sinkhorn_l, sinkhorn_iters) takes the place of the cosine relaxed EMD in
     every region and for every style of a blend, with its weight and in its scalar slot (l_remd); the moment, palette and
-    content terms are unchanged.  One GPU only, as the map above."""
+    content terms are unchanged.  One GPU only, as the map above.  "sliced" (DESIGN.md section 21): the sliced Wasserstein
+    distance between the L2-normalised rows over `sliced_projections` sign directions stands there instead, in the same slot
+    and with the same weight.  The directions of the engine's call number c (one call per region, style and step) are draw c
+    of the Philox stream with key `sliced_seed` (rand.sliced_signs); the draw number lives in device memory, so a captured
+    step draws fresh directions on every replay.  One GPU only."""
 
     N_SCALARS = 4   # loss_c, l_moment, l_remd, l_palette per region
 
@@ -169,13 +179,20 @@ class StepEngine:
                  deterministic: Optional[bool] = None, content_weight: Optional[torch.Tensor] = None,
                  temporal: Optional[Union[TemporalTarget, Sequence[TemporalTarget]]] = None,
                  style_transport: str = "remd", sinkhorn_l: float = DEFAULT_SINKHORN_L,
-                 sinkhorn_iters: int = DEFAULT_SINKHORN_ITERS):
+                 sinkhorn_iters: int = DEFAULT_SINKHORN_ITERS, sliced_projections: int = DEFAULT_SLICED_PROJECTIONS,
+                 sliced_seed: int = 0):
         dev = stylized.device
-        check_style_transport(style_transport, sinkhorn_l, sinkhorn_iters)
+        check_style_transport(style_transport, sinkhorn_l, sinkhorn_iters, sliced_projections)
         if style_transport == "sinkhorn" and (strips is not None or dist_group is not None):
             raise ValueError("the Sinkhorn style term runs on one GPU: image strips and region sharding are not supported "
                              "with it")
+        if style_transport == "sliced" and (strips is not None or dist_group is not None):
+            raise ValueError("the sliced style term runs on one GPU: image strips and region sharding are not supported "
+                             "with it")
         self.style_transport, self.sinkhorn_l, self.sinkhorn_iters = style_transport, float(sinkhorn_l), int(sinkhorn_iters)
+        self.sliced_projections, self.sliced_seed = int(sliced_projections), int(sliced_seed)
+        # the sliced term's draw number: call number c of this engine uses draw c (the entry leaves it one higher)
+        self._sliced_counter = torch.zeros(1, dtype=torch.int32, device=dev) if style_transport == "sliced" else None
         self.params = params
         self.alpha, self.loss_denom, self.lr, self.rho, self.eps = float(alpha), float(loss_denom), float(lr), rho, eps
         self.inv_alpha = 1.0 / max(self.alpha, 1.0)
@@ -402,7 +419,8 @@ class StepEngine:
         # moment / REMD / palette: the region's own scalars for one style, one unweighted value per style of a blend
         outs = (sc[1:], sc[2:], sc[3:]) if len(targets) == 1 else tuple(self._style_scalars[r])
         sinkhorn = self.style_transport == "sinkhorn"      # the separate entries, Sinkhorn where the cosine REMD stands
-        if not sinkhorn and self._style_sets[r] is not None and _ops.step_losses_available():
+        sliced = self.style_transport == "sliced"          # likewise
+        if not sinkhorn and not sliced and self._style_sets[r] is not None and _ops.step_losses_available():
             # one call: 13 launches instead of 21, the three forward GEMMs in one of them (bit for bit the separate entries
             # below for one style); a blend in as many launches
             _ops.step_losses_cw_fwd_bwd(pf, cf, n, self.d, cw, self._style_sets[r], self.alpha * base, base, base,
@@ -416,6 +434,10 @@ class StepEngine:
             if sinkhorn:
                 _ops.sinkhorn_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, self.sinkhorn_l,
                                                         self.sinkhorn_iters, base * w, gp, outs[1][k:])
+            elif sliced:
+                _ops.sliced_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d,
+                                                      self.sliced_projections, self.sliced_seed, self._sliced_counter,
+                                                      base * w, gp, outs[1][k:])
             else:
                 _ops.remd_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, base * w, gp,
                                                     outs[1][k:])
@@ -668,6 +690,8 @@ class StepEngine:
             return
         drawn = example_indices is None        # the draw kernel is the first node of the graph: nothing to upload per step
         state = self.variables + self.rms
+        if self._sliced_counter is not None:
+            state = state + [self._sliced_counter]         # the sliced term's draw number: likewise put back
         if drawn:
             assert self._draw is not None, "capture_graph() without indices needs enable_device_draw()"
             state = state + [self._draw["counters"]]       # warm-up and capture passes draw too: put the counters back
@@ -723,6 +747,8 @@ class StepEngine:
                "l_palette": float(s[:, 3].mean())}
         if self.style_transport == "sinkhorn":    # the slot of l_remd holds the Sinkhorn term: also under its own name
             out["l_sinkhorn"] = out["l_remd"]
+        if self.style_transport == "sliced":      # likewise the sliced term
+            out["l_sliced"] = out["l_remd"]
         if per_style is not None:
             out["per_style"] = per_style         # one dict per style of the blend: its weight and unweighted terms
         t = self._temporal

@@ -105,6 +105,20 @@ class PhiloxStream:
         self._k = 0
 
 
+def sliced_signs(seed: int, t: int, n_proj: int, d: int) -> np.ndarray:
+    """The host twin of the sliced transport's directions (strotss_sliced_cos_fwd_bwd): (n_proj, d)
+    float32 of +-1.  The sign of (direction p, feature k, draw t) is bit k & 31 of word (k >> 5) & 3 of
+    philox4x32_10(ctr = (k >> 7, 2, t, p), key = seed): 1 -> +1, 0 -> -1.  c1 = 2 keeps these blocks apart from the index
+    draw's (c1 = 0, 1: PhiloxStream)."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    n_proj, d = int(n_proj), int(d)
+    q = np.arange((d + 127) // 128, dtype=np.uint64)[None, :]
+    p = np.arange(n_proj, dtype=np.uint64)[:, None]
+    words = np.stack(philox4x32_10(q, 2, int(t) & 0xFFFFFFFF, p, seed & 0xFFFFFFFF, seed >> 32), axis=2)   # (P, blocks, 4)
+    bits = (words[..., None] >> np.arange(32, dtype=np.uint64)) & np.uint64(1)                             # (P, blocks, 4, 32)
+    return (2.0 * bits.reshape(n_proj, -1)[:, :d].astype(np.float32) - 1.0).astype(np.float32)
+
+
 SEED = 0
 np_rng = np.random.default_rng(SEED)          # reference: np_rng (unused there as well)
 index_rng = PhiloxStream(SEED)                # replaces tf_rng for the sampling coordinates

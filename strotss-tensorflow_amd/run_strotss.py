@@ -77,7 +77,7 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
                     content_mask_<frame stem>.png per frame, a region keeping its colour.
   --mask_inertia B  with --track_masks: what is added to the cosine of the prior label, 0..2 (default 0.05, not tuned); 0 is
                     the plain assignment to frame 1's centres, 2 never changes a label that has a prior
-  --style_transport {remd,sinkhorn}
+  --style_transport {remd,sinkhorn,sliced}
                     the transport term of the style loss.  remd (default): the relaxed EMD, every
                     row matched to its nearest neighbour on each side.  sinkhorn: the entropic transport cost between the
                     style's and the result's hypercolumns (cosine cost, uniform marginals, differentiated through the
@@ -88,6 +88,13 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
                     the unregularised plan and needs more scalings
   --sinkhorn_iters T
                     with --style_transport sinkhorn: the number of scalings, 1..64 (default 30)
+                    sliced: the sliced Wasserstein distance -- both sets of L2-normalised
+                    hypercolumns projected on P random sign directions (drawn on the device from --seed, fresh every step),
+                    sorted and matched by rank, which is the exact transport in one dimension: mass-conserving like
+                    sinkhorn, without a regulariser or an iteration count, in 7 launches per region and step.  Combines
+                    and excludes as sinkhorn does.
+  --sliced_projections P
+                    with --style_transport sliced: the number of directions, 1..1024 (default 256, not tuned)
   --strips          under torchrun (one process per GPU): ONE image on all GPUs -- every rank runs the trunk on its strip
                     of the image (+ halo) at the scales where that pays, two all-reduces per step (nn/parallel.py);
                     rank 0 writes the output
@@ -221,16 +228,32 @@ def _preserve_color_input(args):
 
 
 def _style_transport_input(args) -> dict:
-    """--style_transport, --sinkhorn_reg, --sinkhorn_iters: StepEngine's keywords for them.  ValueError, before anything is
-    loaded: an unknown transport, a regulariser or an iteration count without --style_transport sinkhorn or out of range,
-    and with sinkhorn --strips or WORLD_SIZE > 1."""
+    """--style_transport, --sinkhorn_reg, --sinkhorn_iters, --sliced_projections: StepEngine's keywords for them.  ValueError,
+    before anything is loaded: an unknown transport, a regulariser or an iteration count without --style_transport sinkhorn
+    or out of range, a projection count without --style_transport sliced or out of range, and with sinkhorn or sliced
+    --strips or WORLD_SIZE > 1."""
     transport = getattr(args, "style_transport", None) or "remd"
     reg, iters = getattr(args, "sinkhorn_reg", None), getattr(args, "sinkhorn_iters", None)
+    proj = getattr(args, "sliced_projections", None)
     if transport != "sinkhorn" and (reg is not None or iters is not None):
         raise ValueError("--sinkhorn_reg and --sinkhorn_iters need --style_transport sinkhorn")
+    if transport != "sliced" and proj is not None:
+        raise ValueError("--sliced_projections needs --style_transport sliced")
     reg = strotss_engine.DEFAULT_SINKHORN_L if reg is None else reg
     iters = strotss_engine.DEFAULT_SINKHORN_ITERS if iters is None else iters
+    proj = strotss_engine.DEFAULT_SLICED_PROJECTIONS if proj is None else proj
     strotss_engine.check_style_transport(transport, reg, iters)
+    if isinstance(proj, bool) or not isinstance(proj, (int, np.integer)) or \
+            not 1 <= proj <= strotss_engine.SLICED_MAX_PROJECTIONS:
+        raise ValueError(f"--sliced_projections must be a whole number in 1..{strotss_engine.SLICED_MAX_PROJECTIONS}, "
+                         f"got {proj!r}")
+    if transport == "sliced":
+        if getattr(args, "strips", False):
+            raise ValueError("--style_transport sliced cannot be combined with --strips")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise ValueError("--style_transport sliced runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+        return dict(style_transport=transport, sinkhorn_l=float(reg), sinkhorn_iters=int(iters),
+                    sliced_projections=int(proj), sliced_seed=int(getattr(args, "seed", 0) or 0))
     if transport == "sinkhorn":
         if getattr(args, "strips", False):
             raise ValueError("--style_transport sinkhorn cannot be combined with --strips")
@@ -621,13 +644,13 @@ def _optimise_scale(eng, scl: int, content_masks, args, dev, quiet: bool = False
                 bar.set_postfix({k: f'{r[_LOGGED.get(k, k)]:.3f}' for k in _logged_terms(eng)})
 
 
-_LOGGED = {"sinkhorn": "l_sinkhorn"}      # the log line's name of a term -> its key in StepEngine.losses()
+_LOGGED = {"sinkhorn": "l_sinkhorn", "sliced": "l_sliced"}      # the log line's name of a term -> its key in StepEngine.losses()
 
 
 def _logged_terms(eng):
-    """the scalars of the log line: with --style_transport sinkhorn also the transport term, under its name"""
+    """the scalars of the log line: with --style_transport sinkhorn or sliced also the transport term, under its name"""
     terms = ('loss', 'loss_c', 'loss_s')
-    return terms + ('sinkhorn',) if eng.style_transport == "sinkhorn" else terms
+    return terms + (eng.style_transport,) if eng.style_transport in _LOGGED else terms
 
 
 def run(args: argparse.Namespace, trace=None):
@@ -937,14 +960,18 @@ _FLAGS = (
                                help=f"with --track_masks: added to the cosine of a cell's prior label, 0..2 (default "
                                     f"{strotss.MASK_INERTIA:g})")),
     (("--style_transport",), dict(type=str, default="remd", choices=strotss_engine.STYLE_TRANSPORTS,
-                                  help="the transport term of the style loss: the relaxed EMD, or the Sinkhorn transport cost "
-                                       "(mass-conserving, about 60 more launches per region and step)")),
+                                  help="the transport term of the style loss: the relaxed EMD, the Sinkhorn transport cost "
+                                       "(mass-conserving, about 60 more launches per region and step) or the sliced "
+                                       "Wasserstein distance (mass-conserving, sort and match on random sign directions)")),
     (("--sinkhorn_reg",), dict(type=float, default=None, metavar='L',
                                help=f"with --style_transport sinkhorn: K = exp(-L cost), > 0 (default "
                                     f"{strotss_engine.DEFAULT_SINKHORN_L:g})")),
     (("--sinkhorn_iters",), dict(type=int, default=None, metavar='T',
                                  help=f"with --style_transport sinkhorn: scalings, 1..{strotss_engine.SINKHORN_MAX_ITERS} (default "
                                       f"{strotss_engine.DEFAULT_SINKHORN_ITERS})")),
+    (("--sliced_projections",), dict(type=int, default=None, metavar='P',
+                                     help=f"with --style_transport sliced: directions, 1..{strotss_engine.SLICED_MAX_PROJECTIONS} "
+                                          f"(default {strotss_engine.DEFAULT_SLICED_PROJECTIONS}, not tuned)")),
     (("--strips",), dict(action='store_true', help="under torchrun: shard ONE image over the GPUs by image strips")),
     (("--halo",), dict(action='store_true', help="with --strips: per-layer halo EXCHANGE with the neighbouring ranks (16-row "
                                                  "windows margins, one row per layer and direction) instead of a 128-row recompute margin")),
