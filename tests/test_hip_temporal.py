@@ -93,7 +93,11 @@ def test_flow_warp_shapes_channels_borders_and_non_finite_flows(hw):
 
 
 # ------------------------------------------------------------------ 2. the term of one step
-@pytest.mark.parametrize("hw", [(64, 64), (42, 63), (257, 300), (1, 3)])
+BIG = (513, 513)        # 263169 pixels: 257 full workgroups and one of a single pixel -- 258 partial sums, so the last
+                        # workgroup's loop over them (256 per trip) makes a second trip, for partials 256 and 257
+
+
+@pytest.mark.parametrize("hw", [(64, 64), (42, 63), (257, 300), (1, 3), BIG])
 def test_temporal_fwd_bwd_matches_float64(hw):
     from nn import _ops
     h, w = hw
@@ -101,6 +105,8 @@ def test_temporal_fwd_bwd_matches_float64(hw):
     x, tgt = rng.random((h, w, 3)), rng.random((h, w, 3))
     c = rng.random((h, w))
     c[rng.random((h, w)) < 0.3] = 0.0
+    if hw == BIG:       # the last pixel (the last partial's only one): full certainty and the image's largest difference
+        x[-1, -1], tgt[-1, -1], c[-1, -1] = 1.0, 0.0, 1.0
     g0 = rng.standard_normal((h, w, 3)).astype(np.float32) * 1e-3
     lam = 3.5
     g = _dev(g0)
@@ -111,6 +117,10 @@ def test_temporal_fwd_bwd_matches_float64(hw):
     ref_l, ref_g = T.temporal_loss64(xd.cpu().double().numpy(), td.cpu().double().numpy(), cd.cpu().double().numpy())
     ref_g = g0.astype(np.float64) + lam * ref_g
     assert abs(loss.item() - ref_l) <= 1e-5 * abs(ref_l)
+    if hw == BIG:       # on the host, from the float64 reference: without that pixel's term the loss FAILS the bound, so a
+        dropped = ref_l - 1.0 * 3.0 / (3 * h * w)                   # dropped last partial cannot hide inside 1e-5
+        assert -(-h * w // 1024) == 258
+        assert abs(loss.item() - dropped) > 1e-5 * abs(dropped), (loss.item(), dropped)
     got = g.cpu().double().numpy()
     assert float(np.abs(got - ref_g).max()) <= 1e-5 * float(np.abs(ref_g).max())
     assert np.array_equal(got[c == 0], g0[c == 0].astype(np.float64))        # no certainty: untouched

@@ -74,11 +74,18 @@ def _multi(xd, tds, cds, gs, g, loss, ws=None):
     return ws
 
 
-@pytest.mark.parametrize("hw", [(64, 64), (42, 63), (257, 300), (1, 3)])
+BIG = (513, 513)        # 263169 pixels = 258 workgroups: the last-arriving one sums partials 256 and 257 on a second trip
+
+
+@pytest.mark.parametrize("hw", [(64, 64), (42, 63), (257, 300), (1, 3), BIG])
 @pytest.mark.parametrize("count", [2, 3, 4])
 def test_multi_fwd_bwd_matches_float64(hw, count):
     h, w = hw
     x, tg, cs, g0 = _multi_inputs(h, w, count, h + w + count)
+    if hw == BIG:       # the last pixel (the last partial's only one): full certainty and the image's largest difference
+        x[-1, -1] = 1.0
+        for t, c in zip(tg, cs):
+            t[-1, -1], c[-1, -1] = 0.0, 1.0
     gs = [3.5, 0.75, 12.0, 2.0][:count]
     xd, tds, cds = _dev(x), [_dev(t) for t in tg], [_dev(c) for c in cs]
     g = _dev(g0)
@@ -91,6 +98,9 @@ def test_multi_fwd_bwd_matches_float64(hw, count):
     got_l = loss.cpu().double().numpy()
     for j in range(count):
         assert abs(got_l[j] - ref_l[j]) <= 1e-5 * abs(ref_l[j]), (j, got_l[j], ref_l[j])
+        if hw == BIG:   # on the host, from the float64 reference: without that pixel's term the loss FAILS the bound, so
+            dropped = ref_l[j] - 1.0 * 3.0 / (3 * h * w)            # a dropped last partial cannot hide inside 1e-5
+            assert abs(got_l[j] - dropped) > 1e-5 * abs(dropped), (j, got_l[j], dropped)
     got = g.cpu().double().numpy()
     assert float(np.abs(got - ref_g).max()) <= 1e-5 * float(np.abs(ref_g).max())
     none = np.all([c == 0 for c in cs], axis=0)                  # no certainty for any j: untouched
