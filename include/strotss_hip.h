@@ -389,6 +389,23 @@ int strotss_sinkhorn_cos_fwd_bwd_panels(const float* style, const float* rs, con
                                         const float* pred_inv_norm, const void* pred_panels, int n, int d, int ld, float l,
                                         int n_iter, float gscale, float* gpred, float* loss_out, void* workspace,
                                         size_t workspace_bytes, void* stream);
+/* The Sinkhorn term of a train step in the log domain: strotss_sinkhorn_cos_fwd_bwd_panels with the
+ * scalings kept as phi = log u, psi = log v, so that neither exp(-l M) nor a clamp exists and the term stays a transport
+ * cost where the plan is sharp.  With M the cosine distance, px = 1 / ns, py = 1 / n, psi_0 = 0 and LSE the max-shifted
+ * log-sum-exp, n_iter times:
+ *     phi[i] = log px - LSE_j(psi[j] - l M[i][j]),   psi[j] = log py - LSE_i(phi[i] - l M[i][j]),
+ *     loss = sum_ij exp(phi[i] + psi[j] - l M[i][j]) M[i][j],
+ * and gpred += gscale * dloss/dpred through all the iterations.  Where the linear form engages no clamp the two are the same
+ * function.  Arguments, panels and determinism as strotss_sinkhorn_cos_fwd_bwd_panels.  Refusals before any launch, outputs
+ * and workspace untouched: STROTSS_EINVAL (null pointers, sizes, one panel of the two, a workspace below
+ * strotss_sinkhorn_log_step_workspace_bytes), STROTSS_EALIGN (ld % 32 != 0), STROTSS_ERANGE (l not in (0, 1000]: the f32
+ * exponent psi - l M carries about 2 l 2^-24 of absolute error, 1e-4 at 1000; n_iter outside 1..64).  The bytes entry
+ * returns 0 for arguments the call would refuse. */
+size_t strotss_sinkhorn_log_step_workspace_bytes(int ns, int n, int n_iter);
+int strotss_sinkhorn_log_cos_fwd_bwd_panels(const float* style, const float* rs, const void* style_panels, int ns,
+                                            const float* pred, const float* pred_inv_norm, const void* pred_panels, int n, int d,
+                                            int ld, float l, int n_iter, float gscale, float* gpred, float* loss_out,
+                                            void* workspace, size_t workspace_bytes, void* stream);
 /* The sliced Wasserstein distance as the style term of a train step, with the prologue convention of
  * strotss_sinkhorn_cos_fwd_bwd_panels (pred_inv_norm / pred_panels from the content loss's workspace, rs / style_panels made
  * once per scale; both panels: projections on the bf16x3 core, both NULL: on the f32 MFMA from the rows, one of the two:

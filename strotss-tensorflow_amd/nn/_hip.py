@@ -142,6 +142,8 @@ SIGNATURES = {
     "strotss_sinkhorn_cos_fwd_bwd": (_I, [_P, _P, _I, _P, _I, _I, _I, _F, _I, _F, _P, _P, _P, _Z, _P]),
     "strotss_sinkhorn_step_workspace_bytes": (_Z, [_I, _I, _I]),
     "strotss_sinkhorn_cos_fwd_bwd_panels": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _F, _I, _F, _P, _P, _P, _Z, _P]),
+    "strotss_sinkhorn_log_step_workspace_bytes": (_Z, [_I, _I, _I]),
+    "strotss_sinkhorn_log_cos_fwd_bwd_panels": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _F, _I, _F, _P, _P, _P, _Z, _P]),
     "strotss_sliced_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "strotss_sliced_cos_fwd_bwd": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _U, _U, _P, _F, _P, _P, _P, _Z, _P]),
     "strotss_sinkhorn_metric_workspace_bytes": (_Z, [_I, _I, _I]),

@@ -1031,6 +1031,30 @@ def sinkhorn_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, 
           "sinkhorn_cos_fwd_bwd_panels")
 
 
+def sinkhorn_log_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, l, n_iter, gscale, gpred, loss_out):
+    """The step's Sinkhorn term in the log domain (strotss_sinkhorn_log_cos_fwd_bwd_panels), called as
+    sinkhorn_cos_fwd_bwd_after_selfsim is: the prediction rows' norms and x3 panels from the content loss's workspace, both
+    panels NULL where the library hands out none or the StyleTarget has none, and rows other than those the content loss
+    left its record for an error."""
+    l_ = _hip.lib()
+    ld = pred.shape[1]
+    nb = l_.strotss_selfsim_workspace_bytes(n, ld)
+    ws = workspaces.get("selfsim", nb, pred.device)
+    if _selfsim_record != (ws.data_ptr(), nb, ptr(pred), n, int(ld), stream_ptr()):
+        raise _hip.StrotssHipError("sinkhorn_log_cos_fwd_bwd_after_selfsim: selfsim_fwd_bwd has not just run on these rows")
+    rp, xp = C.c_void_p(), C.c_void_p()
+    check(l_.strotss_selfsim_pred_panels(ptr(ws), nb, n, ld, C.byref(rp), C.byref(xp)), "selfsim_pred_panels")
+    both = style_panels is not None and bool(xp.value)
+    nbs = l_.strotss_sinkhorn_log_step_workspace_bytes(ns, n, int(n_iter))
+    if nbs == 0:
+        raise _hip.StrotssHipError(f"sinkhorn_log_cos_fwd_bwd_after_selfsim: invalid sizes ns={ns} n={n} n_iter={n_iter}")
+    wss = workspaces.get("sinkhorn_log_step", nbs, pred.device)
+    check(l_.strotss_sinkhorn_log_cos_fwd_bwd_panels(ptr(style), ptr(rs), ptr(style_panels) if both else None, ns, ptr(pred),
+                                                     rp.value, xp.value if both else None, n, d, ld, float(l), int(n_iter),
+                                                     float(gscale), ptr(gpred), ptr(loss_out), ptr(wss), nbs, stream_ptr()),
+          "sinkhorn_log_cos_fwd_bwd_panels")
+
+
 def sliced_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, n_proj, seed, counter, gscale, gpred, loss_out):
     """The step's sliced Wasserstein term (strotss_sliced_cos_fwd_bwd) for the prediction rows that
     selfsim_fwd_bwd has just processed: their reciprocal norms and x3 panels come from that call's workspace, the style rows'

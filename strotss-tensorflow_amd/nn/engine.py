@@ -72,13 +72,16 @@ class StyleBlend:
 STYLE_TRANSPORTS = ("remd", "sinkhorn", "sliced")
 SINKHORN_MAX_ITERS = 64
 DEFAULT_SINKHORN_L, DEFAULT_SINKHORN_ITERS = 10.0, 30
+SINKHORN_LOG_MAX_L = 1000.0              # the log-domain entry's range: its f32 exponent carries 2 L 2^-24 of absolute error
 SLICED_MAX_PROJECTIONS = 1024            # the library's range
 DEFAULT_SLICED_PROJECTIONS = 256         # not tuned for image quality: a quarter of the range, 7 launches whatever the count
 
 
-def check_style_transport(style_transport, sinkhorn_l, sinkhorn_iters, sliced_projections=DEFAULT_SLICED_PROJECTIONS) -> None:
+def check_style_transport(style_transport, sinkhorn_l, sinkhorn_iters, sliced_projections=DEFAULT_SLICED_PROJECTIONS,
+                          sinkhorn_log=False) -> None:
     """ValueError unless the transport is a known one, sinkhorn_l finite and > 0, sinkhorn_iters a whole number in
-    1..SINKHORN_MAX_ITERS and sliced_projections a whole number in 1..SLICED_MAX_PROJECTIONS (the library's ranges)"""
+    1..SINKHORN_MAX_ITERS and sliced_projections a whole number in 1..SLICED_MAX_PROJECTIONS (the library's ranges);
+    sinkhorn_log goes with "sinkhorn" only, and with sinkhorn_l <= SINKHORN_LOG_MAX_L"""
     if style_transport not in STYLE_TRANSPORTS:
         raise ValueError(f"style_transport must be one of {STYLE_TRANSPORTS}, got {style_transport!r}")
     if isinstance(sinkhorn_l, bool) or not isinstance(sinkhorn_l, (int, float, np.integer, np.floating)) or \
@@ -91,6 +94,12 @@ def check_style_transport(style_transport, sinkhorn_l, sinkhorn_iters, sliced_pr
             not 1 <= sliced_projections <= SLICED_MAX_PROJECTIONS:
         raise ValueError(f"sliced_projections must be a whole number in 1..{SLICED_MAX_PROJECTIONS}, "
                          f"got {sliced_projections!r}")
+    if not isinstance(sinkhorn_log, (bool, np.bool_)):
+        raise ValueError(f"sinkhorn_log must be True or False, got {sinkhorn_log!r}")
+    if sinkhorn_log and style_transport != "sinkhorn":
+        raise ValueError(f"sinkhorn_log needs style_transport 'sinkhorn', got {style_transport!r}")
+    if sinkhorn_log and sinkhorn_l > SINKHORN_LOG_MAX_L:
+        raise ValueError(f"sinkhorn_l must be at most {SINKHORN_LOG_MAX_L:g} with sinkhorn_log, got {sinkhorn_l!r}")
 
 
 @dataclass
@@ -168,7 +177,11 @@ class StepEngine:
     distance between the L2-normalised rows over `sliced_projections` sign directions stands there instead, in the same slot
     and with the same weight.  The directions of the engine's call number c (one call per region, style and step) are draw c
     of the Philox stream with key `sliced_seed` (rand.sliced_signs); the draw number lives in device memory, so a captured
-    step draws fresh directions on every replay.  One GPU only."""
+    step draws fresh directions on every replay.  One GPU only.
+
+    `sinkhorn_log` (with "sinkhorn" only): the same term with the scalings kept as logarithms, which
+    stays a transport cost where exp(-sinkhorn_l * cost) underflows and the linear form's clamps act (it is guaranteed
+    clamp-free only to sinkhorn_l = 13.8); sinkhorn_l up to SINKHORN_LOG_MAX_L.  False runs the linear form unchanged."""
 
     N_SCALARS = 4   # loss_c, l_moment, l_remd, l_palette per region
 
@@ -180,9 +193,10 @@ class StepEngine:
                  temporal: Optional[Union[TemporalTarget, Sequence[TemporalTarget]]] = None,
                  style_transport: str = "remd", sinkhorn_l: float = DEFAULT_SINKHORN_L,
                  sinkhorn_iters: int = DEFAULT_SINKHORN_ITERS, sliced_projections: int = DEFAULT_SLICED_PROJECTIONS,
-                 sliced_seed: int = 0):
+                 sliced_seed: int = 0, sinkhorn_log: bool = False):
         dev = stylized.device
-        check_style_transport(style_transport, sinkhorn_l, sinkhorn_iters, sliced_projections)
+        check_style_transport(style_transport, sinkhorn_l, sinkhorn_iters, sliced_projections, sinkhorn_log)
+        self.sinkhorn_log = bool(sinkhorn_log)
         if style_transport == "sinkhorn" and (strips is not None or dist_group is not None):
             raise ValueError("the Sinkhorn style term runs on one GPU: image strips and region sharding are not supported "
                              "with it")
@@ -432,8 +446,9 @@ class StepEngine:
             # the relaxed EMD borrows the prediction rows' norms and x3 panels from the content loss's workspace (the moment
             # term has its own) and the style rows' panels from the StyleTarget; so does the Sinkhorn term
             if sinkhorn:
-                _ops.sinkhorn_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, self.sinkhorn_l,
-                                                        self.sinkhorn_iters, base * w, gp, outs[1][k:])
+                term = _ops.sinkhorn_log_cos_fwd_bwd_after_selfsim if self.sinkhorn_log else _ops.sinkhorn_cos_fwd_bwd_after_selfsim
+                term(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, self.sinkhorn_l, self.sinkhorn_iters, base * w, gp,
+                     outs[1][k:])
             elif sliced:
                 _ops.sliced_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d,
                                                       self.sliced_projections, self.sliced_seed, self._sliced_counter,

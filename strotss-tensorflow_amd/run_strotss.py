@@ -88,6 +88,9 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
                     the unregularised plan and needs more scalings
   --sinkhorn_iters T
                     with --style_transport sinkhorn: the number of scalings, 1..64 (default 30)
+  --sinkhorn_log    with --style_transport sinkhorn: the scalings in the log domain, for sharp plans:
+                    the linear form is guaranteed free of its clamps only to --sinkhorn_reg 13.8, above it exp(-L * cost)
+                    underflows and rows lose their gradient silently; this form has neither, for --sinkhorn_reg in (0, 1000]
                     sliced: the sliced Wasserstein distance -- both sets of L2-normalised
                     hypercolumns projected on P random sign directions (drawn on the device from --seed, fresh every step),
                     sorted and matched by rank, which is the exact transport in one dimension: mass-conserving like
@@ -228,21 +231,25 @@ def _preserve_color_input(args):
 
 
 def _style_transport_input(args) -> dict:
-    """--style_transport, --sinkhorn_reg, --sinkhorn_iters, --sliced_projections: StepEngine's keywords for them.  ValueError,
-    before anything is loaded: an unknown transport, a regulariser or an iteration count without --style_transport sinkhorn
-    or out of range, a projection count without --style_transport sliced or out of range, and with sinkhorn or sliced
-    --strips or WORLD_SIZE > 1."""
+    """--style_transport, --sinkhorn_reg, --sinkhorn_iters, --sinkhorn_log, --sliced_projections: StepEngine's keywords for
+    them (sinkhorn_log only where the flag is given).  ValueError, before anything is loaded: an unknown transport, a
+    regulariser, an iteration count or --sinkhorn_log without --style_transport sinkhorn or out of range (--sinkhorn_log:
+    --sinkhorn_reg above 1000), a projection count without --style_transport sliced or out of range, and with sinkhorn or
+    sliced --strips or WORLD_SIZE > 1."""
     transport = getattr(args, "style_transport", None) or "remd"
     reg, iters = getattr(args, "sinkhorn_reg", None), getattr(args, "sinkhorn_iters", None)
     proj = getattr(args, "sliced_projections", None)
     if transport != "sinkhorn" and (reg is not None or iters is not None):
         raise ValueError("--sinkhorn_reg and --sinkhorn_iters need --style_transport sinkhorn")
+    log = bool(getattr(args, "sinkhorn_log", False))
+    if log and transport != "sinkhorn":
+        raise ValueError("--sinkhorn_log needs --style_transport sinkhorn")
     if transport != "sliced" and proj is not None:
         raise ValueError("--sliced_projections needs --style_transport sliced")
     reg = strotss_engine.DEFAULT_SINKHORN_L if reg is None else reg
     iters = strotss_engine.DEFAULT_SINKHORN_ITERS if iters is None else iters
     proj = strotss_engine.DEFAULT_SLICED_PROJECTIONS if proj is None else proj
-    strotss_engine.check_style_transport(transport, reg, iters)
+    strotss_engine.check_style_transport(transport, reg, iters, sinkhorn_log=log)
     if isinstance(proj, bool) or not isinstance(proj, (int, np.integer)) or \
             not 1 <= proj <= strotss_engine.SLICED_MAX_PROJECTIONS:
         raise ValueError(f"--sliced_projections must be a whole number in 1..{strotss_engine.SLICED_MAX_PROJECTIONS}, "
@@ -259,7 +266,8 @@ def _style_transport_input(args) -> dict:
             raise ValueError("--style_transport sinkhorn cannot be combined with --strips")
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise ValueError("--style_transport sinkhorn runs on one GPU: not under torchrun with WORLD_SIZE > 1")
-    return dict(style_transport=transport, sinkhorn_l=float(reg), sinkhorn_iters=int(iters))
+    kw = dict(style_transport=transport, sinkhorn_l=float(reg), sinkhorn_iters=int(iters))
+    return dict(kw, sinkhorn_log=True) if log else kw
 
 
 def _photo_smooth_input(args):
@@ -969,6 +977,10 @@ _FLAGS = (
     (("--sinkhorn_iters",), dict(type=int, default=None, metavar='T',
                                  help=f"with --style_transport sinkhorn: scalings, 1..{strotss_engine.SINKHORN_MAX_ITERS} (default "
                                       f"{strotss_engine.DEFAULT_SINKHORN_ITERS})")),
+    (("--sinkhorn_log",), dict(action='store_true',
+                               help=f"with --style_transport sinkhorn: the scalings in the log domain, for sharp plans; "
+                                    f"--sinkhorn_reg in (0, {strotss_engine.SINKHORN_LOG_MAX_L:g}] (the linear form is "
+                                    f"clamp-free only to 13.8)")),
     (("--sliced_projections",), dict(type=int, default=None, metavar='P',
                                      help=f"with --style_transport sliced: directions, 1..{strotss_engine.SLICED_MAX_PROJECTIONS} "
                                           f"(default {strotss_engine.DEFAULT_SLICED_PROJECTIONS}, not tuned)")),
