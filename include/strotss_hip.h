@@ -654,6 +654,47 @@ int strotss_color_affine(const float* img, const float* weight, int h, int w, co
 int strotss_luma_merge(const float* result, const float* content, int h, int w, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Colour distribution transfer: iterative distribution transfer after Pitie, Kokaram and Dahyot (2007)
+ * --------------------------------------------------------------------------------------- */
+/* Images and weight planes as above; a pixel COUNTS when its weight is != 0 (NULL: every pixel).  A basis is a row-major
+ * 3 x 3 float32 matrix R whose COLUMNS are the axes, in HOST memory, read during the call; a set of bases is n_bases of them
+ * back to back.  Axis k of R has the range [lo, hi], computed in double from the float32 R: with lo0 = sum_i min(R_ik, 0) and
+ * hi0 = sum_i max(R_ik, 0) (the unit cube's projection), lo = (lo0 + hi0)/2 - (hi0 - lo0), hi = (lo0 + hi0)/2 + (hi0 - lo0);
+ * lo, hi and scale = bins / (hi - lo) are rounded to float32 once.  A pixel x has, in float32,
+ *   u_k = R_0k x_0 + R_1k x_1 + R_2k x_2 (three fused multiply-adds, left to right),  ub = clamp(u_k, lo, hi) (NaN -> lo),
+ *   pos = (ub - lo) * scale,  bin j = min(int(pos), bins - 1).
+ * Counts are uint32 under integer atomics (LDS, then global memory): the same bits on every run.
+ * The three entries refuse, before anything is launched: STROTSS_EINVAL for a null required pointer, h or w <= 0,
+ * 3 h w > INT_MAX, bins outside 2..4096, n_bases outside 1..64, a basis that is not finite or not orthonormal to
+ * max |R^T R - I| <= 1e-4, exactly one of next_basis / next_hist being NULL; STROTSS_EALIGN for a device pointer that is not
+ * 16-byte aligned. */
+/* the number of bases whose histograms one workgroup of strotss_color_hist holds in LDS: clamp(15360 / (3 bins), 1, 8),
+ * 60 KiB of counters at the most (two workgroups per CU); 0 for bins outside 2..4096 */
+int strotss_color_hist_group(int bins);
+/* hist (n_bases, 3, bins) uint32 = the histograms of the counted pixels' projections on every axis of every basis, in ONE
+ * kernel launch behind a memset of hist on the same stream (the call clears hist itself).  The image is read once per
+ * group of strotss_color_hist_group(bins) bases. */
+int strotss_color_hist(const float* img, const float* weight, int h, int w, const float* bases, int n_bases, int bins,
+                       unsigned* hist, void* stream);
+/* table (3, bins + 1) float32, one entry per bin edge of each axis, from the (3, bins) histograms of the source and of
+ * the target on `basis`; one workgroup per axis, prefix sums in integers.  With S_j, C_i the exclusive cumulative counts
+ * and N_s, N_c the totals (each <= INT_MAX / 3, so that the 64-bit products are exact): a = S_j N_c; i = the smallest
+ * target bin with hist_dst[i] > 0 and C_{i+1} N_s >= a (a == 0: the first target bin that is not empty);
+ * frac = double(a - C_i N_s) / double(hist_dst[i] N_s); table[j] = lo + (i + frac) (hi - lo) / bins in double with the
+ * unrounded lo and hi, rounded to float32 once.  Non-decreasing.  Either histogram all zero: the identity
+ * table[j] = lo + j (hi - lo) / bins.  Totals above INT_MAX / 3 give unspecified finite-or-not VALUES, never a division by
+ * zero or an index out of range. */
+int strotss_color_transfer_table(const unsigned* hist_src, const unsigned* hist_dst, const float* basis, int bins,
+                                 float* table, void* stream);
+/* For every counted pixel and axis k: ub, pos, j as above, f = pos - j, d_k = table_k[j] + f (table_k[j+1] - table_k[j]) - ub;
+ * out_i = img_i + R_i0 d_0 + R_i1 d_1 + R_i2 d_2 (three fused multiply-adds, left to right), NOT clamped to [0, 1].  A pixel
+ * that does not count is copied bit for bit.  out may equal img.  next_basis / next_hist (both or neither): the same launch
+ * also bins the stored float32 values of the counted pixels on next_basis into next_hist (3, bins), which the call clears
+ * (a memset on the same stream) -- bit for bit strotss_color_hist of out with the same weight plane on next_basis. */
+int strotss_color_transfer_apply(const float* img, const float* weight, int h, int w, const float* basis, const float* table,
+                                 int bins, float* out, const float* next_basis, unsigned* next_hist, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Photo smoothing: the guided filter of He, Sun and Tang (2013), the content as colour guide
  * --------------------------------------------------------------------------------------- */
 #define STROTSS_SMOOTH_MAX_RADIUS 64

@@ -179,6 +179,10 @@ SIGNATURES = {
     "strotss_color_stats": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "strotss_color_affine": (_I, [_P, _P, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _P]),
     "strotss_luma_merge": (_I, [_P, _P, _I, _I, _P, _P]),
+    "strotss_color_hist_group": (_I, [_I]),
+    "strotss_color_hist": (_I, [_P, _P, _I, _I, C.POINTER(_F), _I, _I, _P, _P]),
+    "strotss_color_transfer_table": (_I, [_P, _P, C.POINTER(_F), _I, _P, _P]),
+    "strotss_color_transfer_apply": (_I, [_P, _P, _I, _I, C.POINTER(_F), _P, _I, _P, C.POINTER(_F), _P, _P]),
     "strotss_guided_smooth_workspace_bytes": (_Z, [_I, _I, _I]),
     "strotss_guided_smooth": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _Z, _P]),
     "strotss_kmeans_assign": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P]),

@@ -290,6 +290,102 @@ def luma_merge(result: torch.Tensor, content: torch.Tensor, out: Optional[torch.
     return out
 
 
+# ------------------------------------------------------------------ colour distribution transfer
+_transfer_ws = {}
+
+
+def _bases(bases, name: str = "bases"):
+    """(n, 3, 3) or (3, 3) host values -> (n, the n * 9 floats as a ctypes array), rounded to float32 here"""
+    b = np.asarray(bases, dtype=np.float64)
+    if b.ndim == 2:
+        b = b[None]
+    if b.ndim != 3 or b.shape[1:] != (3, 3) or b.shape[0] < 1:
+        raise ValueError(f"{name} of shape {b.shape}: expected (n, 3, 3) or (3, 3)")
+    flat = b.astype(np.float32).reshape(-1)
+    return int(b.shape[0]), (C.c_float * flat.size)(*flat.tolist())
+
+
+def _counts(t: torch.Tensor, shape: Tuple[int, ...], name: str) -> torch.Tensor:
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()) or tuple(t.shape) != shape:
+        raise _hip.StrotssHipError(f"{name} must be a contiguous int32 CUDA/HIP tensor of shape {shape}, got {t.dtype} "
+                                   f"{t.device} {tuple(t.shape)}")
+    return t
+
+
+def color_transfer_workspace(device, bins: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(hist (3, bins) int32, table (3, bins + 1) float32): the running histogram of the moved style and the current
+    table of a transfer, a module-level pair per device and bin count (one transfer at a time)."""
+    key = (str(canonical_device(device)), int(bins))
+    ws = _transfer_ws.get(key)
+    if ws is None:
+        ws = _transfer_ws[key] = (torch.zeros((3, bins), dtype=torch.int32, device=device),
+                                  torch.zeros((3, bins + 1), dtype=torch.float32, device=device))
+    return ws
+
+
+def color_hist(img: torch.Tensor, bases, bins: int, weight: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(n, 3, bins) int32 (the bits of uint32 counts): the histograms of the projections of the pixels whose weight is != 0
+    (None: all) on the three axes of each of the n bases (strotss_color_hist: one kernel launch for all of them)."""
+    h, w = _rgb_image(img, "image")
+    weight = _weight_plane(weight, h, w, "weight plane")
+    n, flat = _bases(bases)
+    if out is None:
+        out = torch.empty((n, 3, int(bins)), dtype=torch.int32, device=img.device)
+    _counts(out, (n, 3, int(bins)), "histograms")
+    check(_hip.lib().strotss_color_hist(ptr(img), ptr(weight), h, w, flat, n, int(bins), ptr(out), stream_ptr()),
+          "color_hist")
+    return out
+
+
+def color_transfer_table(hist_src: torch.Tensor, hist_dst: torch.Tensor, basis, bins: int,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(3, bins + 1) float32: per axis of `basis` the monotone map from the source's bin edges to the target's axis that
+    matches the two (3, bins) histograms (strotss_color_transfer_table)."""
+    n, flat = _bases(basis, "basis")
+    if n != 1:
+        raise ValueError("color_transfer_table takes one basis")
+    _counts(hist_src, (3, int(bins)), "source histogram")
+    _counts(hist_dst, (3, int(bins)), "target histogram")
+    if out is None:
+        out = torch.empty((3, int(bins) + 1), dtype=torch.float32, device=hist_src.device)
+    require(out, "transfer table")
+    assert tuple(out.shape) == (3, int(bins) + 1)
+    check(_hip.lib().strotss_color_transfer_table(ptr(hist_src), ptr(hist_dst), flat, int(bins), ptr(out), stream_ptr()),
+          "color_transfer_table")
+    return out
+
+
+def color_transfer_apply(img: torch.Tensor, basis, table: torch.Tensor, bins: int, weight: Optional[torch.Tensor] = None,
+                         out: Optional[torch.Tensor] = None, next_basis=None,
+                         next_hist: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = img moved along the three axes of `basis` by `table` where weight != 0 (None: everywhere), img elsewhere
+    (strotss_color_transfer_apply; out may be img).  next_basis and next_hist ((3, bins) int32), both or neither: the same
+    launch leaves the histogram of the moved pixels on next_basis in next_hist."""
+    h, w = _rgb_image(img, "image")
+    weight = _weight_plane(weight, h, w, "weight plane")
+    n, flat = _bases(basis, "basis")
+    if n != 1:
+        raise ValueError("color_transfer_apply takes one basis")
+    require(table, "transfer table")
+    assert tuple(table.shape) == (3, int(bins) + 1)
+    if (next_basis is None) != (next_hist is None):
+        raise ValueError("color_transfer_apply: next_basis and next_hist come together")
+    nflat = None
+    if next_basis is not None:
+        n, nflat = _bases(next_basis, "next basis")
+        if n != 1:
+            raise ValueError("color_transfer_apply takes one next basis")
+        _counts(next_hist, (3, int(bins)), "next histogram")
+    if out is None:
+        out = torch.empty_like(img)
+    require(out, "moved image")
+    assert out.numel() == img.numel()
+    check(_hip.lib().strotss_color_transfer_apply(ptr(img), ptr(weight), h, w, flat, ptr(table), int(bins), ptr(out), nflat,
+                                                  ptr(next_hist), stream_ptr()), "color_transfer_apply")
+    return out
+
+
 # ------------------------------------------------------------------ photo smoothing (DESIGN.md section 16)
 _smooth_ws = {}
 

@@ -394,6 +394,63 @@ def match_colour(style, content, style_mask=None, content_mask=None) -> torch.Te
     return out.reshape(tuple(style.shape)) if torch.is_tensor(style) else out
 
 
+# ----------------------------------------------------------------------------- colour transfer
+DEFAULT_TRANSFER_ITERS = 10
+TRANSFER_ITERS_RANGE = (1, 64)           # the bases of one strotss_color_hist call
+TRANSFER_BINS = 1024                     # not tuned: 256 bins land within 20 % of the same distance
+_TRANSFER_SEED = 1000                    # basis t >= 1 is drawn from seed 1000 + t, whatever --seed is
+
+
+def transfer_bases(iters: int) -> np.ndarray:
+    """(iters, 3, 3) float32: the orthonormal colour bases of a transfer, their COLUMNS the axes.  Made in float64 and rounded
+    once: R_0 = I (the channels themselves), R_t for t >= 1 the Q factor of a 3 x 3 normal draw of a fixed seed with the
+    signs chosen so that diag(R) of the factorisation is positive.  The sequence is a prefix of itself for every iters and
+    does not depend on --seed."""
+    lo, hi = TRANSFER_ITERS_RANGE
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not lo <= iters <= hi:
+        raise ValueError(f"transfer iterations {iters!r}: expected a whole number in {lo}..{hi}")
+    out = [np.eye(3)]
+    for t in range(1, int(iters)):
+        q, r = np.linalg.qr(np.random.default_rng(_TRANSFER_SEED + t).standard_normal((3, 3)))
+        out.append(q * np.sign(np.diag(r)))
+    return np.stack(out).astype(np.float32)
+
+
+def transfer_colour(style, content, style_mask=None, content_mask=None, iters: int = DEFAULT_TRANSFER_ITERS,
+                    bins: int = TRANSFER_BINS) -> torch.Tensor:
+    """--preserve_color transfer: the style image with the content's whole colour distribution, by the iterative
+    distribution transfer of Pitie, Kokaram and Dahyot (2007): `iters` times, the style's pixels are projected on an
+    orthonormal basis (transfer_bases) and each of the three axes is histogram-matched to the content's projection on it.
+    2 iters + 2 kernel launches: the content's histograms on every basis (one strotss_color_hist), the style's on the first,
+    then per iteration strotss_color_transfer_table and strotss_color_transfer_apply, which also bins the moved pixels on
+    the next basis.  Not clamped.  With masks ((h, w) planes at each image's size): the pixels with a weight != 0 count,
+    the others of the style are copied.  -> an image of the style's shape.  ValueError, before any launch: shapes that do
+    not match, an image that is not finite, a mask that counts no pixel, iters outside 1..64, bins that are not a multiple
+    of 4 in 4..4096 (iteration t's target is the slice t of the content's (iters, 3, bins) histograms, 12 bins t bytes into
+    them, and strotss_color_transfer_table takes 16-byte aligned pointers; the entries themselves take any bins in 2..4096)."""
+    s, c = _rgb(style, "style image"), _rgb(content, "content image")
+    sm = _plane(style_mask, int(s.shape[0]), int(s.shape[1]), "style mask")
+    cm = _plane(content_mask, int(c.shape[0]), int(c.shape[1]), "content mask")
+    bases = transfer_bases(iters)
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 4 <= bins <= 4096 or bins % 4:
+        raise ValueError(f"transfer bins {bins!r}: expected a multiple of 4 in 4..4096")
+    if not (bool(torch.isfinite(s).all()) and bool(torch.isfinite(c).all())):
+        raise ValueError("colour transfer: the style or the content holds values that are not finite")
+    for m, name in ((sm, "style"), (cm, "content")):
+        if m is not None and not bool((m != 0).any()):
+            raise ValueError(f"colour transfer: the {name} mask counts no pixel")
+    target = _ops.color_hist(c, bases, bins, cm)             # the content never moves: every iteration's target at once
+    hist, table = _ops.color_transfer_workspace(s.device, bins)
+    _ops.color_hist(s, bases[:1], bins, sm, out=hist[None])
+    out = torch.empty_like(s)
+    for t in range(len(bases)):
+        _ops.color_transfer_table(hist, target[t], bases[t], bins, out=table)
+        following = bases[t + 1] if t + 1 < len(bases) else None
+        _ops.color_transfer_apply(s if t == 0 else out, bases[t], table, bins, sm, out=out, next_basis=following,
+                                  next_hist=None if following is None else hist)
+    return out.reshape(tuple(style.shape)) if torch.is_tensor(style) else out
+
+
 def luminance_merge(result, content) -> torch.Tensor:
     """--preserve_color luminance: the luma of `result` on the chroma of `content`, out = content + (Y(result) - Y(content))
     on every channel with Y = 0.299 R + 0.587 G + 0.114 B (strotss_luma_merge).  Two images of one size -> the result's

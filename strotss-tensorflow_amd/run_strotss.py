@@ -36,13 +36,19 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
                     bring better flow from elsewhere.
   --save_flow DIR   with --compute_flow: also write the computed flows to DIR as backward_{t}_{t-j}.flo and
                     forward_{t-j}_{t}.flo (a later run with --flow_dir DIR reads the same floats back)
-  --preserve_color {match,luminance}
+  --preserve_color {match,luminance,transfer}
                     keep the content's colours (Gatys et al. 2016).  match: every style image is
                     recoloured, before anything is sampled from it, with the affine map that gives it the content's colour
                     mean and covariance (each --style_mix image on its own; with masks region by region; with --video
                     against every frame's own colours).  luminance: the written image keeps the luma of the result and takes
-                    the chroma of the content; with --video the temporal targets stay the unmerged results.  One GPU; not
-                    with --strips.
+                    the chroma of the content; with --video the temporal targets stay the unmerged results.  transfer:
+                    where match recolours with one affine map, every style image is given the content's whole colour
+                    distribution by iterative distribution transfer (Pitie, Kokaram and Dahyot 2007):
+                    its pixels are rotated into an orthonormal colour basis, each axis is histogram-matched to the content,
+                    and the loop repeats on the next basis; it runs where and as match runs (per --style_mix image, region by
+                    region, per --video frame).  One GPU; not with --strips.
+  --transfer_iters T
+                    with --preserve_color transfer: the number of bases, 1..64 (default 10; the bases do not depend on --seed)
   --photo_smooth    keep the content's edges: the result is passed through the guided filter of He, Sun and Tang (2013) with
                     the content at the result's size as colour guide before --preserve_color
                     luminance's merge and before it is written; with --video the temporal targets stay the unfiltered
@@ -212,13 +218,21 @@ def _content_weight_input(args):
     return path
 
 
-PRESERVE_COLOR_MODES = ("match", "luminance")
+PRESERVE_COLOR_MODES = ("match", "luminance", "transfer")
 
 
 def _preserve_color_input(args):
-    """--preserve_color: "match", "luminance" or None.  One GPU only: with --strips or under torchrun with WORLD_SIZE > 1 a
-    ValueError (checked before anything is loaded)."""
+    """--preserve_color: "match", "luminance", "transfer" or None.  One GPU only: with --strips or under torchrun with
+    WORLD_SIZE > 1 a ValueError (checked before anything is loaded), as is --transfer_iters without the mode transfer or
+    outside 1..64."""
     mode = getattr(args, "preserve_color", None)
+    iters = getattr(args, "transfer_iters", None)
+    if iters is not None:
+        if mode != "transfer":
+            raise ValueError("--transfer_iters needs --preserve_color transfer")
+        lo, hi = strotss.TRANSFER_ITERS_RANGE
+        if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not lo <= iters <= hi:
+            raise ValueError(f"--transfer_iters must be a whole number in {lo}..{hi}, got {iters!r}")
     if mode is None:
         return None
     if mode not in PRESERVE_COLOR_MODES:
@@ -359,13 +373,15 @@ def _auto_masks_input(args):
     return int(k), (save or None)
 
 
-def _match_styles(styles, content, content_masks, style_masks):
+def _match_styles(styles, content, content_masks, style_masks, recolour=None):
     """--preserve_color match: every style image recoloured toward the content's colour mean and covariance
     (strotss_utils.match_colour), each style on its own.  With masks region by region: the statistics of the style pixels
     in style mask r and of the content pixels in content mask r, the map applied to style mask r's pixels only (the masks
-    resized to the images as mask_at_scale resizes them to a scale); pixels in no region stay."""
+    resized to the images as mask_at_scale resizes them to a scale); pixels in no region stay.  recolour: another
+    (style, content, style_mask, content_mask) -> style in match_colour's place (_recolour_styles)."""
+    recolour = recolour or strotss.match_colour
     if list(content_masks) == [None]:
-        return [strotss.match_colour(s_k, content) for s_k in styles]
+        return [recolour(s_k, content) for s_k in styles]
     ch, cw = int(content.shape[1]), int(content.shape[2])
     out = []
     for s_k in styles:
@@ -373,9 +389,25 @@ def _match_styles(styles, content, content_masks, style_masks):
         for c_mask, s_mask in zip(content_masks, style_masks):
             cm = torch.from_numpy(strotss.mask_at_scale(c_mask, ch, cw).astype(np.float32))
             sm = torch.from_numpy(strotss.mask_at_scale(s_mask, sh, sw).astype(np.float32))
-            s_k = strotss.match_colour(s_k, content, sm, cm)
+            s_k = recolour(s_k, content, sm, cm)
         out.append(s_k)
     return out
+
+
+def _recolour_styles(args, styles, content, content_masks, style_masks):
+    """the styles as --preserve_color leaves them before anything is sampled: recoloured by match or by transfer
+    (--transfer_iters bases) exactly where and as _match_styles recolours them, untouched otherwise"""
+    mode = _preserve_color_input(args)
+    if mode == "match":
+        return _match_styles(styles, content, content_masks, style_masks)
+    if mode == "transfer":
+        iters = getattr(args, "transfer_iters", None)
+        iters = strotss.DEFAULT_TRANSFER_ITERS if iters is None else int(iters)
+
+        def transfer(style, content, style_mask=None, content_mask=None):
+            return strotss.transfer_colour(style, content, style_mask, content_mask, iters=iters)
+        return _match_styles(styles, content, content_masks, style_masks, recolour=transfer)
+    return styles
 
 
 DEFAULT_TEMPORAL_WEIGHT = 1000.0          # DESIGN.md section 12: chosen on the MI355X with the consistency error
@@ -731,8 +763,8 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
                 strotss.save_masks(auto[1], content_masks, style_masks)
     else:
         content_masks, style_masks = _load_masks(args)
-    if _preserve_color_input(args) == "match":               # before any resize: every scale samples the recoloured styles
-        styles = _match_styles(styles, content, content_masks, style_masks)
+    # --preserve_color match / transfer, before any resize: every scale samples the recoloured styles
+    styles = _recolour_styles(args, styles, content, content_masks, style_masks)
     cw_map = strotss.load_content_weight_map(cw_path) if cw_path else None
     sampling = strotss.Sampling(SAMPLE_SIZE)
     masked = bool(getattr(args, "content_mask", None))
@@ -842,11 +874,11 @@ def run_video(args: argparse.Namespace, trace=None):
     temporal term toward the previous result warped along the backward flow and, with
     --temporal_frames, toward the results of frames t-j (the last max(J) results stay on the device).
     With --compute_flow the flows come from strotss_optical_flow on the content frames at the results' size (DESIGN.md
-    section 14; the last max(J) + 1 of those frames stay on the device as well).  --preserve_color match recolours the
-    styles against every frame's own colours (in _stylise); luminance merges only what is written, the temporal targets
-    keep the unmerged results.  --photo_smooth filters only what is written as well, before that
-    merge.  --auto_masks K --track_masks: the regions of frame 1 followed through the sequence
-    (_tracked_masks).  Writes
+    section 14; the last max(J) + 1 of those frames stay on the device as well).  --preserve_color match and
+    transfer recolour the styles against every frame's own colours (in _stylise); luminance merges only what is written,
+    the temporal targets keep the unmerged results (DESIGN.md sections 15 and 23).  --photo_smooth filters only what is
+    written as well, before that merge.  --auto_masks K --track_masks: the regions of frame 1
+    followed through the sequence (_tracked_masks).  Writes
     <output dir>/<frame stem>.jpg; returns the list of the frames' uint8 results.  `trace`: one list per frame."""
     preserve = _preserve_color_input(args)
     smooth = _photo_smooth_input(args)
@@ -945,7 +977,10 @@ _FLAGS = (
     (("--preserve_color",), dict(type=str, default=None, choices=PRESERVE_COLOR_MODES,
                                  help="keep the content's colours: 'match' recolours the style images to the content's colour "
                                       "mean and covariance before anything is sampled, 'luminance' writes the result's luma on "
-                                      "the content's chroma")),
+                                      "the content's chroma, 'transfer' gives the style images the content's whole colour "
+                                      "distribution (iterative distribution transfer)")),
+    (("--transfer_iters",), dict(type=int, default=None, metavar='T',
+                                 help="with --preserve_color transfer: the number of colour bases, 1..64 (default 10)")),
     (("--photo_smooth",), dict(action='store_true', help="keep the content's edges: pass the result through the guided filter "
                                                          "with the content as colour guide before it is written")),
     (("--smooth_radius",), dict(type=int, default=None, metavar='R',
