@@ -807,6 +807,48 @@ int strotss_kmeans_assign_prior(const float* x, const float* inv_norm, int n, in
                                 const int* prior, float beta, int* label, float* best, float* second, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Scribble masks: region labels from a few strokes per image, the kernels of --content_scribbles /
+ * --style_scribbles
+ * --------------------------------------------------------------------------------------- */
+#define STROTSS_SCRIBBLE_MAX_K 7
+#define STROTSS_SCRIBBLE_MAX_ITERS 1024
+/* scores[i k + j] (float32, (n, k)) = s_ij of strotss_kmeans_assign for every row i < n and centre j < k, the same bits (one
+ * kernel source); x, inv_norm, n, d, ld, centres, k as there.  A row with inv_norm_i == 0 gets k zeros.  One launch; the same
+ * bits on every run and stream.  Refused before anything is launched, scores untouched: STROTSS_EINVAL for a null pointer,
+ * n <= 0, d <= 0, d > ld, n ld > INT_MAX, n k > INT_MAX, k outside 1..STROTSS_KMEANS_MAX_K; STROTSS_EALIGN for ld % 32 != 0 or
+ * a pointer that is not 16-byte aligned. */
+int strotss_kmeans_scores(const float* x, const float* inv_norm, int n, int d, int ld, const float* centres, int k,
+                          float* scores, void* stream);
+/* bytes of the workspace of strotss_scribble_labels: 3 k + 2 float32 planes of h w values (the unary q, two buffers of x, the
+ * two edge weights), each in 256-byte slices; 0 for h or w <= 0, k outside 2..STROTSS_SCRIBBLE_MAX_K, k h w > INT_MAX or
+ * 3 h w > INT_MAX */
+size_t strotss_scribble_workspace_bytes(int h, int w, int k);
+/* img: an (h, w, 3) float32 image; stroke: (h, w) int32, a label 0..k-1 on a stroke pixel and any other value elsewhere
+ * (compared, never used as an index); scores: the (gh, gw, k) float32 scores of the cells of the image's feature grid
+ * (strotss_kmeans_scores), 2 <= k <= STROTSS_SCRIBBLE_MAX_K.
+ *   unary    s_r(y, x) = scores plane r sampled bilinearly at u = (y + 0.5) gh / h - 0.5, v = (x + 0.5) gw / w - 0.5 (the
+ *            4-neighbour, edge-clamped rule of strotss_flow_warp);  q_r = softmax_r(s_r / tau), the maximum subtracted first;
+ *            all of it in float64, q rounded once to float32
+ *   weights  w(p, p') = exp(-|img(p) - img(p')|^2 / (2 sigma^2)) for the 4 neighbours inside the image (float64, rounded
+ *            once); a neighbour outside the image is omitted
+ *   sweeps   x^0 = q; on a stroke pixel x is the one-hot of its label, before and after every sweep; every other pixel, in
+ *            each of `iters` Jacobi sweeps (float32):  x_r(p) <- (lambda q_r(p) + sum w x_r(p')) / (lambda + sum w), evaluated as
+ *            q_r(p) + sum w (x_r(p') - q_r(p)) / (lambda + sum w) and clamped to [0, 1]
+ *   labels   label[y w + x] (int32) = the r with the largest x_r, the lowest r on equal values; count[r] (int32, r < k) = the
+ *            number of pixels with label r, by integer atomics; x (k, h, w) float32 or NULL = the planes after the last sweep
+ * iters_per_launch: 1 = one sweep per launch; 2, 4 or 8 = that many sweeps per launch of the blocked kernel (sweeps that do
+ * not fill a launch run one by one); 0 = the library's choice.  Every choice gives the same bits.  No float atomics: the
+ * same bits on every run and stream.  The workspace needs no initialisation.
+ * Refused before anything is launched, the outputs untouched: STROTSS_EINVAL for a null img, stroke, scores, label, count or
+ * workspace, a size <= 0, k outside 2..STROTSS_SCRIBBLE_MAX_K, k h w, 3 h w or gh gw k > INT_MAX, a tau, lambda or sigma that
+ * is not finite or not positive (or so small that its reciprocal overflows, or a lambda that is 0 as float32), iters outside
+ * 1..STROTSS_SCRIBBLE_MAX_ITERS, iters_per_launch not in {0, 1, 2, 4, 8}, workspace_bytes below
+ * strotss_scribble_workspace_bytes(h, w, k); STROTSS_EALIGN for a pointer that is not 16-byte aligned. */
+int strotss_scribble_labels(const float* img, const int* stroke, int h, int w, const float* scores, int gh, int gw, int k,
+                            double tau, double lambda, double sigma, int iters, int iters_per_launch, int* label, int* count,
+                            float* x, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Optimiser + output
  * --------------------------------------------------------------------------------------- */
 typedef struct {

@@ -9,6 +9,9 @@
 //                                    PRIOR = false: label = first arg-max of s, best, second (prior and beta are not read).
 //                                    PRIOR = true: label = first arg-max of s_ij + (prior_i == j ? beta : 0), one float32 add;
 //                                    best = the raw s of that j, second = the largest raw s of the other j.
+//                                    SCORES = true (scribble.hip, strotss_kmeans_scores): all k values
+//                                    s_ij go to scores[i k + j] (0 for a row with inv_norm_i == 0) instead of the best two;
+//                                    label, best and second are not touched.
 #pragma once
 #include <math.h>
 
@@ -22,13 +25,14 @@ namespace {
 #define KM_CHUNK 512                     // columns of the centres in LDS at a time: two float4 per lane
 #define KM_MAX_GRID 2048u                // workgroups of an assign launch at most; a workgroup walks the tiles beyond
 
-template <int KP, bool PRIOR>
+template <int KP, bool PRIOR, bool SCORES = false>
 __global__ __launch_bounds__(KM_ASSIGN_THREADS) void kmeans_assign_kernel(const float* __restrict__ x,
                                                                           const float* __restrict__ inv_norm, int n, int d,
                                                                           int ld, const float* __restrict__ centres, int k,
                                                                           const int* __restrict__ prior, float beta,
                                                                           int* __restrict__ label, float* __restrict__ best,
-                                                                          float* __restrict__ second) {
+                                                                          float* __restrict__ second,
+                                                                          float* __restrict__ scores) {
   __shared__ __attribute__((aligned(16))) float cs[KP][KM_CHUNK];
   const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
   const unsigned ntiles = ((unsigned)n + KM_TILE_ROWS - 1) / KM_TILE_ROWS;
@@ -82,6 +86,12 @@ __global__ __launch_bounds__(KM_ASSIGN_THREADS) void kmeans_assign_kernel(const 
         const int row = row0 + q;
         if (row >= n) continue;
         const float inv = inv_norm[row];
+        if constexpr (SCORES) {
+#pragma unroll
+          for (int j = 0; j < KP; ++j)
+            if (j < k) scores[(size_t)row * k + j] = inv != 0.f ? acc[q][j] * inv : 0.f;
+          continue;
+        }
         int bj = 0;
         float b = 0.f, s2 = 0.f;
         if constexpr (!PRIOR) {
@@ -149,7 +159,24 @@ inline void km_launch_assign(const float* x, const float* inv_norm, int n, int d
   const dim3 grid(min(ntiles, KM_MAX_GRID)), block(KM_ASSIGN_THREADS);
 #define KM_LAUNCH(KP)                                                                                                        \
   hipLaunchKernelGGL((kmeans_assign_kernel<KP, PRIOR>), grid, block, 0, st, x, inv_norm, n, d, ld, centres, k, prior, beta, \
-                     label, best, second)
+                     label, best, second, (float*)nullptr)
+  if (k <= 4)
+    KM_LAUNCH(4);
+  else if (k <= 8)
+    KM_LAUNCH(8);
+  else
+    KM_LAUNCH(16);
+#undef KM_LAUNCH
+}
+
+// The same launch with SCORES = true: scores is (n, k) float32.
+inline void km_launch_scores(const float* x, const float* inv_norm, int n, int d, int ld, const float* centres, int k,
+                             float* scores, hipStream_t st) {
+  const unsigned ntiles = ((unsigned)n + KM_TILE_ROWS - 1) / KM_TILE_ROWS;
+  const dim3 grid(min(ntiles, KM_MAX_GRID)), block(KM_ASSIGN_THREADS);
+#define KM_LAUNCH(KP)                                                                                                        \
+  hipLaunchKernelGGL((kmeans_assign_kernel<KP, false, true>), grid, block, 0, st, x, inv_norm, n, d, ld, centres, k,        \
+                     (const int*)nullptr, 0.f, (int*)nullptr, (float*)nullptr, (float*)nullptr, scores)
   if (k <= 4)
     KM_LAUNCH(4);
   else if (k <= 8)

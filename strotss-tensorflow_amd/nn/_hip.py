@@ -38,6 +38,8 @@ class MapsT(C.Structure):
 MAX_DRAW_REGIONS = 16
 KMEANS_MAX_K = 16          # STROTSS_KMEANS_MAX_K
 REFINE_MAX_RADIUS = 4      # STROTSS_REFINE_MAX_RADIUS
+SCRIBBLE_MAX_K = 7         # STROTSS_SCRIBBLE_MAX_K
+SCRIBBLE_MAX_ITERS = 1024  # STROTSS_SCRIBBLE_MAX_ITERS
 
 
 class DrawT(C.Structure):
@@ -192,6 +194,10 @@ SIGNATURES = {
     "strotss_refine_labels": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, C.c_double, C.c_double, _P, _P, _P, _P, _P, _Z, _P]),
     "strotss_label_warp": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
     "strotss_kmeans_assign_prior": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _F, _P, _P, _P, _P]),
+    "strotss_kmeans_scores": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P]),
+    "strotss_scribble_workspace_bytes": (_Z, [_I, _I, _I]),
+    "strotss_scribble_labels": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, C.c_double, C.c_double, C.c_double, _I, _I, _P, _P, _P, _P,
+                                     _Z, _P]),
     "strotss_rmsprop_step": (_I, [C.POINTER(TensorsT), _F, _F, _F, _P]),
     "strotss_postprocess": (_I, [_P, _L, _P, _P, _P]),
 }

@@ -917,6 +917,44 @@ def kmeans_assign_prior(x: torch.Tensor, inv_norm: torch.Tensor, n: int, d: int,
     return label, best, second
 
 
+# ------------------------------------------------------------------ scribble masks
+def kmeans_scores(x: torch.Tensor, inv_norm: torch.Tensor, n: int, d: int, centres: torch.Tensor, k: int) -> torch.Tensor:
+    """strotss_kmeans_scores: the (n, k) float32 scores (x_i . centres_j) inv_norm_i, the bits kmeans_assign compares"""
+    ld = _kmeans_rows(x, inv_norm, n, d, centres, k)
+    scores = torch.empty((n, k), dtype=torch.float32, device=x.device)
+    check(_hip.lib().strotss_kmeans_scores(ptr(x), ptr(inv_norm), n, d, ld, ptr(centres), k, ptr(scores), stream_ptr()),
+          "kmeans_scores")
+    return scores
+
+
+def scribble_labels(img: torch.Tensor, stroke: torch.Tensor, scores: torch.Tensor, tau: float, lam: float, sigma: float,
+                    iters: int, iters_per_launch: int = 0, planes: bool = False):
+    """strotss_scribble_labels: the strokes of an (h, w, 3) image -- stroke (h, w) int32, a label 0..k-1 or anything else --
+    spread over the image by `iters` Jacobi sweeps of a screened random walker whose unary is the softmax at temperature tau of
+    the bilinearly sampled (gh, gw, k) score grid.  -> (label (h, w) int32, count (k,) int32, x): x the (k, h, w) float32
+    planes after the last sweep with planes=True, else None.  iters_per_launch: 0 (the library's choice), 1, 2, 4 or 8; the
+    same bits for each.  The library refuses k outside 2..7, a tau, lambda or sigma <= 0 and iters outside 1..1024."""
+    h, w = _rgb_image(img, "image")
+    _int32_on_device(stroke, h * w, "the stroke labels")
+    require(scores, "score grid")
+    if scores.dim() != 3 or tuple(stroke.shape) != (h, w):
+        raise ValueError(f"a score grid of shape {tuple(scores.shape)} and strokes of shape {tuple(stroke.shape)} for an image "
+                         f"of {h} x {w}: expected (gh, gw, k) and (h, w)")
+    gh, gw, k = (int(v) for v in scores.shape)
+    lib = _hip.lib()
+    nb = int(lib.strotss_scribble_workspace_bytes(h, w, k))
+    if nb == 0:
+        raise ValueError(f"scribble_labels: {k} regions on an image of {h} x {w} (expected 2..{_hip.SCRIBBLE_MAX_K} regions)")
+    ws = workspaces.get("scribble", nb, img.device)
+    label = torch.empty((h, w), dtype=torch.int32, device=img.device)
+    count = torch.empty(k, dtype=torch.int32, device=img.device)
+    x = torch.empty((k, h, w), dtype=torch.float32, device=img.device) if planes else None
+    check(lib.strotss_scribble_labels(ptr(img), ptr(stroke), h, w, ptr(scores), gh, gw, k, float(tau), float(lam), float(sigma),
+                                      int(iters), int(iters_per_launch), ptr(label), ptr(count), ptr(x), ptr(ws), nb,
+                                      stream_ptr()), "scribble_labels")
+    return label, count, x
+
+
 def cosine_distance(x, rx, nx, y, ry, ny) -> torch.Tensor:
     ldc = pad32(ny)
     Cm = torch.empty((nx, ldc), dtype=torch.float32, device=x.device)

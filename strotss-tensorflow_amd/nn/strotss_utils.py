@@ -564,16 +564,12 @@ def upsample_labels(grid: torch.Tensor, H: int, W: int) -> torch.Tensor:
     return grid[ys][:, xs]
 
 
-def auto_mask_regions(params, content: torch.Tensor, style: torch.Tensor, k: int, min_share: float = AUTO_MASK_MIN_SHARE):
-    """The clustering behind auto_masks, with everything the tests look at: dict(kept = number of regions (0: fewer than
-    two clusters hold min_share of both images' grid points), content_grid / style_grid = (gh, gw) int32 label grids over the
-    kept clusters, centres (kept, ld), rows = the (n_c + n_s, ld) hypercolumn buffer (content rows first), inv_norm, n_c,
-    n_s, d, shares (kept, 2) of the two images' points per region).  One device-to-host read: the (2, k) counts."""
-    lo, hi = 1, _ops._hip.KMEANS_MAX_K
-    if not lo <= int(k) <= hi:
-        raise ValueError(f"{k} clusters: expected {lo}..{hi}")
+def _joint_rows(params, content: torch.Tensor, style: torch.Tensor):
+    """The hypercolumn rows of both images' clustering grids: each image resized to AUTO_MASK_SIZE, one trunk forward, one
+    gather -> (rows = the zero-padded (pad32(n_c + n_s), ld) buffer, content rows first, inv_norm, n_c, n_s, d,
+    grids = [(gh, gw)] * 2, sizes = [(h, w) of the resized image] * 2)"""
     from . import engine
-    grids, blocks, d = [], [], 0
+    grids, sizes, blocks, d = [], [], [], 0
     for image in (content, style):
         small = utils.resize(image, min(AUTO_MASK_SIZE, max(int(image.shape[-3]), int(image.shape[-2]))))
         if small.dim() == 3:
@@ -582,14 +578,26 @@ def auto_mask_regions(params, content: torch.Tensor, style: torch.Tensor, k: int
         ys, xs = auto_mask_grid(int(small.shape[1]), int(small.shape[2]))
         idx = np.stack(np.meshgrid(ys, xs, indexing="ij"), axis=-1).reshape(-1, 2).astype(np.float32)      # (row, col), row-major
         grids.append((len(ys), len(xs)))
+        sizes.append((int(small.shape[1]), int(small.shape[2])))
         blocks.append((feats, torch.from_numpy(idx).to(small.device)))
         d = sum(int(m.shape[-1]) for m in feats)
     n_c, n_s = (g[0] * g[1] for g in grids)
     rows = torch.zeros((_ops.pad32(n_c + n_s), _ops.pad32(d)), dtype=torch.float32, device=blocks[0][1].device)
     _ops.hypercol_gather(blocks[0][0], blocks[0][1], False, out=rows)
     _ops.hypercol_gather(blocks[1][0], blocks[1][1], False, out=rows[n_c:])
+    return rows, _ops.row_inv_norm(rows, n_c + n_s), n_c, n_s, d, grids, sizes
+
+
+def auto_mask_regions(params, content: torch.Tensor, style: torch.Tensor, k: int, min_share: float = AUTO_MASK_MIN_SHARE):
+    """The clustering behind auto_masks, with everything the tests look at: dict(kept = number of regions (0: fewer than
+    two clusters hold min_share of both images' grid points), content_grid / style_grid = (gh, gw) int32 label grids over the
+    kept clusters, centres (kept, ld), rows = the (n_c + n_s, ld) hypercolumn buffer (content rows first), inv_norm, n_c,
+    n_s, d, shares (kept, 2) of the two images' points per region).  One device-to-host read: the (2, k) counts."""
+    lo, hi = 1, _ops._hip.KMEANS_MAX_K
+    if not lo <= int(k) <= hi:
+        raise ValueError(f"{k} clusters: expected {lo}..{hi}")
+    rows, inv_norm, n_c, n_s, d, grids, _ = _joint_rows(params, content, style)
     n = n_c + n_s
-    inv_norm = _ops.row_inv_norm(rows, n)
     label, centres, _, _ = spherical_kmeans(rows, n, d, int(k), inv_norm=inv_norm)
     counts = torch.stack([label_counts(label[:n_c], k), label_counts(label[n_c:], k)]).cpu().numpy()
     keep = np.flatnonzero((counts[0] >= min_share * n_c) & (counts[1] >= min_share * n_s))
@@ -689,6 +697,146 @@ def save_masks(directory: str, content_masks, style_masks) -> None:
     for name, masks in (("content_mask.png", content_masks), ("style_mask.png", style_masks)):
         region = torch.stack([m.reshape(m.shape[0], m.shape[1]) for m in masks]).argmax(dim=0).cpu()
         Image.fromarray(palette[region].numpy(), "RGB").save(os.path.join(directory, name), format="PNG")
+
+
+# ----------------------------------------------------------------------------- scribble masks
+# four documented choices, none tuned
+SCRIBBLE_TAU = 0.05                      # temperature of the unary's softmax over the cosines
+SCRIBBLE_LAMBDA = 0.05                   # the pull toward the unary, against edge weights of at most 1 per neighbour
+SCRIBBLE_ITERS = 128                     # Jacobi sweeps
+SCRIBBLE_SIGMA = REFINE_SIGMA_R          # on [0, 1] colours
+SCRIBBLE_SIGMA_RANGE = (0.01, 1.0)       # --scribble_sigma
+SCRIBBLE_ITERS_RANGE = (1, 1024)         # --scribble_iters (STROTSS_SCRIBBLE_MAX_ITERS)
+SCRIBBLE_RANGE = (2, 7)                  # regions: the eight corner colours without black ("no stroke")
+
+
+def check_scribble_parameters(sigma, iters) -> None:
+    """ValueError for a colour sigma that is not finite or outside [0.01, 1], or a sweep count that is no integer in
+    1..1024 (None: not given)"""
+    lo, hi = SCRIBBLE_SIGMA_RANGE
+    if sigma is not None and not (math.isfinite(sigma) and lo <= sigma <= hi):
+        raise ValueError(f"scribble sigma {sigma!r}: expected a finite value in [{lo}, {hi}]")
+    lo, hi = SCRIBBLE_ITERS_RANGE
+    if iters is not None and not (int(iters) == iters and lo <= int(iters) <= hi):
+        raise ValueError(f"{iters!r} scribble sweeps: expected {lo}..{hi}")
+
+
+def _stroke_colours(path: str) -> np.ndarray:
+    """(h, w) int64 per pixel of a stroke image: the index into MASK_COLOURS of its colour under the mask loader's
+    threshold rule (a channel counts when it is 255); 0 is black, "no stroke".  Host only."""
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"File not found: {path}")
+    from PIL import Image
+    with Image.open(path) as im:
+        q = (np.array(im.convert("RGB")) // 255).astype(np.int64)
+    return q[..., 0] * 4 + q[..., 1] * 2 + q[..., 2]
+
+
+def load_scribbles(content_path: str, style_path: str):
+    """--content_scribbles / --style_scribbles: two RGB images in the corner-colour format of MASK_COLOURS, black meaning
+    "no stroke" -> (content strokes, style strokes, colours): (h, w) int32 host arrays at the files' own sizes, region r
+    (the r-th non-black colour present, ascending (r, g, b)) on its strokes and -1 elsewhere, and the regions' colours.
+    ValueError: a colour present in one file only, fewer than two colours."""
+    found = [_stroke_colours(content_path), _stroke_colours(style_path)]
+    present = [sorted(set(np.unique(f).tolist()) - {0}) for f in found]
+    if present[0] != present[1]:
+        only = sorted(set(present[0]) ^ set(present[1]))
+        raise ValueError(f"scribbles: the colours {[MASK_COLOURS[c] for c in only]} are present in one file only "
+                         f"({content_path}, {style_path}); every region needs a stroke in both images")
+    if len(present[0]) < SCRIBBLE_RANGE[0]:
+        raise ValueError(f"scribbles: {len(present[0])} stroke colours in {content_path}; expected {SCRIBBLE_RANGE[0]}.."
+                         f"{SCRIBBLE_RANGE[1]} of the corner colours {MASK_COLOURS[1:]}")
+    lut = np.full(len(MASK_COLOURS), -1, dtype=np.int32)
+    lut[present[0]] = np.arange(len(present[0]), dtype=np.int32)
+    return lut[found[0]], lut[found[1]], [MASK_COLOURS[c] for c in present[0]]
+
+
+def resize_strokes(strokes: np.ndarray, H: int, W: int) -> np.ndarray:
+    """(h, w) stroke labels at (H, W) by nearest neighbour: pixel (y, x) takes (y h // H, x w // W)"""
+    h, w = strokes.shape
+    return np.ascontiguousarray(strokes[np.arange(H) * h // H][:, np.arange(W) * w // W])
+
+
+def scribble_seeds(strokes: np.ndarray, k: int) -> np.ndarray:
+    """(gh, gw) int32 seed labels of the clustering grid (auto_mask_grid) of a small image from its (h, w) stroke labels:
+    per cell the majority label among the stroke pixels of its g x g block (rows i g .. i g + g - 1), the lowest label on a
+    tie, -1 without a stroke pixel.  Host only: at most 256 x 256 pixels."""
+    h, w = strokes.shape
+    g = -(-max(h, w) // AUTO_MASK_GRID)
+    ys, xs = auto_mask_grid(h, w)
+    gh, gw = len(ys), len(xs)
+    yy, xx = np.nonzero((strokes >= 0) & (strokes < k))
+    inside = (yy // g < gh) & (xx // g < gw)
+    yy, xx = yy[inside], xx[inside]
+    votes = np.zeros((gh, gw, k), dtype=np.int64)
+    np.add.at(votes, (yy // g, xx // g, strokes[yy, xx]), 1)
+    return np.where(votes.sum(axis=2) > 0, votes.argmax(axis=2), -1).astype(np.int32)        # argmax: the first of equal counts
+
+
+def scribble_regions(params, content: torch.Tensor, style: torch.Tensor, content_strokes: np.ndarray,
+                     style_strokes: np.ndarray, k: int, sigma: float = SCRIBBLE_SIGMA, iters: int = SCRIBBLE_ITERS,
+                     tau: float = SCRIBBLE_TAU, lam: float = SCRIBBLE_LAMBDA, iters_per_launch: int = 0, planes: bool = False):
+    """The propagation behind scribble_masks, with everything the tests look at.  The strokes (host label arrays of any
+    size, load_scribbles) are brought to each image's size and to its AUTO_MASK_SIZE copy by nearest neighbour; the cells of
+    the two clustering grids that a stroke crosses seed k centres (one strotss_kmeans_update over both images' rows); every
+    cell's cosines to the centres (strotss_kmeans_scores) are the unary of a screened random walker on each image, whose
+    strokes are fixed (strotss_scribble_labels).  -> dict(k, rows, inv_norm, n_c, n_s, d, seeds = [(gh, gw) int32] * 2 on
+    the host, centres (k, ld), scores (n_c + n_s, k), grid_scores / strokes / labels / x = [content's, style's] on the
+    device ((gh, gw, k), (H, W) int32, (H, W) int32, (k, H, W) or None), counts (2, k) pixels per region, read back).
+    ValueError: k outside 2..7, bad parameters, a region that seeds no cell in either image -- nearest-neighbour sampling
+    of the stroke file keeps every stroke that is at least (file's longer side) / AUTO_MASK_SIZE pixels wide; a thinner one
+    may fall between the samples."""
+    lo, hi = SCRIBBLE_RANGE
+    if not lo <= int(k) <= hi:
+        raise ValueError(f"{k} regions: expected {lo}..{hi}")
+    check_scribble_parameters(sigma, iters)
+    k = int(k)
+    rows, inv_norm, n_c, n_s, d, grids, sizes = _joint_rows(params, content, style)
+    n = n_c + n_s
+    seeds = [scribble_seeds(resize_strokes(strokes, *size), k) for strokes, size in zip((content_strokes, style_strokes), sizes)]
+    joint = np.concatenate([seed.reshape(-1) for seed in seeds])
+    missing = [r for r in range(k) if not (joint == r).any()]
+    if missing:
+        raise ValueError(f"scribbles: the strokes of region(s) {missing} cover no cell of either image's {AUTO_MASK_GRID}-cell "
+                         f"grid (stroke too thin at {AUTO_MASK_SIZE} px: the stroke file is sampled by nearest neighbour at "
+                         f"the image's size and at its {AUTO_MASK_SIZE}-px copy, so draw strokes at least 1/{AUTO_MASK_SIZE} of "
+                         f"the file's longer side wide, e.g. 8 pixels on a 2048-pixel file)")
+    centres = torch.zeros((k, int(rows.shape[1])), dtype=torch.float32, device=rows.device)
+    _ops.kmeans_update(rows, inv_norm, torch.from_numpy(joint).to(rows.device), n, d, k, centres)      # -1: skipped
+    scores = _ops.kmeans_scores(rows, inv_norm, n, d, centres, k)
+    out = dict(k=k, rows=rows, inv_norm=inv_norm, n_c=n_c, n_s=n_s, d=d, seeds=seeds, centres=centres, scores=scores,
+               grid_scores=[], strokes=[], labels=[], x=[])
+    counts = []
+    for image, strokes, part, grid in ((content, content_strokes, scores[:n_c], grids[0]),
+                                       (style, style_strokes, scores[n_c:], grids[1])):
+        img = _rgb(image, "image")
+        grid_scores = part.reshape(grid[0], grid[1], k).clone()              # its own allocation: 16-byte aligned
+        on_image = torch.from_numpy(resize_strokes(strokes, int(img.shape[0]), int(img.shape[1]))).to(img.device)
+        label, count, x = _ops.scribble_labels(img, on_image, grid_scores, tau, lam, sigma, int(iters), iters_per_launch, planes)
+        out["grid_scores"].append(grid_scores)
+        out["strokes"].append(on_image)
+        out["labels"].append(label)
+        out["x"].append(x)
+        counts.append(count)
+    out["counts"] = torch.stack(counts).cpu().numpy()
+    return out
+
+
+def scribble_masks(params, content: torch.Tensor, style: torch.Tensor, content_strokes: np.ndarray, style_strokes: np.ndarray,
+                   k: int, colours=None, sigma: float = SCRIBBLE_SIGMA, iters: int = SCRIBBLE_ITERS,
+                   min_share: float = AUTO_MASK_MIN_SHARE):
+    """--content_scribbles / --style_scribbles: (content_masks, style_masks) as load_mask returns them -- k (H, W, 1) float
+    0/1 masks per image in ascending colour order, a partition of each image -- from a few strokes per image
+    (scribble_regions).  The strokes are the user's statement: a region left with fewer than min_share of either image's
+    pixels is a ValueError that names its colour (colours: the regions' (r, g, b), load_scribbles), never a fallback."""
+    found = scribble_regions(params, content, style, content_strokes, style_strokes, k, sigma, iters)
+    for i, (name, label) in enumerate(zip(("content", "style"), found["labels"])):
+        pixels = int(label.numel())
+        for r in np.flatnonzero(found["counts"][i] < min_share * pixels):
+            colour = f"region {r}" if colours is None else f"the region of colour {tuple(colours[r])}"
+            raise ValueError(f"scribbles: {colour} holds {int(found['counts'][i][r])} of the {name} image's {pixels} pixels, "
+                             f"fewer than {min_share:.3f} of them; draw a longer stroke or drop the colour")
+    return tuple([(label == r).float()[..., None] for r in range(k)] for label in found["labels"])
 
 
 # ----------------------------------------------------------------------------- region tracking (DESIGN.md section 19)

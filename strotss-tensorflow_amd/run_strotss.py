@@ -70,9 +70,26 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
                     grid's blocks.  A region left with less than 1/32 of either image: a warning and the unrefined masks.
   --refine_sigma S  with --refine_masks: the colour scale of the vote on [0, 1] colours, 0.01..1 (default 0.1); smaller
                     follows weaker edges
-  --save_masks DIR  with --auto_masks: write the regions to DIR as content_mask.png and style_mask.png in the colour-coded
-                    format of --content_mask / --style_mask (region r in the r-th of the eight colours with channels in
-                    {0, 255}, ascending (r, g, b)), to be edited and handed back through those two flags
+  --save_masks DIR  with --auto_masks (or the scribble files): write the regions to DIR as content_mask.png and
+                    style_mask.png in the colour-coded format of --content_mask / --style_mask (region r in the r-th of
+                    the eight colours with channels in {0, 255}, ascending (r, g, b)), to be edited and handed back through
+                    those two flags
+  --content_scribbles C.png --style_scribbles S.png
+                    region guidance from a few strokes per image.  Both files are RGB images in the
+                    colour-coded format of --content_mask / --style_mask, of any size (they are brought to their image's
+                    size by nearest neighbour, so a stroke should be at least 1/256 of the file's longer side wide, or it
+                    may fall between the samples: an error then says so): black means "no stroke", each of the other seven corner colours is a region,
+                    drawn as a short stroke on the content and one of the same colour on the style.  The cells of both
+                    images' feature grids under the strokes give one centre per colour; every pixel's likeness to the
+                    centres and the image's own edges then carry the strokes over the whole image (a screened random walker,
+                    128 Jacobi sweeps on the GPU).  2..7 colours, every colour in both files.  A region left with less than
+                    1/32 of either image is an error that names its colour.  --save_masks DIR writes the regions found.
+                    Combines and excludes as --auto_masks does; not with --auto_masks or --video.
+  --scribble_sigma S
+                    with the scribble files: the colour scale of the edge weights on [0, 1] colours, 0.01..1 (default 0.1, not
+                    tuned); smaller stops the strokes at weaker edges
+  --scribble_iters T
+                    with the scribble files: the number of sweeps, 1..1024 (default 128, not tuned)
   --track_masks     with --auto_masks K --video: the regions of the first frame followed through the sequence (DESIGN.md
                     section 19).  Frame 1 is clustered jointly with style_path as a single image is; its regions, their
                     centres and the style masks then stay.  Every later frame's grid cells are assigned to those centres,
@@ -344,16 +361,58 @@ def _track_masks_input(args):
     return float(beta)
 
 
+def _scribble_masks_input(args):
+    """--content_scribbles C --style_scribbles S, --scribble_sigma, --scribble_iters: (C, S, sigma, iters) with the defaults
+    filled in, or None without the two files.  ValueError, before anything is loaded: one file without the other,
+    --scribble_sigma / --scribble_iters without the files or outside 0.01..1 / 1..1024, the files together with
+    --content_mask / --style_mask, --auto_masks, --style_mix, --video, --strips or under torchrun with WORLD_SIZE > 1."""
+    c, s_ = getattr(args, "content_scribbles", None), getattr(args, "style_scribbles", None)
+    sigma, iters = getattr(args, "scribble_sigma", None), getattr(args, "scribble_iters", None)
+    if bool(c) != bool(s_):
+        raise ValueError("--content_scribbles and --style_scribbles go together: every region needs a stroke in both images")
+    if not c:
+        for flag, value in (("--scribble_sigma", sigma), ("--scribble_iters", iters)):
+            if value is not None:
+                raise ValueError(f"{flag} needs --content_scribbles and --style_scribbles")
+        return None
+    try:
+        strotss.check_scribble_parameters(None if sigma is None else float(sigma), None)
+    except (TypeError, ValueError):
+        lo, hi = strotss.SCRIBBLE_SIGMA_RANGE
+        raise ValueError(f"--scribble_sigma takes a colour scale in {lo}..{hi:g}, got {sigma!r}") from None
+    try:
+        strotss.check_scribble_parameters(None, iters)
+    except (TypeError, ValueError):
+        lo, hi = strotss.SCRIBBLE_ITERS_RANGE
+        raise ValueError(f"--scribble_iters takes a number of sweeps in {lo}..{hi}, got {iters!r}") from None
+    if getattr(args, "content_mask", None) or getattr(args, "style_mask", None):
+        raise ValueError("scribbles cannot be combined with --content_mask / --style_mask: the regions are grown or given")
+    if getattr(args, "auto_masks", None) is not None:
+        raise ValueError("scribbles cannot be combined with --auto_masks: the regions are grown from strokes or clustered")
+    if getattr(args, "style_mix", None):
+        raise ValueError("scribbles cannot be combined with --style_mix: masks and blends exclude each other")
+    if getattr(args, "video", False):
+        raise ValueError("scribbles cannot be combined with --video: the strokes belong to one image")
+    if getattr(args, "strips", False):
+        raise ValueError("scribbles cannot be combined with --strips")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("scribbles run on one GPU: not under torchrun with WORLD_SIZE > 1")
+    return (c, s_, strotss.SCRIBBLE_SIGMA if sigma is None else float(sigma),
+            strotss.SCRIBBLE_ITERS if iters is None else int(iters))
+
+
 def _auto_masks_input(args):
     """--auto_masks K, --save_masks DIR: (K, DIR or None), or None without --auto_masks.  ValueError, before anything is
     loaded: K outside 2..8, --save_masks without --auto_masks, --auto_masks with --content_mask / --style_mask, --style_mix,
     --video without --track_masks, --strips or under torchrun with WORLD_SIZE > 1, and the refusals of --refine_masks /
-    --refine_sigma (_refine_masks_input) and of --track_masks / --mask_inertia (_track_masks_input)."""
+    --refine_sigma (_refine_masks_input), of --track_masks / --mask_inertia (_track_masks_input) and of the scribble flags
+    (_scribble_masks_input, with which --save_masks is allowed too)."""
     k, save = getattr(args, "auto_masks", None), getattr(args, "save_masks", None)
     _refine_masks_input(args)
     track = _track_masks_input(args)
+    scribbles = _scribble_masks_input(args)
     if k is None:
-        if save:
+        if save and scribbles is None:
             raise ValueError("--save_masks needs --auto_masks (it writes the regions the run finds)")
         return None
     lo, hi = strotss.AUTO_MASK_RANGE
@@ -745,6 +804,9 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
     frame from the caller (--track_masks), in place of the regions found or loaded here."""
     from nn import parallel
     level, first = int(args.level), int(getattr(args, "start_level", 0))
+    scribbles = _scribble_masks_input(args)
+    if scribbles:                                            # the stroke files' own refusals, before any image is loaded
+        strokes = strotss.load_scribbles(scribbles[0], scribbles[1])
     content = utils.load_image(content_path, max_size=args.max_size)
     style_paths, style_weights = _style_inputs(args)
     styles = [utils.load_image(p, max_size=args.max_size) for p in style_paths]
@@ -761,6 +823,12 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
             utils.logger.info(f'Found {len(content_masks)} regions.')
             if auto[1]:
                 strotss.save_masks(auto[1], content_masks, style_masks)
+    elif scribbles:                                          # regions grown from the strokes, on the images as loaded
+        content_masks, style_masks = strotss.scribble_masks(vgg.params, content, styles[0], strokes[0], strokes[1],
+                                                            len(strokes[2]), strokes[2], scribbles[2], scribbles[3])
+        utils.logger.info(f'Grew {len(content_masks)} regions from the strokes.')
+        if getattr(args, "save_masks", None):
+            strotss.save_masks(args.save_masks, content_masks, style_masks)
     else:
         content_masks, style_masks = _load_masks(args)
     # --preserve_color match / transfer, before any resize: every scale samples the recoloured styles
@@ -997,6 +1065,16 @@ _FLAGS = (
     (("--save_masks",), dict(type=str, default=None, metavar='DIR',
                              help="with --auto_masks: write content_mask.png and style_mask.png there, in the colour-coded "
                                   "format of --content_mask / --style_mask")),
+    (("--content_scribbles",), dict(type=str, default=None, metavar='PATH',
+                                    help="region guidance from strokes: an image with a stroke per region on the content, in "
+                                         "the corner colours of --content_mask (black: no stroke)")),
+    (("--style_scribbles",), dict(type=str, default=None, metavar='PATH',
+                                  help="with --content_scribbles: strokes of the same colours on the style")),
+    (("--scribble_sigma",), dict(type=float, default=None, metavar='S',
+                                 help=f"with the scribble files: colour scale of the edge weights on [0, 1] colours, 0.01..1 "
+                                      f"(default {strotss.SCRIBBLE_SIGMA:g}, not tuned)")),
+    (("--scribble_iters",), dict(type=int, default=None, metavar='T',
+                                 help=f"with the scribble files: sweeps, 1..1024 (default {strotss.SCRIBBLE_ITERS}, not tuned)")),
     (("--track_masks",), dict(action='store_true', help="with --auto_masks K --video: follow the first frame's regions through "
                                                         "the sequence along the backward flow instead of refusing the pair")),
     (("--mask_inertia",), dict(type=float, default=None, metavar='B',
