@@ -466,6 +466,23 @@ int strotss_remd_cos_fwd_bwd_panels(const float* style, const float* rs, const v
 int strotss_palette_remd_fwd_bwd(const float* style, int ns, const float* pred, int n, int ld,
                                  int rgb_to_yuv, float gscale, float* gpred, float* loss_out, int flags,
                                  void* workspace, size_t workspace_bytes, void* stream);
+/* The sliced 1-Wasserstein distance in the place of the palette relaxed EMD.  With
+ * y_i = yuv(pred_i[:3]), s_j = yuv(style_j[:3]) (rgb_to_yuv as in strotss_palette_remd_fwd_bwd) and n_proj unit directions
+ * theta_p of R^3 (dirs: n_proj x 3 floats in device memory; nn/rand.py:palette_directions makes the engine's),
+ *     a[p][i] = <theta_p, y_i>,  b[p][j] = <theta_p, s_j>,  both sorted ascending by (value, row; -0 counts as +0),
+ *     W_p = sum_ij len_ij |a_(i) - b_(j)|,  len_ij = max(0, min((i+1) ns, (j+1) n) - max(i ns, j n)) / (n ns),
+ *     loss_out[0] = (2 / (sqrt(3) n_proj)) sum_p W_p,
+ *     gpred[i][:3] += gscale * dloss/dpred_i[:3] (through the sort, piecewise constant; sign(0) = 0), each added value
+ *     rounded on its own; rows >= n and columns >= 3 of gpred are not written.
+ * 2 launches, no float atomics: the same bits on every call and stream.  Refusals before any launch, outputs and workspace
+ * untouched: STROTSS_EINVAL (null pointers, non-positive sizes, ld < 3, a workspace below
+ * strotss_palette_sliced_workspace_bytes), STROTSS_ERANGE (n or ns above 1024, n_proj above 1024).  As
+ * strotss_palette_remd_fwd_bwd, the entry reads three scalars a row and takes every ld >= 3 (no STROTSS_EALIGN).  The query
+ * returns 0 for arguments the entry refuses. */
+size_t strotss_palette_sliced_workspace_bytes(int ns, int n, int n_proj);
+int strotss_palette_sliced_fwd_bwd(const float* style, int ns, const float* pred, int n, int ld, int rgb_to_yuv,
+                                   const float* dirs, int n_proj, float gscale, float* gpred, float* loss_out,
+                                   void* workspace, size_t workspace_bytes, void* stream);
 /* relaxed_emd(style, pred, distance) for the other two entries of dist_metrics (losses.py:27-28) at ANY width d:
  * metric STROTSS_METRIC_L2 -> l2_distance (losses.py:18-24), STROTSS_METRIC_BOTH -> cosine + l2.  Same reductions and
  * tie rules as strotss_remd_cos_fwd_bwd (tf.reduce_min splits among ties, tf.maximum -> first argument);

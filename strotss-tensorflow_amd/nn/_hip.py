@@ -155,6 +155,8 @@ SIGNATURES = {
     "strotss_selfsim_pred_panels": (_I, [_P, _Z, _I, _I, C.POINTER(_P), C.POINTER(_P)]),
     "strotss_remd_cos_fwd_bwd_panels": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _Z, _P]),
     "strotss_palette_remd_fwd_bwd": (_I, [_P, _I, _P, _I, _I, _I, _F, _P, _P, _I, _P, _Z, _P]),
+    "strotss_palette_sliced_workspace_bytes": (_Z, [_I, _I, _I]),
+    "strotss_palette_sliced_fwd_bwd": (_I, [_P, _I, _P, _I, _I, _I, _P, _I, _F, _P, _P, _P, _Z, _P]),
     "strotss_remd_metric_workspace_bytes": (_Z, [_I, _I]),
     "strotss_remd_metric_fwd_bwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _F, _P, _P, _I, _P, _Z, _P]),
     "strotss_step_losses_available": (_I, []),

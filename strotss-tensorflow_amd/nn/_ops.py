@@ -1232,6 +1232,19 @@ def palette_remd_fwd_bwd(style, ns, pred, n, gscale, gpred, loss_out, rgb_to_yuv
                                          ptr(gpred), ptr(loss_out), int(swapped), ptr(ws), nb, stream_ptr()), "palette_remd_fwd_bwd")
 
 
+def palette_sliced_fwd_bwd(style, ns, pred, n, dirs, gscale, gpred, loss_out, rgb_to_yuv=True):
+    """The sliced palette term (strotss_palette_sliced_fwd_bwd) where palette_remd_fwd_bwd stands:
+    dirs an (n_proj, 3) float32 device tensor of unit directions (rand.palette_directions)"""
+    l = _hip.lib()
+    assert style.shape[1] == pred.shape[1] and dirs.dtype == torch.float32 and dirs.is_contiguous() and dirs.shape[1] == 3
+    n_proj = int(dirs.shape[0])
+    nb = l.strotss_palette_sliced_workspace_bytes(ns, n, n_proj)
+    ws = workspaces.get("palette_sliced", nb, pred.device)
+    check(l.strotss_palette_sliced_fwd_bwd(ptr(style), ns, ptr(pred), n, pred.shape[1], int(rgb_to_yuv), ptr(dirs), n_proj,
+                                           gscale, ptr(gpred), ptr(loss_out), ptr(ws), nb, stream_ptr()),
+          "palette_sliced_fwd_bwd")
+
+
 REMD_METRICS = {"l2": 1, "both": 2}      # STROTSS_METRIC_L2 / STROTSS_METRIC_BOTH (include/strotss_hip.h)
 
 

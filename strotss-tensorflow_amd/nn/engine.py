@@ -19,7 +19,7 @@ from typing import List, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from . import _hip, _ops, parallel
+from . import _hip, _ops, parallel, rand
 from .model import VGGParams, VGGTrunk
 
 
@@ -102,6 +102,22 @@ def check_style_transport(style_transport, sinkhorn_l, sinkhorn_iters, sliced_pr
         raise ValueError(f"sinkhorn_l must be at most {SINKHORN_LOG_MAX_L:g} with sinkhorn_log, got {sinkhorn_l!r}")
 
 
+PALETTE_TRANSPORTS = ("remd", "sliced")
+PALETTE_MAX_PROJECTIONS = 1024           # the library's range
+DEFAULT_PALETTE_PROJECTIONS = 64         # not tuned for image quality: the lattice estimates |v| to 1.5 % there
+
+
+def check_palette_transport(palette_transport, palette_projections=DEFAULT_PALETTE_PROJECTIONS) -> None:
+    """ValueError unless the palette transport is a known one and palette_projections a whole number in
+    1..PALETTE_MAX_PROJECTIONS (the library's range)"""
+    if palette_transport not in PALETTE_TRANSPORTS:
+        raise ValueError(f"palette_transport must be one of {PALETTE_TRANSPORTS}, got {palette_transport!r}")
+    if isinstance(palette_projections, bool) or not isinstance(palette_projections, (int, np.integer)) or \
+            not 1 <= palette_projections <= PALETTE_MAX_PROJECTIONS:
+        raise ValueError(f"palette_projections must be a whole number in 1..{PALETTE_MAX_PROJECTIONS}, "
+                         f"got {palette_projections!r}")
+
+
 @dataclass
 class TemporalTarget:
     """The temporal term of a frame sequence at one scale: `target` (h, w, 3) the warped previous
@@ -181,7 +197,15 @@ class StepEngine:
 
     `sinkhorn_log` (with "sinkhorn" only): the same term with the scalings kept as logarithms, which
     stays a transport cost where exp(-sinkhorn_l * cost) underflows and the linear form's clamps act (it is guaranteed
-    clamp-free only to sinkhorn_l = 13.8); sinkhorn_l up to SINKHORN_LOG_MAX_L.  False runs the linear form unchanged."""
+    clamp-free only to sinkhorn_l = 13.8); sinkhorn_l up to SINKHORN_LOG_MAX_L.  False runs the linear form unchanged.
+
+    `palette_transport`: "remd" (the palette relaxed EMD, the code it always ran, launch for launch) or "sliced" (DESIGN.md
+    section 25): the sliced 1-Wasserstein distance between the YUV colours over `palette_projections` fixed directions
+    (rand.palette_directions, one device buffer, the same on every step) stands where the palette relaxed EMD stands, for
+    every region and every style of a blend, with the same weight and in the same scalar slot (l_palette, also returned as
+    l_palette_sliced).  It conserves mass, which the relaxed EMD does not.  With "sliced" every `style_transport` takes the
+    separate entries: with "remd" that is their 21 launches (19 with the new term's 2 in place of the palette relaxed EMD's
+    4), not the grouped call's 13.  One GPU only."""
 
     N_SCALARS = 4   # loss_c, l_moment, l_remd, l_palette per region
 
@@ -193,8 +217,17 @@ class StepEngine:
                  temporal: Optional[Union[TemporalTarget, Sequence[TemporalTarget]]] = None,
                  style_transport: str = "remd", sinkhorn_l: float = DEFAULT_SINKHORN_L,
                  sinkhorn_iters: int = DEFAULT_SINKHORN_ITERS, sliced_projections: int = DEFAULT_SLICED_PROJECTIONS,
-                 sliced_seed: int = 0, sinkhorn_log: bool = False):
+                 sliced_seed: int = 0, sinkhorn_log: bool = False, palette_transport: str = "remd",
+                 palette_projections: int = DEFAULT_PALETTE_PROJECTIONS):
         dev = stylized.device
+        check_palette_transport(palette_transport, palette_projections)
+        if palette_transport == "sliced" and (strips is not None or dist_group is not None):
+            raise ValueError("the sliced palette term runs on one GPU: image strips and region sharding are not supported "
+                             "with it")
+        self.palette_transport, self.palette_projections = palette_transport, int(palette_projections)
+        # the sliced palette term's directions: fixed for the life of the engine (a captured graph reads them at replay)
+        self._palette_dirs = (torch.from_numpy(rand.palette_directions(self.palette_projections)).to(dev).contiguous()
+                              if palette_transport == "sliced" else None)
         check_style_transport(style_transport, sinkhorn_l, sinkhorn_iters, sliced_projections, sinkhorn_log)
         self.sinkhorn_log = bool(sinkhorn_log)
         if style_transport == "sinkhorn" and (strips is not None or dist_group is not None):
@@ -434,7 +467,8 @@ class StepEngine:
         outs = (sc[1:], sc[2:], sc[3:]) if len(targets) == 1 else tuple(self._style_scalars[r])
         sinkhorn = self.style_transport == "sinkhorn"      # the separate entries, Sinkhorn where the cosine REMD stands
         sliced = self.style_transport == "sliced"          # likewise
-        if not sinkhorn and not sliced and self._style_sets[r] is not None and _ops.step_losses_available():
+        pal_sliced = self.palette_transport == "sliced"    # the separate entries, the sliced term where the palette REMD stands
+        if not sinkhorn and not sliced and not pal_sliced and self._style_sets[r] is not None and _ops.step_losses_available():
             # one call: 13 launches instead of 21, the three forward GEMMs in one of them (bit for bit the separate entries
             # below for one style); a blend in as many launches
             _ops.step_losses_cw_fwd_bwd(pf, cf, n, self.d, cw, self._style_sets[r], self.alpha * base, base, base,
@@ -456,7 +490,11 @@ class StepEngine:
             else:
                 _ops.remd_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, base * w, gp,
                                                     outs[1][k:])
-            _ops.palette_remd_fwd_bwd(st.feats, st.ns, pf, n, self.inv_alpha * base * w, gp, outs[2][k:])
+            if pal_sliced:
+                _ops.palette_sliced_fwd_bwd(st.feats, st.ns, pf, n, self._palette_dirs, self.inv_alpha * base * w, gp,
+                                            outs[2][k:])
+            else:
+                _ops.palette_remd_fwd_bwd(st.feats, st.ns, pf, n, self.inv_alpha * base * w, gp, outs[2][k:])
 
     def _scatter_maps(self, r: int):
         """descriptor + sample count of region r's tap adjoint: strips (recompute margin) = this rank's block of the samples
@@ -764,6 +802,8 @@ class StepEngine:
             out["l_sinkhorn"] = out["l_remd"]
         if self.style_transport == "sliced":      # likewise the sliced term
             out["l_sliced"] = out["l_remd"]
+        if self.palette_transport == "sliced":    # the slot of l_palette holds the sliced palette term
+            out["l_palette_sliced"] = out["l_palette"]
         if per_style is not None:
             out["per_style"] = per_style         # one dict per style of the blend: its weight and unweighted terms
         t = self._temporal

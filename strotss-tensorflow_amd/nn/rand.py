@@ -119,6 +119,19 @@ def sliced_signs(seed: int, t: int, n_proj: int, d: int) -> np.ndarray:
     return (2.0 * bits.reshape(n_proj, -1)[:, :d].astype(np.float32) - 1.0).astype(np.float32)
 
 
+def palette_directions(n_proj: int) -> np.ndarray:
+    """The directions of the sliced palette term (strotss_palette_sliced_fwd_bwd): (n_proj, 3) float32
+    unit vectors, a Fibonacci lattice on the upper hemisphere (antipodes project alike).  For k < P:
+    z_k = (k + 0.5) / P, phi_k = k pi (3 - sqrt(5)), theta_k = (sqrt(1 - z_k^2) cos phi_k, sqrt(1 - z_k^2) sin phi_k, z_k),
+    computed in float64 and rounded to float32 once.  No seed: the same on every step and run."""
+    n_proj = int(n_proj)
+    k = np.arange(n_proj, dtype=np.float64)
+    z = (k + 0.5) / n_proj
+    phi = k * (np.pi * (3.0 - np.sqrt(5.0)))
+    r = np.sqrt(1.0 - z * z)
+    return np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1).astype(np.float32)
+
+
 SEED = 0
 np_rng = np.random.default_rng(SEED)          # reference: np_rng (unused there as well)
 index_rng = PhiloxStream(SEED)                # replaces tf_rng for the sampling coordinates

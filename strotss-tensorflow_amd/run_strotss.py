@@ -121,6 +121,19 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
                     and excludes as sinkhorn does.
   --sliced_projections P
                     with --style_transport sliced: the number of directions, 1..1024 (default 256, not tuned)
+  --palette_transport {remd,sliced}
+                    the palette term of the style loss.  remd (default): the relaxed EMD between the
+                    YUV colours of the style's and the result's samples, every colour matched to its nearest neighbour: a
+                    result with one blue sample among red ones matches a style that is half red and half blue at no
+                    cost.  sliced: the sliced
+                    Wasserstein distance between the two colour sets -- projected on P fixed directions, sorted and matched
+                    by rank -- which conserves mass: the style's colours are matched in proportion.  2 launches per region
+                    and step; with --style_transport remd the step then runs its separate loss launches, not the grouped 13.
+                    Combines with masks, --auto_masks, the scribble files, --style_mix, --video, --content_weight_map and
+                    every --style_transport; one GPU, not with --strips.
+  --palette_projections P
+                    with --palette_transport sliced: the number of directions, 1..1024 (default 64, not tuned for image
+                    quality; a Fibonacci lattice on the hemisphere, the same on every step, independent of --seed)
   --strips          under torchrun (one process per GPU): ONE image on all GPUs -- every rank runs the trunk on its strip
                     of the image (+ halo) at the scales where that pays, two all-reduces per step (nn/parallel.py);
                     rank 0 writes the output
@@ -299,6 +312,30 @@ def _style_transport_input(args) -> dict:
             raise ValueError("--style_transport sinkhorn runs on one GPU: not under torchrun with WORLD_SIZE > 1")
     kw = dict(style_transport=transport, sinkhorn_l=float(reg), sinkhorn_iters=int(iters))
     return dict(kw, sinkhorn_log=True) if log else kw
+
+
+def _palette_transport_input(args) -> dict:
+    """--palette_transport, --palette_projections: StepEngine's keywords for them, none for remd (the engine is then built as
+    it always was).  ValueError, before anything is loaded: an unknown transport, a direction count without
+    --palette_transport sliced or out of range, and with sliced --strips or WORLD_SIZE > 1."""
+    transport = getattr(args, "palette_transport", None) or "remd"
+    proj = getattr(args, "palette_projections", None)
+    if transport not in strotss_engine.PALETTE_TRANSPORTS:
+        raise ValueError(f"--palette_transport takes one of {strotss_engine.PALETTE_TRANSPORTS}, got {transport!r}")
+    if transport != "sliced":
+        if proj is not None:
+            raise ValueError("--palette_projections needs --palette_transport sliced")
+        return {}
+    proj = strotss_engine.DEFAULT_PALETTE_PROJECTIONS if proj is None else proj
+    if isinstance(proj, bool) or not isinstance(proj, (int, np.integer)) or \
+            not 1 <= proj <= strotss_engine.PALETTE_MAX_PROJECTIONS:
+        raise ValueError(f"--palette_projections must be a whole number in 1..{strotss_engine.PALETTE_MAX_PROJECTIONS}, "
+                         f"got {proj!r}")
+    if getattr(args, "strips", False):
+        raise ValueError("--palette_transport sliced cannot be combined with --strips")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("--palette_transport sliced runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    return dict(palette_transport=transport, palette_projections=int(proj))
 
 
 def _photo_smooth_input(args):
@@ -758,6 +795,7 @@ def run(args: argparse.Namespace, trace=None):
     result -- what the parity test of the schedule compares with the oracle's run_scales.  --video: run_video."""
     _auto_masks_input(args)                                  # refusals first, --video among them
     _style_transport_input(args)
+    _palette_transport_input(args)
     if getattr(args, "video", False):
         return run_video(args, trace)
     timer = utils.Timer()
@@ -836,7 +874,7 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
     cw_map = strotss.load_content_weight_map(cw_path) if cw_path else None
     sampling = strotss.Sampling(SAMPLE_SIZE)
     masked = bool(getattr(args, "content_mask", None))
-    transport = _style_transport_input(args)
+    transport = dict(_style_transport_input(args), **_palette_transport_input(args))
 
     # alpha = 16 (x3500 with Keras weights), halved after every scale -- also after skipped ones
     alpha = args.alpha * 16.0 * (3500 if args.use_keras_weight else 1) / 2.0 ** first
@@ -1097,6 +1135,14 @@ _FLAGS = (
     (("--sliced_projections",), dict(type=int, default=None, metavar='P',
                                      help=f"with --style_transport sliced: directions, 1..{strotss_engine.SLICED_MAX_PROJECTIONS} "
                                           f"(default {strotss_engine.DEFAULT_SLICED_PROJECTIONS}, not tuned)")),
+    (("--palette_transport",), dict(type=str, default="remd", choices=strotss_engine.PALETTE_TRANSPORTS,
+                                    help="the palette term of the style loss: the relaxed EMD between the samples' YUV "
+                                         "colours, or their sliced Wasserstein distance (mass-conserving: the style's "
+                                         "colours are matched in proportion)")),
+    (("--palette_projections",), dict(type=int, default=None, metavar='P',
+                                      help=f"with --palette_transport sliced: directions, "
+                                           f"1..{strotss_engine.PALETTE_MAX_PROJECTIONS} (default "
+                                           f"{strotss_engine.DEFAULT_PALETTE_PROJECTIONS}, not tuned for image quality)")),
     (("--strips",), dict(action='store_true', help="under torchrun: shard ONE image over the GPUs by image strips")),
     (("--halo",), dict(action='store_true', help="with --strips: per-layer halo EXCHANGE with the neighbouring ranks (16-row "
                                                  "windows margins, one row per layer and direction) instead of a 128-row recompute margin")),
