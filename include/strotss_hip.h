@@ -614,6 +614,51 @@ int strotss_temporal_multi_fwd_bwd(const float* img, const strotss_temporal_set_
                                    float* loss_out, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Pixel-space priors of the step: a Laplacian detail term against the content and a total variation
+ * --------------------------------------------------------------------------------------- */
+/* P_p of an (h, w, ch) array, ch 1 or 3, p in {1, 2, 4, 8, 16}: out (ceil(h / p), ceil(w / p), ch), cell (i, j) the mean of
+ * the pixels [i p, min((i+1) p, h)) x [j p, min((j+1) p, w)) it covers: every row summed left to right, the row sums added top
+ * to bottom, in float32, the total divided by their count.  ONE launch.  STROTSS_EINVAL: null pointers, h, w <= 0, ch not 1 or 3, 3 h w > INT_MAX;
+ * STROTSS_ERANGE: p not in the set; STROTSS_EALIGN: a pointer not 16-byte aligned. */
+int strotss_pool_mean(const float* img, int h, int w, int ch, int p, float* out, void* stream);
+#define STROTSS_MAX_DETAIL_POOLS 3
+typedef struct {
+  int count;                                       /* 1 .. STROTSS_MAX_DETAIL_POOLS */
+  int pool[STROTSS_MAX_DETAIL_POOLS];              /* distinct values of {1, 2, 4, 8, 16}, ascending */
+  const float* content[STROTSS_MAX_DETAIL_POOLS];  /* P_p(content): (hp, wp, 3), from strotss_pool_mean */
+  const float* weight[STROTSS_MAX_DETAIL_POOLS];   /* cell weights m_p >= 0: (hp, wp), or NULL for 1 */
+  float gscale[STROTSS_MAX_DETAIL_POOLS];
+} strotss_detail_set_t;
+/* bytes of the workspace of strotss_detail_fwd_bwd for any set (0 for h, w <= 0 or 3 h w > INT_MAX) */
+size_t strotss_detail_workspace_bytes(int h, int w);
+/* The Laplacian detail term of one step (img, gimg: (h, w, 3)).  Per pool size p = pool[j], hp = ceil(h / p),
+ * wp = ceil(w / p), L the graph Laplacian of the hp x wp 4-neighbour grid ((L u)(k) = deg(k) u(k) - sum of the neighbours
+ * inside the grid), D = L (P_p(img) - content[j]) per channel:
+ *   loss_out[j] = (1 / (3 hp wp)) sum_k m(k) sum_ch D(k, ch)^2,
+ *   gimg(q, ch) += (2 gscale[j] / (3 hp wp cnt(k))) (L (m D))(k, ch) for every pixel q of cell k, cnt(k) its pixel count,
+ * the pool sizes in ascending order.  Per pool size ONE launch, after one strotss_pool_mean launch of img into the workspace
+ * when p > 1.  A gradient value that is exactly 0 is not added: gscale[j] == 0 for every j stores nothing, a cell whose own
+ * and whose neighbours' weights are 0 leaves its pixels' gimg bit for bit, and img == content pixel for pixel gives
+ * loss_out[j] == 0 and leaves gimg bit for bit.  Fixed-order reductions, no float atomics.  workspace:
+ * strotss_detail_workspace_bytes(h, w) bytes, 16-byte aligned, ZEROED before its first use (one call at a time).
+ * Refused before anything is launched: STROTSS_EINVAL (null img, set, gimg, loss_out, workspace or content[j], h, w <= 0,
+ * 3 h w > INT_MAX), STROTSS_ERANGE (count outside 1 .. STROTSS_MAX_DETAIL_POOLS, a pool size not in the set or not
+ * ascending), STROTSS_EALIGN (a pointer not 16-byte aligned). */
+int strotss_detail_fwd_bwd(const float* img, int h, int w, const strotss_detail_set_t* set, float* gimg, float* loss_out,
+                           void* workspace, void* stream);
+/* bytes of the workspace of strotss_tv_fwd_bwd (0 for h, w <= 0 or 3 h w > INT_MAX) */
+size_t strotss_tv_workspace_bytes(int h, int w);
+/* The total variation of one step in ONE launch (img, gimg: (h, w, 3)): dx(r, s) = img(r, s+1) - img(r, s), 0 in the last
+ * column, dy likewise, 0 in the last row, per channel;
+ *   loss_out[0] = (1 / (3 h w)) sum_q sum_ch (sqrt(dx^2 + dy^2 + eps^2) - eps),   gimg += gscale * dloss/dimg.
+ * gscale == 0 stores nothing; a gradient value that is exactly 0 is not added (a constant image: loss 0, gimg bit for bit).
+ * Fixed-order reduction, no float atomics.  workspace: strotss_tv_workspace_bytes(h, w) bytes, 16-byte aligned, ZEROED before
+ * its first use.  Refused before anything is launched: STROTSS_EINVAL (null pointers, h, w <= 0, 3 h w > INT_MAX),
+ * STROTSS_ERANGE (eps not finite or <= 0), STROTSS_EALIGN (a pointer not 16-byte aligned). */
+int strotss_tv_fwd_bwd(const float* img, int h, int w, float eps, float gscale, float* gimg, float* loss_out,
+                       void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Optical flow between two frames: what strotss_flow_warp consumes, computed by the library
  * --------------------------------------------------------------------------------------- */
 /* Coarse-to-fine Horn-Schunck with warping, solved by Jacobi iterations (Meinhardt-Llopis, Sanchez, Kondermann, IPOL 2013,

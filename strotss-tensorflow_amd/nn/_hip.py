@@ -82,6 +82,17 @@ class TemporalSetT(C.Structure):
                 ("gscale", C.c_float * MAX_TEMPORAL)]
 
 
+MAX_DETAIL_POOLS = 3
+DETAIL_POOLS = (1, 2, 4, 8, 16)      # the pool sizes strotss_pool_mean and strotss_detail_fwd_bwd take
+
+
+class DetailSetT(C.Structure):
+    """strotss_detail_set_t (include/strotss_hip.h): the pool sizes of the Laplacian detail term, ascending"""
+    _fields_ = [("count", C.c_int), ("pool", C.c_int * MAX_DETAIL_POOLS),
+                ("content", C.c_void_p * MAX_DETAIL_POOLS), ("weight", C.c_void_p * MAX_DETAIL_POOLS),
+                ("gscale", C.c_float * MAX_DETAIL_POOLS)]
+
+
 class FlowParamsT(C.Structure):
     """strotss_flow_params_t (include/strotss_hip.h): the parameters of strotss_optical_flow"""
     _fields_ = [("alpha2", C.c_float), ("warps", C.c_int), ("iters", C.c_int), ("min_side", C.c_int),
@@ -176,6 +187,11 @@ SIGNATURES = {
     "strotss_temporal_long_certainty": (_I, [_P, _I, _I, _I, _P, _P]),
     "strotss_temporal_multi_workspace_bytes": (_Z, [_I, _I, _I]),
     "strotss_temporal_multi_fwd_bwd": (_I, [_P, C.POINTER(TemporalSetT), _I, _I, _P, _P, _P, _P]),
+    "strotss_pool_mean": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "strotss_detail_workspace_bytes": (_Z, [_I, _I]),
+    "strotss_detail_fwd_bwd": (_I, [_P, _I, _I, C.POINTER(DetailSetT), _P, _P, _P, _P]),
+    "strotss_tv_workspace_bytes": (_Z, [_I, _I]),
+    "strotss_tv_fwd_bwd": (_I, [_P, _I, _I, _F, _F, _P, _P, _P, _P]),
     "strotss_flow_default_params": (None, [C.POINTER(FlowParamsT)]),
     "strotss_flow_workspace_bytes": (_Z, [_I, _I, C.POINTER(FlowParamsT)]),
     "strotss_optical_flow": (_I, [_P, _P, _I, _I, C.POINTER(FlowParamsT), _P, _P, _Z, _P]),

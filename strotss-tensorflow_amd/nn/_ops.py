@@ -181,6 +181,95 @@ def temporal_multi_fwd_bwd(img: torch.Tensor, targets: Sequence[torch.Tensor], c
                                                     stream_ptr()), "temporal_multi_fwd_bwd")
 
 
+TV_EPS = 1.0 / 255.0        # the total variation's smoothing: one grey level; a convention, not tuned
+
+
+def pooled_shape(h: int, w: int, p: int) -> Tuple[int, int]:
+    """(ceil(h / p), ceil(w / p)): the cell grid of pool size p"""
+    return -(-int(h) // int(p)), -(-int(w) // int(p))
+
+
+def check_detail_pools(pools) -> List[int]:
+    """the pool sizes of the detail term as a list: 1..MAX_DETAIL_POOLS distinct values of DETAIL_POOLS, ascending
+    (ValueError otherwise)"""
+    ps = list(pools) if isinstance(pools, (list, tuple)) else None
+    if ps is None or not 1 <= len(ps) <= _hip.MAX_DETAIL_POOLS or \
+            any(isinstance(p, bool) or not isinstance(p, (int, np.integer)) or int(p) not in _hip.DETAIL_POOLS for p in ps) or \
+            any(int(b) <= int(a) for a, b in zip(ps, ps[1:])):
+        raise ValueError(f"detail pool sizes must be 1..{_hip.MAX_DETAIL_POOLS} distinct values of {_hip.DETAIL_POOLS}, "
+                         f"ascending, got {pools!r}")
+    return [int(p) for p in ps]
+
+
+def pool_mean(img: torch.Tensor, p: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """P_p(img) (strotss_pool_mean): img (h, w, ch) or (1, h, w, ch), ch 1 or 3 -> (hp, wp, ch), every
+    cell the mean of the pixels it covers"""
+    require(img, "image to pool")
+    h, w, ch = hwc(img)
+    assert img.numel() == h * w * ch
+    hp, wp = pooled_shape(h, w, p)
+    if out is None:
+        out = torch.empty((hp, wp, ch), dtype=torch.float32, device=img.device)
+    require(out, "pooled image")
+    assert out.numel() == hp * wp * ch
+    check(_hip.lib().strotss_pool_mean(ptr(img), h, w, ch, int(p), ptr(out), stream_ptr()), "pool_mean")
+    return out
+
+
+def detail_workspace(h: int, w: int, device) -> torch.Tensor:
+    """a zeroed workspace of strotss_detail_fwd_bwd for (h, w) (as temporal_workspace)"""
+    nb = int(_hip.lib().strotss_detail_workspace_bytes(int(h), int(w)))
+    return torch.zeros(max(nb, 16), dtype=torch.uint8, device=device)
+
+
+def detail_fwd_bwd(img: torch.Tensor, pools: Sequence[int], contents: Sequence[torch.Tensor],
+                   weights: Sequence[Optional[torch.Tensor]], gscales: Sequence[float], gimg: torch.Tensor,
+                   loss_out: torch.Tensor, workspace: torch.Tensor) -> None:
+    """loss_out[j] = the Laplacian detail term of pool size pools[j], gimg += sum_j gscales[j] * dloss_j/dimg
+    (strotss_detail_fwd_bwd; img, gimg (h, w, 3) or (1, h, w, 3), contents[j] = pool_mean(content, pools[j]), weights[j] the
+    (hp, wp) cell weights or None).  workspace: detail_workspace(h, w)."""
+    count = len(pools)
+    if not 1 <= count <= _hip.MAX_DETAIL_POOLS or len(contents) != count or len(weights) != count or len(gscales) != count:
+        raise ValueError(f"{count} pool sizes, {len(contents)} pooled contents, {len(weights)} cell weights, {len(gscales)} "
+                         f"weights: expected 1..{_hip.MAX_DETAIL_POOLS} of each")
+    for t, name in ((img, "image"), (gimg, "pixel gradient"), (loss_out, "detail losses")):
+        require(t, name)
+    h, w, c = hwc(img)
+    assert c == 3 and gimg.numel() == 3 * h * w and loss_out.numel() >= count
+    s = _hip.DetailSetT()
+    s.count = count
+    for j, (p, ct, wt, g) in enumerate(zip(pools, contents, weights, gscales)):
+        require(ct, f"pooled content {j}")
+        s.pool[j], s.content[j], s.gscale[j] = int(p), ct.data_ptr(), float(g)
+        if int(p) in _hip.DETAIL_POOLS:          # (another value: the library refuses it)
+            hp, wp = pooled_shape(h, w, p)
+            assert ct.numel() == 3 * hp * wp
+        if wt is not None:
+            require(wt, f"cell weights {j}")
+            assert int(p) not in _hip.DETAIL_POOLS or wt.numel() == hp * wp
+            s.weight[j] = wt.data_ptr()
+    check(_hip.lib().strotss_detail_fwd_bwd(ptr(img), h, w, C.byref(s), ptr(gimg), ptr(loss_out), ptr(workspace),
+                                            stream_ptr()), "detail_fwd_bwd")
+
+
+def tv_workspace(h: int, w: int, device) -> torch.Tensor:
+    """a zeroed workspace of strotss_tv_fwd_bwd for (h, w) (as temporal_workspace)"""
+    nb = int(_hip.lib().strotss_tv_workspace_bytes(int(h), int(w)))
+    return torch.zeros(max(nb, 16), dtype=torch.uint8, device=device)
+
+
+def tv_fwd_bwd(img: torch.Tensor, gscale: float, gimg: torch.Tensor, loss_out: torch.Tensor, workspace: torch.Tensor,
+               eps: float = TV_EPS) -> None:
+    """loss_out[0] = (1/(3hw)) sum (sqrt(dx^2 + dy^2 + eps^2) - eps), gimg += gscale * dloss/dimg (strotss_tv_fwd_bwd; img,
+    gimg (h, w, 3) or (1, h, w, 3)).  workspace: tv_workspace(h, w)."""
+    for t, name in ((img, "image"), (gimg, "pixel gradient"), (loss_out, "tv loss")):
+        require(t, name)
+    h, w, c = hwc(img)
+    assert c == 3 and gimg.numel() == 3 * h * w
+    check(_hip.lib().strotss_tv_fwd_bwd(ptr(img), h, w, float(eps), float(gscale), ptr(gimg), ptr(loss_out), ptr(workspace),
+                                        stream_ptr()), "tv_fwd_bwd")
+
+
 def flow_params(**overrides) -> "_hip.FlowParamsT":
     """strotss_flow_params_t with the library's defaults (strotss_flow_default_params; needs no GPU), fields overridden by
     name: alpha2, warps, iters, min_side, max_levels, iters_per_launch"""

@@ -129,6 +129,18 @@ class TemporalTarget:
     weight: float
 
 
+@dataclass
+class DetailTarget:
+    """The Laplacian detail term at one scale: `content` (h, w, 3) or (1, h, w, 3) the content image at
+    this scale, `pools` 1..3 distinct pool sizes of {1, 2, 4, 8, 16}, ascending, `weight` >= 0, `cell_map` an optional (h, w)
+    map, finite and >= 0, whose pooled values weigh the cells (the content-weight map at this scale).  The step adds
+    weight * sum_p L_p, L_p = (1 / (3 hp wp)) sum_k m_p(k) |L (P_p(x) - P_p(content))(k)|^2, to its loss."""
+    content: torch.Tensor
+    pools: Sequence[int]
+    weight: float
+    cell_map: Optional[torch.Tensor] = None
+
+
 def extract_features(params: VGGParams, image: torch.Tensor) -> List[torch.Tensor]:
     """[image] + vgg(image)  (run_strotss.py:95-96), taps cloned out of a temporary trunk."""
     h, w = int(image.shape[1]), int(image.shape[2])
@@ -205,7 +217,13 @@ class StepEngine:
     every region and every style of a blend, with the same weight and in the same scalar slot (l_palette, also returned as
     l_palette_sliced).  It conserves mass, which the relaxed EMD does not.  With "sliced" every `style_transport` takes the
     separate entries: with "remd" that is their 21 launches (19 with the new term's 2 in place of the palette relaxed EMD's
-    4), not the grouped call's 13.  One GPU only."""
+    4), not the grouped call's 13.  One GPU only.
+
+    `detail`: a DetailTarget at this scale's size, `tv_weight` > 0: two pixel-space priors whose
+    gradients join the pixel gradient right after the temporal term and before the fold adjoint -- the Laplacian detail term
+    against the content (one pooling launch per pool size above 1 and one launch per pool size) and the total variation of
+    the folded image (one launch).  Both are added once per step, not averaged over the regions.  A DetailTarget of weight 0
+    runs the term and leaves the step bit for bit; tv_weight 0 is no term.  One GPU only."""
 
     N_SCALARS = 4   # loss_c, l_moment, l_remd, l_palette per region
 
@@ -218,7 +236,8 @@ class StepEngine:
                  style_transport: str = "remd", sinkhorn_l: float = DEFAULT_SINKHORN_L,
                  sinkhorn_iters: int = DEFAULT_SINKHORN_ITERS, sliced_projections: int = DEFAULT_SLICED_PROJECTIONS,
                  sliced_seed: int = 0, sinkhorn_log: bool = False, palette_transport: str = "remd",
-                 palette_projections: int = DEFAULT_PALETTE_PROJECTIONS):
+                 palette_projections: int = DEFAULT_PALETTE_PROJECTIONS, detail: Optional[DetailTarget] = None,
+                 tv_weight: float = 0.0):
         dev = stylized.device
         check_palette_transport(palette_transport, palette_projections)
         if palette_transport == "sliced" and (strips is not None or dist_group is not None):
@@ -295,6 +314,39 @@ class StepEngine:
                 self._temporal = dict(weights=[float(tt.weight) for tt in terms], targets=targets, certainties=certainties,
                                       loss=torch.zeros(len(terms), dtype=torch.float32, device=dev),
                                       ws=_ops.temporal_multi_workspace(h, w, len(terms), dev))
+        self._detail = self._tv = None
+        if isinstance(tv_weight, bool) or not isinstance(tv_weight, (int, float, np.integer, np.floating)) or \
+                not np.isfinite(tv_weight) or tv_weight < 0:
+            raise ValueError(f"tv_weight must be finite and >= 0, got {tv_weight!r}")
+        if (detail is not None or tv_weight > 0) and (strips is not None or dist_group is not None):
+            raise ValueError("the pixel-space priors (detail, tv_weight) run on one GPU: image strips and region sharding are "
+                             "not supported with them")
+        if detail is not None:
+            if not isinstance(detail, DetailTarget):
+                raise ValueError(f"detail must be a DetailTarget, got {type(detail).__name__}")
+            pools = _ops.check_detail_pools(detail.pools)
+            dwt = detail.weight
+            if isinstance(dwt, bool) or not isinstance(dwt, (int, float, np.integer, np.floating)) or \
+                    not np.isfinite(dwt) or dwt < 0:
+                raise ValueError(f"detail weight must be finite and >= 0, got {dwt!r}")
+            dc = detail.content
+            if dc.numel() != 3 * h * w or tuple(dc.shape[-3:]) != (h, w, 3):
+                raise ValueError(f"detail content of shape {tuple(dc.shape)}: expected ({h}, {w}, 3)")
+            cells = [None] * len(pools)
+            if detail.cell_map is not None:
+                from .strotss_utils import check_content_weight
+                cmap = check_content_weight(detail.cell_map, h, w).to(dev).reshape(h, w, 1).contiguous()
+                cells = [_ops.pool_mean(cmap, p).reshape(_ops.pooled_shape(h, w, p)) for p in pools]
+            # the engine's own fixed buffers (a captured graph reads them at replay): the content pooled by the kernel that
+            # pools the step's image, the pooled map, the scalars and the workspace
+            dc = dc.float().to(dev).reshape(h, w, 3).contiguous()
+            self._detail = dict(weight=float(dwt), pools=pools, contents=[_ops.pool_mean(dc, p) for p in pools], cells=cells,
+                                gscales=[float(dwt)] * len(pools),
+                                loss=torch.zeros(len(pools), dtype=torch.float32, device=dev),
+                                ws=_ops.detail_workspace(h, w, dev))
+        if tv_weight > 0:
+            self._tv = dict(weight=float(tv_weight), loss=torch.zeros(1, dtype=torch.float32, device=dev),
+                            ws=_ops.tv_workspace(h, w, dev))
         # --- variables = make_laplacian_pyramid(stylized) (run_strotss.py:89), rms slots start at 0
         from .strotss_utils import make_laplacian_pyramid
         self.variables = [v.contiguous() for v in make_laplacian_pyramid(stylized.contiguous(), levels)]
@@ -524,8 +576,8 @@ class StepEngine:
     def _stages(self, indices: Optional[Sequence[torch.Tensor]], apply: bool = True):
         """The step as [(device segment, host collective after it or None)], a segment a list of calls: what the eager step
         runs, capture_graph captures (one graph per segment) and a replay interleaves with the same collectives.
-            plain            [pixel gradient, temporal, fold adjoint]
-            region-sharded   [pixel gradient] | all-reduce _reduce_buf | [temporal, fold adjoint]
+            plain            [pixel gradient, temporal, pixel priors, fold adjoint]
+            region-sharded   [pixel gradient] | all-reduce _reduce_buf | [temporal, pixel priors, fold adjoint]
             image strips     [_strip_stage_a] | all-reduce _pf_all | [_strip_stage_b] | all-reduce gimg_full | [fold adjoint]
         apply: apply_gradients ends the last segment.  indices: the index sets of the pixel gradient, None = the draw kernel
         at the head of the step (image strips: the sets _strip_inputs has put in place)."""
@@ -536,7 +588,7 @@ class StepEngine:
                     ([self._strip_stage_b], lambda: parallel.allreduce_sum_(self.gimg_full, self.group)),
                     (end, None)]
         head = [lambda: self._pixel_gradient(self._draw_indices() if indices is None else indices)]
-        tail = [self._temporal_term] + end
+        tail = [self._temporal_term, self._pixel_prior] + end
         return [(head, self._reduce), (tail, None)] if self.sharded else [(head + tail, None)]
 
     @staticmethod
@@ -602,6 +654,16 @@ class StepEngine:
                                         t["loss"], t["ws"])
         else:
             _ops.temporal_fwd_bwd(self.fold[0], t["target"], t["certainty"], t["weight"], self.gvars[0], t["loss"], t["ws"])
+
+    def _pixel_prior(self) -> None:
+        """gvars[0] += detail_weight * dL_detail/dx + tv_weight * dL_tv/dx and the terms' scalars, x the folded image of this
+        step (neither term: nothing)"""
+        d, t = self._detail, self._tv
+        if d is not None:
+            _ops.detail_fwd_bwd(self.fold[0], d["pools"], d["contents"], d["cells"], d["gscales"], self.gvars[0], d["loss"],
+                                d["ws"])
+        if t is not None:
+            _ops.tv_fwd_bwd(self.fold[0], t["weight"], self.gvars[0], t["loss"], t["ws"])
 
     def _fold_adjoint(self) -> None:
         """gvars[k] = up^T(gvars[k-1]): adjoint of the fold"""
@@ -816,6 +878,14 @@ class StepEngine:
             lt = float(t["loss"].item())
             out["loss_t"] = lt
             out["loss"] = float(loss) + t["weight"] * lt
+        if self._detail is not None:             # the pixel-space priors: once per step as well
+            terms = [float(v) for v in self._detail["loss"].tolist()]
+            out["loss_detail"] = float(sum(terms))
+            out["loss_detail_terms"] = terms
+            out["loss"] = out["loss"] + self._detail["weight"] * out["loss_detail"]
+        if self._tv is not None:
+            out["loss_tv"] = float(self._tv["loss"].item())
+            out["loss"] = out["loss"] + self._tv["weight"] * out["loss_tv"]
         return out
 
     def stylized(self) -> torch.Tensor:

@@ -137,6 +137,20 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
   --strips          under torchrun (one process per GPU): ONE image on all GPUs -- every rank runs the trunk on its strip
                     of the image (+ halo) at the scales where that pays, two all-reduces per step (nn/parallel.py);
                     rank 0 writes the output
+  --detail_weight W
+                    a Laplacian detail term against the content: the result and the content are
+                    average-pooled at every size of --detail_pool, the graph Laplacian of the pooled difference is
+                    penalised, and its gradient joins the pixel gradient of every step -- edges, lettering and thin lines
+                    finer than the sample spacing stay where the content has them.  Off unless given (finite, >= 0).  With
+                    --content_weight_map the pooled map weighs the cells: white keeps the content's detail, black lets it
+                    go.  Combines with masks, --auto_masks, the scribble files, --track_masks, --style_mix, every transport
+                    flag, --preserve_color, --photo_smooth and --video (the target is the current frame's content); one
+                    GPU, not with --strips.
+  --detail_pool P [P ...]
+                    with --detail_weight: 1..3 distinct pool sizes of {1, 2, 4, 8, 16}, ascending (default 1 4, not tuned)
+  --tv_weight W     the total variation of the result, sqrt(dx^2 + dy^2 + (1/255)^2) per pixel and channel, as a term of
+                    every step: penalises pixel-level grain.  Off unless given (finite, >= 0).
+                    Combines as --detail_weight; one GPU, not with --strips.
 Under torchrun WITH masks (region-guided run, BASELINE config 4) the mask regions are dealt round-robin to the ranks:
 every rank runs the replicated trunk forward, its own regions' samples + losses and their data-gradient, ONE RCCL
 all-reduce sums the pixel gradient, every rank applies the identical update; rank 0 writes the output.
@@ -336,6 +350,33 @@ def _palette_transport_input(args) -> dict:
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise ValueError("--palette_transport sliced runs on one GPU: not under torchrun with WORLD_SIZE > 1")
     return dict(palette_transport=transport, palette_projections=int(proj))
+
+
+DEFAULT_DETAIL_POOLS = (1, 4)             # pixel-level edges and 4-pixel structure; a convention, not tuned
+
+
+def _pixel_prior_input(args) -> dict:
+    """--detail_weight, --detail_pool, --tv_weight: {"detail": (weight, pools) or None, "tv": weight},
+    both off unless given.  ValueError, before anything is loaded, for a weight that is not finite or negative,
+    --detail_pool without --detail_weight or not 1..3 distinct ascending values of {1, 2, 4, 8, 16}, and for either flag
+    with --strips or under torchrun with WORLD_SIZE > 1."""
+    dw, pools, tv = (getattr(args, k, None) for k in ("detail_weight", "detail_pool", "tv_weight"))
+    for flag, val in (("--detail_weight", dw), ("--tv_weight", tv)):
+        if val is not None and (not np.isfinite(val) or val < 0):
+            raise ValueError(f"{flag} must be finite and >= 0, got {val}")
+    if pools is not None and dw is None:
+        raise ValueError("--detail_pool needs --detail_weight")
+    if dw is None and tv is None:
+        return dict(detail=None, tv=0.0)
+    from nn import _ops
+    if dw is not None:
+        pools = _ops.check_detail_pools(list(DEFAULT_DETAIL_POOLS) if pools is None else list(pools))
+    flags = " / ".join(f for f, v in (("--detail_weight", dw), ("--tv_weight", tv)) if v is not None)
+    if getattr(args, "strips", False):
+        raise ValueError(f"{flags} cannot be combined with --strips")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError(f"{flags} runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    return dict(detail=None if dw is None else (float(dw), pools), tv=0.0 if tv is None else float(tv))
 
 
 def _photo_smooth_input(args):
@@ -796,6 +837,7 @@ def run(args: argparse.Namespace, trace=None):
     _auto_masks_input(args)                                  # refusals first, --video among them
     _style_transport_input(args)
     _palette_transport_input(args)
+    _pixel_prior_input(args)
     if getattr(args, "video", False):
         return run_video(args, trace)
     timer = utils.Timer()
@@ -875,6 +917,7 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
     sampling = strotss.Sampling(SAMPLE_SIZE)
     masked = bool(getattr(args, "content_mask", None))
     transport = dict(_style_transport_input(args), **_palette_transport_input(args))
+    prior = _pixel_prior_input(args)
 
     # alpha = 16 (x3500 with Keras weights), halved after every scale -- also after skipped ones
     alpha = args.alpha * 16.0 * (3500 if args.use_keras_weight else 1) / 2.0 ** first
@@ -903,12 +946,17 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
         # a scale is too small for strips to pay (strip_plan -> None) a masked run falls back to dealing its regions out
         plan = (parallel.strip_plan(int(scl_content.shape[1]), world, rank, halo=bool(getattr(args, "halo", False)))
                 if world > 1 and getattr(args, "strips", False) else None)
+        cw_scaled = None if cw_map is None else strotss.content_weight_at_scale(cw_map, hs, ws)
+        if prior["detail"] is not None:                      # the detail target: this image's content at this scale
+            transport["detail"] = strotss_engine.DetailTarget(scl_content, prior["detail"][1], prior["detail"][0], cw_scaled)
+        if prior["tv"] > 0:
+            transport["tv_weight"] = prior["tv"]
         eng = strotss_engine.StepEngine(
             vgg.params, strotss_engine.extract_features(vgg.params, scl_content),
             _style_targets(vgg.params, scl_style, style_masks, sampling, style_weights), stylized, alpha,
             loss_denom=2. + alpha + 1. / max(alpha, 1.), lr=lr, sample_size=SAMPLE_SIZE, strips=plan,
             dist_group=parallel.WORLD if (world > 1 and masked and plan is None) else None,
-            content_weight=(None if cw_map is None else strotss.content_weight_at_scale(cw_map, hs, ws)), temporal=tt,
+            content_weight=cw_scaled, temporal=tt,
             **transport)
         rec = None
         if trace is not None:
@@ -1146,6 +1194,15 @@ _FLAGS = (
     (("--strips",), dict(action='store_true', help="under torchrun: shard ONE image over the GPUs by image strips")),
     (("--halo",), dict(action='store_true', help="with --strips: per-layer halo EXCHANGE with the neighbouring ranks (16-row "
                                                  "windows margins, one row per layer and direction) instead of a 128-row recompute margin")),
+    (("--detail_weight",), dict(type=float, default=None, metavar='W',
+                                help="weight of the Laplacian detail term: keeps the content's edges at the pool sizes of "
+                                     "--detail_pool (off unless given; finite, >= 0)")),
+    (("--detail_pool",), dict(type=int, nargs='+', default=None, metavar='P',
+                              help="with --detail_weight: 1..3 distinct pool sizes of {1, 2, 4, 8, 16}, ascending (default "
+                                   "1 4, not tuned)")),
+    (("--tv_weight",), dict(type=float, default=None, metavar='W',
+                            help="weight of the total variation of the result: penalises pixel-level grain (off unless "
+                                 "given; finite, >= 0)")),
 )
 
 
