@@ -779,6 +779,31 @@ int strotss_guided_smooth(const float* img, const float* guide, int h, int w, in
                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Guided upsampling: the result at the content's own resolution, after He and Sun's fast guided filter
+ * --------------------------------------------------------------------------------------- */
+#define STROTSS_UPSAMPLE_GUIDED 0
+#define STROTSS_UPSAMPLE_RESIDUAL 1
+/* bytes of the workspace of strotss_guided_upsample: 280 per LOW-resolution pixel (the 216 of strotss_guided_smooth + one
+ * 16-float record); 0 where strotss_guided_smooth_workspace_bytes is 0 */
+size_t strotss_guided_upsample_workspace_bytes(int h, int w, int radius);
+/* out (H, W, 3) = img (h, w, 3) brought to the size of guide_hi (H, W, 3), H >= h, W >= w; guide_lo (h, w, 3) is the same
+ * guide at img's size.  The window means abar (3 x 3) and bbar (3) of strotss_guided_smooth(img, guide_lo) at (h, w),
+ * rounded to float32 as there, and d = img - q with q that entry's output; up() is strotss_resize_bilinear from (h, w) to
+ * (H, W) (half-pixel centres, clamped taps, along x then along y, a + (b - a) t with the difference rounded and one fused
+ * multiply-add: a weight of 0 returns the sample).  Per pixel and channel c, in float32, not clamped:
+ *   STROTSS_UPSAMPLE_GUIDED    out_c = fma(A_c2, I_2, fma(A_c1, I_1, fma(A_c0, I_0, B_c))), A = up(abar), B = up(bbar),
+ *                              I = guide_hi: at H == h, W == w, guide_hi == guide_lo the bits of strotss_guided_smooth
+ *   STROTSS_UPSAMPLE_RESIDUAL  that + up(d): the texture of img that the guide does not explain is kept
+ * Five launches on `stream`, no atomics, the same bits on every run; the workspace needs no initialisation.
+ * Refused before anything is launched: STROTSS_EINVAL for a null pointer, h, w, H or W <= 0, H < h, W < w,
+ * 3 H W > INT_MAX, a radius outside 1..STROTSS_SMOOTH_MAX_RADIUS, eps not finite or outside [1e-4, 1], an unknown mode,
+ * workspace_bytes below strotss_guided_upsample_workspace_bytes(h, w, radius), out overlapping guide_hi, guide_lo or img;
+ * STROTSS_EALIGN for a pointer that is not 16-byte aligned. */
+int strotss_guided_upsample(const float* img, const float* guide_lo, int h, int w, const float* guide_hi, int H, int W,
+                            int radius, float eps, int mode, float* out, void* workspace, size_t workspace_bytes,
+                            void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Region clustering: spherical k-means on sampled feature rows, the kernels of --auto_masks
  * --------------------------------------------------------------------------------------- */
 #define STROTSS_KMEANS_MAX_K 16

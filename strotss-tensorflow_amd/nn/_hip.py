@@ -205,6 +205,8 @@ SIGNATURES = {
     "strotss_color_transfer_apply": (_I, [_P, _P, _I, _I, C.POINTER(_F), _P, _I, _P, C.POINTER(_F), _P, _P]),
     "strotss_guided_smooth_workspace_bytes": (_Z, [_I, _I, _I]),
     "strotss_guided_smooth": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _Z, _P]),
+    "strotss_guided_upsample_workspace_bytes": (_Z, [_I, _I, _I]),
+    "strotss_guided_upsample": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _F, _I, _P, _P, _Z, _P]),
     "strotss_kmeans_assign": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
     "strotss_kmeans_update_workspace_bytes": (_Z, [_I, _I, _I]),
     "strotss_kmeans_update": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),

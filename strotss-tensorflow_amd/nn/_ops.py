@@ -505,6 +505,43 @@ def guided_smooth(img: torch.Tensor, guide: torch.Tensor, radius: int, eps: floa
     return out
 
 
+# ------------------------------------------------------------------ guided upsampling
+UPSAMPLE_MODES = {"guided": 0, "residual": 1}        # STROTSS_UPSAMPLE_GUIDED, STROTSS_UPSAMPLE_RESIDUAL
+_upsample_ws = {}
+
+
+def guided_upsample(img: torch.Tensor, guide_lo: torch.Tensor, guide_hi: torch.Tensor, radius: int, eps: float, mode: str,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the (h, w, 3) image brought to the size of `guide_hi` (H, W, 3), H >= h and W >= w, by the guided filter's window
+    means at (h, w) (guide_lo: the guide at the image's size) interpolated and applied to guide_hi; mode "guided" or
+    "residual" (that plus the interpolated img - filter(img)).  strotss_guided_upsample: five launches on the current
+    stream, the same bits on every run.  out may overlap none of the inputs.  The workspace (280 bytes per low-resolution
+    pixel) is a module-level one per device and low-resolution size; the library refuses what strotss_guided_smooth
+    refuses, a smaller guide_hi and 3 H W > INT_MAX."""
+    h, w = _rgb_image(img, "image")
+    if _rgb_image(guide_lo, "low-resolution guide") != (h, w):
+        raise ValueError(f"image of shape {tuple(img.shape)} and guide of shape {tuple(guide_lo.shape)} differ in size")
+    H, W = _rgb_image(guide_hi, "full-resolution guide")
+    if mode not in UPSAMPLE_MODES:
+        raise ValueError(f"upsampling mode {mode!r}: expected one of {tuple(UPSAMPLE_MODES)}")
+    lib = _hip.lib()
+    key = (str(img.device), h, w)
+    workspace = _upsample_ws.get(key)
+    if workspace is None:
+        nb = int(lib.strotss_guided_upsample_workspace_bytes(h, w, 1))      # the size does not depend on the radius
+        if nb == 0:
+            raise _hip.StrotssHipError(f"guided_upsample: bad size {h} x {w}")
+        workspace = _upsample_ws[key] = torch.empty(nb, dtype=torch.uint8, device=img.device)
+    if out is None:
+        out = torch.empty_like(guide_hi)
+    require(out, "upsampled image")
+    assert out.numel() == guide_hi.numel()
+    check(lib.strotss_guided_upsample(ptr(img), ptr(guide_lo), h, w, ptr(guide_hi), H, W, int(radius), float(eps),
+                                      UPSAMPLE_MODES[mode], ptr(out), ptr(workspace), workspace.numel(), stream_ptr()),
+          "guided_upsample")
+    return out
+
+
 def resize_bilinear_adjoint(gout: torch.Tensor, ih: int, iw: int,
                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
     require(gout, "resize adjoint input")

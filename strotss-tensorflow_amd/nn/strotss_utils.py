@@ -496,6 +496,49 @@ def guided_smooth(result, content, radius=None, eps=DEFAULT_SMOOTH_EPS) -> torch
     return out.reshape(tuple(result.shape)) if torch.is_tensor(result) else out
 
 
+# ----------------------------------------------------------------------------- guided upsampling
+UPSAMPLE_MODES = ("residual", "guided")
+DEFAULT_UPSAMPLE_EPS = 1e-3              # residual: about 0.03^2, the guide explains weaker edges and less is left to the
+#                                          interpolated residual; a documented choice, not tuned.  guided: DEFAULT_SMOOTH_EPS
+UPSAMPLE_SIZE_RANGE = (64, 16384)        # --output_size in pixels
+
+
+def default_upsample_eps(mode: str) -> float:
+    return DEFAULT_UPSAMPLE_EPS if mode == "residual" else DEFAULT_SMOOTH_EPS
+
+
+def check_upsample_sizes(h: int, w: int, H: int, W: int) -> None:
+    """ValueError for a target (H, W) smaller than the result (h, w) in either dimension or with 3 H W > INT_MAX"""
+    if H < h or W < w:
+        raise ValueError(f"upsampling target {H} x {W} is smaller than the result {h} x {w}")
+    if 3 * H * W > 2 ** 31 - 1:
+        raise ValueError(f"upsampling target {H} x {W}: 3 H W exceeds {2 ** 31 - 1}")
+
+
+def guided_upsample(result, content_lo, content_hi, radius=None, eps=None, mode="residual") -> torch.Tensor:
+    """--output_size: `result` (h, w, 3) or (1, h, w, 3) brought to the size of `content_hi` (H, W, 3) or (1, H, W, 3) by
+    joint upsampling with the content as guide (He and Sun 2015; strotss_guided_upsample; not clamped): the guided
+    filter's coefficients of (result, content_lo) at the result's size, interpolated and applied to content_hi; mode
+    "residual" adds the interpolated result - filter(result), which keeps the optimiser's texture, "guided" does not.
+    -> (H, W, 3), with the leading 1 when the result has one.  radius None: default_smooth_radius(h, w); eps None: 1e-3 for
+    residual, DEFAULT_SMOOTH_EPS for guided.  ValueError for an unknown mode, result and content_lo of different sizes, a
+    content_hi smaller than the result in either dimension, 3 H W > INT_MAX, a radius outside 1..64, an eps that is not
+    finite or outside [1e-4, 1]."""
+    if mode not in UPSAMPLE_MODES:
+        raise ValueError(f"upsampling mode {mode!r}: expected one of {UPSAMPLE_MODES}")
+    check_smooth_parameters(radius, eps)
+    r, lo, hi = _rgb(result, "result"), _rgb(content_lo, "content at the result's size"), _rgb(content_hi, "content")
+    if tuple(r.shape) != tuple(lo.shape):
+        raise ValueError(f"result of shape {tuple(r.shape)} and content of shape {tuple(lo.shape)} differ in size")
+    check_upsample_sizes(int(r.shape[0]), int(r.shape[1]), int(hi.shape[0]), int(hi.shape[1]))
+    if radius is None:
+        radius = default_smooth_radius(int(r.shape[0]), int(r.shape[1]))
+    if eps is None:
+        eps = default_upsample_eps(mode)
+    out = _ops.guided_upsample(r, lo, hi, int(radius), float(eps), mode)
+    return out[None] if torch.is_tensor(result) and result.dim() == 4 else out
+
+
 # ----------------------------------------------------------------------------- automatic region masks (DESIGN.md section 17)
 AUTO_MASK_ITERS = 16                     # k-means iterations, fixed (no convergence test: no host synchronisation)
 AUTO_MASK_SIZE = 256                     # long side at which the two images are clustered

@@ -55,6 +55,18 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
                     results.  One GPU; not with --strips.
   --smooth_radius R with --photo_smooth: the window radius in pixels, 1..64 (default: 1/64 of the result's longer side)
   --smooth_eps E    with --photo_smooth: the regulariser on [0, 1] colours, 1e-4..1 (default 1e-2); smaller keeps weaker edges
+  --output_size SIZE
+                    write the result at the content's own resolution: SIZE is `full` (the content
+                    file as decoded) or a long side in pixels, 64..16384.  The guided filter's coefficients of the result
+                    against the content are computed at the result's size, interpolated and applied to the content at the
+                    target size (He and Sun 2015); after --photo_smooth, before --preserve_color luminance's merge, which
+                    then runs at the target size.  In --video only what is written is upsampled.  One GPU; not with --strips.
+  --upsample_mode {residual,guided}
+                    with --output_size: residual (default) adds the interpolated difference between the result and its
+                    filter, which keeps the optimiser's texture; guided is the filter alone
+  --upsample_radius R, --upsample_eps E
+                    with --output_size: the window radius at the result's size, 1..64 (default 1/64 of its longer side),
+                    and the regulariser, 1e-4..1 (default 1e-3 for residual, 1e-2 for guided)
   --auto_masks K    region guidance without painted masks: the hypercolumns of the content and of
                     style_path on a regular grid are clustered jointly into K groups (2..8) by spherical k-means on the GPU;
                     every cluster that holds 1/32 of both images' grid points is a content region and the style region it
@@ -393,6 +405,54 @@ def _photo_smooth_input(args):
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise ValueError("--photo_smooth runs on one GPU: not under torchrun with WORLD_SIZE > 1")
     return (None if radius is None else int(radius)), (strotss.DEFAULT_SMOOTH_EPS if eps is None else float(eps))
+
+
+def _output_size_input(args):
+    """--output_size: dict(size="full" or the long side in pixels, mode, radius or None, eps or None), or None when the
+    flag is absent.  ValueError, before anything is loaded: --upsample_mode, --upsample_radius or --upsample_eps without
+    the flag, a size that is neither "full" nor a whole number in 64..16384, an unknown mode, a radius outside 1..64, an eps
+    outside [1e-4, 1], --strips, WORLD_SIZE > 1."""
+    size = getattr(args, "output_size", None)
+    mode, radius, eps = (getattr(args, "upsample_" + k, None) for k in ("mode", "radius", "eps"))
+    if size is None:
+        if mode is not None or radius is not None or eps is not None:
+            raise ValueError("--upsample_mode, --upsample_radius and --upsample_eps need --output_size")
+        return None
+    if size != "full":
+        lo, hi = strotss.UPSAMPLE_SIZE_RANGE
+        try:
+            pixels = int(str(size), 10)
+        except ValueError:
+            pixels = None
+        if pixels is None or not lo <= pixels <= hi:
+            raise ValueError(f"--output_size {size!r}: expected 'full' or a whole number in {lo}..{hi}")
+        size = pixels
+    mode = "residual" if mode is None else mode
+    if mode not in strotss.UPSAMPLE_MODES:
+        raise ValueError(f"--upsample_mode takes one of {strotss.UPSAMPLE_MODES}, got {mode!r}")
+    for flag, kw in (("--upsample_radius", dict(radius=radius, eps=None)), ("--upsample_eps", dict(radius=None, eps=eps))):
+        try:
+            strotss.check_smooth_parameters(**kw)
+        except ValueError as e:
+            raise ValueError(f"{flag}: {e}") from None
+    if getattr(args, "strips", False):
+        raise ValueError("--output_size cannot be combined with --strips")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("--output_size runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    return dict(size=size, mode=mode, radius=None if radius is None else int(radius), eps=None if eps is None else float(eps))
+
+
+def _output_guides(args, upsample: dict, path: str, guide_lo=None):
+    """--output_size: (the content at the result's size, the content at the target size), both (h, w, 3) on the device.
+    ValueError for a target smaller than the result in either dimension or with 3 H W > INT_MAX."""
+    lo = _frame_at_result_size(args, path) if guide_lo is None else guide_lo
+    hi = utils.load_image(path, max_size=None if upsample["size"] == "full" else upsample["size"])[0].contiguous()
+    strotss.check_upsample_sizes(int(lo.shape[0]), int(lo.shape[1]), int(hi.shape[0]), int(hi.shape[1]))
+    return lo, hi
+
+
+def _upsampled(upsample: dict, image: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor) -> torch.Tensor:
+    return strotss.guided_upsample(image, lo, hi, upsample["radius"], upsample["eps"], upsample["mode"])
 
 
 def _refine_masks_input(args):
@@ -846,6 +906,7 @@ def run(args: argparse.Namespace, trace=None):
     cw_path = _content_weight_input(args)
     preserve = _preserve_color_input(args)
     smooth = _photo_smooth_input(args)
+    upsample = _output_size_input(args)
     _video_inputs(args)                                      # the sequence flags without --video: ValueError
     seed = int(getattr(args, "seed", 0))
     rand.seed_everything(seed)
@@ -858,11 +919,16 @@ def run(args: argparse.Namespace, trace=None):
     dev = utils.device()
 
     vgg = VGG(use_keras_weight=args.use_keras_weight, weights=getattr(args, "weights", None), seed=seed, device=dev)
+    if upsample:                                             # the target's size is refused before the first step
+        guide, guide_hi = _output_guides(args, upsample, args.content_path)
     stylized = _stylise(args, vgg, args.content_path, cw_path, dev, rank, world, trace)
-    guide = _frame_at_result_size(args, args.content_path) if smooth or preserve == "luminance" else None
+    if not upsample:
+        guide = _frame_at_result_size(args, args.content_path) if smooth or preserve == "luminance" else None
     if smooth:                                               # the content's edges back into the result, then its colours
         stylized = strotss.guided_smooth(stylized, guide, *smooth)
-    if preserve == "luminance":                              # the result's luma on the content's chroma, at the result's size
+    if upsample:                                             # --output_size: to the target size, the content as guide
+        stylized, guide = _upsampled(upsample, stylized, guide, guide_hi), guide_hi
+    if preserve == "luminance":                              # the result's luma on the content's chroma, at the written size
         stylized = strotss.luminance_merge(stylized, guide)
     final = strotss.postprocess(stylized)
     if torch.cuda.is_available():
@@ -1036,6 +1102,7 @@ def run_video(args: argparse.Namespace, trace=None):
     <output dir>/<frame stem>.jpg; returns the list of the frames' uint8 results.  `trace`: one list per frame."""
     preserve = _preserve_color_input(args)
     smooth = _photo_smooth_input(args)
+    upsample = _output_size_input(args)
     frames, lam = _video_inputs(args)
     cw_path = _content_weight_input(args)
     seed = int(getattr(args, "seed", 0))
@@ -1072,13 +1139,17 @@ def run_video(args: argparse.Namespace, trace=None):
         masks = None
         if tracking is not None:
             masks = _tracked_masks(args, vgg, tracking, t, frame, offsets[0], nearest, auto, inertia)
+        if upsample:                        # --output_size: the target's size is refused before the frame's first step
+            guide, guide_hi = _output_guides(args, upsample, frame, flow_frames[t] if flow_frames is not None else None)
         previous = _stylise(args, vgg, frame, cw_path, dev, trace=rec, temporal=temporal, temporal_weight=lam, masks=masks)
         results = [previous] + results[:offsets[-1] - 1]
-        written = previous                  # only what is written is filtered or merged: the temporal targets and
-        if smooth or preserve == "luminance":                    # --temporal_init keep the optimiser's own results
+        written = previous                  # only what is written is filtered, upsampled or merged: the temporal targets
+        if not upsample and (smooth or preserve == "luminance"):     # and --temporal_init keep the optimiser's own results
             guide = flow_frames[t] if flow_frames is not None else _frame_at_result_size(args, frame)
         if smooth:
             written = strotss.guided_smooth(written, guide, *smooth)
+        if upsample:
+            written, guide = _upsampled(upsample, written, guide, guide_hi), guide_hi
         if preserve == "luminance":
             written = strotss.luminance_merge(written, guide)
         final = strotss.postprocess(written)
@@ -1141,6 +1212,18 @@ _FLAGS = (
                                 help="with --photo_smooth: window radius in pixels, 1..64 (default: 1/64 of the longer side)")),
     (("--smooth_eps",), dict(type=float, default=None, metavar='E',
                              help="with --photo_smooth: regulariser on [0, 1] colours, 1e-4..1 (default 1e-2)")),
+    (("--output_size",), dict(type=str, default=None, metavar='SIZE',
+                              help="write the result at the content's resolution: 'full' (the content file as decoded) or a "
+                                   "long side in pixels, 64..16384; joint upsampling with the content as guide")),
+    (("--upsample_mode",), dict(type=str, default=None, choices=strotss.UPSAMPLE_MODES,
+                                help="with --output_size: 'residual' (default) keeps the optimiser's texture, 'guided' is the "
+                                     "guided filter alone (photorealistic; goes with --photo_smooth)")),
+    (("--upsample_radius",), dict(type=int, default=None, metavar='R',
+                                  help="with --output_size: window radius at the result's size, 1..64 (default: 1/64 of its "
+                                       "longer side)")),
+    (("--upsample_eps",), dict(type=float, default=None, metavar='E',
+                               help="with --output_size: regulariser on [0, 1] colours, 1e-4..1 (default 1e-3 for residual, "
+                                    "1e-2 for guided)")),
     (("--auto_masks",), dict(type=int, default=None, metavar='K',
                              help="region guidance without painted masks: cluster the hypercolumns of content and style "
                                   "jointly into K groups (2..8); every cluster found in both images is a region")),
