@@ -33,10 +33,7 @@ __device__ __forceinline__ void color_accum(double (&a)[COLOR_SUMS], float m, fl
 // The ten sums of the block in every thread: a fixed shuffle tree per wave, the 4 waves in a fixed order.
 __device__ __forceinline__ void block_sum10_256(double (&a)[COLOR_SUMS], double (*red)[COLOR_SUMS]) {
 #pragma unroll
-  for (int k = 0; k < COLOR_SUMS; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a[k] += __shfl_xor(a[k], o, 64);
-  }
+  for (int k = 0; k < COLOR_SUMS; ++k) a[k] = wave_sum(a[k]);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll

@@ -18,12 +18,31 @@
     return e__ == hipSuccess ? 0 : (int)e__; \
   } while (0)
 
+// After a launch inside a longer entry: return the launch's error if there is one, else go on.
+#define ST_LAUNCH_OK()                        \
+  do {                                        \
+    hipError_t e__ = hipGetLastError();       \
+    if (e__ != hipSuccess) return (int)e__;   \
+  } while (0)
+
+// Return a callee's non-zero code.
+#define ST_TRY(expr)            \
+  do {                          \
+    int rc__ = (expr);          \
+    if (rc__ != 0) return rc__; \
+  } while (0)
+
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;

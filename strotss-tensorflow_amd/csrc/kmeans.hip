@@ -22,11 +22,6 @@ namespace {
 #define KM_MAX_ROW_BLOCKS 32             // update: row blocks at most (the partials are row blocks x k x ld doubles)
 #define KM_MIN_BLOCK_ROWS 64             // update: rows per row block at least
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ int wave_sum_i32(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -73,7 +68,7 @@ __global__ __launch_bounds__(256) void kmeans_finish_kernel(const int* __restric
     sum[c] = s;                                                         // read back below by this thread only
     sq = fma(s, s, sq);
   }
-  sq = wave_sum_f64(sq);
+  sq = wave_sum(sq);
   if ((t & 63) == 0) red[t >> 6] = sq;
   __syncthreads();
   const double norm = sqrt((red[0] + red[1]) + (red[2] + red[3]));

@@ -1223,17 +1223,6 @@ __global__ __launch_bounds__(256) void sk_assemble_metric_kernel(const float* __
   if (threadIdx.x == 0) { q2[j] = tot2; q[j] = tot; }
 }
 
-#define CHK(expr)            \
-  do {                       \
-    int rc__ = (expr);       \
-    if (rc__ != 0) return rc__; \
-  } while (0)
-#define LAUNCH_OK()                                  \
-  do {                                               \
-    hipError_t e__ = hipGetLastError();              \
-    if (e__ != hipSuccess) return (int)e__;          \
-  } while (0)
-
 bool feat_ok(int n, int d, int ld) { return n > 0 && d > 0 && ld >= d; }
 
 // STROTSS_X3 = 0 or STROTSS_X3_MOMENT = 0 keeps the covariance GEMMs of moment_matching on the f32 MFMA.
@@ -1383,7 +1372,7 @@ int strotss_l2_distance(const float* x, int nx, const float* y, int ny, int d, i
   float* ys = workspace + nx;
   hipLaunchKernelGGL(row_sq_norm_kernel, dim3(cdiv(nx, 4)), dim3(256), 0, st, x, nx, ld, xs);
   hipLaunchKernelGGL(row_sq_norm_kernel, dim3(cdiv(ny, 4)), dim3(256), 0, st, y, ny, ld, ys);
-  LAUNCH_OK();
+  ST_LAUNCH_OK();
   return st_l2_distance(x, xs, nx, y, ys, ny, ld, d, C, ldc, st);
 }
 
@@ -1423,15 +1412,15 @@ static int selfsim_impl(const float* pred, const float* content, const float* cw
   if (cost_x3()) {      // cost matrices on the bf16x3 core: the norm pass also writes the rows' x3 panels
     hipLaunchKernelGGL(row_inv_norm_x3_kernel, dim3(cdiv(n, 4), 2), dim3(256), 0, st, pred, n, ld, s.rp, s.xp, content, n,
                        s.rc, s.xc);
-    LAUNCH_OK();
+    ST_LAUNCH_OK();
     // both symmetric matrices in ONE launch (2 x 136 upper-triangular tiles at n = 1024: one round of the 512 slots)
-    CHK(st_cosine_distance_x3(s.xp, s.rp, n, s.xp, s.rp, n, ld, 1, s.Dx, ldc, 2, s.xc - s.xp, s.rc - s.rp, s.Dy - s.Dx, st));
+    ST_TRY(st_cosine_distance_x3(s.xp, s.rp, n, s.xp, s.rp, n, ld, 1, s.Dx, ldc, 2, s.xc - s.xp, s.rc - s.rp, s.Dy - s.Dx, st));
   } else {
     hipLaunchKernelGGL(row_inv_norm_kernel, dim3(cdiv(n, 4)), dim3(256), 0, st, pred, n, ld, s.rp);
     hipLaunchKernelGGL(row_inv_norm_kernel, dim3(cdiv(n, 4)), dim3(256), 0, st, content, n, ld, s.rc);
-    LAUNCH_OK();
-    CHK(st_cosine_distance(pred, s.rp, n, pred, s.rp, n, ld, s.Dx, ldc, st));
-    CHK(st_cosine_distance(content, s.rc, n, content, s.rc, n, ld, s.Dy, ldc, st));
+    ST_LAUNCH_OK();
+    ST_TRY(st_cosine_distance(pred, s.rp, n, pred, s.rp, n, ld, s.Dx, ldc, st));
+    ST_TRY(st_cosine_distance(content, s.rc, n, content, s.rc, n, ld, s.Dy, ldc, st));
   }
   // loss = mean(|A-B|) * n = (1/n) sum |A-B|  ->  dL/dA = sign/n.  Two passes over the two matrices in all: the rows'
   // statistics (sx and sy hold the RECIPROCAL clamped row sums), then the symmetrised gradient + the loss
@@ -1444,7 +1433,7 @@ static int selfsim_impl(const float* pred, const float* content, const float* cw
   if (bx3)
     hipLaunchKernelGGL(center_x3_kernel, dim3(ld / 32, ldc / 32), dim3(256), 0, st, pred, n, ldc, ld, (const float*)nullptr,
                        (__bf16*)nullptr, s.xt);
-  LAUNCH_OK();
+  ST_LAUNCH_OK();
   if (bx3) return st_selfsim_bwd_x3(s.mp, ldc, s.xt, pred, s.rp, s.qdot, n, ld, gscale, gpred, st);
   return st_selfsim_bwd_gemm(s.Mq, ldc, ldc, pred, pred, s.rp, s.qdot, n, ld, gscale, gpred, st);
 }
@@ -1487,7 +1476,7 @@ static int sinkhorn_iterate(SinkhornWs& s, int ns, int n, float l, int T, float*
                        s.U + (size_t)(t - 1) * ns, 0, py, s.V + (size_t)t * n, (const float*)nullptr, (float*)nullptr,
                        (float*)nullptr);
   }
-  LAUNCH_OK();
+  ST_LAUNCH_OK();
   // cost = sum_j v_T[j] ((K o M)^T u_T)[j]; the same pass gives gv -> db_T
   const float* uT = s.U + (size_t)(T - 1) * ns;
   const float* vT = s.V + (size_t)T * n;
@@ -1506,9 +1495,9 @@ static int sinkhorn_iterate(SinkhornWs& s, int ns, int n, float l, int T, float*
                          s.DA + (size_t)(t - 1) * ns, 1, py, (float*)nullptr, s.V + (size_t)(t - 1) * n,
                          s.DB + (size_t)(t - 2) * n, (float*)nullptr);
   }
-  LAUNCH_OK();
+  ST_LAUNCH_OK();
   const int rows = round_up(n, 64);
-  if (rows > n) CHK((int)hipMemsetAsync(s.W + (size_t)n * ldm, 0, sizeof(float) * (size_t)(rows - n) * ldm, st));
+  if (rows > n) ST_TRY((int)hipMemsetAsync(s.W + (size_t)n * ldm, 0, sizeof(float) * (size_t)(rows - n) * ldm, st));
   return 0;
 }
 
@@ -1524,12 +1513,12 @@ int strotss_sinkhorn_cos_fwd_bwd(const float* style, const float* rs, int ns, co
   hipStream_t st = (hipStream_t)stream;
   const int ldm = s.ldm, T = n_iter;
   hipLaunchKernelGGL(row_inv_norm_kernel, dim3(cdiv(n, 4)), dim3(256), 0, st, pred, n, ld, s.rp);
-  LAUNCH_OK();
-  CHK(st_cosine_distance(pred, s.rp, n, style, rs, ns, ld, s.Mt, ldm, st));          // Mt[j][i] = 1 - <yhat_j, xhat_i>
-  CHK(sinkhorn_iterate(s, ns, n, l, T, loss_out, st));
+  ST_LAUNCH_OK();
+  ST_TRY(st_cosine_distance(pred, s.rp, n, style, rs, ns, ld, s.Mt, ldm, st));          // Mt[j][i] = 1 - <yhat_j, xhat_i>
+  ST_TRY(sinkhorn_iterate(s, ns, n, l, T, loss_out, st));
   hipLaunchKernelGGL(sk_assemble_kernel, dim3(n), dim3(256), 0, st, s.Kt, s.Mt, ns, ldm, T, l, s.U, s.DA, s.V, s.DB, n, rs,
                      s.W, s.q);
-  LAUNCH_OK();
+  ST_LAUNCH_OK();
   return st_selfsim_bwd_gemm(s.W, ldm, ldm, style, pred, s.rp, s.q, n, ld, gscale, gpred, st);
 }
 
@@ -1554,12 +1543,12 @@ int strotss_sinkhorn_cos_fwd_bwd_panels(const float* style, const float* rs, con
   ST_CHECK_ARG(s.plan(w, ns, n, n_iter), STROTSS_EINVAL);
   hipStream_t st = (hipStream_t)stream;
   const int ldm = s.ldm, T = n_iter;
-  if (pred_panels) CHK(st_cosine_distance_x3(pred_panels, pred_inv_norm, n, style_panels, rs, ns, ld, 0, s.Mt, ldm, 1, 0, 0, 0, st));
-  else CHK(st_cosine_distance(pred, pred_inv_norm, n, style, rs, ns, ld, s.Mt, ldm, st));     // Mt[j][i] = 1 - <yhat_j, xhat_i>
-  CHK(sinkhorn_iterate(s, ns, n, l, T, loss_out, st));
+  if (pred_panels) ST_TRY(st_cosine_distance_x3(pred_panels, pred_inv_norm, n, style_panels, rs, ns, ld, 0, s.Mt, ldm, 1, 0, 0, 0, st));
+  else ST_TRY(st_cosine_distance(pred, pred_inv_norm, n, style, rs, ns, ld, s.Mt, ldm, st));     // Mt[j][i] = 1 - <yhat_j, xhat_i>
+  ST_TRY(sinkhorn_iterate(s, ns, n, l, T, loss_out, st));
   hipLaunchKernelGGL(sk_assemble_kernel, dim3(n), dim3(256), 0, st, s.Kt, s.Mt, ns, ldm, T, l, s.U, s.DA, s.V, s.DB, n, rs,
                      s.W, s.q);
-  LAUNCH_OK();
+  ST_LAUNCH_OK();
   return st_selfsim_bwd_gemm(s.W, ldm, ldm, style, pred, pred_inv_norm, s.q, n, ld, gscale, gpred, st);
 }
 
@@ -1601,15 +1590,15 @@ int strotss_sinkhorn_metric_fwd_bwd(const float* style, int ns, const float* pre
   hipLaunchKernelGGL(row_sq_norm_kernel, dim3(cdiv(n, 4)), dim3(256), 0, st, pred, n, ld, m.sp);
   hipLaunchKernelGGL(row_sq_norm_kernel, dim3(cdiv(ns, 4)), dim3(256), 0, st, style, ns, ld, m.ss);
   hipLaunchKernelGGL(sk_fill_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, m.ones, n, 1.0f);
-  LAUNCH_OK();
-  CHK(st_remd_cost(pred, s.rp, m.sp, n, style, m.rs, m.ss, ns, ld, d, metric, s.Mt, m.S, ldm, st));      // pred-major
-  CHK(sinkhorn_iterate(s, ns, n, l, T, loss_out, st));
+  ST_LAUNCH_OK();
+  ST_TRY(st_remd_cost(pred, s.rp, m.sp, n, style, m.rs, m.ss, ns, ld, d, metric, s.Mt, m.S, ldm, st));      // pred-major
+  ST_TRY(sinkhorn_iterate(s, ns, n, l, T, loss_out, st));
   const int rows = round_up(n, 64);
-  if (rows > n) CHK((int)hipMemsetAsync(m.W2 + (size_t)n * ldm, 0, sizeof(float) * (size_t)(rows - n) * ldm, st));
+  if (rows > n) ST_TRY((int)hipMemsetAsync(m.W2 + (size_t)n * ldm, 0, sizeof(float) * (size_t)(rows - n) * ldm, st));
   hipLaunchKernelGGL(sk_assemble_metric_kernel, dim3(n), dim3(256), 0, st, s.Kt, s.Mt, m.S, ns, ldm, T, l, s.U, s.DA, s.V, s.DB,
                      n, m.rs, (float)d, metric, s.W, s.q, m.W2, m.q2);
-  LAUNCH_OK();
-  CHK(st_selfsim_bwd_gemm(m.W2, ldm, ldm, style, pred, m.ones, m.q2, n, ld, gscale, gpred, st));
+  ST_LAUNCH_OK();
+  ST_TRY(st_selfsim_bwd_gemm(m.W2, ldm, ldm, style, pred, m.ones, m.q2, n, ld, gscale, gpred, st));
   if (metric == STROTSS_METRIC_BOTH) return st_selfsim_bwd_gemm(s.W, ldm, ldm, style, pred, s.rp, s.q, n, ld, gscale, gpred, st);
   return 0;
 }
@@ -1637,8 +1626,8 @@ static int remd_cos_core(const float* style, const float* rs, const __bf16* xs, 
   // order), so that the backward kernel's scans of "column j" are contiguous: minima over i per prediction row j
   // are row minima (cmin), minima over j per style row i column minima (rmin)
   const int ldt = s.ldt;
-  if (xp && xs) CHK(st_cosine_distance_x3(xp, rp, n, xs, rs, ns, ld, 0, s.C, ldt, 1, 0, 0, 0, st));
-  else CHK(st_cosine_distance(pred, rp, n, style, rs, ns, ld, s.C, ldt, st));
+  if (xp && xs) ST_TRY(st_cosine_distance_x3(xp, rp, n, xs, rs, ns, ld, 0, s.C, ldt, 1, 0, 0, 0, st));
+  else ST_TRY(st_cosine_distance(pred, rp, n, style, rs, ns, ld, s.C, ldt, st));
   hipLaunchKernelGGL(row_col_min_kernel, dim3(n + cdiv(ns, 64) * COL_CHUNKS), dim3(256), 0, st, s.C, n, ns, ldt, s.cmin,
                      s.ccnt, s.pmin, s.pcnt);
   hipLaunchKernelGGL(col_min_final_select_kernel, dim3(1), dim3(1024), 0, st, s.pmin, s.pcnt, ns, ldt, s.rmin, s.rcnt,
@@ -1666,7 +1655,7 @@ int strotss_remd_cos_fwd_bwd(const float* style, const float* rs, int ns, const 
   } else {
     hipLaunchKernelGGL(row_inv_norm_kernel, dim3(cdiv(n, 4)), dim3(256), 0, st, pred, n, ld, s.rp);
   }
-  LAUNCH_OK();
+  ST_LAUNCH_OK();
   return remd_cos_core(style, rs, x3 ? s.xs : nullptr, ns, pred, s.rp, x3 ? s.xp : nullptr, n, ld, gscale, gpred, loss_out, s,
                        st, flags & STROTSS_REMD_SWAPPED);
 }
@@ -1718,11 +1707,11 @@ int strotss_remd_metric_fwd_bwd(const float* style, int ns, const float* pred, i
   hipLaunchKernelGGL(row_inv_norm_kernel, dim3(cdiv(ns, 4)), dim3(256), 0, st, style, ns, ld, s.rs);
   hipLaunchKernelGGL(row_sq_norm_kernel, dim3(cdiv(n, 4)), dim3(256), 0, st, pred, n, ld, s.sp);
   hipLaunchKernelGGL(row_sq_norm_kernel, dim3(cdiv(ns, 4)), dim3(256), 0, st, style, ns, ld, s.ss);
-  LAUNCH_OK();
+  ST_LAUNCH_OK();
   // pred-major cost matrix Ct[j][i], as in strotss_remd_cos_fwd_bwd: row minima = minima over the style rows per
   // prediction (cmin, the R_Y side), column minima = minima over the predictions per style row (rmin, the R_X side)
   const int ldt = s.ldt;
-  CHK(st_remd_cost(pred, s.rp, s.sp, n, style, s.rs, s.ss, ns, ld, d, metric, s.C, s.S, ldt, st));
+  ST_TRY(st_remd_cost(pred, s.rp, s.sp, n, style, s.rs, s.ss, ns, ld, d, metric, s.C, s.S, ldt, st));
   hipLaunchKernelGGL(row_col_min_kernel, dim3(n + cdiv(ns, 64) * COL_CHUNKS), dim3(256), 0, st, s.C, n, ns, ldt, s.cmin,
                      s.ccnt, s.pmin, s.pcnt);
   hipLaunchKernelGGL(col_min_final_select_kernel, dim3(1), dim3(1024), 0, st, s.pmin, s.pcnt, ns, ldt, s.rmin, s.rcnt,
@@ -1771,13 +1760,13 @@ int strotss_moment_stats(const float* x, int n, int d, int ld, float* mean_out, 
   if (moment_x3()) {      // same GEMM core as the prediction side (strotss_moment_fwd_bwd): identical statistics, bit for bit
     hipLaunchKernelGGL(center_x3_kernel, dim3(ld / 32, s.rows / 32), dim3(256), 0, st, x, n, s.rows, ld,
                        (const float*)nullptr, (__bf16*)nullptr, s.Pt, (const float*)s.psum, mean_out);   // (means: in here)
-    LAUNCH_OK();
+    ST_LAUNCH_OK();
     return st_gram_tn_x3(s.Pt, s.rows, ld, 1.0f / (float)n, cov_out, st);
   }
   hipLaunchKernelGGL(col_mean_final_kernel, dim3(cdiv(ld, 256)), dim3(256), 0, st, s.psum, n, ld, mean_out);
   hipLaunchKernelGGL(center_kernel, dim3(min(2048, cdiv((size_t)s.rows * ld / 4, 256))), dim3(256), 0, st, x,
                      n, s.rows, ld, mean_out, s.cy);
-  LAUNCH_OK();
+  ST_LAUNCH_OK();
   return st_gram_tn(s.cy, s.rows, ld, 1.0f / (float)n, cov_out, st);
 }
 
@@ -1797,18 +1786,18 @@ int strotss_moment_fwd_bwd(const float* style_mean, const float* style_cov, cons
   if (x3) {           // both GEMMs on the bf16x3 core (csrc/mfma_x3.h); the column means are finished inside the centring
     hipLaunchKernelGGL(center_x3_kernel, dim3(ld / 32, s.rows / 32), dim3(256), 0, st, pred, n, s.rows, ld,
                        (const float*)nullptr, s.Pc, s.Pt, (const float*)s.psum, s.mean);
-    LAUNCH_OK();
-    CHK(st_moment_fwd_x3(s.Pt, s.rows, ld, style_cov, s.Tp, 1.0f / (float)n, s.partial, &n_partial, st));
+    ST_LAUNCH_OK();
+    ST_TRY(st_moment_fwd_x3(s.Pt, s.rows, ld, style_cov, s.Tp, 1.0f / (float)n, s.partial, &n_partial, st));
   } else {
     hipLaunchKernelGGL(col_mean_final_kernel, dim3(cdiv(ld, 256)), dim3(256), 0, st, s.psum, n, ld, s.mean);
     hipLaunchKernelGGL(center_kernel, dim3(min(2048, cdiv((size_t)s.rows * ld / 4, 256))), dim3(256), 0, st,
                        pred, n, s.rows, ld, s.mean, s.cy);
-    LAUNCH_OK();
-    CHK(st_moment_fwd_gemm(s.cy, s.rows, ld, style_cov, s.T, 1.0f / (float)n, s.partial, &n_partial, st));
+    ST_LAUNCH_OK();
+    ST_TRY(st_moment_fwd_gemm(s.cy, s.rows, ld, style_cov, s.T, 1.0f / (float)n, s.partial, &n_partial, st));
   }
   hipLaunchKernelGGL(moment_finalize_kernel, dim3(1), dim3(256), 0, st, s.partial, n_partial, style_mean,
                      s.mean, d, ld, s.sgn, loss_out);
-  LAUNCH_OK();
+  ST_LAUNCH_OK();
   // dL/dcy = cy (T + T^T) / (n d^2) = 2 cy T / (n d^2) (T symmetric); centring adjoint drops the
   // column mean of dL/dcy, which is zero up to rounding because sum_i cy[i,:] = 0.
   const float a = gscale * 2.0f / ((float)n * (float)d * (float)d);
@@ -1856,10 +1845,10 @@ static int step_losses_impl(const float* pred, const float* content, const float
   // the centred rows (both ways round) need the column sums: their own launch
   hipLaunchKernelGGL(center_x3_kernel, dim3(ld / 32, m.rows / 32), dim3(256), 0, st, pred, n, m.rows, ld,
                      (const float*)nullptr, m.Pc, m.Pt, (const float*)m.psum, m.mean);
-  LAUNCH_OK();
+  ST_LAUNCH_OK();
   // ---- the three forward products, one launch
   int n_partial = 0;
-  CHK(st_loss_forward_group_x3(m.Pt, m.rows, ld, style_cov, m.Tp, 1.0f / (float)n, m.partial, &n_partial,
+  ST_TRY(st_loss_forward_group_x3(m.Pt, m.rows, ld, style_cov, m.Tp, 1.0f / (float)n, m.partial, &n_partial,
                                s.xp, s.rp, n, s.xc - s.xp, s.rc - s.rp, s.Dx, ldc, s.Dy - s.Dx,
                                style_panels, style_inv_norm, ns, r.C, r.ldt, st));
   // ---- every statistic of the forward products: self-similarity rows | moment scalars + mean-gradient signs | REMD minima |
@@ -1876,9 +1865,9 @@ static int step_losses_impl(const float* pred, const float* content, const float
                      SelectArgs{nullptr, nullptr, n, 0, pl.cmin, pl.ccnt, pl.rmin, ns, 0, loss_palette, pl.sel, 0},
                      SelfsimSymArgs{s.Dx, s.Dy, s.sx, s.sy, s.tt, s.rp, n, ldc, ldc, 1.0f / (float)n, s.Mq, s.qdot, s.mp,
                                     s.lossrow, 1.0f / (float)n, loss_content, cw});
-  LAUNCH_OK();
-  CHK(st_selfsim_bwd_x3(s.mp, ldc, s.xt, pred, s.rp, s.qdot, n, ld, g_content, gpred, st));
-  CHK(st_moment_bwd_x3(m.Pc, n, ld, m.Tp, g_moment * 2.0f / ((float)n * (float)d * (float)d), m.sgn,
+  ST_LAUNCH_OK();
+  ST_TRY(st_selfsim_bwd_x3(s.mp, ldc, s.xt, pred, s.rp, s.qdot, n, ld, g_content, gpred, st));
+  ST_TRY(st_moment_bwd_x3(m.Pc, n, ld, m.Tp, g_moment * 2.0f / ((float)n * (float)d * (float)d), m.sgn,
                        g_moment / ((float)d * (float)n), gpred, st));
   // ---- relaxed EMD and palette: sparse backward kernels
   hipLaunchKernelGGL(remd_cos_bwd_kernel, dim3(n), dim3(256), 0, st, r.C, ldt, style, style_inv_norm, ns, pred, s.rp, n,
@@ -1934,7 +1923,7 @@ static int blend_impl(const float* pred, const float* content, const float* cw, 
                       void* workspace, size_t workspace_bytes, void* stream) {
   ST_CHECK_ARG(pred && content && styles && gpred && loss_content && loss_moment && loss_remd && loss_palette && workspace &&
                feat_ok(n, d, ld), STROTSS_EINVAL);
-  CHK(blend_check(styles));
+  ST_TRY(blend_check(styles));
   ST_CHECK_ARG(ld % 32 == 0, STROTSS_EALIGN);
   const strotss_style_set_t& ss = *styles;
   const int K = ss.n_styles;
@@ -1976,9 +1965,9 @@ static int blend_impl(const float* pred, const float* content, const float* cw, 
                      pa, ba);
   hipLaunchKernelGGL(center_x3_kernel, dim3(ld / 32, m.rows / 32), dim3(256), 0, st, pred, n, m.rows, ld,
                      (const float*)nullptr, m.Pc, m.Pt, (const float*)m.psum, m.mean);
-  LAUNCH_OK();
+  ST_LAUNCH_OK();
   // ---- the forward products, one launch
-  CHK(st_loss_forward_blend_x3(m.Pt, m.rows, ld, 1.0f / (float)n, b.sigma, s.xp, s.rp, n, s.xc - s.xp, s.rc - s.rp, s.Dx, ldc,
+  ST_TRY(st_loss_forward_blend_x3(m.Pt, m.rows, ld, 1.0f / (float)n, b.sigma, s.xp, s.rp, n, s.xc - s.xp, s.rc - s.rp, s.Dx, ldc,
                                s.Dy - s.Dx, K, xs, rs, nsv, Ct, ldt, st));
   // ---- statistics: self-similarity rows | moment rows | REMD minima per style | palette minima per style
   BlendStatsArgs sa{s.Dx, s.Dy, n, ldc, 1.0f / (float)n, s.sx, s.sy, s.tt, s.lossrow, b.sigma, ld, b.sp, b.mpart, yp, cw};
@@ -1988,9 +1977,9 @@ static int blend_impl(const float* pred, const float* content, const float* cw, 
                      BlendMomentArgs{b.mpart, ld, d, n, m.mean, b.msgn, loss_moment, loss_remd, loss_palette},
                      SelfsimSymArgs{s.Dx, s.Dy, s.sx, s.sy, s.tt, s.rp, n, ldc, ldc, 1.0f / (float)n, s.Mq, s.qdot, s.mp,
                                     s.lossrow, 1.0f / (float)n, loss_content, cw});
-  LAUNCH_OK();
-  CHK(st_selfsim_bwd_x3(s.mp, ldc, s.xt, pred, s.rp, s.qdot, n, ld, g_content, gpred, st));
-  CHK(st_moment_bwd_x3_full(m.Pc, n, ld, b.sp, g_moment * 2.0f / ((float)n * (float)d * (float)d), b.msgn,
+  ST_LAUNCH_OK();
+  ST_TRY(st_selfsim_bwd_x3(s.mp, ldc, s.xt, pred, s.rp, s.qdot, n, ld, g_content, gpred, st));
+  ST_TRY(st_moment_bwd_x3_full(m.Pc, n, ld, b.sp, g_moment * 2.0f / ((float)n * (float)d * (float)d), b.msgn,
                             g_moment / ((float)d * (float)n), gpred, st));
   hipLaunchKernelGGL(blend_remd_bwd_kernel, dim3(n), dim3(256), 0, st, ba, pred, s.rp, n, ld, g_remd, gpred);
   hipLaunchKernelGGL(blend_palette_bwd_kernel, dim3(n), dim3(64), 0, st, ba, (const f32x4*)yp, n, g_palette, gpred, ld);

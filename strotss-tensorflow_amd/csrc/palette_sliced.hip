@@ -4,7 +4,7 @@
 // of section 21) gives the direction's cost and the gradient coefficients.
 //
 //     match    one workgroup of 1024 threads per direction: thread t converts and projects prediction row t and style row t
-//              (D = 3: no GEMM), both sides are sorted by (value, row) on the bitonic network of sliced.hip, then
+//              (D = 3: no GEMM), both sides are sorted by (value, row) on the bitonic network of sort_match.h, then
 //              W_p = sum_ij len_ij |a_(i) - b_(j)| and dW_p/da = sum_j len_ij sign(a_(i) - b_(j)) at the element's original row
 //     finish   one thread per row: dy_i = (2 / (sqrt(3) P)) sum_p G[p][i] theta_p (p ascending), gpred[i][:3] += gscale M^T dy_i;
 //              loss = (2 / (sqrt(3) P)) sum_p W_p in a fixed order
@@ -12,6 +12,7 @@
 // Two launches, no float atomics: every coefficient, every gradient element and the scalar is written by one thread in a
 // fixed order.
 #include "internal.h"
+#include "sort_match.h"
 
 namespace {
 
@@ -29,19 +30,6 @@ struct PaletteSlicedWs {
   }
 };
 
-// order-preserving key of a float (-0 counts as +0, negative values below positive ones) above the row index: the pairs of
-// sliced_match_kernel
-__device__ __forceinline__ unsigned long long ps_pack(float v, int idx) {
-  unsigned b = __float_as_uint(v);
-  if (b == 0x80000000u) b = 0u;
-  const unsigned key = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-  return ((unsigned long long)key << 32) | (unsigned)idx;
-}
-__device__ __forceinline__ float ps_value(unsigned long long c) {
-  const unsigned key = (unsigned)(c >> 32);
-  return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
-}
-
 // <theta, yuv(row)>: convert_rgb_to_yuv with the constants of palette_prepare_kernel_body, every product rounded on its own
 // and every sum taken left to right (no contraction): the float32 restatement of the tests computes the same bits, so both
 // decide every near-tie of a sort and every sign alike
@@ -58,76 +46,26 @@ __device__ __forceinline__ float ps_project(const float* __restrict__ row, int c
 }
 
 // One direction a workgroup.  Thread tid holds one (key, row) pair of each side in registers (~0 past the side's end: sorts
-// last); the bitonic network runs on both at once over the first S = pow2 >= max(n, ns) slots -- stages within a wave by lane
-// shuffles, cross-wave stages through two alternating LDS buffers a side (consecutive 8-byte slots, partner tid ^ j with
-// j >= 64: conflict-free), ONE barrier a stage, at most 10 such stages.  LDS: 32 KB + 4 KB.
+// last); both are sorted at once over the first S = pow2 >= max(n, ns) slots, then matched (sort_match.h): the overlaps are
+// whole numbers, so the coefficient's sum is exact (at most ns <= 1024) and only the cost is rounded.  LDS: 32 KB + 4 KB.
 __global__ __launch_bounds__(PS_T) void palette_sliced_match_kernel(const float* __restrict__ style, int ns,
                                                                     const float* __restrict__ pred, int n, int ld, int convert,
                                                                     const float* __restrict__ dirs, float* __restrict__ G,
                                                                     float* __restrict__ Wp) {
-  __shared__ unsigned long long xa[2][PS_T], xb[2][PS_T];
+  __shared__ unsigned long long x[2][2 * PS_T];
   __shared__ float sb[PS_T];
   __shared__ double red[PS_T / 64];
   const int p = blockIdx.x, tid = threadIdx.x;
   const float t0 = dirs[3 * p], t1 = dirs[3 * p + 1], t2 = dirs[3 * p + 2];
-  unsigned long long va = tid < n ? ps_pack(ps_project(pred + (size_t)tid * ld, convert, t0, t1, t2), tid) : ~0ull;
-  unsigned long long vb = tid < ns ? ps_pack(ps_project(style + (size_t)tid * ld, convert, t0, t1, t2), tid) : ~0ull;
+  unsigned long long v[2] = {tid < n ? ordered_pack(ps_project(pred + (size_t)tid * ld, convert, t0, t1, t2), tid) : ~0ull,
+                             tid < ns ? ordered_pack(ps_project(style + (size_t)tid * ld, convert, t0, t1, t2), tid) : ~0ull};
   int S = 64;
   while (S < max(n, ns)) S <<= 1;
-  int flip = 0;
-#pragma unroll
-  for (int k = 2; k <= PS_T; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      if (k > S) continue;                               // uniform: slots >= S hold ~0 on both sides
-      unsigned long long pa, pb;
-      if (j < 64) {
-        pa = ((unsigned long long)__shfl_xor((unsigned)(va >> 32), j, 64) << 32) | __shfl_xor((unsigned)va, j, 64);
-        pb = ((unsigned long long)__shfl_xor((unsigned)(vb >> 32), j, 64) << 32) | __shfl_xor((unsigned)vb, j, 64);
-      } else {
-        xa[flip][tid] = va;
-        xb[flip][tid] = vb;
-        __syncthreads();
-        pa = xa[flip][tid ^ j];
-        pb = xb[flip][tid ^ j];
-        flip ^= 1;
-      }
-      const bool keep_low = ((tid & j) == 0) == ((tid & k) == 0);
-      va = (va < pa) == keep_low ? va : pa;
-      vb = (vb < pb) == keep_low ? vb : pb;
-    }
-  }
-  if (tid < ns) sb[tid] = ps_value(vb);
-  __syncthreads();
-  // the overlap of the quantile cells [i/n, (i+1)/n] and [j/ns, (j+1)/ns], in units of 1 / (n ns): whole numbers, so the
-  // coefficient's sum is exact (at most ns <= 1024) and only the cost is rounded
-  float w = 0.f;
-  if (tid < n) {
-    const float a = ps_value(va);
-    const int row = (int)(unsigned)(va & 0xFFFFFFFFull);
-    const int lo = tid * ns, hi = lo + ns;
-    float g = 0.f;
-    for (int j = lo / n; j < ns && j * n < hi; ++j) {
-      const float len = (float)(min(hi, (j + 1) * n) - max(lo, j * n));
-      const float diff = a - sb[j];
-      g += diff > 0.f ? len : (diff < 0.f ? -len : 0.f);
-      w += len * fabsf(diff);
-    }
-    const float inv = (float)(1.0 / ((double)n * ns));
-    G[(size_t)p * PS_LD + row] = g * inv;
-    w *= inv;
-  }
-  double wd = (double)w;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) wd += __shfl_xor(wd, o, 64);
-  if ((tid & 63) == 0) red[tid >> 6] = wd;
-  __syncthreads();
-  if (tid == 0) {
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < PS_T / 64; ++i) s += red[i];
-    Wp[p] = (float)s;
-  }
+  bitonic_sort_1024<2>(v, x[0], x[1], S);
+  const QuantileMatch m = quantile_match<AbsoluteCost>(v[0], v[1], n, ns, sb);
+  if (tid < n) G[(size_t)p * PS_LD + m.row] = m.coef;
+  const double s = block_sum_f64_1024((double)m.cost, red);
+  if (tid == 0) Wp[p] = (float)s;
 }
 
 // One row a thread: the directions in ascending order, then M^T (d_rgb = d_yuv @ M^T as palette_bwd_body) and gscale.  The
@@ -143,8 +81,7 @@ __global__ __launch_bounds__(256) void palette_sliced_finish_kernel(const float*
   if (blockIdx.x == 0 && threadIdx.x < 64) {
     double s = 0.0;
     for (int p = threadIdx.x; p < n_proj; p += 64) s += (double)Wp[p];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    s = wave_sum(s);
     if (threadIdx.x == 0) loss_out[0] = (float)(s * scale);
   }
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -199,10 +136,7 @@ int strotss_palette_sliced_fwd_bwd(const float* style, int ns, const float* pred
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(palette_sliced_match_kernel, dim3(n_proj), dim3(PS_T), 0, st, style, ns, pred, n, ld, rgb_to_yuv, dirs,
                      s.G, s.Wp);
-  {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-  }
+  ST_LAUNCH_OK();
   hipLaunchKernelGGL(palette_sliced_finish_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, s.G, s.Wp, dirs, n, n_proj, ld,
                      rgb_to_yuv, gscale, gpred, loss_out);
   ST_LAUNCH_RET();

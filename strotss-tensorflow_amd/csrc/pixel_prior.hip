@@ -214,8 +214,7 @@ int launch_pool_mean(const float* img, int h, int w, int ch, int p, float* out, 
   const int hp = (int)cells(h, p), wp = (int)cells(w, p);
   const long long n = (long long)hp * wp * ch;
   hipLaunchKernelGGL(pool_mean_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, img, h, w, ch, p, hp, wp, out);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  ST_LAUNCH_RET();
 }
 
 }  // namespace
@@ -255,8 +254,7 @@ int strotss_detail_fwd_bwd(const float* img, int h, int w, const strotss_detail_
     const int hp = (int)cells(h, p), wp = (int)cells(w, p);
     const float* X = img;                // P_1(x) is x
     if (p > 1) {
-      const int rc = launch_pool_mean(img, h, w, 3, p, plane, st);
-      if (rc != 0) return rc;
+      ST_TRY(launch_pool_mean(img, h, w, 3, p, plane, st));
       X = plane;
     }
     const int tc = prior_tile_cells(p);
@@ -266,8 +264,7 @@ int strotss_detail_fwd_bwd(const float* img, int h, int w, const strotss_detail_
     const int nbx = (int)cells(wp, tc);                    // a flat grid: tile rows x tile columns, row-major
     hipLaunchKernelGGL(detail_fwd_bwd_kernel, dim3((unsigned)(cells(hp, tc) * nbx)), dim3(256), lds, st, X, set->content[j],
                        set->weight[j], h, w, hp, wp, p, tc, nbx, coef, inv_n, gimg, loss_out + j, ticket, partials);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    ST_LAUNCH_OK();
   }
   return 0;
 }

@@ -33,12 +33,6 @@ namespace {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ double rf_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // first pixel row (column) of cell i: the smallest y with y g / n >= i
 __device__ __forceinline__ int rf_cell_start(int i, int g, int n) { return (int)(((long long)i * n + g - 1) / g); }
 // the cell of pixel row (column) y: y g / n < g for every y < n
@@ -58,9 +52,9 @@ __device__ __forceinline__ void refine_cell_mean(const float* __restrict__ img, 
     s1 += (double)img[at + 1];
     s2 += (double)img[at + 2];
   }
-  s0 = rf_wave_sum(s0);
-  s1 = rf_wave_sum(s1);
-  s2 = rf_wave_sum(s2);
+  s0 = wave_sum(s0);
+  s1 = wave_sum(s1);
+  s2 = wave_sum(s2);
   if (lane == 0) {
     const double dn = (double)n;
     mean[cell * 3] = (float)(s0 / dn);

@@ -28,17 +28,6 @@ namespace {
 #define SKL_MAX_ITERS 64
 #define SKL_MAX_L 1000.0f
 
-#define CHK(expr)               \
-  do {                          \
-    int rc__ = (expr);          \
-    if (rc__ != 0) return rc__; \
-  } while (0)
-#define LAUNCH_OK()                         \
-  do {                                      \
-    hipError_t e__ = hipGetLastError();     \
-    if (e__ != hipSuccess) return (int)e__; \
-  } while (0)
-
 struct SinkhornLogWs {
   float *Mt, *W, *PHI, *DA, *PSI, *DB, *pmax, *psum, *q;
   int ldm;
@@ -222,7 +211,7 @@ int sinkhorn_log_iterate(SinkhornLogWs& s, int ns, int n, float l, int T, float*
   const float inv_px = (float)ns, inv_py = (float)n;
   const float log_px = -logf((float)ns), log_py = -logf((float)n);
   const dim3 gcol(cdiv(ns, 64), SKL_CHUNKS), gfin(cdiv(ns, 256));
-  CHK((int)hipMemsetAsync(s.PSI, 0, sizeof(float) * (size_t)n, st));                        // psi_0 = 0
+  ST_TRY((int)hipMemsetAsync(s.PSI, 0, sizeof(float) * (size_t)n, st));                        // psi_0 = 0
   for (int t = 1; t <= T; ++t) {
     hipLaunchKernelGGL(skl_col_lse_partial_kernel, gcol, dim3(256), 0, st, s.Mt, n, ns, ldm, l, s.PSI + (size_t)(t - 1) * n,
                        s.pmax, s.psum);
@@ -231,7 +220,7 @@ int sinkhorn_log_iterate(SinkhornLogWs& s, int ns, int n, float l, int T, float*
     hipLaunchKernelGGL(skl_row_lse_kernel, dim3(n), dim3(256), 0, st, s.Mt, ns, ldm, l, s.PHI + (size_t)(t - 1) * ns, log_py,
                        s.PSI + (size_t)t * n);
   }
-  LAUNCH_OK();
+  ST_LAUNCH_OK();
   const float* phiT = s.PHI + (size_t)(T - 1) * ns;
   const float* psiT = s.PSI + (size_t)T * n;
   hipLaunchKernelGGL(skl_cost_kernel, dim3(n), dim3(256), 0, st, s.Mt, ns, ldm, l, phiT, psiT, s.DB + (size_t)(T - 1) * n);
@@ -244,9 +233,9 @@ int sinkhorn_log_iterate(SinkhornLogWs& s, int ns, int n, float l, int T, float*
       hipLaunchKernelGGL(skl_row_adj_kernel, dim3(n), dim3(256), 0, st, s.Mt, ns, ldm, l, s.PHI + (size_t)(t - 1) * ns,
                          s.DA + (size_t)(t - 1) * ns, s.PSI + (size_t)(t - 1) * n, inv_px, s.DB + (size_t)(t - 2) * n);
   }
-  LAUNCH_OK();
+  ST_LAUNCH_OK();
   const int rows = round_up(n, 64);
-  if (rows > n) CHK((int)hipMemsetAsync(s.W + (size_t)n * ldm, 0, sizeof(float) * (size_t)(rows - n) * ldm, st));
+  if (rows > n) ST_TRY((int)hipMemsetAsync(s.W + (size_t)n * ldm, 0, sizeof(float) * (size_t)(rows - n) * ldm, st));
   return 0;
 }
 
@@ -276,12 +265,12 @@ int strotss_sinkhorn_log_cos_fwd_bwd_panels(const float* style, const float* rs,
   ST_CHECK_ARG(s.plan(w, ns, n, n_iter), STROTSS_EINVAL);
   hipStream_t st = (hipStream_t)stream;
   const int ldm = s.ldm, T = n_iter;
-  if (pred_panels) CHK(st_cosine_distance_x3(pred_panels, pred_inv_norm, n, style_panels, rs, ns, ld, 0, s.Mt, ldm, 1, 0, 0, 0, st));
-  else CHK(st_cosine_distance(pred, pred_inv_norm, n, style, rs, ns, ld, s.Mt, ldm, st));     // Mt[j][i] = 1 - <yhat_j, xhat_i>
-  CHK(sinkhorn_log_iterate(s, ns, n, l, T, loss_out, st));
+  if (pred_panels) ST_TRY(st_cosine_distance_x3(pred_panels, pred_inv_norm, n, style_panels, rs, ns, ld, 0, s.Mt, ldm, 1, 0, 0, 0, st));
+  else ST_TRY(st_cosine_distance(pred, pred_inv_norm, n, style, rs, ns, ld, s.Mt, ldm, st));     // Mt[j][i] = 1 - <yhat_j, xhat_i>
+  ST_TRY(sinkhorn_log_iterate(s, ns, n, l, T, loss_out, st));
   hipLaunchKernelGGL(skl_assemble_kernel, dim3(n), dim3(256), 0, st, s.Mt, ns, ldm, T, l, s.PHI, s.DA, s.PSI, s.DB, n,
                      (float)ns, (float)n, rs, s.W, s.q);
-  LAUNCH_OK();
+  ST_LAUNCH_OK();
   return st_selfsim_bwd_gemm(s.W, ldm, ldm, style, pred, pred_inv_norm, s.q, n, ld, gscale, gpred, st);
 }
 

@@ -6,7 +6,7 @@
 //                  1 -> +1, 0 -> -1, columns k >= d zero; t = *counter.  nn/rand.py:sliced_signs is the host twin.
 //     projection   a[p][i] = <eps_p, x_i> r_i, b[p][j] = <eps_p, s_j> rs_j on the GEMM cores of gemm.hip (x3 panels or f32 MFMA),
 //                  the reciprocal norms in the epilogue, one direction's values contiguous
-//     sort, match  one workgroup of 1024 threads per direction: both sides by (value, row) on the bitonic network of draw.hip,
+//     sort, match  one workgroup of 1024 threads per direction: both sides by (value, row) on the bitonic network of sort_match.h,
 //                  then W_p = sum_ij len_ij (a_(i) - b_(j))^2 and dloss/da at the element's original row
 //     backward     q_i = sum_p G[p][i] a[p][i], then dx += gscale r_i (G^T eps - xhat_i q_i) (st_selfsim_bwd_gemm_tn)
 //     finish       loss = sum_p W_p / (2 P) in a fixed order, *counter = t + 1
@@ -14,6 +14,7 @@
 // No float atomics: every coefficient, every gradient element and every scalar is written by one thread in a fixed order.
 #include "internal.h"
 #include "philox.h"
+#include "sort_match.h"
 
 namespace {
 
@@ -79,94 +80,31 @@ __global__ __launch_bounds__(256) void sliced_directions_kernel(const unsigned* 
   }
 }
 
-// order-preserving key of a float (-0 counts as +0, negative values below positive ones) above the row index
-__device__ __forceinline__ unsigned long long sliced_pack(float v, int idx) {
-  unsigned b = __float_as_uint(v);
-  if (b == 0x80000000u) b = 0u;
-  const unsigned key = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-  return ((unsigned long long)key << 32) | (unsigned)idx;
-}
-__device__ __forceinline__ float sliced_value(unsigned long long c) {
-  const unsigned key = (unsigned)(c >> 32);
-  return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
-}
-
 // One direction a workgroup.  Thread tid holds one (key, row) pair of each side in registers (~0 past the side's end: sorts
-// last); the bitonic network of draw.hip runs on both at once over the first S = pow2 >= max(n, ns) slots -- stages within
-// a wave by lane shuffles, cross-wave stages through two alternating LDS buffers a side (consecutive 8-byte slots, partner
-// tid ^ j with j >= 64: conflict-free), ONE barrier a stage, at most 10 such stages.  LDS: 32 KB + 4 KB.
+// last); both are sorted at once over the first S = pow2 >= max(n, ns) slots, then matched (sort_match.h).  LDS: 32 KB + 4 KB.
 __global__ __launch_bounds__(SL_T) void sliced_match_kernel(const float* __restrict__ A, const float* __restrict__ B, int n,
                                                             int ns, int n_proj, float* __restrict__ Gt,
                                                             float* __restrict__ Wp) {
-  __shared__ unsigned long long xa[2][SL_T], xb[2][SL_T];
+  __shared__ unsigned long long x[2][2 * SL_T];
   __shared__ float sb[SL_T];
   __shared__ double red[SL_T / 64];
   const int p = blockIdx.x, tid = threadIdx.x;
   const int n4 = (n + 3) & ~3;
   float* g_row = Gt + (size_t)p * SL_LD;
-  if (p >= n_proj) {                                     // the backward product's K padding
+  if (p >= n_proj) {                                     // the backward product's K padding; uniform, before any barrier
     if (tid < n4) g_row[tid] = 0.f;
     return;
   }
-  unsigned long long va = tid < n ? sliced_pack(A[(size_t)p * SL_LD + tid], tid) : ~0ull;
-  unsigned long long vb = tid < ns ? sliced_pack(B[(size_t)p * SL_LD + tid], tid) : ~0ull;
+  unsigned long long v[2] = {tid < n ? ordered_pack(A[(size_t)p * SL_LD + tid], tid) : ~0ull,
+                             tid < ns ? ordered_pack(B[(size_t)p * SL_LD + tid], tid) : ~0ull};
   int S = 64;
   while (S < max(n, ns)) S <<= 1;
-  int flip = 0;
-#pragma unroll
-  for (int k = 2; k <= SL_T; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      if (k > S) continue;                               // uniform: slots >= S hold ~0 on both sides
-      unsigned long long pa, pb;
-      if (j < 64) {
-        pa = ((unsigned long long)__shfl_xor((unsigned)(va >> 32), j, 64) << 32) | __shfl_xor((unsigned)va, j, 64);
-        pb = ((unsigned long long)__shfl_xor((unsigned)(vb >> 32), j, 64) << 32) | __shfl_xor((unsigned)vb, j, 64);
-      } else {
-        xa[flip][tid] = va;
-        xb[flip][tid] = vb;
-        __syncthreads();
-        pa = xa[flip][tid ^ j];
-        pb = xb[flip][tid ^ j];
-        flip ^= 1;
-      }
-      const bool keep_low = ((tid & j) == 0) == ((tid & k) == 0);
-      va = (va < pa) == keep_low ? va : pa;
-      vb = (vb < pb) == keep_low ? vb : pb;
-    }
-  }
-  if (tid < ns) sb[tid] = sliced_value(vb);
-  __syncthreads();
-  // the overlap of the quantile cells [i/n, (i+1)/n] and [j/ns, (j+1)/ns], in units of 1 / (n ns): whole numbers
-  float w = 0.f;
-  if (tid < n) {
-    const float a = sliced_value(va);
-    const int row = (int)(unsigned)(va & 0xFFFFFFFFull);
-    const int lo = tid * ns, hi = lo + ns;
-    float g = 0.f;
-    for (int j = lo / n; j < ns && j * n < hi; ++j) {
-      const float len = (float)(min(hi, (j + 1) * n) - max(lo, j * n));
-      const float diff = a - sb[j];
-      g += len * diff;
-      w += len * diff * diff;
-    }
-    const float inv = (float)(1.0 / ((double)n * ns));
-    g_row[row] = g * inv / (float)n_proj;
-    w *= inv;
-  } else if (tid < n4) {
-    g_row[tid] = 0.f;
-  }
-  double wd = (double)w;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) wd += __shfl_xor(wd, o, 64);
-  if ((tid & 63) == 0) red[tid >> 6] = wd;
-  __syncthreads();
-  if (tid == 0) {
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < SL_T / 64; ++i) s += red[i];
-    Wp[p] = (float)s;
-  }
+  bitonic_sort_1024<2>(v, x[0], x[1], S);
+  const QuantileMatch m = quantile_match<SquaredCost>(v[0], v[1], n, ns, sb);
+  if (tid < n) g_row[m.row] = m.coef / (float)n_proj;
+  else if (tid < n4) g_row[tid] = 0.f;
+  const double s = block_sum_f64_1024((double)m.cost, red);
+  if (tid == 0) Wp[p] = (float)s;
 }
 
 // q_i = sum_p G[p][i] a[p][i]: 64 rows a workgroup, wave wv takes the directions wv, wv + 16, ..; the 16 partial sums are
@@ -194,24 +132,12 @@ __global__ __launch_bounds__(64) void sliced_finish_kernel(const float* __restri
                                                            unsigned* __restrict__ counter) {
   double s = 0.0;
   for (int p = threadIdx.x; p < n_proj; p += 64) s += (double)Wp[p];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  s = wave_sum(s);
   if (threadIdx.x == 0) {
     loss_out[0] = (float)(s / (2.0 * n_proj));
     *counter = *counter + 1u;
   }
 }
-
-#define SL_CHK(expr)         \
-  do {                       \
-    int rc__ = (expr);       \
-    if (rc__ != 0) return rc__; \
-  } while (0)
-#define SL_LAUNCH_OK()                               \
-  do {                                               \
-    hipError_t e__ = hipGetLastError();              \
-    if (e__ != hipSuccess) return (int)e__;          \
-  } while (0)
 
 }  // namespace
 
@@ -240,19 +166,19 @@ int strotss_sliced_cos_fwd_bwd(const float* style, const float* rs, const void* 
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(sliced_directions_kernel, dim3(s.kpad), dim3(256), 0, st, counter, seed_lo, seed_hi, n_proj, d, ld, s.E,
                      s.Ep);
-  SL_LAUNCH_OK();
+  ST_LAUNCH_OK();
   if (pred_panels) {
-    SL_CHK(st_rows_project_x3(s.Ep, n_proj, pred_panels, pred_inv_norm, n, ld, s.A, SL_LD, st));
-    SL_CHK(st_rows_project_x3(s.Ep, n_proj, style_panels, rs, ns, ld, s.B, SL_LD, st));
+    ST_TRY(st_rows_project_x3(s.Ep, n_proj, pred_panels, pred_inv_norm, n, ld, s.A, SL_LD, st));
+    ST_TRY(st_rows_project_x3(s.Ep, n_proj, style_panels, rs, ns, ld, s.B, SL_LD, st));
   } else {
-    SL_CHK(st_rows_project(s.E, n_proj, pred, pred_inv_norm, n, ld, s.A, SL_LD, st));
-    SL_CHK(st_rows_project(s.E, n_proj, style, rs, ns, ld, s.B, SL_LD, st));
+    ST_TRY(st_rows_project(s.E, n_proj, pred, pred_inv_norm, n, ld, s.A, SL_LD, st));
+    ST_TRY(st_rows_project(s.E, n_proj, style, rs, ns, ld, s.B, SL_LD, st));
   }
   hipLaunchKernelGGL(sliced_match_kernel, dim3(s.kpad), dim3(SL_T), 0, st, s.A, s.B, n, ns, n_proj, s.Gt, s.Wp);
-  SL_LAUNCH_OK();
+  ST_LAUNCH_OK();
   hipLaunchKernelGGL(sliced_rowdot_kernel, dim3(cdiv(n, 64)), dim3(SL_T), 0, st, s.Gt, s.A, n, n_proj, s.q);
-  SL_LAUNCH_OK();
-  SL_CHK(st_selfsim_bwd_gemm_tn(s.Gt, SL_LD, s.kpad, s.E, pred, pred_inv_norm, s.q, n, ld, gscale, gpred, st));
+  ST_LAUNCH_OK();
+  ST_TRY(st_selfsim_bwd_gemm_tn(s.Gt, SL_LD, s.kpad, s.E, pred, pred_inv_norm, s.q, n, ld, gscale, gpred, st));
   hipLaunchKernelGGL(sliced_finish_kernel, dim3(1), dim3(64), 0, st, s.Wp, n_proj, loss_out, counter);
   ST_LAUNCH_RET();
 }

@@ -1159,29 +1159,47 @@ def remd_cos_fwd_bwd(style, rs, ns, pred, n, d, gscale, gpred, loss_out, swapped
                                      ptr(gpred), ptr(loss_out), int(swapped), ptr(ws), nb, stream_ptr()), "remd_cos_fwd_bwd")
 
 
-def remd_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, gscale, gpred, loss_out):
-    """remd_cos_fwd_bwd for the prediction rows that selfsim_fwd_bwd has just processed (checked against the record that
-    call leaves; a mismatch -- other rows, a regrown workspace, another stream -- falls back to the plain call): their reciprocal norms and x3 panels are taken from that workspace, the style rows' panels
-    from `style_panels` (row_inv_norm_x3(style)[1], constant within a scale) -- bit for bit remd_cos_fwd_bwd, one launch and
-    two passes over the rows less.  style_panels None or the cost matrices on the f32 MFMA: the plain call."""
+def _pred_panels_after_selfsim(pred, n, style_panels):
+    """What selfsim_fwd_bwd is KNOWN to have left in its workspace for exactly these prediction rows: (reciprocal norms,
+    prediction panels, style panels) as pointers, or None where the record that call leaves does not match -- other rows, a
+    regrown or re-used buffer, another count or stride, another stream.  The panels come as a pair: both are None where the
+    library hands out none (the cost matrices on the f32 MFMA, STROTSS_X3=0) or the StyleTarget has none."""
     l = _hip.lib()
-    ld = pred.shape[1]
+    ld = int(pred.shape[1])
     nb = l.strotss_selfsim_workspace_bytes(n, ld)
     ws = workspaces.get("selfsim", nb, pred.device)
-    # borrow only what selfsim_fwd_bwd is KNOWN to have left there: same buffer (not regrown or re-used since), same rows,
-    # same count and stride, same stream -- anything else takes the plain call, which makes its own norms and panels
-    if _selfsim_record != (ws.data_ptr(), nb, ptr(pred), n, int(ld), stream_ptr()):
-        remd_borrow_stats["plain"] += 1
-        return remd_cos_fwd_bwd(style, rs, ns, pred, n, d, gscale, gpred, loss_out)
+    if _selfsim_record != (ws.data_ptr(), nb, ptr(pred), n, ld, stream_ptr()):
+        return None
     rp, xp = C.c_void_p(), C.c_void_p()
     check(l.strotss_selfsim_pred_panels(ptr(ws), nb, n, ld, C.byref(rp), C.byref(xp)), "selfsim_pred_panels")
-    if style_panels is None or not xp.value:
+    both = style_panels is not None and bool(xp.value)
+    return rp.value, xp.value if both else None, ptr(style_panels) if both else None
+
+
+def _pred_panels_or_raise(who, pred, n, style_panels):
+    """_pred_panels_after_selfsim for the terms that have no plain call to fall back to: a mismatch is an error"""
+    got = _pred_panels_after_selfsim(pred, n, style_panels)
+    if got is None:
+        raise _hip.StrotssHipError(f"{who}: selfsim_fwd_bwd has not just run on these rows")
+    return got
+
+
+def remd_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, gscale, gpred, loss_out):
+    """remd_cos_fwd_bwd for the prediction rows that selfsim_fwd_bwd has just processed (_pred_panels_after_selfsim; a
+    mismatch falls back to the plain call, which makes its own norms and panels): their reciprocal norms and x3 panels are
+    taken from that workspace, the style rows' panels from `style_panels` (row_inv_norm_x3(style)[1], constant within a
+    scale) -- bit for bit remd_cos_fwd_bwd, one launch and two passes over the rows less.  No pair of panels: the plain call."""
+    got = _pred_panels_after_selfsim(pred, n, style_panels)
+    if got is None or got[1] is None:
         remd_borrow_stats["plain"] += 1
         return remd_cos_fwd_bwd(style, rs, ns, pred, n, d, gscale, gpred, loss_out)
+    rp, xp, sp = got
     remd_borrow_stats["borrowed"] += 1
+    l = _hip.lib()
+    ld = pred.shape[1]
     nbr = l.strotss_remd_workspace_bytes(ns, n, ld)
     wsr = workspaces.get("remd", nbr, pred.device)
-    check(l.strotss_remd_cos_fwd_bwd_panels(ptr(style), ptr(rs), ptr(style_panels), ns, ptr(pred), rp.value, xp.value, n, d, ld,
+    check(l.strotss_remd_cos_fwd_bwd_panels(ptr(style), ptr(rs), sp, ns, ptr(pred), rp, xp, n, d, ld,
                                             gscale, ptr(gpred), ptr(loss_out), ptr(wsr), nbr, stream_ptr()),
           "remd_cos_fwd_bwd_panels")
 
@@ -1271,72 +1289,52 @@ def sinkhorn_cos_fwd_bwd(style, rs, ns, pred, n, d, l, n_iter, gscale, gpred, lo
 def sinkhorn_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, l, n_iter, gscale, gpred, loss_out):
     """The step's Sinkhorn term (strotss_sinkhorn_cos_fwd_bwd_panels) for the prediction rows that
     selfsim_fwd_bwd has just processed: their reciprocal norms and x3 panels come from that call's workspace, the style rows'
-    panels from `style_panels`.  Where the cost matrices run on the f32 MFMA (STROTSS_X3=0: the library hands out no panels)
-    or the StyleTarget has none, both panels are passed as NULL.  Unlike the relaxed EMD there is no plain call to fall back
-    to: rows other than those the content loss left its record for are an error."""
+    panels from `style_panels` (_pred_panels_after_selfsim: both panels or neither).  Unlike the relaxed EMD there is no plain
+    call to fall back to: rows other than those the content loss left its record for are an error."""
     l_ = _hip.lib()
     ld = pred.shape[1]
-    nb = l_.strotss_selfsim_workspace_bytes(n, ld)
-    ws = workspaces.get("selfsim", nb, pred.device)
-    if _selfsim_record != (ws.data_ptr(), nb, ptr(pred), n, int(ld), stream_ptr()):
-        raise _hip.StrotssHipError("sinkhorn_cos_fwd_bwd_after_selfsim: selfsim_fwd_bwd has not just run on these rows")
-    rp, xp = C.c_void_p(), C.c_void_p()
-    check(l_.strotss_selfsim_pred_panels(ptr(ws), nb, n, ld, C.byref(rp), C.byref(xp)), "selfsim_pred_panels")
-    both = style_panels is not None and bool(xp.value)
+    rp, xp, sp = _pred_panels_or_raise("sinkhorn_cos_fwd_bwd_after_selfsim", pred, n, style_panels)
     nbs = l_.strotss_sinkhorn_step_workspace_bytes(ns, n, int(n_iter))
     wss = workspaces.get("sinkhorn_step", nbs, pred.device)
-    check(l_.strotss_sinkhorn_cos_fwd_bwd_panels(ptr(style), ptr(rs), ptr(style_panels) if both else None, ns, ptr(pred),
-                                                 rp.value, xp.value if both else None, n, d, ld, float(l), int(n_iter),
-                                                 float(gscale), ptr(gpred), ptr(loss_out), ptr(wss), nbs, stream_ptr()),
+    check(l_.strotss_sinkhorn_cos_fwd_bwd_panels(ptr(style), ptr(rs), sp, ns, ptr(pred), rp, xp, n, d, ld, float(l),
+                                                 int(n_iter), float(gscale), ptr(gpred), ptr(loss_out), ptr(wss), nbs,
+                                                 stream_ptr()),
           "sinkhorn_cos_fwd_bwd_panels")
 
 
 def sinkhorn_log_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, l, n_iter, gscale, gpred, loss_out):
     """The step's Sinkhorn term in the log domain (strotss_sinkhorn_log_cos_fwd_bwd_panels), called as
     sinkhorn_cos_fwd_bwd_after_selfsim is: the prediction rows' norms and x3 panels from the content loss's workspace, both
-    panels NULL where the library hands out none or the StyleTarget has none, and rows other than those the content loss
-    left its record for an error."""
+    panels or neither, and rows other than those the content loss left its record for an error."""
     l_ = _hip.lib()
     ld = pred.shape[1]
-    nb = l_.strotss_selfsim_workspace_bytes(n, ld)
-    ws = workspaces.get("selfsim", nb, pred.device)
-    if _selfsim_record != (ws.data_ptr(), nb, ptr(pred), n, int(ld), stream_ptr()):
-        raise _hip.StrotssHipError("sinkhorn_log_cos_fwd_bwd_after_selfsim: selfsim_fwd_bwd has not just run on these rows")
-    rp, xp = C.c_void_p(), C.c_void_p()
-    check(l_.strotss_selfsim_pred_panels(ptr(ws), nb, n, ld, C.byref(rp), C.byref(xp)), "selfsim_pred_panels")
-    both = style_panels is not None and bool(xp.value)
+    rp, xp, sp = _pred_panels_or_raise("sinkhorn_log_cos_fwd_bwd_after_selfsim", pred, n, style_panels)
     nbs = l_.strotss_sinkhorn_log_step_workspace_bytes(ns, n, int(n_iter))
     if nbs == 0:
         raise _hip.StrotssHipError(f"sinkhorn_log_cos_fwd_bwd_after_selfsim: invalid sizes ns={ns} n={n} n_iter={n_iter}")
     wss = workspaces.get("sinkhorn_log_step", nbs, pred.device)
-    check(l_.strotss_sinkhorn_log_cos_fwd_bwd_panels(ptr(style), ptr(rs), ptr(style_panels) if both else None, ns, ptr(pred),
-                                                     rp.value, xp.value if both else None, n, d, ld, float(l), int(n_iter),
-                                                     float(gscale), ptr(gpred), ptr(loss_out), ptr(wss), nbs, stream_ptr()),
+    check(l_.strotss_sinkhorn_log_cos_fwd_bwd_panels(ptr(style), ptr(rs), sp, ns, ptr(pred), rp, xp, n, d, ld, float(l),
+                                                     int(n_iter), float(gscale), ptr(gpred), ptr(loss_out), ptr(wss), nbs,
+                                                     stream_ptr()),
           "sinkhorn_log_cos_fwd_bwd_panels")
 
 
 def sliced_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, n_proj, seed, counter, gscale, gpred, loss_out):
     """The step's sliced Wasserstein term (strotss_sliced_cos_fwd_bwd) for the prediction rows that
     selfsim_fwd_bwd has just processed: their reciprocal norms and x3 panels come from that call's workspace, the style rows'
-    panels from `style_panels`; both panels are passed as NULL where the library hands out none (STROTSS_X3=0) or the
-    StyleTarget has none.  `counter`: one int32 on the device, the draw number of the directions; the call leaves it one
-    higher.  As for the Sinkhorn term, rows other than those the content loss left its record for are an error."""
+    panels from `style_panels` (_pred_panels_after_selfsim: both panels or neither).  `counter`: one int32 on the device, the
+    draw number of the directions; the call leaves it one higher.  As for the Sinkhorn term, rows other than those the
+    content loss left its record for are an error."""
     l_ = _hip.lib()
     ld = pred.shape[1]
     assert counter.dtype == torch.int32 and counter.numel() >= 1 and counter.is_cuda
-    nb = l_.strotss_selfsim_workspace_bytes(n, ld)
-    ws = workspaces.get("selfsim", nb, pred.device)
-    if _selfsim_record != (ws.data_ptr(), nb, ptr(pred), n, int(ld), stream_ptr()):
-        raise _hip.StrotssHipError("sliced_cos_fwd_bwd_after_selfsim: selfsim_fwd_bwd has not just run on these rows")
-    rp, xp = C.c_void_p(), C.c_void_p()
-    check(l_.strotss_selfsim_pred_panels(ptr(ws), nb, n, ld, C.byref(rp), C.byref(xp)), "selfsim_pred_panels")
-    both = style_panels is not None and bool(xp.value)
+    rp, xp, sp = _pred_panels_or_raise("sliced_cos_fwd_bwd_after_selfsim", pred, n, style_panels)
     nbs = l_.strotss_sliced_workspace_bytes(ns, n, ld, int(n_proj))
     wss = workspaces.get("sliced_step", nbs, pred.device)
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    check(l_.strotss_sliced_cos_fwd_bwd(ptr(style), ptr(rs), ptr(style_panels) if both else None, ns, ptr(pred), rp.value,
-                                        xp.value if both else None, n, d, ld, int(n_proj), seed & 0xFFFFFFFF, seed >> 32,
-                                        ptr(counter), float(gscale), ptr(gpred), ptr(loss_out), ptr(wss), nbs, stream_ptr()),
+    check(l_.strotss_sliced_cos_fwd_bwd(ptr(style), ptr(rs), sp, ns, ptr(pred), rp, xp, n, d, ld, int(n_proj),
+                                        seed & 0xFFFFFFFF, seed >> 32, ptr(counter), float(gscale), ptr(gpred), ptr(loss_out),
+                                        ptr(wss), nbs, stream_ptr()),
           "sliced_cos_fwd_bwd")
 
 

@@ -240,21 +240,17 @@ class StepEngine:
                  tv_weight: float = 0.0):
         dev = stylized.device
         check_palette_transport(palette_transport, palette_projections)
-        if palette_transport == "sliced" and (strips is not None or dist_group is not None):
-            raise ValueError("the sliced palette term runs on one GPU: image strips and region sharding are not supported "
-                             "with it")
+        check_style_transport(style_transport, sinkhorn_l, sinkhorn_iters, sliced_projections, sinkhorn_log)
+        for chosen, what in ((palette_transport == "sliced", "the sliced palette term"),
+                             (style_transport == "sinkhorn", "the Sinkhorn style term"),
+                             (style_transport == "sliced", "the sliced style term")):
+            if chosen and (strips is not None or dist_group is not None):
+                raise ValueError(f"{what} runs on one GPU: image strips and region sharding are not supported with it")
         self.palette_transport, self.palette_projections = palette_transport, int(palette_projections)
         # the sliced palette term's directions: fixed for the life of the engine (a captured graph reads them at replay)
         self._palette_dirs = (torch.from_numpy(rand.palette_directions(self.palette_projections)).to(dev).contiguous()
                               if palette_transport == "sliced" else None)
-        check_style_transport(style_transport, sinkhorn_l, sinkhorn_iters, sliced_projections, sinkhorn_log)
         self.sinkhorn_log = bool(sinkhorn_log)
-        if style_transport == "sinkhorn" and (strips is not None or dist_group is not None):
-            raise ValueError("the Sinkhorn style term runs on one GPU: image strips and region sharding are not supported "
-                             "with it")
-        if style_transport == "sliced" and (strips is not None or dist_group is not None):
-            raise ValueError("the sliced style term runs on one GPU: image strips and region sharding are not supported "
-                             "with it")
         self.style_transport, self.sinkhorn_l, self.sinkhorn_iters = style_transport, float(sinkhorn_l), int(sinkhorn_iters)
         self.sliced_projections, self.sliced_seed = int(sliced_projections), int(sliced_seed)
         # the sliced term's draw number: call number c of this engine uses draw c (the entry leaves it one higher)
@@ -395,6 +391,11 @@ class StepEngine:
         self._styles = [(t.targets, t.weights) if isinstance(t, StyleBlend) else ([t], [1.0]) for t in self.style_targets]
         self._style_sets = [_ops.make_style_set(ts, ws) if len(ts) > 1 or ts[0].panels is not None else None
                             for ts, ws in self._styles]
+        # the terms of a region, decided once: the grouped call stands for the relaxed EMDs only and needs a style set;
+        # otherwise the separate entries with the style and the palette term of the engine's transports
+        self._grouped_ok = [style_transport == "remd" and palette_transport == "remd" and s is not None
+                            for s in self._style_sets]
+        self._style_term, self._palette_term = self._choose_terms()
         # content-weight map: every region's weights of its samples (rows >= n zero), gathered with its features
         self._cw = self._mt_cw = None
         if self._cw_map is not None:
@@ -504,6 +505,31 @@ class StepEngine:
                                                        self.gp[r].data_ptr(), int(self.gp[r].shape[0]), _hip.stream_ptr()),
                    "hypercol_gather2")
 
+    def _choose_terms(self):
+        """The style term and the palette term of the separate entries, chosen once from the engine's transports: each is
+        f(style target, pf, n, gscale, gp, out).  The relaxed EMD borrows the prediction rows' norms and x3 panels from the
+        content loss's workspace (the moment term has its own) and the style rows' panels from the StyleTarget; so do the
+        Sinkhorn and the sliced term."""
+        if self.style_transport == "sinkhorn":
+            entry = _ops.sinkhorn_log_cos_fwd_bwd_after_selfsim if self.sinkhorn_log else _ops.sinkhorn_cos_fwd_bwd_after_selfsim
+
+            def style_term(st, pf, n, g, gp, out):
+                entry(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, self.sinkhorn_l, self.sinkhorn_iters, g, gp, out)
+        elif self.style_transport == "sliced":
+            def style_term(st, pf, n, g, gp, out):
+                _ops.sliced_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d,
+                                                      self.sliced_projections, self.sliced_seed, self._sliced_counter, g, gp, out)
+        else:
+            def style_term(st, pf, n, g, gp, out):
+                _ops.remd_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, g, gp, out)
+        if self.palette_transport == "sliced":
+            def palette_term(st, pf, n, g, gp, out):
+                _ops.palette_sliced_fwd_bwd(st.feats, st.ns, pf, n, self._palette_dirs, g, gp, out)
+        else:
+            def palette_term(st, pf, n, g, gp, out):
+                _ops.palette_remd_fwd_bwd(st.feats, st.ns, pf, n, g, gp, out)
+        return style_term, palette_term
+
     def _losses(self, r: int, n: int, zeroed: bool = False):
         """(alpha*loss_c + loss_s)/loss_denom/R and its gradient w.r.t. the sampled prediction.  zeroed: the gradient rows
         were cleared by _gather_both already."""
@@ -517,10 +543,7 @@ class StepEngine:
         cw = self._cw[r] if self._cw is not None else None     # the samples' content weights (content-weight map)
         # moment / REMD / palette: the region's own scalars for one style, one unweighted value per style of a blend
         outs = (sc[1:], sc[2:], sc[3:]) if len(targets) == 1 else tuple(self._style_scalars[r])
-        sinkhorn = self.style_transport == "sinkhorn"      # the separate entries, Sinkhorn where the cosine REMD stands
-        sliced = self.style_transport == "sliced"          # likewise
-        pal_sliced = self.palette_transport == "sliced"    # the separate entries, the sliced term where the palette REMD stands
-        if not sinkhorn and not sliced and not pal_sliced and self._style_sets[r] is not None and _ops.step_losses_available():
+        if self._grouped_ok[r] and _ops.step_losses_available():
             # one call: 13 launches instead of 21, the three forward GEMMs in one of them (bit for bit the separate entries
             # below for one style); a blend in as many launches
             _ops.step_losses_cw_fwd_bwd(pf, cf, n, self.d, cw, self._style_sets[r], self.alpha * base, base, base,
@@ -529,24 +552,8 @@ class StepEngine:
         _ops.selfsim_weighted_fwd_bwd(pf, cf, cw, n, self.d, self.alpha * base, gp, sc[0:])
         for k, (st, w) in enumerate(zip(targets, weights)):
             _ops.moment_fwd_bwd(st.mean, st.cov, pf, n, self.d, base * w, gp, outs[0][k:])
-            # the relaxed EMD borrows the prediction rows' norms and x3 panels from the content loss's workspace (the moment
-            # term has its own) and the style rows' panels from the StyleTarget; so does the Sinkhorn term
-            if sinkhorn:
-                term = _ops.sinkhorn_log_cos_fwd_bwd_after_selfsim if self.sinkhorn_log else _ops.sinkhorn_cos_fwd_bwd_after_selfsim
-                term(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, self.sinkhorn_l, self.sinkhorn_iters, base * w, gp,
-                     outs[1][k:])
-            elif sliced:
-                _ops.sliced_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d,
-                                                      self.sliced_projections, self.sliced_seed, self._sliced_counter,
-                                                      base * w, gp, outs[1][k:])
-            else:
-                _ops.remd_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, base * w, gp,
-                                                    outs[1][k:])
-            if pal_sliced:
-                _ops.palette_sliced_fwd_bwd(st.feats, st.ns, pf, n, self._palette_dirs, self.inv_alpha * base * w, gp,
-                                            outs[2][k:])
-            else:
-                _ops.palette_remd_fwd_bwd(st.feats, st.ns, pf, n, self.inv_alpha * base * w, gp, outs[2][k:])
+            self._style_term(st, pf, n, base * w, gp, outs[1][k:])
+            self._palette_term(st, pf, n, self.inv_alpha * base * w, gp, outs[2][k:])
 
     def _scatter_maps(self, r: int):
         """descriptor + sample count of region r's tap adjoint: strips (recompute margin) = this rank's block of the samples
