@@ -11,7 +11,7 @@
 
 namespace {
 
-#define COLOR_THREADS 256
+#define COLOR_THREADS 256                // ticket_sum_256's workgroup
 #define COLOR_PIX_PER_BLOCK (4 * COLOR_THREADS)
 #define COLOR_MAX_BLOCKS 2048            // above 2^21 pixels the blocks stride over the groups: the partials stay 160 KB
 #define COLOR_SUMS 10                    // W, S_0, S_1, S_2, S_00, S_01, S_02, S_11, S_12, S_22
@@ -30,24 +30,9 @@ __device__ __forceinline__ void color_accum(double (&a)[COLOR_SUMS], float m, fl
   a[9] += dm * (d2 * d2);
 }
 
-// The ten sums of the block in every thread: a fixed shuffle tree per wave, the 4 waves in a fixed order.
-__device__ __forceinline__ void block_sum10_256(double (&a)[COLOR_SUMS], double (*red)[COLOR_SUMS]) {
-#pragma unroll
-  for (int k = 0; k < COLOR_SUMS; ++k) a[k] = wave_sum(a[k]);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < COLOR_SUMS; ++k) red[threadIdx.x >> 6][k] = a[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < COLOR_SUMS; ++k) a[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
-}
-
 // Thread t of block b takes the groups (b + i gridDim) 256 + t, i = 0, 1, ... in ascending order, the 4 pixels of a group in
-// ascending order: per-thread float64 sums in element order.  One fixed tree per block; the block that takes the last
-// ticket sums the block partials in a fixed order (thread t: partials t, t + 256, ...; then the same tree) and resets the
-// ticket.  No float atomics: the ten doubles are the same bits on every run.
+// ascending order: per-thread float64 sums in element order, then ticket_sum_256 (csrc/ticket_sum.h) with scale 1.0, which
+// is exact.  No float atomics: the ten doubles are the same bits on every run.
 __global__ __launch_bounds__(COLOR_THREADS) void color_stats_kernel(const float* __restrict__ img,
                                                                     const float* __restrict__ weight, int npix,
                                                                     double* __restrict__ out, unsigned* __restrict__ ticket,
@@ -75,29 +60,7 @@ __global__ __launch_bounds__(COLOR_THREADS) void color_stats_kernel(const float*
         color_accum(a, weight ? weight[p] : 1.f, img[3 * p], img[3 * p + 1], img[3 * p + 2]);
     }
   }
-  block_sum10_256(a, red);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < COLOR_SUMS; ++k) partials[(size_t)blockIdx.x * COLOR_SUMS + k] = a[k];
-    __threadfence();                                  // the partials are visible before the ticket is taken
-    is_last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-  }
-  __syncthreads();
-  if (!is_last) return;
-  __threadfence();
-#pragma unroll
-  for (int k = 0; k < COLOR_SUMS; ++k) a[k] = 0.0;
-  for (int i = threadIdx.x; i < (int)gridDim.x; i += COLOR_THREADS) {
-#pragma unroll
-    for (int k = 0; k < COLOR_SUMS; ++k)
-      a[k] += __hip_atomic_load(&partials[(size_t)i * COLOR_SUMS + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  block_sum10_256(a, red);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < COLOR_SUMS; ++k) out[k] = a[k];
-    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next call
-  }
+  ticket_sum_256(a, 1.0, out, ticket, partials, red, &is_last);
 }
 
 // the 12 floats of a group as 3 float4 stores
@@ -183,7 +146,6 @@ __global__ __launch_bounds__(COLOR_THREADS) void luma_merge_kernel(const float* 
   }
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 inline bool image_size_ok(int h, int w) { return h > 0 && w > 0 && 3LL * h * w <= 0x7fffffffLL; }
 inline unsigned stats_blocks(long long npix) {
   const long long b = (npix + COLOR_PIX_PER_BLOCK - 1) / COLOR_PIX_PER_BLOCK;

@@ -250,7 +250,6 @@ __global__ __launch_bounds__(CT_THREADS) void color_apply_kernel(const float* im
   }
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 inline bool image_size_ok(int h, int w) { return h > 0 && w > 0 && 3LL * h * w <= 0x7fffffffLL; }
 inline bool bins_ok(int bins) { return bins >= 2 && bins <= CT_MAX_BINS; }
 inline unsigned walk_blocks(long long npix) {

@@ -33,6 +33,8 @@
   } while (0)
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// What the float4 paths ask of every pointer an entry takes (NULL passes: an optional plane may be absent).
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));

@@ -219,7 +219,6 @@ __global__ __launch_bounds__(256) void flow_pack_kernel(const float* __restrict_
   out[2 * (size_t)p + 1] = v[p];
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 const strotss_flow_params_t kFlowDefaults = {0.01f, 5, 32, 12, 8, 8};
 

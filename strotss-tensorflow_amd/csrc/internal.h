@@ -1,6 +1,7 @@
 // Internal (non-ABI) launchers shared between the translation units of libstrotss_hip.so.
 #pragma once
 #include "common.h"
+#include "ticket_sum.h"
 
 // gemm.hip
 int st_cosine_distance(const float* x, const float* rx, int nx, const float* y, const float* ry, int ny,

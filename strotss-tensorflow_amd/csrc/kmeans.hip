@@ -75,7 +75,6 @@ __global__ __launch_bounds__(256) void kmeans_finish_kernel(const int* __restric
   for (int c = t; c < ld; c += 256) centres[(size_t)j * ld + c] = (c < d && norm > 0.0) ? (float)(sum[c] / norm) : 0.f;
 }
 
-inline bool aligned16(const void* p) { return km_aligned16(p); }
 inline bool rows_ok(int n, int d, int ld) { return km_rows_ok(n, d, ld); }
 inline bool k_ok(int k) { return km_k_ok(k); }
 inline int row_blocks(int n) { return min(KM_MAX_ROW_BLOCKS, (n + KM_MIN_BLOCK_ROWS - 1) / KM_MIN_BLOCK_ROWS); }

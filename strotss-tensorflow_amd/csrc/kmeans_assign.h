@@ -147,7 +147,6 @@ __global__ __launch_bounds__(KM_ASSIGN_THREADS) void kmeans_assign_kernel(const 
   }
 }
 
-inline bool km_aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 inline bool km_rows_ok(int n, int d, int ld) { return n > 0 && d > 0 && d <= ld && (long long)n * ld <= 0x7fffffffLL; }
 inline bool km_k_ok(int k) { return k >= 1 && k <= STROTSS_KMEANS_MAX_K; }
 

@@ -6,8 +6,8 @@
 //     loss = (1 / (3 hp wp)) sum m D^2, gimg += (2 gscale / (3 hp wp cnt)) L (m D) at every pixel of the cell.
 //   - tv_fwd_bwd_kernel: one launch.  loss = (1 / (3 h w)) sum (sqrt(dx^2 + dy^2 + eps^2) - eps), forward differences that
 //     are 0 in the last column / row, gimg += gscale * dloss/dimg.
-// Scalars as csrc/temporal.hip: block partials in a fixed tree, summed in a fixed order by the last block (integer ticket,
-// no float atomics).  A gradient value of exactly 0 is not added: the element of gimg keeps its bits, a -0.0 included.
+// Scalars by ticket_sum_256 (csrc/ticket_sum.h): block partials in a fixed tree, summed in a fixed order by the last block,
+// no float atomics; every thread reaches it (no kernel below returns early).  A gradient value of exactly 0 is not added: the element of gimg keeps its bits, a -0.0 included.
 #include "internal.h"
 
 #include <math.h>
@@ -43,29 +43,6 @@ __global__ __launch_bounds__(256) void pool_mean_kernel(const float* __restrict_
   out[e] = acc / (float)((r1 - r0) * (s1 - s0));
 }
 
-// Shared tail of the two terms: the block's partial, the ticket, the last block's fixed-order sum.
-__device__ __forceinline__ void prior_reduce(float acc, float inv_n, float* __restrict__ loss_out, unsigned* __restrict__ ticket,
-                                             float* __restrict__ partials, float* red, int* is_last) {
-  const unsigned nblocks = gridDim.x, bid = blockIdx.x;
-  const float s = block_sum_256(acc, red);
-  if (threadIdx.x == 0) {
-    partials[bid] = s;
-    __threadfence();                                  // the partial is visible before the ticket is taken
-    *is_last = atomicAdd(ticket, 1u) == nblocks - 1;
-  }
-  __syncthreads();
-  if (!*is_last) return;
-  __threadfence();
-  float a = 0.f;
-  for (unsigned i = threadIdx.x; i < nblocks; i += 256)
-    a += __hip_atomic_load(&partials[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  a = block_sum_256(a, red);
-  if (threadIdx.x == 0) {
-    loss_out[0] = a * inv_n;
-    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next launch
-  }
-}
-
 // One workgroup per tile of tc x tc cells.  LDS: d = X - C on the tile and a 2-cell halo (0 outside the grid), e = m * (L d)
 // on the tile and a 1-cell halo (0 outside the grid), g = (coef / cnt) * (L e) on the tile; then the tile's pixels, row by
 // row (coalesced), take their cell's g.  X is the pooled image (the image itself at p = 1), C the pooled content, M the cell
@@ -76,7 +53,7 @@ __global__ __launch_bounds__(256) void detail_fwd_bwd_kernel(const float* __rest
                                                              float* __restrict__ loss_out, unsigned* __restrict__ ticket,
                                                              float* __restrict__ partials) {
   extern __shared__ float lds[];
-  __shared__ float red[4];
+  __shared__ float red[4][1];
   __shared__ int is_last;
   const int t = threadIdx.x;
   const int dw = tc + 4, ew = tc + 2;
@@ -142,7 +119,8 @@ __global__ __launch_bounds__(256) void detail_fwd_bwd_kernel(const float* __rest
       }
     }
   }
-  prior_reduce(acc, inv_n, loss_out, ticket, partials, red, &is_last);
+  float sum[1] = {acc};
+  ticket_sum_256(sum, inv_n, loss_out, ticket, partials, red, &is_last);
 }
 
 // One workgroup per 32 x 32 pixels.  LDS: x on the tile, one row above / column left of it and one below / right (34 x 34),
@@ -158,7 +136,7 @@ __global__ __launch_bounds__(256) void tv_fwd_bwd_kernel(const float* __restrict
   __shared__ float xs[TV_XW * TV_XW * 3];
   __shared__ float as[TV_AW * TV_AW * 3];
   __shared__ float bs[TV_AW * TV_AW * 3];
-  __shared__ float red[4];
+  __shared__ float red[4][1];
   __shared__ int is_last;
   const int t = threadIdx.x;
   const int r0 = (int)(blockIdx.x / nbx) * PRIOR_TILE_PX, s0 = (int)(blockIdx.x % nbx) * PRIOR_TILE_PX;
@@ -201,10 +179,10 @@ __global__ __launch_bounds__(256) void tv_fwd_bwd_kernel(const float* __restrict
       }
     }
   }
-  prior_reduce(acc, inv_n, loss_out, ticket, partials, red, &is_last);
+  float sum[1] = {acc};
+  ticket_sum_256(sum, inv_n, loss_out, ticket, partials, red, &is_last);
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 inline bool pool_ok(int p) { return p == 1 || p == 2 || p == 4 || p == 8 || p == 16; }
 inline long long cells(int n, int p) { return ((long long)n + p - 1) / p; }
 inline long long prior_blocks(int h, int w) { return cells(h, PRIOR_TILE_PX) * cells(w, PRIOR_TILE_PX); }

@@ -159,7 +159,6 @@ __global__ __launch_bounds__(RF_THREADS) void refine_vote_kernel(const float* __
   if (t < k && cnt[t]) atomicAdd(&count[t], cnt[t]);                    // integer: one per label and workgroup
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 inline bool sizes_ok(int h, int w, int gh, int gw) {
   return h > 0 && w > 0 && gh > 0 && gw > 0 && gh <= h && gw <= w && 3LL * h * w <= 0x7fffffffLL;
 }

@@ -243,7 +243,6 @@ __global__ __launch_bounds__(SC_THREADS) void scribble_label_kernel(const float*
   if (t < k && cnt[t]) atomicAdd(&count[t], cnt[t]);                    // integer: one per label and workgroup
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 inline bool sc_k_ok(int k) { return k >= 2 && k <= SC_MAX_K; }
 inline bool sc_sizes_ok(int h, int w, int k) {
   return h > 0 && w > 0 && sc_k_ok(k) && (long long)k * h * w <= 0x7fffffffLL && 3LL * h * w <= 0x7fffffffLL;
@@ -266,7 +265,7 @@ int strotss_kmeans_scores(const float* x, const float* inv_norm, int n, int d, i
   ST_CHECK_ARG(x && inv_norm && centres && scores && km_rows_ok(n, d, ld) && km_k_ok(k), STROTSS_EINVAL);
   ST_CHECK_ARG((long long)n * k <= 0x7fffffffLL, STROTSS_EINVAL);
   ST_CHECK_ARG(ld % 32 == 0, STROTSS_EALIGN);
-  ST_CHECK_ARG(km_aligned16(x) && km_aligned16(inv_norm) && km_aligned16(centres) && km_aligned16(scores), STROTSS_EALIGN);
+  ST_CHECK_ARG(aligned16(x) && aligned16(inv_norm) && aligned16(centres) && aligned16(scores), STROTSS_EALIGN);
   km_launch_scores(x, inv_norm, n, d, ld, centres, k, scores, (hipStream_t)stream);
   ST_LAUNCH_RET();
 }

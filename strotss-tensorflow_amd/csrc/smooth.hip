@@ -397,7 +397,6 @@ __global__ __launch_bounds__(UPS_THREADS) void upsample_apply_kernel(const float
     apply_tile<MODE>(tile, px, records, h, w, guide, H, W, sy, sx, out);
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 inline bool image_size_ok(int h, int w) { return h > 0 && w > 0 && 3LL * h * w <= 0x7fffffffLL; }
 inline bool radius_ok(int r) { return r >= 1 && r <= STROTSS_SMOOTH_MAX_RADIUS; }
 

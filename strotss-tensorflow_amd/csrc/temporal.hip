@@ -1,9 +1,9 @@
 // Temporal consistency of frame sequences: the short-term temporal loss of Ruder et al. (2016).
 //   - flow_warp_kernel: once per frame, the previous stylised frame warped along the backward flow + its {0, 1} certainty;
-//   - temporal_fwd_bwd_kernel: once per step (inside the captured graph), L_t = (1/(3hw)) sum_p c(p) |x(p) - w(p)|^2 and
-//     gimg += gscale * dL_t/dx, between the trunk's pixel gradient and the fold adjoint.
-//   - temporal_long_certainty_kernel, temporal_multi_fwd_bwd_kernel: the long-term terms of several earlier frames
-//     (DESIGN.md section 13), once per frame and once per step.
+//   - temporal_multi_fwd_bwd_kernel<N>: once per step (inside the captured graph), for each of the N = 1..4 targets
+//     L_t = (1/(3hw)) sum_p c(p) |x(p) - w(p)|^2 and gimg += gscale * dL_t/dx, between the trunk's pixel gradient and the
+//     fold adjoint.  N = 1 is the short-term term, N >= 2 the long-term terms of several earlier frames.
+//   - temporal_long_certainty_kernel: the long-term certainties, once per frame.
 #include "internal.h"
 
 namespace {
@@ -63,86 +63,7 @@ __global__ __launch_bounds__(256) void flow_warp_kernel(const float* __restrict_
   certainty[p] = ok ? 1.f : 0.f;
 }
 
-// One workgroup per 1024 pixels = 3072 floats = 768 float4 of x, of the target and of the gradient: thread t takes float4 t,
-// t + 256 and t + 512 of each (coalesced), the block's 1024 certainties staged in LDS first (element e of the block belongs
-// to pixel e / 3).  The last block, if partial, goes element by element.  c(p) == 0 or gscale == 0 leaves gimg bit for bit
-// (the unchanged value is stored back, or nothing at all).  The scalar: per-thread sums in a fixed element order, a fixed
-// tree per block, the partials of the blocks summed in a fixed order by whichever block arrives last (integer ticket, no
-// float atomics).
 #define TEMPORAL_PIX_PER_BLOCK 1024
-__global__ __launch_bounds__(256) void temporal_fwd_bwd_kernel(const float* __restrict__ img, const float* __restrict__ tgt,
-                                                               const float* __restrict__ cert, int npix, float coef,
-                                                               float inv_n, float* __restrict__ gimg,
-                                                               float* __restrict__ loss_out, unsigned* __restrict__ ticket,
-                                                               float* __restrict__ partials) {
-  __shared__ float cs[TEMPORAL_PIX_PER_BLOCK];
-  __shared__ float red[4];
-  __shared__ int is_last;
-  const int t = threadIdx.x;
-  const int base = blockIdx.x * TEMPORAL_PIX_PER_BLOCK;
-  const int count = min(TEMPORAL_PIX_PER_BLOCK, npix - base);
-  const bool full = count == TEMPORAL_PIX_PER_BLOCK;
-  const size_t f0 = 3 * (size_t)base;
-  float acc = 0.f;
-  if (full) {
-    // every global load of the thread in flight at once (a grid of a few waves per SIMD: latency, not bandwidth, bounds it)
-    const f32x4* x4 = reinterpret_cast<const f32x4*>(img + f0);
-    const f32x4* y4 = reinterpret_cast<const f32x4*>(tgt + f0);
-    f32x4* g4 = reinterpret_cast<f32x4*>(gimg + f0);
-    const f32x4 c4 = reinterpret_cast<const f32x4*>(cert + base)[t];
-    f32x4 xv[3], yv[3], gv[3] = {};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      xv[k] = x4[t + 256 * k];
-      yv[k] = y4[t + 256 * k];
-    }
-    if (coef != 0.f) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) gv[k] = g4[t + 256 * k];
-    }
-    reinterpret_cast<f32x4*>(cs)[t] = c4;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const f32x4 d = xv[k] - yv[k];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float ce = cs[(4 * (t + 256 * k) + e) / 3];
-        acc += ce * (d[e] * d[e]);
-        gv[k][e] = ce != 0.f ? gv[k][e] + (coef * ce) * d[e] : gv[k][e];
-      }
-    }
-    if (coef != 0.f) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) g4[t + 256 * k] = gv[k];
-    }
-  } else {
-    for (int p = t; p < count; p += 256) cs[p] = cert[base + p];
-    __syncthreads();
-    for (int i = t; i < 3 * count; i += 256) {
-      const float ce = cs[i / 3], d = img[f0 + i] - tgt[f0 + i];
-      acc += ce * (d * d);
-      if (coef != 0.f && ce != 0.f) gimg[f0 + i] += (coef * ce) * d;
-    }
-  }
-  const float s = block_sum_256(acc, red);
-  if (threadIdx.x == 0) {
-    partials[blockIdx.x] = s;
-    __threadfence();                                  // the partial is visible before the ticket is taken
-    is_last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-  }
-  __syncthreads();
-  if (!is_last) return;
-  __threadfence();
-  float a = 0.f;
-  for (int i = threadIdx.x; i < (int)gridDim.x; i += 256)
-    a += __hip_atomic_load(&partials[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  a = block_sum_256(a, red);
-  if (threadIdx.x == 0) {
-    loss_out[0] = a * inv_n;
-    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next call
-  }
-}
 
 // Long-term certainties, once per frame, one thread per pixel: plane j keeps only what the nearer
 // planes k < j do not already cover, the covered amount summed in ascending k in float32.
@@ -161,11 +82,13 @@ __global__ __launch_bounds__(256) void temporal_long_certainty_kernel(const floa
   }
 }
 
-// The temporal terms of N >= 2 targets in one launch: temporal_fwd_bwd_kernel's layout (1024 pixels per workgroup, thread t
-// takes float4 t, t + 256, t + 512 of x, gimg and every target, the block's N x 1024 certainties staged in LDS) with x and
-// gimg read once.  Per element the N terms are added to the gradient in ascending j, each exactly as the single-term
-// kernel adds its one (c_j == 0 or gscale_j == 0 adds nothing).  One fixed tree per j per block; the last block by the
-// integer ticket sums partials[j * gridDim.x ..] in a fixed order for every j.
+// The temporal terms of N targets in one launch.  One workgroup per 1024 pixels = 3072 floats = 768 float4 of x, of every
+// target and of the gradient: thread t takes float4 t, t + 256 and t + 512 of each (coalesced; every global load of the
+// thread in flight at once: a grid of a few waves per SIMD, latency, not bandwidth, bounds it), the block's N x 1024
+// certainties staged in LDS first (element e of the block belongs to pixel e / 3), x and gimg read once.  The last block,
+// if partial, goes element by element.  Per element the N terms are added to the gradient in ascending j; c_j(p) == 0 or
+// gscale_j == 0 adds nothing, and an element that no term touches keeps its bits (the unchanged value is stored back, or
+// nothing at all).  The N scalars: per-thread sums in a fixed element order, then ticket_sum_256 (csrc/ticket_sum.h).
 template <int N>
 struct TemporalSetArgs {
   const float* tgt[N];
@@ -180,7 +103,7 @@ __global__ __launch_bounds__(256) void temporal_multi_fwd_bwd_kernel(const float
                                                                      unsigned* __restrict__ ticket,
                                                                      float* __restrict__ partials) {
   __shared__ float cs[N][TEMPORAL_PIX_PER_BLOCK];
-  __shared__ float red[4];
+  __shared__ float red[4][N];
   __shared__ int is_last;
   const int t = threadIdx.x;
   const int base = blockIdx.x * TEMPORAL_PIX_PER_BLOCK;
@@ -253,33 +176,38 @@ __global__ __launch_bounds__(256) void temporal_multi_fwd_bwd_kernel(const float
       if (touched) gimg[f0 + i] = g;
     }
   }
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    const float b = block_sum_256(acc[j], red);
-    if (threadIdx.x == 0) partials[(size_t)j * gridDim.x + blockIdx.x] = b;
-  }
-  if (threadIdx.x == 0) {
-    __threadfence();                                  // the partials are visible before the ticket is taken
-    is_last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-  }
-  __syncthreads();
-  if (!is_last) return;
-  __threadfence();
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    const float* pj = partials + (size_t)j * gridDim.x;
-    float a = 0.f;
-    for (int i = threadIdx.x; i < (int)gridDim.x; i += 256)
-      a += __hip_atomic_load(&pj[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    a = block_sum_256(a, red);
-    if (threadIdx.x == 0) loss_out[j] = a * inv_n;
-  }
-  if (threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next call
+  ticket_sum_256(acc, inv_n, loss_out, ticket, partials, red, &is_last);
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 inline long long temporal_blocks(int h, int w) {
   return ((long long)h * w + TEMPORAL_PIX_PER_BLOCK - 1) / TEMPORAL_PIX_PER_BLOCK;
+}
+
+template <int N>
+void launch_temporal_multi(const float* img, const strotss_temporal_set_t* set, int h, int w, float* gimg, float* loss_out,
+                           void* workspace, hipStream_t stream) {
+  const double n = 3.0 * (double)h * (double)w;
+  TemporalSetArgs<N> a;
+  for (int j = 0; j < N; ++j) {
+    a.tgt[j] = set->target[j];
+    a.cert[j] = set->certainty[j];
+    a.coef[j] = (float)(2.0 * (double)set->gscale[j] / n);
+  }
+  unsigned* ticket = (unsigned*)workspace;
+  float* partials = (float*)((char*)workspace + 16);
+  hipLaunchKernelGGL(temporal_multi_fwd_bwd_kernel<N>, dim3((unsigned)temporal_blocks(h, w)), dim3(256), 0, stream, img, a,
+                     h * w, (float)(1.0 / n), gimg, loss_out, ticket, partials);
+}
+
+// Both entries, their arguments checked: set->count in 1 .. STROTSS_MAX_TEMPORAL picks the instantiation.
+int launch_temporal(const float* img, const strotss_temporal_set_t* set, int h, int w, float* gimg, float* loss_out,
+                    void* workspace, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
+  if (set->count == 1) launch_temporal_multi<1>(img, set, h, w, gimg, loss_out, workspace, st);
+  else if (set->count == 2) launch_temporal_multi<2>(img, set, h, w, gimg, loss_out, workspace, st);
+  else if (set->count == 3) launch_temporal_multi<3>(img, set, h, w, gimg, loss_out, workspace, st);
+  else launch_temporal_multi<4>(img, set, h, w, gimg, loss_out, workspace, st);
+  ST_LAUNCH_RET();
 }
 
 }  // namespace
@@ -294,25 +222,20 @@ int strotss_flow_warp(const float* prev, int h, int w, int c, const float* flow_
   ST_LAUNCH_RET();
 }
 
-size_t strotss_temporal_workspace_bytes(int h, int w) {
-  if (h <= 0 || w <= 0) return 0;
-  return 16 + 4 * (size_t)temporal_blocks(h, w);
-}
+size_t strotss_temporal_workspace_bytes(int h, int w) { return strotss_temporal_multi_workspace_bytes(h, w, 1); }
 
 int strotss_temporal_fwd_bwd(const float* img, const float* target, const float* certainty, int h, int w, float gscale,
                              float* gimg, float* loss_out, void* workspace, void* stream) {
   ST_CHECK_ARG(img && target && certainty && gimg && loss_out && workspace && h > 0 && w > 0, STROTSS_EINVAL);
-  const long long npix = (long long)h * w;
-  ST_CHECK_ARG(3 * npix <= 0x7fffffffLL, STROTSS_EINVAL);
+  ST_CHECK_ARG(3LL * h * w <= 0x7fffffffLL, STROTSS_EINVAL);
   ST_CHECK_ARG(aligned16(img) && aligned16(target) && aligned16(certainty) && aligned16(gimg) && aligned16(workspace),
                STROTSS_EALIGN);
-  const double n = 3.0 * (double)npix;
-  const float coef = (float)(2.0 * (double)gscale / n), inv_n = (float)(1.0 / n);
-  unsigned* ticket = (unsigned*)workspace;
-  float* partials = (float*)((char*)workspace + 16);
-  hipLaunchKernelGGL(temporal_fwd_bwd_kernel, dim3((unsigned)temporal_blocks(h, w)), dim3(256), 0, (hipStream_t)stream, img,
-                     target, certainty, (int)npix, coef, inv_n, gimg, loss_out, ticket, partials);
-  ST_LAUNCH_RET();
+  strotss_temporal_set_t set = {};
+  set.count = 1;
+  set.target[0] = target;
+  set.certainty[0] = certainty;
+  set.gscale[0] = gscale;
+  return launch_temporal(img, &set, h, w, gimg, loss_out, workspace, stream);
 }
 
 int strotss_temporal_long_certainty(const float* raw, int count, int h, int w, float* out, void* stream) {
@@ -330,41 +253,14 @@ size_t strotss_temporal_multi_workspace_bytes(int h, int w, int count) {
   return 16 + 4 * (size_t)count * (size_t)temporal_blocks(h, w);
 }
 
-namespace {
-template <int N>
-void launch_temporal_multi(const float* img, const strotss_temporal_set_t* set, int npix, double n, float* gimg,
-                           float* loss_out, unsigned* ticket, float* partials, hipStream_t stream) {
-  TemporalSetArgs<N> a;
-  for (int j = 0; j < N; ++j) {
-    a.tgt[j] = set->target[j];
-    a.cert[j] = set->certainty[j];
-    a.coef[j] = (float)(2.0 * (double)set->gscale[j] / n);     // as strotss_temporal_fwd_bwd rounds its one coefficient
-  }
-  hipLaunchKernelGGL(temporal_multi_fwd_bwd_kernel<N>, dim3((unsigned)((npix + TEMPORAL_PIX_PER_BLOCK - 1) /
-                                                                       TEMPORAL_PIX_PER_BLOCK)),
-                     dim3(256), 0, stream, img, a, npix, (float)(1.0 / n), gimg, loss_out, ticket, partials);
-}
-}  // namespace
-
 int strotss_temporal_multi_fwd_bwd(const float* img, const strotss_temporal_set_t* set, int h, int w, float* gimg,
                                    float* loss_out, void* workspace, void* stream) {
   ST_CHECK_ARG(img && set && gimg && loss_out && workspace && h > 0 && w > 0, STROTSS_EINVAL);
   const int count = set->count;
   ST_CHECK_ARG(count >= 1 && count <= STROTSS_MAX_TEMPORAL, STROTSS_EINVAL);
   for (int j = 0; j < count; ++j) ST_CHECK_ARG(set->target[j] && set->certainty[j], STROTSS_EINVAL);
-  const long long npix = (long long)h * w;
-  ST_CHECK_ARG(3 * npix <= 0x7fffffffLL, STROTSS_EINVAL);
+  ST_CHECK_ARG(3LL * h * w <= 0x7fffffffLL, STROTSS_EINVAL);
   ST_CHECK_ARG(aligned16(img) && aligned16(gimg) && aligned16(workspace), STROTSS_EALIGN);
   for (int j = 0; j < count; ++j) ST_CHECK_ARG(aligned16(set->target[j]) && aligned16(set->certainty[j]), STROTSS_EALIGN);
-  if (count == 1)          // the single-term kernel itself: bit for bit, and its workspace layout is this one's
-    return strotss_temporal_fwd_bwd(img, set->target[0], set->certainty[0], h, w, set->gscale[0], gimg, loss_out,
-                                    workspace, stream);
-  const double n = 3.0 * (double)npix;
-  unsigned* ticket = (unsigned*)workspace;
-  float* partials = (float*)((char*)workspace + 16);
-  const hipStream_t st = (hipStream_t)stream;
-  if (count == 2) launch_temporal_multi<2>(img, set, (int)npix, n, gimg, loss_out, ticket, partials, st);
-  else if (count == 3) launch_temporal_multi<3>(img, set, (int)npix, n, gimg, loss_out, ticket, partials, st);
-  else launch_temporal_multi<4>(img, set, (int)npix, n, gimg, loss_out, ticket, partials, st);
-  ST_LAUNCH_RET();
+  return launch_temporal(img, set, h, w, gimg, loss_out, workspace, stream);
 }

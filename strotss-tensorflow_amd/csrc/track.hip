@@ -52,7 +52,7 @@ inline bool sizes_ok(int h, int w, int gh, int gw) {
 int strotss_label_warp(const int* prev_grid, int gh, int gw, int k, const float* flow, const float* certainty, int h, int w,
                        int* prior, void* stream) {
   ST_CHECK_ARG(prev_grid && flow && prior && sizes_ok(h, w, gh, gw) && km_k_ok(k), STROTSS_EINVAL);
-  ST_CHECK_ARG(km_aligned16(prev_grid) && km_aligned16(flow) && km_aligned16(certainty) && km_aligned16(prior), STROTSS_EALIGN);
+  ST_CHECK_ARG(aligned16(prev_grid) && aligned16(flow) && aligned16(certainty) && aligned16(prior), STROTSS_EALIGN);
   const size_t cells = (size_t)gh * gw;                                 // <= h w < 2^31: the blocks fit a launch
   hipLaunchKernelGGL(label_warp_kernel, dim3((unsigned)((cells + TR_THREADS - 1) / TR_THREADS)), dim3(TR_THREADS), 0,
                      (hipStream_t)stream, prev_grid, gh, gw, k, flow, certainty, h, w, prior);
@@ -65,8 +65,8 @@ int strotss_kmeans_assign_prior(const float* x, const float* inv_norm, int n, in
                STROTSS_EINVAL);
   ST_CHECK_ARG(isfinite(beta) && beta >= 0.f && beta <= 2.f, STROTSS_EINVAL);
   ST_CHECK_ARG(ld % 32 == 0, STROTSS_EALIGN);
-  ST_CHECK_ARG(km_aligned16(x) && km_aligned16(inv_norm) && km_aligned16(centres) && km_aligned16(prior) &&
-                   km_aligned16(label) && km_aligned16(best) && km_aligned16(second),
+  ST_CHECK_ARG(aligned16(x) && aligned16(inv_norm) && aligned16(centres) && aligned16(prior) &&
+                   aligned16(label) && aligned16(best) && aligned16(second),
                STROTSS_EALIGN);
   km_launch_assign<true>(x, inv_norm, n, d, ld, centres, k, prior, beta, label, best, second, (hipStream_t)stream);
   ST_LAUNCH_RET();

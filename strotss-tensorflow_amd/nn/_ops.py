@@ -105,11 +105,15 @@ def flow_warp(prev: torch.Tensor, flow_b: torch.Tensor, flow_f: Optional[torch.T
     return warped, certainty
 
 
+def _zeroed_workspace(nbytes: int, device) -> torch.Tensor:
+    """a zeroed workspace of `nbytes` (at least 16) for one of the ticketed reductions: the call's ticket counter starts at 0
+    and every call leaves it there.  One per caller that may run concurrently (an engine owns its own)."""
+    return torch.zeros(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+
+
 def temporal_workspace(h: int, w: int, device) -> torch.Tensor:
-    """a zeroed workspace of strotss_temporal_fwd_bwd for (h, w): the call's ticket counter starts at 0 and every call
-    leaves it there.  One per caller that may run concurrently (an engine owns its own)."""
-    nb = int(_hip.lib().strotss_temporal_workspace_bytes(int(h), int(w)))
-    return torch.zeros(max(nb, 16), dtype=torch.uint8, device=device)
+    """a zeroed workspace of strotss_temporal_fwd_bwd for (h, w): temporal_multi_workspace for one target"""
+    return temporal_multi_workspace(h, w, 1, device)
 
 
 _temporal_ws = {}
@@ -117,21 +121,15 @@ _temporal_ws = {}
 
 def temporal_fwd_bwd(img: torch.Tensor, target: torch.Tensor, certainty: torch.Tensor, gscale: float, gimg: torch.Tensor,
                      loss_out: torch.Tensor, workspace: Optional[torch.Tensor] = None) -> None:
-    """loss_out[0] = (1/(3hw)) sum_p certainty(p) |img(p) - target(p)|^2, gimg += gscale * dloss/dimg
-    (strotss_temporal_fwd_bwd; img, target, gimg (h, w, 3) or (1, h, w, 3), certainty (h, w)).  workspace: from
-    temporal_workspace, or None for a module-level one per device and size."""
-    for t, name in ((img, "image"), (target, "temporal target"), (certainty, "certainty"), (gimg, "pixel gradient"),
-                    (loss_out, "temporal loss")):
-        require(t, name)
-    h, w, c = hwc(img)
-    assert c == 3 and target.numel() == gimg.numel() == 3 * h * w and certainty.numel() == h * w
+    """loss_out[0] = (1/(3hw)) sum_p certainty(p) |img(p) - target(p)|^2, gimg += gscale * dloss/dimg: temporal_multi_fwd_bwd
+    with one target.  workspace: from temporal_workspace, or None for a module-level one per device and size."""
     if workspace is None:
+        h, w, _ = hwc(img)
         key = (str(img.device), h, w)
         workspace = _temporal_ws.get(key)
         if workspace is None:
             workspace = _temporal_ws[key] = temporal_workspace(h, w, img.device)
-    check(_hip.lib().strotss_temporal_fwd_bwd(ptr(img), ptr(target), ptr(certainty), h, w, float(gscale), ptr(gimg),
-                                              ptr(loss_out), ptr(workspace), stream_ptr()), "temporal_fwd_bwd")
+    temporal_multi_fwd_bwd(img, [target], [certainty], [gscale], gimg, loss_out, workspace)
 
 
 def temporal_long_certainty(stack: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -151,9 +149,8 @@ def temporal_long_certainty(stack: torch.Tensor, out: Optional[torch.Tensor] = N
 
 
 def temporal_multi_workspace(h: int, w: int, count: int, device) -> torch.Tensor:
-    """a zeroed workspace of strotss_temporal_multi_fwd_bwd for (h, w) and `count` targets (as temporal_workspace)"""
-    nb = int(_hip.lib().strotss_temporal_multi_workspace_bytes(int(h), int(w), int(count)))
-    return torch.zeros(max(nb, 16), dtype=torch.uint8, device=device)
+    """a zeroed workspace of strotss_temporal_multi_fwd_bwd for (h, w) and `count` targets"""
+    return _zeroed_workspace(_hip.lib().strotss_temporal_multi_workspace_bytes(int(h), int(w), int(count)), device)
 
 
 def temporal_multi_fwd_bwd(img: torch.Tensor, targets: Sequence[torch.Tensor], certainties: Sequence[torch.Tensor],
@@ -217,9 +214,8 @@ def pool_mean(img: torch.Tensor, p: int, out: Optional[torch.Tensor] = None) -> 
 
 
 def detail_workspace(h: int, w: int, device) -> torch.Tensor:
-    """a zeroed workspace of strotss_detail_fwd_bwd for (h, w) (as temporal_workspace)"""
-    nb = int(_hip.lib().strotss_detail_workspace_bytes(int(h), int(w)))
-    return torch.zeros(max(nb, 16), dtype=torch.uint8, device=device)
+    """a zeroed workspace of strotss_detail_fwd_bwd for (h, w)"""
+    return _zeroed_workspace(_hip.lib().strotss_detail_workspace_bytes(int(h), int(w)), device)
 
 
 def detail_fwd_bwd(img: torch.Tensor, pools: Sequence[int], contents: Sequence[torch.Tensor],
@@ -253,9 +249,8 @@ def detail_fwd_bwd(img: torch.Tensor, pools: Sequence[int], contents: Sequence[t
 
 
 def tv_workspace(h: int, w: int, device) -> torch.Tensor:
-    """a zeroed workspace of strotss_tv_fwd_bwd for (h, w) (as temporal_workspace)"""
-    nb = int(_hip.lib().strotss_tv_workspace_bytes(int(h), int(w)))
-    return torch.zeros(max(nb, 16), dtype=torch.uint8, device=device)
+    """a zeroed workspace of strotss_tv_fwd_bwd for (h, w)"""
+    return _zeroed_workspace(_hip.lib().strotss_tv_workspace_bytes(int(h), int(w)), device)
 
 
 def tv_fwd_bwd(img: torch.Tensor, gscale: float, gimg: torch.Tensor, loss_out: torch.Tensor, workspace: torch.Tensor,

@@ -13,6 +13,7 @@ strotss_utils.py:83-121), so identical index streams give comparable trajectorie
 """
 from __future__ import annotations
 
+import gc
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Union
 
@@ -118,6 +119,13 @@ def check_palette_transport(palette_transport, palette_projections=DEFAULT_PALET
                          f"got {palette_projections!r}")
 
 
+def _check_prior_weight(weight, name: str) -> None:
+    """ValueError unless `weight` is a real number, not a bool, finite and >= 0"""
+    if isinstance(weight, bool) or not isinstance(weight, (int, float, np.integer, np.floating)) or \
+            not np.isfinite(weight) or weight < 0:
+        raise ValueError(f"{name} must be finite and >= 0, got {weight!r}")
+
+
 @dataclass
 class TemporalTarget:
     """The temporal term of a frame sequence at one scale: `target` (h, w, 3) the warped previous
@@ -151,33 +159,42 @@ def extract_features(params: VGGParams, image: torch.Tensor) -> List[torch.Tenso
 
 class _Capture:
     """`torch.cuda.graph(g)` without its gc.collect() + torch.cuda.empty_cache() (12 ms per capture, five captures per run:
-    the step allocates nothing, so there is no allocator state to tidy up before a capture)."""
+    the step allocates nothing, so there is no allocator state to tidy up before a capture).  The cyclic collector is held
+    off while the stream captures: an earlier scale's engine is cyclic garbage (its stage lists hold bound methods), and a
+    collection that lands inside the capture would run the destructors of its graphs and buffers -- runtime calls that a
+    capturing stream does not allow -- at a moment that only the allocation count decides."""
 
     def __init__(self, graph: "torch.cuda.CUDAGraph", stream: "torch.cuda.Stream"):
         self.graph, self.stream = graph, stream
 
     def __enter__(self):
         torch.cuda.synchronize()
+        self._gc = gc.isenabled()
+        gc.disable()
         self._ctx = torch.cuda.stream(self.stream)
         self._ctx.__enter__()
         self.graph.capture_begin()
         return self
 
     def __exit__(self, *exc):
-        if exc[0] is None:
+        try:
+            if exc[0] is None:
+                try:
+                    self.graph.capture_end()
+                finally:
+                    self._ctx.__exit__(None, None, None)
+                return False
+            # the body raised: end the (now invalid) capture so the stream is usable again, but never let that second error
+            # replace the one the caller has to see
             try:
                 self.graph.capture_end()
-            finally:
-                self._ctx.__exit__(None, None, None)
+            except Exception:
+                pass
+            self._ctx.__exit__(*exc)
             return False
-        # the body raised: end the (now invalid) capture so the stream is usable again, but never let that second error
-        # replace the one the caller has to see
-        try:
-            self.graph.capture_end()
-        except Exception:
-            pass
-        self._ctx.__exit__(*exc)
-        return False
+        finally:
+            if self._gc:
+                gc.enable()
 
 
 class StepEngine:
@@ -276,17 +293,14 @@ class StepEngine:
             from .strotss_utils import check_content_weight
             self._cw_map = check_content_weight(content_weight, h, w).to(dev).clone()     # the engine's own copy
         self._temporal = None
-        if temporal is not None and not isinstance(temporal, TemporalTarget):
-            temporal = list(temporal)            # long-term targets, nearest frame first
-            if not 1 <= len(temporal) <= _hip.MAX_TEMPORAL:
-                raise ValueError(f"the temporal term takes 1..{_hip.MAX_TEMPORAL} targets, got {len(temporal)}")
-            if len(temporal) == 1:               # one target IS the TemporalTarget path, bit for bit
-                temporal = temporal[0]
         if temporal is not None:
+            # one target, or a list of them: long-term targets, nearest frame first
+            terms = [temporal] if isinstance(temporal, TemporalTarget) else list(temporal)
+            if not 1 <= len(terms) <= _hip.MAX_TEMPORAL:
+                raise ValueError(f"the temporal term takes 1..{_hip.MAX_TEMPORAL} targets, got {len(terms)}")
             if strips is not None or dist_group is not None:
                 raise ValueError("the temporal term runs on one GPU: image strips and region sharding are not supported "
                                  "with it")
-            terms = [temporal] if isinstance(temporal, TemporalTarget) else temporal
             for tt in terms:
                 if not isinstance(tt, TemporalTarget):
                     raise ValueError(f"temporal targets must be TemporalTarget, got {type(tt).__name__}")
@@ -302,18 +316,11 @@ class StepEngine:
             # workspace
             targets = [tt.target.float().to(dev).reshape(h, w, 3).contiguous().clone() for tt in terms]
             certainties = [tt.certainty.float().to(dev).reshape(h, w).contiguous().clone() for tt in terms]
-            if isinstance(temporal, TemporalTarget):
-                self._temporal = dict(weight=float(temporal.weight), target=targets[0], certainty=certainties[0],
-                                      loss=torch.zeros(1, dtype=torch.float32, device=dev),
-                                      ws=_ops.temporal_workspace(h, w, dev))
-            else:
-                self._temporal = dict(weights=[float(tt.weight) for tt in terms], targets=targets, certainties=certainties,
-                                      loss=torch.zeros(len(terms), dtype=torch.float32, device=dev),
-                                      ws=_ops.temporal_multi_workspace(h, w, len(terms), dev))
+            self._temporal = dict(weights=[float(tt.weight) for tt in terms], targets=targets, certainties=certainties,
+                                  loss=torch.zeros(len(terms), dtype=torch.float32, device=dev),
+                                  ws=_ops.temporal_multi_workspace(h, w, len(terms), dev))
         self._detail = self._tv = None
-        if isinstance(tv_weight, bool) or not isinstance(tv_weight, (int, float, np.integer, np.floating)) or \
-                not np.isfinite(tv_weight) or tv_weight < 0:
-            raise ValueError(f"tv_weight must be finite and >= 0, got {tv_weight!r}")
+        _check_prior_weight(tv_weight, "tv_weight")
         if (detail is not None or tv_weight > 0) and (strips is not None or dist_group is not None):
             raise ValueError("the pixel-space priors (detail, tv_weight) run on one GPU: image strips and region sharding are "
                              "not supported with them")
@@ -322,9 +329,7 @@ class StepEngine:
                 raise ValueError(f"detail must be a DetailTarget, got {type(detail).__name__}")
             pools = _ops.check_detail_pools(detail.pools)
             dwt = detail.weight
-            if isinstance(dwt, bool) or not isinstance(dwt, (int, float, np.integer, np.floating)) or \
-                    not np.isfinite(dwt) or dwt < 0:
-                raise ValueError(f"detail weight must be finite and >= 0, got {dwt!r}")
+            _check_prior_weight(dwt, "detail weight")
             dc = detail.content
             if dc.numel() != 3 * h * w or tuple(dc.shape[-3:]) != (h, w, 3):
                 raise ValueError(f"detail content of shape {tuple(dc.shape)}: expected ({h}, {w}, 3)")
@@ -656,11 +661,8 @@ class StepEngine:
         t = self._temporal
         if t is None:
             return
-        if "targets" in t:                      # several targets: one launch for all of them
-            _ops.temporal_multi_fwd_bwd(self.fold[0], t["targets"], t["certainties"], t["weights"], self.gvars[0],
-                                        t["loss"], t["ws"])
-        else:
-            _ops.temporal_fwd_bwd(self.fold[0], t["target"], t["certainty"], t["weight"], self.gvars[0], t["loss"], t["ws"])
+        _ops.temporal_multi_fwd_bwd(self.fold[0], t["targets"], t["certainties"], t["weights"], self.gvars[0], t["loss"],
+                                    t["ws"])                 # one launch for all the targets
 
     def _pixel_prior(self) -> None:
         """gvars[0] += detail_weight * dL_detail/dx + tv_weight * dL_tv/dx and the terms' scalars, x the folded image of this
@@ -876,15 +878,12 @@ class StepEngine:
         if per_style is not None:
             out["per_style"] = per_style         # one dict per style of the blend: its weight and unweighted terms
         t = self._temporal
-        if t is not None and "targets" in t:     # several targets: loss_t = sum_j L_j, loss + sum_j lambda_j L_j
-            terms = [float(v) for v in t["loss"].tolist()]
+        if t is not None:                        # loss_t = sum_j L_j, loss + sum_j lambda_j L_j: once per step, not averaged
+            terms = [float(v) for v in t["loss"].tolist()]     # over the regions
             out["loss_t"] = float(sum(terms))
-            out["loss_t_terms"] = terms
+            if len(terms) > 1:
+                out["loss_t_terms"] = terms
             out["loss"] = float(loss) + sum(lam * lt for lam, lt in zip(t["weights"], terms))
-        elif t is not None:                      # added once per step, not averaged over the regions
-            lt = float(t["loss"].item())
-            out["loss_t"] = lt
-            out["loss"] = float(loss) + t["weight"] * lt
         if self._detail is not None:             # the pixel-space priors: once per step as well
             terms = [float(v) for v in self._detail["loss"].tolist()]
             out["loss_detail"] = float(sum(terms))

@@ -6,8 +6,10 @@ Detail term: (h, w, pools, cell weights).  x and c are drawn independently in [0
     ragged cells    partial cells on the last row, the last column or both; 17 x 16 at p = 16: a full and a 1-row cell
     workgroups      257 x 300 at p = 1, 2, 8: 9 x 10, 5 x 5 and 2 x 2 tiles; 33 x 33 at p = 1, 2, 4 and 65 x 65 at p = 8, 16:
                     one pixel more than a tile (32 pixels up to p = 8, 64 at p = 16) in both axes
+    ticket wrap     3 x 8193 at p = 1, 4 (and for TV): 257 tiles in one row, so the block that takes the last ticket makes a
+                    second trip over the 256-strided partials; three rows keep the vertical neighbours
     cell weights    absent | random | random with a block of zeros (so that some cell and its neighbours weigh 0) | all zero
-TV: (h, w); 42 x 63 and 257 x 300 span several 32 x 32 tiles both ways."""
+TV: (h, w); 42 x 63 and 257 x 300 span several 32 x 32 tiles both ways, 3 x 8193 is the ticket wrap."""
 import functools
 
 import numpy as np
@@ -35,8 +37,9 @@ DETAIL = [
     (257, 300, (1, 2, 8), "random"),
     (33, 33, (1, 2, 4), "random"),
     (65, 65, (8, 16), "zeros_block"),
+    (3, 8193, (1, 4), "random"),
 ]
-TV = [(1, 1), (1, 5), (5, 1), (2, 2), (42, 63), (257, 300)]
+TV = [(1, 1), (1, 5), (5, 1), (2, 2), (42, 63), (257, 300), (3, 8193)]
 
 
 def detail_label(case):
