@@ -312,6 +312,22 @@ typedef struct strotss_draw_t {
 int strotss_index_draw_max_candidates(int h, int w, int step_x, int step_y);
 int strotss_index_draw(const strotss_draw_t* d, void* stream);
 
+/* The same draw with IMPORTANCE LEVELS (--sample_map): region r may carry level[r], (h, w) uint16
+ * values at this scale.  Everything up to and including the shuffle keys is strotss_index_draw's statement, unchanged.
+ * Position j of the filtered list also draws the acceptance word a_j = philox(ctr = (j >> 2, 3, t, 0), key = seed)[j & 3]
+ * (c1 = 3 is used by nothing else: 0 and 1 belong to the index draw, 2 to the sliced transport), and its candidate at
+ * (x, y) is ACCEPTED iff  level[r][x*w + y] == 65535  ||  (a_j >> 16) < level[r][x*w + y]:  level 65535 always, level 0
+ * never.  Written are the min(sample_size, kept) positions with the smallest (rejected ? 1 : 0, key, j), ascending: the
+ * accepted are a uniform draw among themselves, so a candidate's inclusion is proportional to its level; where fewer than
+ * sample_size are accepted the rejected fill up in key order, so the count never depends on the levels.  Integer
+ * arithmetic only: nn/rand.py:PhiloxStream.permutation_head_weighted is the host twin, element for element.  All levels
+ * 65535, or all 0, give strotss_index_draw's bits; so does a region with level[r] == NULL.  n_out and the counters as
+ * above; one launch, one workgroup a region.  lv == NULL: STROTSS_EINVAL; every other refusal as strotss_index_draw. */
+typedef struct strotss_draw_levels_t {
+  const unsigned short* level[STROTSS_DRAW_MAX_REGIONS];   /* (h, w) levels at THIS scale, or NULL: uniform */
+} strotss_draw_levels_t;
+int strotss_index_draw_weighted(const strotss_draw_t* d, const strotss_draw_levels_t* lv, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Pairwise / moment losses  (nn/losses.py:12-80, run_strotss.py:21-40).
  * Every loss entry computes the loss value AND d(loss)/d(pred) scaled by `gscale`, added

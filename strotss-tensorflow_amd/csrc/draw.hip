@@ -15,6 +15,10 @@
 // histograms), ties at the threshold are taken in position order, the <= 1024 selected (key, candidate) pairs are sorted by
 // a bitonic network.  No global traffic besides the mask bytes and the 8 KB result.  Each wave owns a contiguous segment
 // of the candidate list (lane-consecutive addresses: conflict-free), positions under a mask come from ballots.
+//
+// strotss_index_draw_weighted (--sample_map) is the same body with importance levels: one more Philox word and one 2-byte
+// level read per candidate decide acceptance, a 4 KB bitset holds it, and the selection runs over the accepted or, where
+// they are too few, over the rejected.  The unweighted kernel is the body's other instantiation and names none of it.
 #include "internal.h"
 #include "philox.h"
 #include "sort_match.h"
@@ -43,12 +47,35 @@ __device__ __forceinline__ unsigned wave_totals_scan(unsigned wave_value, unsign
   return pre;
 }
 
-__global__ __launch_bounds__(DRAW_T) void index_draw_kernel(strotss_draw_t d) {
+// The (class, key, candidate) composite of the selection and the final sort.  The unweighted draw has one class and keeps
+// key << 32 | candidate; the weighted one puts the class bit above the key: class << 63 | key << 31 | candidate
+// (candidate < 32768 < 2^31).  The padding ~0 lies above every composite of either form.
+template <bool WEIGHTED>
+__device__ __forceinline__ unsigned long long draw_pack(unsigned cls, unsigned k, int c) {
+  if constexpr (WEIGHTED) return ((unsigned long long)cls << 63) | ((unsigned long long)k << 31) | (unsigned)c;
+  else return ((unsigned long long)k << 32) | (unsigned)c;
+}
+
+// The draw of region blockIdx.x.  WEIGHTED (strotss_index_draw_weighted) and `lev` non-null: position j
+// also draws the acceptance word philox(ctr = (j >> 2, 3, t, 0))[j & 3], its candidate at (x, y) is ACCEPTED iff
+// lev[x][y] == 65535 or (word >> 16) < lev[x][y], and the output is the n_out smallest (rejected, key, j).  Selection in two
+// passes over the SAME code: the accepted are counted (A) with ballots; A >= n_out: the rejected leave `vbits` and the
+// selection below runs as it is; A < n_out: all A accepted are in, the accepted leave `vbits`, and the selection takes the
+// n_out - A best of the rejected, which carry the class bit into the final sort.  `lev` null: the unweighted statement.
+// LEVELS is empty for the unweighted kernel -- its argument list and its instructions are what they were before the
+// weighted form existed -- and one strotss_draw_levels_t for the weighted one.
+template <bool WEIGHTED, class... LEVELS>
+__global__ __launch_bounds__(DRAW_T) void index_draw_kernel(strotss_draw_t d, LEVELS... lv) {
+  const unsigned short* lev = nullptr;
+  if constexpr (WEIGHTED) lev = (lv.level[blockIdx.x], ...);
   __shared__ unsigned keys[DRAW_MAXC];
   __shared__ unsigned vbits[DRAW_MAXC / 32];
   __shared__ unsigned hist[DRAW_BINS];
   __shared__ unsigned long long list[DRAW_T];
   __shared__ unsigned sh[32];
+  // LDS of the weighted form: keys 128 KB + vbits 4 KB + hist 8 KB + list 8 KB + sh 128 B + abits 4 KB = 152.1 KB of the
+  // 160 KB a gfx950 workgroup may hold.  The unweighted form never names abits and keeps its 148.1 KB.
+  __shared__ unsigned abits[WEIGHTED ? DRAW_MAXC / 32 : 1];
   const int r = blockIdx.x, tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
   const unsigned t = d.counter[r];
   const unsigned char* mask = d.mask[r];
@@ -125,6 +152,34 @@ __global__ __launch_bounds__(DRAW_T) void index_draw_kernel(strotss_draw_t d) {
   // debug_flags bit 0 so that the tests run it): two more radix levels (11 + 10 bits) give the threshold key T, ties at T are
   // taken in position order.
   unsigned prefix = 0, pmask = 0, need = (unsigned)n_out;
+  unsigned cls = 0;                         // the class of what the selection takes: 1 = the rejected fill up the accepted
+  if constexpr (WEIGHTED) {
+    if (lev) {                              // (uniform over the workgroup)
+      unsigned running = wave_base, wave_acc = 0;      // unmasked: wave_base = c_begin and j = c
+      for (int i = 0; i < trips; ++i) {
+        const int c = c_begin + i * 64 + lane;
+        const bool v = c < M && ((vbits[c >> 5] >> (c & 31)) & 1u);
+        const unsigned long long b = __ballot(v);
+        bool acc = false;
+        if (v) {
+          const unsigned j = running + (unsigned)__popcll(b & lt_mask);
+          const int x = off_x + (c % nx) * d.step_x, y = off_y + (c / nx) * d.step_y;
+          const unsigned q = lev[(size_t)x * d.w + y];
+          philox4x32_10(j >> 2, 3u, t, 0u, d.seed_lo, d.seed_hi, o4);
+          acc = q == 65535u || (o4[j & 3] >> 16) < q;
+        }
+        const unsigned long long ab = __ballot(acc);
+        if (lane == 0) { abits[c >> 5] = (unsigned)ab; abits[(c >> 5) + 1] = (unsigned)(ab >> 32); }
+        running += (unsigned)__popcll(b);
+        wave_acc += (unsigned)__popcll(ab);
+      }
+      unsigned A;
+      wave_totals_scan(wave_acc, sh, &A);              // (its barriers also publish abits)
+      if (A < (unsigned)n_out) { cls = 1u; need -= A; }
+      for (int i = c_begin / 32 + lane; i < (c_begin + seg) / 32; i += 64) vbits[i] &= cls ? ~abits[i] : abits[i];
+      __syncthreads();
+    }
+  }
   auto radix_level = [&](int shift, unsigned nb) {
     for (int i = tid; i < DRAW_BINS; i += DRAW_T) hist[i] = 0u;
     __syncthreads();
@@ -172,7 +227,7 @@ __global__ __launch_bounds__(DRAW_T) void index_draw_kernel(strotss_draw_t d) {
       const int c = c_begin + i * 64 + lane;
       if (c < M && ((vbits[c >> 5] >> (c & 31)) & 1u)) {
         const unsigned k = keys[c], top = k >> 21;
-        const unsigned long long comp = ((unsigned long long)k << 32) | (unsigned)c;
+        const unsigned long long comp = draw_pack<WEIGHTED>(cls, k, c);
         if (top < bin0) list[atomicAdd(&sh[24], 1u)] = comp;
         else if (top == bin0) cont[atomicAdd(&sh[25], 1u)] = comp;
       }
@@ -207,12 +262,20 @@ __global__ __launch_bounds__(DRAW_T) void index_draw_kernel(strotss_draw_t d) {
       tie_run += (unsigned)__popcll(b);
       if (take) {
         const unsigned slot = atomicAdd(&sh[24], 1u);
-        list[slot] = ((unsigned long long)k << 32) | (unsigned)c;
+        list[slot] = draw_pack<WEIGHTED>(cls, k, c);
+      }
+    }
+  }
+  if constexpr (WEIGHTED) {
+    if (cls) {                              // every accepted candidate is in: class 0, behind the selection's `need` slots
+      for (int i = 0; i < trips; ++i) {
+        const int c = c_begin + i * 64 + lane;
+        if (c < M && ((abits[c >> 5] >> (c & 31)) & 1u)) list[atomicAdd(&sh[24], 1u)] = draw_pack<WEIGHTED>(0u, keys[c], c);
       }
     }
   }
   __syncthreads();
-  // ---- bitonic sort of the 1024 slots, ascending by (key, candidate): one element per thread, kept in registers
+  // ---- bitonic sort of the 1024 slots, ascending by (class, key, candidate): one element per thread, kept in registers
   // (sort_match.h).  Its cross-wave stages alternate between `list` and the histogram's space, free by now: the kernel has no
   // LDS to spare.  It is a single workgroup of 16 waves and was spending most of its time at its ~85 barriers.
   unsigned long long v[1] = {tid < n_out ? list[tid] : ~0ull};
@@ -222,13 +285,23 @@ __global__ __launch_bounds__(DRAW_T) void index_draw_kernel(strotss_draw_t d) {
   if (tid < d.sample_size) {
     float fx = 0.f, fy = 0.f;
     if (tid < n_out) {
-      const int c = (int)(unsigned)(v[0] & 0xFFFFFFFFull);
+      const int c = (int)(unsigned)(v[0] & (WEIGHTED ? 0x7FFFFFFFull : 0xFFFFFFFFull));
       fx = (float)(off_x + (c % nx) * d.step_x);
       fy = (float)(off_y + (c / nx) * d.step_y);
     }
     out[2 * tid] = fx; out[2 * tid + 1] = fy;
   }
   if (tid == 0) { if (d.n_out) d.n_out[r] = n_out; d.counter[r] = t + d.counter_stride; }
+}
+
+// the refusals of both entries, before any launch
+int draw_check(const strotss_draw_t* d) {
+  ST_CHECK_ARG(d && d->counter && d->h > 0 && d->w > 0 && d->step_x > 0 && d->step_y > 0, STROTSS_EINVAL);
+  ST_CHECK_ARG(d->n_regions > 0 && d->n_regions <= STROTSS_DRAW_MAX_REGIONS, STROTSS_EINVAL);
+  ST_CHECK_ARG(d->sample_size > 0 && d->sample_size <= DRAW_T, STROTSS_EINVAL);
+  ST_CHECK_ARG(strotss_index_draw_max_candidates(d->h, d->w, d->step_x, d->step_y) <= DRAW_MAXC, STROTSS_ERANGE);
+  for (int r = 0; r < d->n_regions; ++r) ST_CHECK_ARG(d->idx[r] != nullptr, STROTSS_EINVAL);
+  return 0;
 }
 
 }  // namespace
@@ -241,12 +314,16 @@ int strotss_index_draw_max_candidates(int h, int w, int step_x, int step_y) {
 }
 
 int strotss_index_draw(const strotss_draw_t* d, void* stream) {
-  ST_CHECK_ARG(d && d->counter && d->h > 0 && d->w > 0 && d->step_x > 0 && d->step_y > 0, STROTSS_EINVAL);
-  ST_CHECK_ARG(d->n_regions > 0 && d->n_regions <= STROTSS_DRAW_MAX_REGIONS, STROTSS_EINVAL);
-  ST_CHECK_ARG(d->sample_size > 0 && d->sample_size <= DRAW_T, STROTSS_EINVAL);
-  ST_CHECK_ARG(strotss_index_draw_max_candidates(d->h, d->w, d->step_x, d->step_y) <= DRAW_MAXC, STROTSS_ERANGE);
-  for (int r = 0; r < d->n_regions; ++r) ST_CHECK_ARG(d->idx[r] != nullptr, STROTSS_EINVAL);
-  hipLaunchKernelGGL(index_draw_kernel, dim3((unsigned)d->n_regions), dim3(DRAW_T), 0, (hipStream_t)stream, *d);
+  ST_TRY(draw_check(d));
+  hipLaunchKernelGGL((index_draw_kernel<false>), dim3((unsigned)d->n_regions), dim3(DRAW_T), 0, (hipStream_t)stream, *d);
+  ST_LAUNCH_RET();
+}
+
+int strotss_index_draw_weighted(const strotss_draw_t* d, const strotss_draw_levels_t* lv, void* stream) {
+  ST_CHECK_ARG(lv != nullptr, STROTSS_EINVAL);
+  ST_TRY(draw_check(d));
+  hipLaunchKernelGGL((index_draw_kernel<true, strotss_draw_levels_t>), dim3((unsigned)d->n_regions), dim3(DRAW_T), 0,
+                     (hipStream_t)stream, *d, *lv);
   ST_LAUNCH_RET();
 }
 

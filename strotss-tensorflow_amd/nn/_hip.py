@@ -50,6 +50,11 @@ class DrawT(C.Structure):
                 ("counter", C.c_void_p), ("n_out", C.c_void_p), ("debug_flags", C.c_int)]
 
 
+class DrawLevelsT(C.Structure):
+    """strotss_draw_levels_t (include/strotss_hip.h): per region the (h, w) uint16 importance levels of the weighted draw"""
+    _fields_ = [("level", C.c_void_p * MAX_DRAW_REGIONS)]
+
+
 class PyramidT(C.Structure):
     _fields_ = [("n_levels", C.c_int), ("h", C.c_int * 8), ("w", C.c_int * 8), ("var", C.c_void_p * 8)]
 
@@ -142,6 +147,7 @@ SIGNATURES = {
     "strotss_calib_chase": (_I, [_P, C.c_uint, _I, _I, _P, _P, _P]),
     "strotss_index_draw_max_candidates": (_I, [_I, _I, _I, _I]),
     "strotss_index_draw": (_I, [C.POINTER(DrawT), _P]),
+    "strotss_index_draw_weighted": (_I, [C.POINTER(DrawT), C.POINTER(DrawLevelsT), _P]),
     "strotss_row_inv_norm": (_I, [_P, _I, _I, _P, _P]),
     "strotss_cosine_distance": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _I, _P]),
     "strotss_l2_distance": (_I, [_P, _I, _P, _I, _I, _I, _P, _I, _P, _P]),

@@ -850,6 +850,12 @@ def index_draw(h: int, w: int, sample_size: int, seed: int, counters: torch.Tens
     next draw of its stream (draw number counters[r], advanced by `stride` afterwards) -> out_idx[r] (sample_size, 2) float32.
     masks: per region a (h, w) uint8 device tensor at THIS scale (nonzero = keep) or None; n_out: int32 (R,) or None.
     nn/rand.py:PhiloxStream(seed, t) is the host twin of draw number t."""
+    check(_hip.lib().strotss_index_draw(C.byref(_draw_t(h, w, sample_size, seed, counters, out_idx, masks, n_out, stride,
+                                                        general_path)), stream_ptr()), "index_draw")
+
+
+def _draw_t(h, w, sample_size, seed, counters, out_idx, masks, n_out, stride, general_path) -> "_hip.DrawT":
+    """the strotss_draw_t of index_draw and index_draw_weighted, its tensors checked"""
     from .strotss_utils import sampling_steps
     R = len(out_idx)
     assert 0 < R <= _hip.MAX_DRAW_REGIONS and counters.dtype == torch.int32 and counters.numel() >= R and counters.is_cuda
@@ -872,7 +878,23 @@ def index_draw(h: int, w: int, sample_size: int, seed: int, counters: torch.Tens
     if n_out is not None:
         assert n_out.dtype == torch.int32 and n_out.numel() >= R and n_out.is_cuda
         d.n_out = n_out.data_ptr()
-    check(_hip.lib().strotss_index_draw(C.byref(d), stream_ptr()), "index_draw")
+    return d
+
+
+def index_draw_weighted(h: int, w: int, sample_size: int, seed: int, counters: torch.Tensor, out_idx, levels, masks=None,
+                        n_out=None, stride=None, general_path: bool = False) -> None:
+    """One launch of strotss_index_draw_weighted (csrc/draw.hip): index_draw with importance levels.
+    levels: per region a (h, w) uint16 device tensor at THIS scale (65535 = always accepted, 0 = only where nothing else is
+    left) or None (that region draws as index_draw does).  nn/strotss_utils.py:make_indices_weighted_np on
+    rand.PhiloxStream(seed, t) is the host twin of draw number t."""
+    d = _draw_t(h, w, sample_size, seed, counters, out_idx, masks, n_out, stride, general_path)
+    assert len(levels) == len(out_idx)
+    lv = _hip.DrawLevelsT()
+    for r, q in enumerate(levels):
+        if q is not None:
+            assert q.is_cuda and q.dtype == torch.uint16 and q.is_contiguous() and tuple(q.shape) == (int(h), int(w))
+            lv.level[r] = q.data_ptr()
+    check(_hip.lib().strotss_index_draw_weighted(C.byref(d), C.byref(lv), stream_ptr()), "index_draw_weighted")
 
 
 def index_draw_counts(h: int, w: int, masks=None):

@@ -737,11 +737,14 @@ class StepEngine:
         self.gimg_full[:, self.strips.win1:].zero_()
 
     # ---- the step's sample coordinates drawn on the device (csrc/draw.hip), inside the step and inside its graph
-    def enable_device_draw(self, seed: int, t0: int = 0, masks: Optional[Sequence] = None) -> bool:
+    def enable_device_draw(self, seed: int, t0: int = 0, masks: Optional[Sequence] = None, sample_levels=None) -> bool:
         """Draw every step's index sets on the device (reference: Sampling._make_indices inside the traced train_step,
         strotss_utils.py:83-121 / run_strotss.py:136, 115): region r of step s uses draw number t0 + s*R + r of the Philox
         stream with key `seed` -- what `make_indices_np(..., rng=rand.PhiloxStream(seed, t0))` called region by region, step
         by step, returns on the host.  masks: per region a boolean (h, w) host array at this scale, or None.
+        sample_levels (--sample_map): one (h, w) uint16 host array of importance levels used for every
+        region, or a per-region list (None: that region draws uniformly); the draw is then strotss_index_draw_weighted and
+        `make_indices_weighted_np` its host twin.
         Returns False (and changes nothing) where the device draw does not apply: image strips (the host orders every set
         by owning rank), a grid of more than 32768 candidates, or a region that an unlucky offset leaves with fewer
         candidates than samples (the sample count must be the same at every step: it shapes the launches)."""
@@ -756,7 +759,20 @@ class StepEngine:
         counters = torch.tensor([int(t0) + r for r in range(self.R)], dtype=torch.int64).to(torch.int32).to(dev)
         mask_dev = [None if m is None else torch.from_numpy(np.ascontiguousarray(m, dtype=np.uint8)).to(dev) for m in masks]
         idx = [torch.zeros((self.sample_size, 2), dtype=torch.float32, device=dev) for _ in range(self.R)]
-        self._draw = dict(seed=int(seed), t0=int(t0), counters=counters, masks=mask_dev, idx=idx)
+        levels = None
+        if sample_levels is not None:
+            per_region = list(sample_levels) if isinstance(sample_levels, (list, tuple)) else [sample_levels] * self.R
+            assert len(per_region) == self.R
+            shared = {}                          # one device copy of a map that several regions use
+            for q in per_region:
+                if q is not None and id(q) not in shared:
+                    a = np.ascontiguousarray(q)
+                    if a.dtype != np.uint16 or a.shape != (self.h, self.w):
+                        raise ValueError(f"sample levels of dtype {a.dtype} and shape {a.shape}: expected uint16 "
+                                         f"({self.h}, {self.w})")
+                    shared[id(q)] = torch.from_numpy(a).to(dev)
+            levels = [None if q is None else shared[id(q)] for q in per_region]
+        self._draw = dict(seed=int(seed), t0=int(t0), counters=counters, masks=mask_dev, idx=idx, levels=levels)
         return True
 
     def draws_done(self) -> int:
@@ -765,7 +781,11 @@ class StepEngine:
 
     def _draw_indices(self) -> List[torch.Tensor]:
         dr = self._draw
-        _ops.index_draw(self.h, self.w, self.sample_size, dr["seed"], dr["counters"], dr["idx"], dr["masks"])
+        if dr["levels"] is not None:
+            _ops.index_draw_weighted(self.h, self.w, self.sample_size, dr["seed"], dr["counters"], dr["idx"], dr["levels"],
+                                     dr["masks"])
+        else:
+            _ops.index_draw(self.h, self.w, self.sample_size, dr["seed"], dr["counters"], dr["idx"], dr["masks"])
         return dr["idx"]
 
     def apply_gradients(self) -> None:

@@ -49,6 +49,8 @@ class PhiloxStream:
     exactly one `permutation`, which ends the draw (t += 1).
         integers(0, n), k-th call of the draw   philox(ctr = (0, 1, t, 0))[k] mod n
         permutation(m)                          order of the positions j < m by (philox(ctr = (j >> 2, 0, t, 0))[j & 3], j)
+    The weighted draw (strotss_index_draw_weighted) ends with permutation_head_weighted instead, which also reads
+        accept_words(m)                         philox(ctr = (j >> 2, 3, t, 0))[j & 3]
     """
 
     def __init__(self, seed: int = 0, t: int = 0):
@@ -95,6 +97,26 @@ class PhiloxStream:
         ties = np.flatnonzero(keys == T)[:k - below.size]            # flatnonzero is ascending: ties in position order
         sel = np.concatenate([below, ties])
         order = sel[np.lexsort((sel, keys[sel]))]
+        self.t += 1
+        self._k = 0
+        return order
+
+    def accept_words(self, m: int) -> np.ndarray:
+        """acceptance words of the positions 0..m-1 of this draw (strotss_index_draw_weighted): the c1 = 3 twin of keys(m),
+        philox(ctr = (j >> 2, 3, t, 0))[j & 3]"""
+        q = np.arange((m + 3) // 4, dtype=np.uint64)
+        out = philox4x32_10(q, 3, self.t & 0xFFFFFFFF, 0, *self.key)
+        return np.stack(out, axis=1).reshape(-1)[:m]
+
+    def permutation_head_weighted(self, m, k, levels_of_positions):
+        """The weighted head (strotss_index_draw_weighted): position j with level q_j (uint16) is
+        accepted iff q_j == 65535 or (accept_words[j] >> 16) < q_j; returned are the min(k, m) positions with the smallest
+        (rejected, key, position), in that order.  Integer arithmetic only.  Ends the draw like permutation."""
+        m, k = int(m), int(k)
+        q = np.asarray(levels_of_positions).astype(np.uint64).reshape(-1)
+        assert q.size == m
+        accepted = (q == np.uint64(65535)) | ((self.accept_words(m) >> np.uint64(16)) < q)
+        order = np.lexsort((np.arange(m), self.keys(m), ~accepted))[:min(k, m)]
         self.t += 1
         self._k = 0
         return order

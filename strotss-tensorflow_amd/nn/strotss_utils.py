@@ -94,6 +94,52 @@ def make_indices_np(h: int, w: int, bilinear_sampling: bool, sample_size: int, r
     return ret.astype(np.float32)
 
 
+def make_indices_weighted_np(h: int, w: int, sample_size: int, rng, levels_hw: np.ndarray,
+                             mask_hw: Optional[np.ndarray] = None) -> np.ndarray:
+    """make_indices_np's bilinear branch with the weighted head (--sample_map): the host twin of
+    strotss_index_draw_weighted.  levels_hw: (h, w) uint16 levels at this scale (sample_levels_at_scale); rng: a
+    rand.PhiloxStream, consumed exactly as make_indices_np consumes it (one draw number per call)."""
+    levels_hw = np.asarray(levels_hw)
+    if levels_hw.dtype != np.uint16 or levels_hw.shape != (h, w):
+        raise ValueError(f"sample levels of dtype {levels_hw.dtype} and shape {levels_hw.shape}: expected uint16 ({h}, {w})")
+    step_x, step_y = sampling_steps(h, w)
+    off_x = int(rng.integers(0, step_x))
+    off_y = int(rng.integers(0, step_y))
+    XX, YY = np.meshgrid(np.arange(h)[off_x::step_x], np.arange(w)[off_y::step_y])
+    ret = np.stack([XX.reshape(-1), YY.reshape(-1)], axis=1)
+    if mask_hw is not None:
+        ret = ret[mask_hw[ret[:, 0], ret[:, 1]]]
+    ret = ret[rng.permutation_head_weighted(ret.shape[0], sample_size, levels_hw[ret[:, 0], ret[:, 1]])]
+    return ret.astype(np.float32)
+
+
+def load_sample_map(path: str) -> torch.Tensor:
+    """--sample_map: the image read as greyscale, divided by 255 -> (H, W) float32 host tensor in [0, 1]."""
+    return load_content_weight_map(path)
+
+
+def sample_levels_at_scale(sample_map, h: int, w: int) -> np.ndarray:
+    """The levels of a scale: the user's (H, W) map, finite (ValueError otherwise), resized
+    bilinearly to (h, w) as content_weight_at_scale resizes, clipped to [0, 1], rint(v * 65535) -> (h, w) uint16 host array.
+    The rounding runs on the host, once per scale; an all-zero result is a ValueError (such a map says nothing)."""
+    m = sample_map if torch.is_tensor(sample_map) else torch.as_tensor(np.asarray(sample_map))
+    if m.dim() == 3 and m.shape[-1] == 1:
+        m = m[..., 0]
+    if m.dim() != 2 or m.shape[0] < 1 or m.shape[1] < 1:
+        raise ValueError(f"sample map of shape {tuple(m.shape)}: expected (H, W) or (H, W, 1)")
+    m = m.float()
+    if not bool(torch.isfinite(m).all()):
+        raise ValueError("sample map: values must be finite")
+    if not bool((m > 0).any()):                  # (nothing positive stays so under a bilinear resize: refused before it runs)
+        raise ValueError("sample map: every level is zero")
+    m = _ops.resize_bilinear(m.reshape(1, *m.shape, 1).to(utils.device()).contiguous(), int(h), int(w))[0, ..., 0]
+    v =np.clip(m.detach().cpu().numpy().astype(np.float64), 0.0, 1.0)
+    levels = np.rint(v * 65535.0).astype(np.uint16)
+    if not levels.any():
+        raise ValueError("sample map: every level is zero at this scale")
+    return np.ascontiguousarray(levels)
+
+
 def mask_at_scale(mask: torch.Tensor, h: int, w: int) -> np.ndarray:
     """reference strotss_utils.py:105-110: bilinear resize of the (H,W,1) float mask to the scale,
     `> 0.5` (or all-true if the resized mask is all < 0.1).  Boolean (h,w) host array."""

@@ -19,6 +19,13 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
                     per-pixel content strength: a greyscale image (white = keep the content, black = let it go), divided
                     by 255 and resized to every scale; weights each sample's column of the content term (DESIGN.md
                     section 11).  Combines with masks and --style_mix; not with --strips or a multi-process run.
+  --sample_map PATH
+                    where the step looks: a greyscale image, white samples densely and black is sampled only when nothing
+                    else is left.  Divided by 255, resized to every scale and rounded to 16-bit levels; every step's 1024
+                    sample coordinates are drawn with inclusion proportional to the level, inside the step's graph
+                    (strotss_index_draw_weighted).  The sample count does not change.  Combines with
+                    masks, --auto_masks, the scribble files, --style_mix, --content_weight_map, every transport and --video
+                    (one map for every frame); not with --strips or a multi-process run.  The style's samples stay uniform.
   --video           content_path is a directory of frames (sorted by name, all of one size) and -o an output directory:
                     frame <stem> is written as <stem>.jpg.  With --flow_dir DIR (backward_{t}_{t-1}.flo, optional
                     forward_{t-1}_{t}.flo and reliable_{t}_{t-1}.pgm, t the 1-based position of the frame: the naming of
@@ -271,6 +278,21 @@ def _content_weight_input(args):
         raise ValueError("--content_weight_map cannot be combined with --strips")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise ValueError("--content_weight_map runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    return path
+
+
+def _sample_map_input(args):
+    """--sample_map: its path, or None.  One GPU only: with --strips, under torchrun with WORLD_SIZE > 1 or for a file that
+    does not exist a ValueError (checked before anything is loaded)."""
+    path = getattr(args, "sample_map", None)
+    if not path:
+        return None
+    if getattr(args, "strips", False):
+        raise ValueError("--sample_map cannot be combined with --strips")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("--sample_map runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    if not os.path.isfile(path):
+        raise ValueError(f"--sample_map: no such file: {path}")
     return path
 
 
@@ -815,9 +837,11 @@ def _style_targets(params, style, style_masks, sampling, weights=None):
     return targets
 
 
-def _optimise_scale(eng, scl: int, content_masks, args, dev, quiet: bool = False, step_trace=None):
+def _optimise_scale(eng, scl: int, content_masks, args, dev, quiet: bool = False, step_trace=None, sample_levels=None):
     """`max_iter` RMSprop steps; fresh sample coordinates every step (they are drawn inside the reference's
-    traced train_step as well).  `step_trace`: a list receiving every step's loss dict (one host sync per step)."""
+    traced train_step as well).  `step_trace`: a list receiving every step's loss dict (one host sync per step).
+    sample_levels: the scale's (h, w) uint16 importance levels (--sample_map) or None; the device draw and the host loop
+    below then draw the same weighted sequence."""
     from nn import parallel
     masks_here = [None if m is None else strotss.mask_at_scale(m, eng.h, eng.w) for m in content_masks]
     log_every = max(1, int(getattr(args, "log_every", 10)))
@@ -830,7 +854,8 @@ def _optimise_scale(eng, scl: int, content_masks, args, dev, quiet: bool = False
     # the sample count cannot vary from step to step.  No upload, no ring, nothing for the host to do per step.
     stream = rand.index_rng
     if (dev.type == "cuda" and not getattr(args, "host_draw", False) and isinstance(stream, rand.PhiloxStream)
-            and eng.enable_device_draw(stream.seed, stream.t, masks_here)):
+            and (eng.enable_device_draw(stream.seed, stream.t, masks_here) if sample_levels is None else
+                 eng.enable_device_draw(stream.seed, stream.t, masks_here, sample_levels=sample_levels))):
         with tqdm(range(args.max_iter), disable=quiet) as bar:
             for it in bar:
                 if it == 0 and not getattr(args, "no_graph", False):
@@ -847,7 +872,11 @@ def _optimise_scale(eng, scl: int, content_masks, args, dev, quiet: bool = False
     ring, slots = 8, {}
     with tqdm(range(args.max_iter), disable=quiet) as bar:
         for it in bar:
-            idx_np = [strotss.make_indices_np(eng.h, eng.w, True, SAMPLE_SIZE, rand.index_rng, mk) for mk in masks_here]
+            if sample_levels is None:
+                idx_np = [strotss.make_indices_np(eng.h, eng.w, True, SAMPLE_SIZE, rand.index_rng, mk) for mk in masks_here]
+            else:
+                idx_np = [strotss.make_indices_weighted_np(eng.h, eng.w, SAMPLE_SIZE, rand.index_rng, sample_levels, mk)
+                          for mk in masks_here]
             offsets = None
             if eng.strips is not None:            # same seed on every rank: identical draws, every region's set ordered by owner
                 offsets = []
@@ -898,6 +927,7 @@ def run(args: argparse.Namespace, trace=None):
     _style_transport_input(args)
     _palette_transport_input(args)
     _pixel_prior_input(args)
+    _sample_map_input(args)
     if getattr(args, "video", False):
         return run_video(args, trace)
     timer = utils.Timer()
@@ -980,6 +1010,8 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
     # --preserve_color match / transfer, before any resize: every scale samples the recoloured styles
     styles = _recolour_styles(args, styles, content, content_masks, style_masks)
     cw_map = strotss.load_content_weight_map(cw_path) if cw_path else None
+    sm_path = _sample_map_input(args)
+    sm_map = strotss.load_sample_map(sm_path) if sm_path else None
     sampling = strotss.Sampling(SAMPLE_SIZE)
     masked = bool(getattr(args, "content_mask", None))
     transport = dict(_style_transport_input(args), **_palette_transport_input(args))
@@ -1029,7 +1061,11 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
             rec = dict(i=i, scl=scl, lr=lr, alpha=alpha, loss_denom=eng.loss_denom, init=stylized.clone(), steps=[],
                        hw=(eng.h, eng.w))
             trace.append(rec)
-        _optimise_scale(eng, scl, content_masks, args, dev, quiet=rank != 0, step_trace=None if rec is None else rec["steps"])
+        if sm_map is None:
+            _optimise_scale(eng, scl, content_masks, args, dev, quiet=rank != 0, step_trace=None if rec is None else rec["steps"])
+        else:                                                # --sample_map: the levels of this scale, rounded once
+            _optimise_scale(eng, scl, content_masks, args, dev, quiet=rank != 0, step_trace=None if rec is None else rec["steps"],
+                            sample_levels=strotss.sample_levels_at_scale(sm_map, hs, ws))
         stylized = eng.stylized()
         if rec is not None:
             rec["final"] = stylized.clone()
@@ -1277,6 +1313,9 @@ _FLAGS = (
     (("--strips",), dict(action='store_true', help="under torchrun: shard ONE image over the GPUs by image strips")),
     (("--halo",), dict(action='store_true', help="with --strips: per-layer halo EXCHANGE with the neighbouring ranks (16-row "
                                                  "windows margins, one row per layer and direction) instead of a 128-row recompute margin")),
+    (("--sample_map",), dict(type=str, default=None, metavar='PATH',
+                             help="greyscale image: where the step's sample coordinates are drawn (white densely, black only "
+                                  "when nothing else is left), resized to every scale")),
     (("--detail_weight",), dict(type=float, default=None, metavar='W',
                                 help="weight of the Laplacian detail term: keeps the content's edges at the pool sizes of "
                                      "--detail_pool (off unless given; finite, >= 0)")),
