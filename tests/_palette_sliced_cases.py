@@ -13,6 +13,19 @@ The DUPLICATE case holds two identical prediction rows and two identical style r
 and the row index breaks them; every other gap is held to MIN_GAP, and the seed is one at which the two tied prediction rows
 take different coefficients in some direction (so that the order of the tie shows in the gradient).
 
+LINE cases are tie-free BY CONSTRUCTION, at the widths the product runs (S = 256, which no searched case reaches, 512 and 1024).
+A search cannot reach them: 2048 colours in [0, 1] leave a direction's smallest neighbour gap near 1e-7, and every a-versus-b
+gap counts as well.  Instead the m = n + ns points 0.5 + t_k u lie on ONE line through the cube's centre, t_k = 0.98 ((k + 0.5 +
+U(-0.25, 0.25)) / m - 0.5), u of max-norm 1, so every colour stays in [0.01, 0.99]; the points are dealt at random to the two
+sides and each side is permuted.  A direction's projections are 0.5 <dir, M 1> + t_k <dir, M u> (M the RGB->YUV matrix where the
+flag is set): one grid for both sides, neighbours at least half a step apart, the step being 0.98 |<dir, M u>| / m.  u is the
+best of LINE_TRIES seeded candidates by min_p |<dir_p, M u>| over the case's directions: 0.49 raw and 0.29 YUV at P = 8.  With
+P = 1 u lies along the direction itself.  Measured gaps (float64, gap_of): 1.2e-4 raw and 7.2e-5 YUV at 1024 x 1024, 2.5e-4 and
+1.5e-4 at 512 x 512; all at least 3.4 times MIN_GAP.  A random deal makes rank r of one side lead or trail rank r of the other by
+a random walk, so the signs, and with them the coefficients, come in long runs: exchanging two neighbouring ranks changes the
+gradient at only 14 of the 510 upper slots of 1024 x 1024 (tests/test_palette_sliced_cpu.py counts them).  The LINE_PAIRS case
+deals points 2k and 2k + 1 one to each side by a coin: the sign of a_(r) - b_(r) is that coin, and every second exchange shows.
+
 FULL-SHAPE cases (the step's own sizes) are not tie-free and are compared in norm (tests/_palette_sliced_ref.py)."""
 import functools
 import zlib
@@ -53,7 +66,31 @@ SPECS = [
     ("n65_ns33_p1", 65, 33, 1, 32, 1, "plain"),
     ("n65_ns33_p8", 65, 33, 8, 2208, 0, "plain"),
     ("n65_ns33_p4_dup", 65, 33, 4, 32, 1, "dup"),
+    # constructed, no seed search: S = 256 ...
+    ("line_n130_ns130_p8", 130, 130, 8, 32, 1, "line"),
+    ("line_n256_ns200_p8", 256, 200, 8, 2208, 0, "line"),
+    # ... S = 512 ...
+    ("line_n257_ns512_p8", 257, 512, 8, 32, 0, "line"),
+    ("line_n512_ns512_p8", 512, 512, 8, 2208, 1, "line"),
+    # ... and S = 1024
+    ("line_n513_ns300_p8", 513, 300, 8, 2208, 0, "line"),
+    ("line_n1024_ns1024_p8", 1024, 1024, 8, 32, 1, "line"),
+    ("line_n1024_ns1024_p1", 1024, 1024, 1, 2208, 0, "line"),     # u along the one direction: whole-number coefficients
+    ("line_n1023_ns1024_p8", 1023, 1024, 8, 2208, 1, "line"),
+    ("line_n1024_ns513_p8", 1024, 513, 8, 32, 0, "line"),
+    ("line_n1024_ns1024_p8_pairs", 1024, 1024, 8, 2208, 0, "line_pairs"),
 ]
+CONSTRUCTED = [s[0] for s in SPECS if s[6].startswith("line")]
+LINE_TRIES = 4096
+SWAP_LABEL, INTEGER_LABEL = "line_n1024_ns1024_p8", "line_n1024_ns1024_p1"
+
+
+def width(n, ns):
+    """the sort's width: the power of two >= max(n, ns), clamped to [64, 1024]"""
+    S = 64
+    while S < min(max(n, ns), 1024):
+        S *= 2
+    return S
 ELEMENTWISE = [s[0] for s in SPECS]
 TIE_FREE = [s[0] for s in SPECS if s[6] == "plain"]
 DUP_LABEL = "n65_ns33_p4_dup"
@@ -83,12 +120,45 @@ def tie_shows(case):
     return bool(np.abs(g - gm).max() > 1e-3 * np.abs(g).max())
 
 
+def line_margin(u, n_proj, convert):
+    """min_p |<dir_p, M u>|: what a step of t is worth in the direction that separates the points least"""
+    from nn import rand
+    mu = PR.yuv(np.asarray(u, np.float64)[None, :], convert)[0]
+    return float(np.abs(rand.palette_directions(n_proj).astype(np.float64) @ mu).min())
+
+
+@functools.lru_cache(maxsize=None)
+def line_direction(n_proj, convert, seed):
+    """u of max-norm 1: along the direction at P = 1, else the best of LINE_TRIES seeded candidates by line_margin"""
+    from nn import rand
+    if n_proj == 1:
+        u = rand.palette_directions(1)[0].astype(np.float64)
+        return u / np.abs(u).max()
+    cand = np.random.default_rng(seed).standard_normal((LINE_TRIES, 3))
+    cand /= np.abs(cand).max(1, keepdims=True)
+    dirs = rand.palette_directions(n_proj).astype(np.float64)
+    margins = np.abs(PR.yuv(cand, convert) @ dirs.T).min(1)
+    return cand[int(np.argmax(margins))]
+
+
 @functools.lru_cache(maxsize=None)
 def make_case(label):
     spec = [s for s in SPECS if s[0] == label]
     assert spec, label
     _, n, ns, P, ld, convert, kind = spec[0]
     base = zlib.crc32(label.encode())
+    if kind.startswith("line"):
+        rng = np.random.default_rng(base)
+        m = n + ns
+        t = 0.98 * ((np.arange(m) + 0.5 + rng.uniform(-0.25, 0.25, m)) / m - 0.5)
+        pts = 0.5 + t[:, None] * line_direction(P, convert, base)[None, :]
+        deal = rng.permutation(m)
+        if kind == "line_pairs":
+            coin = rng.integers(0, 2, n)
+            deal = np.concatenate([rng.permutation(2 * np.arange(n) + coin), rng.permutation(2 * np.arange(n) + 1 - coin)])
+        c = Case(label, n, ns, P, ld, convert, kind, pts[deal[n:]], pts[deal[:n]], base, base)
+        assert gap_of(c) >= MIN_GAP, (label, gap_of(c))
+        return c
     for k in range(TRIES):
         rng = np.random.default_rng(base + k)
         x, y = rng.random((ns, 3)), rng.random((n, 3))

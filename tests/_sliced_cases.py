@@ -12,6 +12,20 @@ The DUPLICATE case holds two identical prediction rows and two identical style r
 and the row index breaks them, as the stable sort of the restatement does; every other gap is held to MIN_GAP.  The SIGN case
 holds projections of both signs and an exact zero: prediction row 0 is made orthogonal to direction 0.
 
+ARC cases are tie-free BY CONSTRUCTION, at the widths the product runs (max(n, ns) in 257 .. 1024, where the sort has six or ten
+cross-wave stages).  A search cannot reach them: among 1024 random rows the smallest of the ~1023 neighbour gaps of ONE direction
+is about 1e-6, and a seed whose every direction and side holds 2e-5 turns up with a probability of about 1e-9 per try.  Instead
+row i is s_i (cos th_i, sin th_i, 0.5), th_i = lo + (hi - lo)(i + 0.5 + U(-0.25, 0.25)) / m on lo = pi/4 + 0.3, hi = 3 pi/4 - 0.3,
+s_i uniform in [0.5, 2] (so the reciprocal norms differ), the rows then permuted at random.  On that range sin th > |cos th|, so
+the projection on every direction (+-1, +-1, +-1) is strictly monotone in th -- descending where the first sign is +1, ascending
+where it is -1: the case tables give each case P >= 4 and tests/test_sliced_cpu.py asserts that both occur -- and neighbours
+are at least half a grid step apart: (hi - lo) / (2 m) * sqrt(2) sin(0.3) / sqrt(1.25) = 1.8e-4 at m = 1024.  The wide form
+(d = 35) holds (cos th, sin th) in columns 0 and 1 and ONE fixed non-zero tail of norm 0.5 in columns 2 .. 34 of every row of both
+sides: the tail adds a constant to a direction's projections and leaves the gaps alone.  Measured gaps (float64, gap_of):
+1.99e-4 at 1024 x 1024 (d = 3 and d = 35), 2.28e-4 at 1024 x 513, 4.3e-4 at 257 x 512; all at least nine times MIN_GAP.  The ARC
+DUPLICATE case copies row 5 to row 900 on both sides: the tied pair starts in two different waves, so the row index has to
+break the tie across cross-wave stages.
+
 FULL-SHAPE cases (the step's own sizes, d = 2179) are not tie-free -- a smallest float64 gap of 8e-9 was seen at 1024 x 1024
 with 256 directions -- and are compared in norm (tests/_sliced_ref.py)."""
 import functools
@@ -52,11 +66,36 @@ SPECS = [
     ("n200_ns3_p2", 200, 3, 35, 2, "plain"),
     ("n64_ns64_p4_dup", 64, 64, 35, 4, "dup"),
     ("n64_ns64_p2_sign", 64, 64, 35, 2, "sign"),
+    # constructed, no seed search: S = 512 ...
+    ("arc_n257_ns512_p8", 257, 512, 3, 8, "arc"),              # the first slot past 256
+    ("arc_n512_ns512_p4", 512, 512, 35, 4, "arc"),
+    # ... and S = 1024
+    ("arc_n513_ns300_p4", 513, 300, 35, 4, "arc"),             # the smallest
+    ("arc_n1024_ns1024_p4", 1024, 1024, 3, 4, "arc"),
+    ("arc_n1024_ns1024_p4_wide", 1024, 1024, 35, 4, "arc"),
+    ("arc_n1023_ns1024_p4", 1023, 1024, 3, 4, "arc"),          # coprime: every cell overlaps two
+    ("arc_n1024_ns513_p4", 1024, 513, 35, 4, "arc"),
+    ("arc_n1024_ns1_p4", 1024, 1, 3, 4, "arc"),                # the one-atom limits of the cell walk at full width
+    ("arc_n1_ns1024_p4", 1, 1024, 35, 4, "arc"),
+    ("arc_n1024_ns1024_p4_dup", 1024, 1024, 35, 4, "arc_dup"),
 ]
 TIE_FREE = [s[0] for s in SPECS if s[5] == "plain"]
 ELEMENTWISE = [s[0] for s in SPECS]
+CONSTRUCTED = [s[0] for s in SPECS if s[5].startswith("arc")]
 DUP_LABEL, SIGN_LABEL = "n64_ns64_p4_dup", "n64_ns64_p2_sign"
 DUP_PRED, DUP_STYLE = (5, 9), (3, 7)
+ARC_DUP_LABEL = "arc_n1024_ns1024_p4_dup"
+ARC_DUP = (5, 900)                                             # on both sides: wave 0 and wave 14
+ARC_LO, ARC_HI = np.pi / 4 + 0.3, 3 * np.pi / 4 - 0.3
+SWAP_LABEL = "arc_n1024_ns1024_p4_wide"                        # the planted rank swap of tests/test_sliced_cpu.py
+
+
+def width(n, ns):
+    """the sort's width: the power of two >= max(n, ns), clamped to [64, 1024]"""
+    S = 64
+    while S < min(max(n, ns), 1024):
+        S *= 2
+    return S
 
 # (label, n, ns, d, P): seeded by the label, compared in norm
 FULL = [
@@ -72,6 +111,20 @@ def _rows(rng, m, d):
     return LC.hyper_rows(rng, m, max(d, 3))[:, :d].copy()
 
 
+def _arc_tail(rng, d):
+    """columns 2 .. d - 1 of every arc row before its scale: 0.5 at d = 3, else d - 2 non-zero entries of norm 0.5"""
+    tail = rng.uniform(0.5, 1.0, d - 2) * rng.choice([-1.0, 1.0], d - 2)
+    return 0.5 * tail / np.linalg.norm(tail)
+
+
+def _arc_rows(rng, m, tail):
+    theta = ARC_LO + (ARC_HI - ARC_LO) * (np.arange(m) + 0.5 + rng.uniform(-0.25, 0.25, m)) / m
+    rows = np.empty((m, 2 + len(tail)))
+    rows[:, 0], rows[:, 1], rows[:, 2:] = np.cos(theta), np.sin(theta), tail[None, :]
+    rows *= rng.uniform(0.5, 2.0, m)[:, None]
+    return rows[rng.permutation(m)]
+
+
 def gap_of(case):
     """the smallest gap between sorted neighbours (float64), the exact ties of the duplicate case left out"""
     import torch
@@ -82,7 +135,7 @@ def gap_of(case):
         if v.shape[1] < 2:
             continue
         gaps = (v[:, 1:] - v[:, :-1]).numpy()
-        if case.kind == "dup":
+        if case.kind.endswith("dup"):
             zero = gaps == 0.0
             assert (zero.sum(1) == 1).all(), "the duplicate case holds one exact tie per direction and side"
             gaps = np.where(zero, np.inf, gaps)
@@ -97,6 +150,16 @@ def make_case(label):
     _, n, ns, d, P, kind = spec[0]
     base = zlib.crc32(label.encode())
     from nn import rand
+    if kind.startswith("arc"):
+        rng = np.random.default_rng(base)
+        tail = _arc_tail(rng, d)
+        x, y = _arc_rows(rng, ns, tail), _arc_rows(rng, n, tail)
+        if kind == "arc_dup":
+            x[ARC_DUP[1]] = x[ARC_DUP[0]]
+            y[ARC_DUP[1]] = y[ARC_DUP[0]]
+        c = Case(label, n, ns, d, P, kind, base, x, y, base)
+        assert gap_of(c) >= MIN_GAP, (label, gap_of(c))
+        return c
     for k in range(TRIES):
         rng = np.random.default_rng(base + k)
         x, y = _rows(rng, ns, d), _rows(rng, n, d)

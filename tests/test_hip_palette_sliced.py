@@ -1,5 +1,7 @@
 """The sliced palette term on the GPU: strotss_palette_sliced_fwd_bwd against the float64 restatement of
-tests/_palette_sliced_ref.py -- element by element at the tie-free and duplicate cases of tests/_palette_sliced_cases.py, in
+tests/_palette_sliced_ref.py -- element by element at the tie-free and duplicate cases of tests/_palette_sliced_cases.py
+(searched at sort widths 64 and 128, constructed at 256, 512 and 1024, where the same bits are also asked of three calls and
+the whole-number coefficients of one direction are recovered), in
 norm at the full-shape cases -- its output contract, determinism and refusals; then StepEngine(palette_transport="sliced")
 against the float64 restatement of the step (tests/_palette_step_cases.py), graph capture, the bits of the default engine and
 the command line."""
@@ -108,6 +110,49 @@ def test_entry_matches_float64_in_norm_at_full_shapes(label):
     print(f"MEASURE palette_sliced {label} loss {rel:.3e} grad_fro {err:.3e} of tol {PR.TOL_FRO[label]:.3e}")
     assert rel <= PR.LOSS_TOL, (loss, ref_l)
     assert err <= PR.TOL_FRO[label], err
+
+
+@pytest.mark.parametrize("label", PC.CONSTRUCTED)
+def test_wide_sorts_give_the_same_bits_three_times(label):
+    """widths 256, 512 and 1024 (three, six and ten cross-wave stages on two alternating LDS buffers): twice from fresh
+    NaN-byte workspaces and once more on the workspace the second call left.  A buffer reused a stage early or a missing barrier
+    shows as a changed bit before it shows as a wrong rank"""
+    c = PC.make_case(label)
+    assert PC.width(c.n, c.ns) in (256, 512, 1024)
+    outs, call = [], None
+    for fresh in (True, True, False):
+        if fresh:
+            call = Call(c)
+        g, lo = call.zeros()
+        assert call(g, lo) == 0
+        torch.cuda.synchronize()
+        outs.append((g, lo))
+    g0, l0 = outs[0]
+    assert bool(torch.isfinite(g0).all()) and bool(g0[:c.n, :3].any()) and float(l0[0]) > 0
+    for g, lo in outs[1:]:
+        assert torch.equal(g, g0) and torch.equal(lo, l0)
+
+
+def test_coefficients_at_full_width_are_the_restatements_whole_numbers():
+    """1024 x 1024, P = 1, no YUV, the points on a line along the direction: a row's gradient is (2 / sqrt(3)) K / (n ns) times
+    the direction with K a whole number (a sum of +-len).  K recovered from either non-zero component equals the
+    restatement's to 0.5; float32 division costs about n ns 2^-24 = 0.06"""
+    c = PC.make_case(PC.INTEGER_LABEL)
+    assert (c.n, c.ns, c.n_proj, c.rgb_to_yuv) == (1024, 1024, 1, 0)
+    _, ref_g = ref64(c.label)
+    g, _ = _run(c, 1.0)
+    theta = c.dirs[0].astype(np.float64)
+    live = [k for k in range(3) if abs(theta[k]) > 0.1]
+    assert len(live) >= 2
+    for k in live:
+        unit = c.n * c.ns / (2.0 / np.sqrt(3.0) * theta[k])
+        want = ref_g[:, k] * unit
+        assert np.abs(want - np.rint(want)).max() <= 1e-6 and set(np.abs(np.rint(want))) == {float(c.n)}
+        worst = np.abs(g[:, k] * unit - np.rint(want)).max()
+        print(f"MEASURE palette_sliced whole numbers {c.label} component {k}: worst {worst:.3e} of 0.5")
+        assert worst <= 0.5
+    for k in set(range(3)) - set(live):
+        assert not g[:, k].any()
 
 
 def test_packed_rgb_rows_are_taken_as_the_relaxed_emd_entry_takes_them():

@@ -1,5 +1,6 @@
 """The sliced Wasserstein style term on the GPU: strotss_sliced_cos_fwd_bwd against float64 autograd of
-tests/_sliced_ref.py -- element by element at the tie-free, duplicate and sign cases of tests/_sliced_cases.py, in norm at the
+tests/_sliced_ref.py -- element by element at the tie-free, duplicate and sign cases of tests/_sliced_cases.py (searched at sort
+widths 64 .. 256, constructed at 512 and 1024, where the same bits are also asked of three calls), in norm at the
 full-shape cases, with x3 panels and with both panels NULL -- its output contract, counter, determinism and refusals; then
 StepEngine(style_transport="sliced") against the float64 restatement of the step, the other transports' bits, graph capture
 and the command line."""
@@ -120,6 +121,28 @@ def test_entry_matches_float64_in_norm_at_full_shapes(ops, label, panels):
 def _zero_out(c):
     return (torch.zeros((LC_pad(c.n), LC_pad(c.d)), dtype=torch.float32, device=DEV),
             torch.zeros(4, dtype=torch.float32, device=DEV))
+
+
+@pytest.mark.parametrize("panels", (True, False), ids=("x3", "f32"))
+@pytest.mark.parametrize("label", SC.CONSTRUCTED)
+def test_wide_sorts_give_the_same_bits_three_times(ops, label, panels):
+    """widths 512 and 1024 (six and ten cross-wave stages on two alternating LDS buffers): twice from fresh NaN-byte
+    workspaces and once more on the workspace the second call left.  A buffer reused a stage early or a missing barrier shows as
+    a changed bit before it shows as a wrong rank"""
+    c = SC.make_case(label)
+    assert SC.width(c.n, c.ns) in (512, 1024)
+    outs, call = [], None
+    for fresh in (True, True, False):
+        if fresh:
+            call = Call(ops, c, panels)
+        g, lo = _zero_out(c)
+        assert call(g, lo, t=c.t) == 0
+        torch.cuda.synchronize()
+        outs.append((g, lo))
+    g0, l0 = outs[0]
+    assert bool(torch.isfinite(g0).all()) and bool(g0[:c.n, :c.d].any()) and float(l0[0]) > 0
+    for g, lo in outs[1:]:
+        assert torch.equal(g, g0) and torch.equal(lo, l0)
 
 
 def test_contract_accumulation_padding_counter_and_bits(ops):

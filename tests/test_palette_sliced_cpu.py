@@ -141,6 +141,44 @@ def test_every_tie_free_case_holds_its_gap():
     assert PC.tie_shows(c)
 
 
+def test_elementwise_cases_cover_every_sort_width():
+    """S = the power of two >= max(n, ns), clamped to [64, 1024]: 0, 1, 3, 6 and 10 cross-wave stages"""
+    def width(n, ns):
+        return min(1024, max(64, 1 << (max(n, ns) - 1).bit_length()))
+    by_width = {}
+    for label, n, ns, P, ld, convert, kind in PC.SPECS:
+        assert width(n, ns) == PC.width(n, ns)
+        by_width.setdefault(width(n, ns), []).append((label, ld, convert))
+    assert sorted(by_width) == [64, 128, 256, 512, 1024]
+    assert {lb for S in (256, 512, 1024) for lb, _, _ in by_width[S]} == set(PC.CONSTRUCTED)
+    for S in (512, 1024):
+        assert {ld for _, ld, _ in by_width[S]} == {32, 2208} and {cv for _, _, cv in by_width[S]} == {0, 1}
+    assert {(s[1], s[2], s[3]) for s in PC.SPECS if s[0] in PC.CONSTRUCTED} >= {
+        (130, 130, 8), (256, 200, 8), (257, 512, 8), (512, 512, 8), (513, 300, 8), (1024, 1024, 8), (1024, 1024, 1),
+        (1023, 1024, 8), (1024, 513, 8)}
+
+
+@pytest.mark.parametrize("label", PC.CONSTRUCTED)
+def test_constructed_cases_lie_on_their_line(label):
+    c = PC.make_case(label)
+    u = PC.line_direction(c.n_proj, c.rgb_to_yuv, c.seed)
+    assert np.abs(u).max() == 1.0
+    margin = PC.line_margin(u, c.n_proj, c.rgb_to_yuv)
+    print(f"MEASURE line {label} margin {margin:.3f} gap {PC.gap_of(c):.3e}")
+    assert margin >= (0.27 if c.rgb_to_yuv else 0.45)
+    pts = np.concatenate([c.x, c.y])
+    assert pts.min() >= 0.01 and pts.max() <= 0.99
+    t = (pts - 0.5) @ u / (u @ u)
+    assert np.abs(pts - 0.5 - t[:, None] * u[None, :]).max() <= 1e-15
+    assert np.diff(np.sort(t)).min() >= 0.98 * 0.5 / len(t) * (1 - 1e-9), "neighbours are at least half a grid step apart"
+    # the sides interleave: neither is a block of the line
+    side = np.r_[np.zeros(c.ns), np.ones(c.n)][np.argsort(t)]
+    assert np.count_nonzero(np.diff(side)) > min(c.n, c.ns) // 2
+    if c.label == PC.INTEGER_LABEL:
+        d0 = c.dirs[0].astype(np.float64)
+        assert c.n_proj == 1 and not c.rgb_to_yuv and np.abs(np.cross(u, d0)).max() <= 1e-15
+
+
 def test_float32_yardstick_is_what_is_pinned():
     worst = {}
     for label in PC.ELEMENTWISE:
@@ -194,11 +232,49 @@ def test_planted_errors_fail_the_comparison(name):
     if name == "descending_ties":             # only exact ties tell
         assert caught == [PC.DUP_LABEL]
     elif name == "weights_1_over_max":        # equal sizes have len_ij = 1 / n on the diagonal: only unequal ones tell
-        assert set(caught) == set(unequal) and len(unequal) == 7
+        assert set(caught) == set(unequal) and len(unequal) == 7 + 5
+        assert {"line_n256_ns200_p8", "line_n257_ns512_p8", "line_n513_ns300_p8", "line_n1023_ns1024_p8",
+                "line_n1024_ns513_p8"} <= set(unequal)
     elif name == "m_for_m_transposed":        # only where the matrix is applied
         assert set(caught) == {s[0] for s in PC.SPECS if s[5]}
     else:
         assert set(caught) == set(PC.ELEMENTWISE)
+
+
+def _swap_slots(c, p, g64, tol):
+    """the slots r >= S / 2 of direction p at which exchanging the sorted prediction ranks r and r + 1 moves some gradient
+    element by more than tol of max|ref|, with the largest such move and the largest relative Frobenius size"""
+    slots, worst, fro = [], 0.0, 0.0
+    for r in range(PC.width(c.n, c.ns) // 2, c.n - 1):
+        _, gm = PR.palette_sliced(c.x, c.y, c.dirs, c.rgb_to_yuv, swap_rank=(p, r))
+        moved = PR.err_over_max(gm, g64)
+        if moved > tol:
+            slots.append(r)
+            worst, fro = max(worst, moved), max(fro, PR.rel_fro(gm, g64))
+    return slots, worst, fro
+
+
+def test_one_swapped_rank_at_full_width_is_caught_element_by_element():
+    """Two adjacent sorted prediction ranks of ONE direction exchanged at a slot >= S / 2, planted in the float64 restatement.
+    The coefficients are sums of +-len, so an exchange shows only where the two ranks' coefficients differ: at 14 of the 511
+    upper slots of the randomly dealt 1024 x 1024 case (the first is slot 959) and at 375 of the pair-dealt one.  Where it
+    shows it moves a gradient element by up to 0.37 (0.67 pair-dealt) of max|ref| at P = 8, against a TOL_GRAD of 9.6e-7.  In
+    relative Frobenius norm the exchange is worth up to 1.6e-2, which does NOT fall under the full shapes' TOL_FRO (8.0e-7 at
+    1024 x 1024, P = 64): the palette term's float32 yardstick is itself only 1e-7, so the norm comparison saw such an
+    exchange already -- wherever float32 did not decide the sign itself.  What the constructed cases add for this term is
+    the width S = 256, the element-wise bound at 512 and 1024, and inputs at which float32 decides no rank and no sign."""
+    counts = {}
+    for label in (PC.SWAP_LABEL, "line_n1024_ns1024_p8_pairs"):
+        c = PC.make_case(label)
+        assert (c.n, c.ns, PC.width(c.n, c.ns)) == (1024, 1024, 1024)
+        _, g64 = PR.palette_sliced(c.x, c.y, c.dirs, c.rgb_to_yuv)
+        tol = PR.TOL_GRAD[PR.family(c)]
+        slots, worst, fro = _swap_slots(c, 0, g64, tol)
+        print(f"MEASURE swap {label}: {len(slots)} of {c.n - 1 - 512} slots show, first {slots[:3]}, max {worst:.3e} of tol "
+              f"{tol:.3e}, fro {fro:.3e} of TOL_FRO {PR.TOL_FRO['full_n1024_ns1024_p64']:.3e}")
+        counts[label] = len(slots)
+        assert slots and slots[0] >= 512 and worst > tol
+    assert counts["line_n1024_ns1024_p8_pairs"] > 510 // 3
 
 
 # ------------------------------------------------------------------ the step's bounds

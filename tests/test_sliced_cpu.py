@@ -121,6 +121,45 @@ def test_every_tie_free_case_holds_its_gap():
     assert float(a[0, 0]) == 0.0 and bool((a[0] < 0).any()) and bool((a[0] > 0).any())
     c = SC.make_case(SC.DUP_LABEL)
     assert np.array_equal(c.y[SC.DUP_PRED[0]], c.y[SC.DUP_PRED[1]]) and np.array_equal(c.x[SC.DUP_STYLE[0]], c.x[SC.DUP_STYLE[1]])
+    c = SC.make_case(SC.ARC_DUP_LABEL)
+    i, j = SC.ARC_DUP
+    assert np.array_equal(c.y[i], c.y[j]) and np.array_equal(c.x[i], c.x[j]) and i // 64 != j // 64
+
+
+def test_elementwise_cases_cover_every_sort_width():
+    """S = the power of two >= max(n, ns), clamped to [64, 1024]: 0, 1, 3, 6 and 10 cross-wave stages"""
+    def width(n, ns):
+        return min(1024, max(64, 1 << (max(n, ns) - 1).bit_length()))
+    assert [width(*m) for m in ((1, 1), (64, 3), (65, 1), (128, 128), (129, 2), (256, 256), (257, 1), (512, 512), (513, 1),
+                                (1024, 1024))] == [64, 64, 128, 128, 256, 256, 512, 512, 1024, 1024]
+    by_width = {}
+    for label, n, ns, d, P, kind in SC.SPECS:
+        assert width(n, ns) == SC.width(n, ns)
+        by_width.setdefault(width(n, ns), []).append(label)
+    assert sorted(by_width) == [64, 128, 256, 512, 1024]
+    assert set(by_width[512] + by_width[1024]) == set(SC.CONSTRUCTED) and len(SC.CONSTRUCTED) == 10
+    assert {(s[1], s[2], s[3]) for s in SC.SPECS if s[0] in SC.CONSTRUCTED} >= {
+        (257, 512, 3), (512, 512, 35), (513, 300, 35), (1024, 1024, 3), (1024, 1024, 35), (1023, 1024, 3), (1024, 513, 35),
+        (1024, 1, 3), (1, 1024, 35)}
+
+
+@pytest.mark.parametrize("label", SC.CONSTRUCTED)
+def test_constructed_cases_sort_in_both_directions(label):
+    """the projection of an arc row falls with its angle where the direction's first sign is +1 and rises where it is -1:
+    every case holds both, and two such directions sort the rows in exactly opposite orders"""
+    c = SC.make_case(label)
+    s = c.signs
+    assert c.n_proj >= 4 and set(s[:, 0]) == {-1.0, 1.0}
+    if c.kind == "arc_dup":
+        return
+    rows = c.y if c.n > 1 else c.x
+    a = SR.projections(torch.as_tensor(rows), torch.as_tensor(s, dtype=torch.float64)).numpy()
+    up, down = int(np.flatnonzero(s[:, 0] < 0)[0]), int(np.flatnonzero(s[:, 0] > 0)[0])
+    assert np.array_equal(np.argsort(a[up]), np.argsort(a[down])[::-1])
+    theta = np.arctan2(rows[:, 1], rows[:, 0])
+    assert SC.ARC_LO < theta.min() and theta.max() < SC.ARC_HI and np.array_equal(np.argsort(a[up]), np.argsort(theta))
+    norms = np.linalg.norm(rows, axis=1)
+    assert norms.max() / norms.min() > 1.5 or len(rows) < 8, "the reciprocal norms differ"
 
 
 def test_float32_yardstick_is_what_is_pinned():
@@ -165,11 +204,39 @@ def test_planted_errors_fail_the_comparison(name):
             caught.append(label)
     print(f"MEASURE mutant {name} caught on {caught}")
     if name == "descending_ties":             # only exact ties tell
-        assert caught == [SC.DUP_LABEL]
+        assert caught == [SC.DUP_LABEL, SC.ARC_DUP_LABEL]
     elif name == "weights_1_over_max":        # equal sizes have len_ij = 1 / n on the diagonal: only unequal ones tell
         assert "n65_ns40_p4" in caught and "n3_ns200_p2" in caught and "n64_ns64_p8" not in caught
+        assert {"arc_n257_ns512_p8", "arc_n513_ns300_p4", "arc_n1023_ns1024_p4", "arc_n1024_ns513_p4"} <= set(caught)
+        assert "arc_n1024_ns1024_p4" not in caught
     else:
         assert set(caught) == set(SC.ELEMENTWISE)
+
+
+def test_one_swapped_rank_at_full_width_is_caught_element_by_element():
+    """Two adjacent sorted prediction ranks of ONE direction exchanged at a slot >= S / 2 -- what a cross-wave exchange that
+    reads a slot one stage late leaves behind -- planted in the float64 restatement.  At the constructed 1024 x 1024 case the
+    swap moves a gradient element by 6.4e-2 .. 3.3e-1 of max|ref|, against the family's TOL_GRAD of 4.9e-3: the element-wise
+    comparison catches it.  The same swap at the full-shape case 1024 x 1024, P = 256 is worth 5.4e-5 of relative Frobenius
+    norm, a hundredth of that case's TOL_FRO of 5.4e-3: the norm comparison, the only one the suite held at this width
+    before, lets it pass."""
+    c = SC.make_case(SC.SWAP_LABEL)
+    assert (c.n, c.ns, SC.width(c.n, c.ns)) == (1024, 1024, 1024)
+    _, g64 = SR.sliced(c.x, c.y, c.signs)
+    tol = SR.TOL_GRAD[SR.family(c)]
+    for r in (512, 777, 1022):
+        _, gm = SR.sliced(c.x, c.y, c.signs, swap_rank=(1, r))
+        moved = SR.err_over_max(gm, g64)
+        print(f"MEASURE swap {c.label} slot {r}: max {moved:.3e} of tol {tol:.3e}, fro {SR.rel_fro(gm, g64):.3e}")
+        assert moved > tol
+        assert np.count_nonzero(np.abs(gm - g64).max(1)) == 2, "two rows move, no other"
+    label = "full_n1024_ns1024_p256"
+    f = SC.make_full(label)
+    _, g64 = SR.sliced(f.x, f.y, f.signs)
+    _, gm = SR.sliced(f.x, f.y, f.signs, swap_rank=(1, 777))
+    fro = SR.rel_fro(gm, g64)
+    print(f"MEASURE swap {label} slot 777: fro {fro:.3e} of TOL_FRO {SR.TOL_FRO[label]:.3e}, max {SR.err_over_max(gm, g64):.3e}")
+    assert 0.0 < fro < SR.TOL_FRO[label], "the gap the constructed cases close"
 
 
 # ------------------------------------------------------------------ the step's bounds
