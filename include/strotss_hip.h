@@ -952,6 +952,28 @@ int strotss_scribble_labels(const float* img, const int* stroke, int h, int w, c
                             float* x, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Detail map (--sample_map auto): where an image has local structure
+ * --------------------------------------------------------------------------------------- */
+/* bytes of the workspace of strotss_detail_map: 32 + 8 per workgroup of its row pass + 8 per pixel (one float64 plane of
+ * column sums); 0 for h, w <= 0 or 3 h w > INT_MAX */
+size_t strotss_detail_map_workspace_bytes(int h, int w);
+/* out (h, w) = the detail map of img (h, w, 3), float32 RGB in [0, 1]:
+ *   Y = 0.299 R + 0.587 G + 0.114 B                                        (the grey of strotss_flow)
+ *   e = gx^2 + gy^2,  gx = (Y(y, x+1) - Y(y, x-1)) / 2, gy likewise, indices clamped to the image (a 1-pixel axis gives 0)
+ *   s(p) = sqrt(mean of e over the window [y-r, y+r] x [x-r, x+r] clipped to the image), the divisor the count of pixels
+ *          inside the clipped window; the window sums in float64, a column pass and a row pass of direct sums
+ *   m = mean of s over the image, in float64, a fixed-order reduction (no float atomics)
+ *   out(p) = floor + (1 - floor) * min(1, s(p) / (gain * m));  m == 0 (a constant image): out = 1 everywhere, and where
+ *            the minimum is 1 out is 1 itself.
+ * Y, e, the mean's division, the root and the last line are float32 operations, each rounded on its own (no contraction).
+ * Three launches on `stream`; the same bits on every run.  The workspace is 16-byte aligned and zero before its first use
+ * (one call at a time; a call leaves it ready for the next).  Refused before anything is launched: STROTSS_EINVAL for a
+ * null pointer, h or w <= 0, 3 h w > INT_MAX; STROTSS_ERANGE for a radius outside 1..64, a gain that is not finite or
+ * <= 0, a floor that is not finite or outside [0, 1]; STROTSS_EALIGN for a pointer that is not 16-byte aligned. */
+int strotss_detail_map(const float* img, int h, int w, int radius, float gain, float floor, float* out, void* workspace,
+                       void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Optimiser + output
  * --------------------------------------------------------------------------------------- */
 typedef struct {

@@ -224,6 +224,8 @@ SIGNATURES = {
     "strotss_scribble_workspace_bytes": (_Z, [_I, _I, _I]),
     "strotss_scribble_labels": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, C.c_double, C.c_double, C.c_double, _I, _I, _P, _P, _P, _P,
                                      _Z, _P]),
+    "strotss_detail_map_workspace_bytes": (_Z, [_I, _I]),
+    "strotss_detail_map": (_I, [_P, _I, _I, _I, _F, _F, _P, _P, _P]),
     "strotss_rmsprop_step": (_I, [C.POINTER(TensorsT), _F, _F, _F, _P]),
     "strotss_postprocess": (_I, [_P, _L, _P, _P, _P]),
 }

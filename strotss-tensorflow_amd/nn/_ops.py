@@ -537,6 +537,33 @@ def guided_upsample(img: torch.Tensor, guide_lo: torch.Tensor, guide_hi: torch.T
     return out
 
 
+# ------------------------------------------------------------------ detail map
+_detail_ws = {}
+
+
+def detail_map(img: torch.Tensor, radius: Optional[int] = None, gain: float = 2.0, floor: float = 0.25) -> torch.Tensor:
+    """the (h, w) float32 detail map of an (h, w, 3) image in [floor, 1]: the root of the windowed mean gradient energy of
+    its luma over gain times that root's image mean, clamped at 1 (strotss_detail_map; three launches on the current stream,
+    the same bits on every run).  radius None: max(1, longer side // 64), at most 64.  The workspace (8 bytes per pixel) is
+    a module-level one per device and size, zeroed when made; the library refuses a radius outside 1..64, a gain that is
+    not finite or <= 0 and a floor outside [0, 1]."""
+    h, w = _rgb_image(img, "image")
+    if radius is None:
+        radius = max(1, min(64, max(h, w) // 64))
+    lib = _hip.lib()
+    key = (str(img.device), h, w)
+    workspace = _detail_ws.get(key)
+    if workspace is None:
+        nb = int(lib.strotss_detail_map_workspace_bytes(h, w))
+        if nb == 0:
+            raise _hip.StrotssHipError(f"detail_map: bad size {h} x {w}")
+        workspace = _detail_ws[key] = torch.zeros(nb, dtype=torch.uint8, device=img.device)
+    out = torch.empty((h, w), dtype=torch.float32, device=img.device)
+    check(lib.strotss_detail_map(ptr(img), h, w, int(radius), float(gain), float(floor), ptr(out), ptr(workspace),
+                                 stream_ptr()), "detail_map")
+    return out
+
+
 def resize_bilinear_adjoint(gout: torch.Tensor, ih: int, iw: int,
                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
     require(gout, "resize adjoint input")

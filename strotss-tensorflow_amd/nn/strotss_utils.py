@@ -118,6 +118,49 @@ def load_sample_map(path: str) -> torch.Tensor:
     return load_content_weight_map(path)
 
 
+SAMPLE_MAX_RADIUS = 64                   # strotss_detail_map's window radius, 1..64
+DEFAULT_SAMPLE_GAIN = 2.0                # detail at `gain` times the image's mean detail saturates the map; not tuned
+DEFAULT_SAMPLE_FLOOR = 0.25              # the level of a flat region: it is still sampled, four times less densely; not tuned
+
+
+def default_sample_radius(h: int, w: int) -> int:
+    """max(1, longer side // 64), at most 64 (a documented choice, not a tuned value)"""
+    return max(1, min(SAMPLE_MAX_RADIUS, max(int(h), int(w)) // 64))
+
+
+def check_sample_parameters(radius, gain, floor) -> None:
+    """ValueError for a radius that is not an integer in 1..64, a gain that is not finite or <= 0, a floor that is not
+    finite or outside [0, 1] (None: not given)"""
+    if radius is not None and (int(radius) != radius or not 1 <= int(radius) <= SAMPLE_MAX_RADIUS):
+        raise ValueError(f"sample radius {radius!r}: expected an integer in 1..{SAMPLE_MAX_RADIUS}")
+    if gain is not None and not (math.isfinite(gain) and gain > 0):
+        raise ValueError(f"sample gain {gain!r}: expected a finite value above 0")
+    if floor is not None and not (math.isfinite(floor) and 0 <= floor <= 1):
+        raise ValueError(f"sample floor {floor!r}: expected a finite value in [0, 1]")
+
+
+def auto_sample_map(content, radius=None, gain=None, floor=None) -> torch.Tensor:
+    """--sample_map auto: the detail map of the content as utils.load_image returns it ((1, h, w, 3)
+    or (h, w, 3)) -> (h, w) float32 host tensor in [floor, 1], what load_sample_map returns for a painted map
+    (strotss_detail_map on the device).  None: default_sample_radius(h, w), DEFAULT_SAMPLE_GAIN, DEFAULT_SAMPLE_FLOOR.
+    ValueError as check_sample_parameters."""
+    check_sample_parameters(radius, gain, floor)
+    c = _rgb(content, "content")
+    if radius is None:
+        radius = default_sample_radius(int(c.shape[0]), int(c.shape[1]))
+    out = _ops.detail_map(c, int(radius), DEFAULT_SAMPLE_GAIN if gain is None else float(gain),
+                          DEFAULT_SAMPLE_FLOOR if floor is None else float(floor))
+    return out.cpu()
+
+
+def save_sample_map(path: str, sample_map) -> None:
+    """--save_sample_map: the (h, w) map in [0, 1] as an 8-bit greyscale PNG, rint(255 v), which load_sample_map reads"""
+    from PIL import Image
+    m = sample_map.detach().cpu().numpy() if torch.is_tensor(sample_map) else np.asarray(sample_map)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    Image.fromarray(np.rint(np.clip(m.astype(np.float64), 0.0, 1.0) * 255.0).astype(np.uint8), "L").save(path, format="PNG")
+
+
 def sample_levels_at_scale(sample_map, h: int, w: int) -> np.ndarray:
     """The levels of a scale: the user's (H, W) map, finite (ValueError otherwise), resized
     bilinearly to (h, w) as content_weight_at_scale resizes, clipped to [0, 1], rint(v * 65535) -> (h, w) uint16 host array.

@@ -26,6 +26,17 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
                     (strotss_index_draw_weighted).  The sample count does not change.  Combines with
                     masks, --auto_masks, the scribble files, --style_mix, --content_weight_map, every transport and --video
                     (one map for every frame); not with --strips or a multi-process run.  The style's samples stay uniform.
+                    --sample_map auto (the word in place of a path) computes the map from the content instead: a detail
+                    map, the root of the windowed mean gradient energy of the content's luma over --sample_gain times its
+                    image mean, clamped at 1 and lifted to --sample_floor (strotss_detail_map), at
+                    the content's loaded size, once per image; with --video once per frame, so it follows what moves.
+  --sample_radius R with --sample_map auto: the window radius in pixels, 1..64 (default: the longer side // 64, at least 1)
+  --sample_gain G   with --sample_map auto: detail at G times the image's mean detail reaches level 1 (default 2, > 0; not
+                    tuned for image quality)
+  --sample_floor F  with --sample_map auto: the level of a flat region, 0..1 (default 0.25; not tuned for image quality)
+  --save_sample_map DIR
+                    with --sample_map auto: write the map to DIR as the 8-bit sample_map.png (with --video
+                    sample_map_<frame stem>.png), which --sample_map PATH reads back
   --video           content_path is a directory of frames (sorted by name, all of one size) and -o an output directory:
                     frame <stem> is written as <stem>.jpg.  With --flow_dir DIR (backward_{t}_{t-1}.flo, optional
                     forward_{t-1}_{t}.flo and reliable_{t}_{t-1}.pgm, t the 1-based position of the frame: the naming of
@@ -282,8 +293,9 @@ def _content_weight_input(args):
 
 
 def _sample_map_input(args):
-    """--sample_map: its path, or None.  One GPU only: with --strips, under torchrun with WORLD_SIZE > 1 or for a file that
-    does not exist a ValueError (checked before anything is loaded)."""
+    """--sample_map: its path, the word "auto" (the map is computed from the content, _auto_sample_input), or None.  One
+    GPU only: with --strips, under torchrun with WORLD_SIZE > 1 or for a file that does not exist a ValueError (checked
+    before anything is loaded)."""
     path = getattr(args, "sample_map", None)
     if not path:
         return None
@@ -291,9 +303,28 @@ def _sample_map_input(args):
         raise ValueError("--sample_map cannot be combined with --strips")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise ValueError("--sample_map runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    if path == SAMPLE_MAP_AUTO:
+        return path
     if not os.path.isfile(path):
         raise ValueError(f"--sample_map: no such file: {path}")
     return path
+
+
+SAMPLE_MAP_AUTO = "auto"
+
+
+def _auto_sample_input(args):
+    """--sample_map auto: (radius or None, gain or None, floor or None, --save_sample_map's DIR or None), or None without
+    it.  ValueError, before anything is loaded: one of --sample_radius, --sample_gain, --sample_floor, --save_sample_map
+    without --sample_map auto, or a value out of range (strotss.check_sample_parameters)."""
+    given = {f: getattr(args, f, None) for f in ("sample_radius", "sample_gain", "sample_floor", "save_sample_map")}
+    if _sample_map_input(args) != SAMPLE_MAP_AUTO:
+        for flag, value in given.items():
+            if value is not None:
+                raise ValueError(f"--{flag} needs --sample_map auto (the map computed from the content)")
+        return None
+    strotss.check_sample_parameters(given["sample_radius"], given["sample_gain"], given["sample_floor"])
+    return given["sample_radius"], given["sample_gain"], given["sample_floor"], given["save_sample_map"]
 
 
 PRESERVE_COLOR_MODES = ("match", "luminance", "transfer")
@@ -927,7 +958,7 @@ def run(args: argparse.Namespace, trace=None):
     _style_transport_input(args)
     _palette_transport_input(args)
     _pixel_prior_input(args)
-    _sample_map_input(args)
+    _auto_sample_input(args)                                 # --sample_map's refusals, then those of auto's four flags
     if getattr(args, "video", False):
         return run_video(args, trace)
     timer = utils.Timer()
@@ -1011,7 +1042,14 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
     styles = _recolour_styles(args, styles, content, content_masks, style_masks)
     cw_map = strotss.load_content_weight_map(cw_path) if cw_path else None
     sm_path = _sample_map_input(args)
-    sm_map = strotss.load_sample_map(sm_path) if sm_path else None
+    sm_map = strotss.load_sample_map(sm_path) if sm_path and sm_path != SAMPLE_MAP_AUTO else None
+    auto_sample = _auto_sample_input(args)
+    if auto_sample:                                          # --sample_map auto: this image's own detail map (per --video frame)
+        sm_map = strotss.auto_sample_map(content, *auto_sample[:3])
+        if auto_sample[3] and rank == 0:
+            stem = os.path.splitext(os.path.basename(content_path))[0]
+            name = f"sample_map_{stem}.png" if getattr(args, "video", False) else "sample_map.png"
+            strotss.save_sample_map(os.path.join(auto_sample[3], name), sm_map)
     sampling = strotss.Sampling(SAMPLE_SIZE)
     masked = bool(getattr(args, "content_mask", None))
     transport = dict(_style_transport_input(args), **_palette_transport_input(args))
@@ -1315,7 +1353,20 @@ _FLAGS = (
                                                  "windows margins, one row per layer and direction) instead of a 128-row recompute margin")),
     (("--sample_map",), dict(type=str, default=None, metavar='PATH',
                              help="greyscale image: where the step's sample coordinates are drawn (white densely, black only "
-                                  "when nothing else is left), resized to every scale")),
+                                  "when nothing else is left), resized to every scale; or the word auto: a detail map "
+                                  "computed from the content (with --video from every frame)")),
+    (("--sample_radius",), dict(type=int, default=None, metavar='R',
+                                help="with --sample_map auto: window radius in pixels, 1..64 (default: the longer side // 64, "
+                                     "at least 1)")),
+    (("--sample_gain",), dict(type=float, default=None, metavar='G',
+                              help="with --sample_map auto: detail at G times the image's mean detail reaches level 1 "
+                                   f"(default {strotss.DEFAULT_SAMPLE_GAIN:g}, > 0; not tuned for image quality)")),
+    (("--sample_floor",), dict(type=float, default=None, metavar='F',
+                               help="with --sample_map auto: the level of a flat region, 0..1 "
+                                    f"(default {strotss.DEFAULT_SAMPLE_FLOOR:g}; not tuned for image quality)")),
+    (("--save_sample_map",), dict(type=str, default=None, metavar='DIR',
+                                  help="with --sample_map auto: write the map to DIR as sample_map.png (with --video "
+                                       "sample_map_<frame stem>.png), readable through --sample_map PATH")),
     (("--detail_weight",), dict(type=float, default=None, metavar='W',
                                 help="weight of the Laplacian detail term: keeps the content's edges at the pool sizes of "
                                      "--detail_pool (off unless given; finite, >= 0)")),
