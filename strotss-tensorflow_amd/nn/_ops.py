@@ -116,19 +116,14 @@ def temporal_workspace(h: int, w: int, device) -> torch.Tensor:
     return temporal_multi_workspace(h, w, 1, device)
 
 
-_temporal_ws = {}
-
-
 def temporal_fwd_bwd(img: torch.Tensor, target: torch.Tensor, certainty: torch.Tensor, gscale: float, gimg: torch.Tensor,
-                     loss_out: torch.Tensor, workspace: Optional[torch.Tensor] = None) -> None:
+                     loss_out: torch.Tensor, workspace: Optional[torch.Tensor] = None, ws: Optional["Workspaces"] = None) -> None:
     """loss_out[0] = (1/(3hw)) sum_p certainty(p) |img(p) - target(p)|^2, gimg += gscale * dloss/dimg: temporal_multi_fwd_bwd
-    with one target.  workspace: from temporal_workspace, or None for a module-level one per device and size."""
+    with one target.  workspace: from temporal_workspace, or None for the one per device and size of `ws` (Workspaces.zeroed)."""
     if workspace is None:
         h, w, _ = hwc(img)
-        key = (str(img.device), h, w)
-        workspace = _temporal_ws.get(key)
-        if workspace is None:
-            workspace = _temporal_ws[key] = temporal_workspace(h, w, img.device)
+        nb = _hip.lib().strotss_temporal_multi_workspace_bytes(h, w, 1)
+        workspace = (ws or workspaces).zeroed("temporal", (h, w), nb, img.device)
     temporal_multi_fwd_bwd(img, [target], [certainty], [gscale], gimg, loss_out, workspace)
 
 
@@ -306,9 +301,6 @@ def optical_flow(frame_a: torch.Tensor, frame_b: torch.Tensor, params: Optional[
 
 
 # ------------------------------------------------------------------ colour preservation
-_color_ws = {}
-
-
 def _rgb_image(t: torch.Tensor, name: str) -> Tuple[int, int]:
     """(h, w) of an (h, w, 3) or (1, h, w, 3) image on the device; ValueError for another shape"""
     require(t, name)
@@ -326,20 +318,17 @@ def _weight_plane(weight: Optional[torch.Tensor], h: int, w: int, name: str) -> 
     return weight
 
 
-def color_stats(img: torch.Tensor, weight: Optional[torch.Tensor] = None) -> torch.Tensor:
+def color_stats(img: torch.Tensor, weight: Optional[torch.Tensor] = None, ws: Optional["Workspaces"] = None) -> torch.Tensor:
     """the ten float64 sums (W, S_0, S_1, S_2, S_00, S_01, S_02, S_11, S_12, S_22) of an (h, w, 3) image under an optional
-    (h, w) weight plane, on the device (strotss_color_stats; one launch, the same bits on every run).  The workspace is a
-    module-level one per device and size, zeroed when it is made."""
+    (h, w) weight plane, on the device (strotss_color_stats; one launch, the same bits on every run).  The workspace is
+    one per device and size (Workspaces.zeroed)."""
     h, w = _rgb_image(img, "image")
     weight = _weight_plane(weight, h, w, "weight plane")
     lib = _hip.lib()
-    key = (str(img.device), h, w)
-    workspace = _color_ws.get(key)
-    if workspace is None:
-        nb = int(lib.strotss_color_stats_workspace_bytes(h, w))
-        if nb == 0:
-            raise _hip.StrotssHipError(f"color_stats: bad size {h} x {w}")
-        workspace = _color_ws[key] = torch.zeros(nb, dtype=torch.uint8, device=img.device)
+    nb = int(lib.strotss_color_stats_workspace_bytes(h, w))
+    if nb == 0:
+        raise _hip.StrotssHipError(f"color_stats: bad size {h} x {w}")
+    workspace = (ws or workspaces).zeroed("color_stats", (h, w), nb, img.device)
     out = torch.empty(10, dtype=torch.float64, device=img.device)
     check(lib.strotss_color_stats(ptr(img), ptr(weight), h, w, ptr(out), ptr(workspace), stream_ptr()), "color_stats")
     return out
@@ -375,7 +364,7 @@ def luma_merge(result: torch.Tensor, content: torch.Tensor, out: Optional[torch.
 
 
 # ------------------------------------------------------------------ colour distribution transfer
-_transfer_ws = {}
+_transfer_ws = {}      # not scratch: the typed running state (histogram, table) of the one transfer at a time
 
 
 def _bases(bases, name: str = "bases"):
@@ -471,26 +460,20 @@ def color_transfer_apply(img: torch.Tensor, basis, table: torch.Tensor, bins: in
 
 
 # ------------------------------------------------------------------ photo smoothing
-_smooth_ws = {}
-
-
 def guided_smooth(img: torch.Tensor, guide: torch.Tensor, radius: int, eps: float,
-                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  out: Optional[torch.Tensor] = None, ws: Optional["Workspaces"] = None) -> torch.Tensor:
     """the guided filter of an (h, w, 3) image with `guide` (the same size) as colour guide, windows of radius `radius`
     clipped to the image, regulariser `eps` at its float32 value (strotss_guided_smooth; four launches on the current
-    stream, the same bits on every run).  out may be img, not guide.  The workspace (216 bytes per pixel) is a module-level
-    one per device and size; the library refuses a radius outside 1..64 and an eps outside [1e-4, 1]."""
+    stream, the same bits on every run).  out may be img, not guide.  The workspace (216 bytes per pixel) is grow-only
+    scratch of `ws`; the library refuses a radius outside 1..64 and an eps outside [1e-4, 1]."""
     h, w = _rgb_image(img, "image")
     if _rgb_image(guide, "guide") != (h, w):
         raise ValueError(f"image of shape {tuple(img.shape)} and guide of shape {tuple(guide.shape)} differ in size")
     lib = _hip.lib()
-    key = (str(img.device), h, w)
-    workspace = _smooth_ws.get(key)
-    if workspace is None:
-        nb = int(lib.strotss_guided_smooth_workspace_bytes(h, w, 1))        # the size does not depend on the radius
-        if nb == 0:
-            raise _hip.StrotssHipError(f"guided_smooth: bad size {h} x {w}")
-        workspace = _smooth_ws[key] = torch.empty(nb, dtype=torch.uint8, device=img.device)
+    nb = int(lib.strotss_guided_smooth_workspace_bytes(h, w, 1))        # the size does not depend on the radius
+    if nb == 0:
+        raise _hip.StrotssHipError(f"guided_smooth: bad size {h} x {w}")
+    workspace = (ws or workspaces).get("guided_smooth", nb, img.device)
     if out is None:
         out = torch.empty_like(img)
     require(out, "smoothed image")
@@ -502,17 +485,16 @@ def guided_smooth(img: torch.Tensor, guide: torch.Tensor, radius: int, eps: floa
 
 # ------------------------------------------------------------------ guided upsampling
 UPSAMPLE_MODES = {"guided": 0, "residual": 1}        # STROTSS_UPSAMPLE_GUIDED, STROTSS_UPSAMPLE_RESIDUAL
-_upsample_ws = {}
 
 
 def guided_upsample(img: torch.Tensor, guide_lo: torch.Tensor, guide_hi: torch.Tensor, radius: int, eps: float, mode: str,
-                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    out: Optional[torch.Tensor] = None, ws: Optional["Workspaces"] = None) -> torch.Tensor:
     """the (h, w, 3) image brought to the size of `guide_hi` (H, W, 3), H >= h and W >= w, by the guided filter's window
     means at (h, w) (guide_lo: the guide at the image's size) interpolated and applied to guide_hi; mode "guided" or
     "residual" (that plus the interpolated img - filter(img)).  strotss_guided_upsample: five launches on the current
     stream, the same bits on every run.  out may overlap none of the inputs.  The workspace (280 bytes per low-resolution
-    pixel) is a module-level one per device and low-resolution size; the library refuses what strotss_guided_smooth
-    refuses, a smaller guide_hi and 3 H W > INT_MAX."""
+    pixel) is grow-only scratch of `ws`; the library refuses what strotss_guided_smooth refuses, a smaller guide_hi and
+    3 H W > INT_MAX."""
     h, w = _rgb_image(img, "image")
     if _rgb_image(guide_lo, "low-resolution guide") != (h, w):
         raise ValueError(f"image of shape {tuple(img.shape)} and guide of shape {tuple(guide_lo.shape)} differ in size")
@@ -520,13 +502,10 @@ def guided_upsample(img: torch.Tensor, guide_lo: torch.Tensor, guide_hi: torch.T
     if mode not in UPSAMPLE_MODES:
         raise ValueError(f"upsampling mode {mode!r}: expected one of {tuple(UPSAMPLE_MODES)}")
     lib = _hip.lib()
-    key = (str(img.device), h, w)
-    workspace = _upsample_ws.get(key)
-    if workspace is None:
-        nb = int(lib.strotss_guided_upsample_workspace_bytes(h, w, 1))      # the size does not depend on the radius
-        if nb == 0:
-            raise _hip.StrotssHipError(f"guided_upsample: bad size {h} x {w}")
-        workspace = _upsample_ws[key] = torch.empty(nb, dtype=torch.uint8, device=img.device)
+    nb = int(lib.strotss_guided_upsample_workspace_bytes(h, w, 1))      # the size does not depend on the radius
+    if nb == 0:
+        raise _hip.StrotssHipError(f"guided_upsample: bad size {h} x {w}")
+    workspace = (ws or workspaces).get("guided_upsample", nb, img.device)
     if out is None:
         out = torch.empty_like(guide_hi)
     require(out, "upsampled image")
@@ -538,26 +517,20 @@ def guided_upsample(img: torch.Tensor, guide_lo: torch.Tensor, guide_hi: torch.T
 
 
 # ------------------------------------------------------------------ detail map
-_detail_ws = {}
-
-
-def detail_map(img: torch.Tensor, radius: Optional[int] = None, gain: float = 2.0, floor: float = 0.25) -> torch.Tensor:
+def detail_map(img: torch.Tensor, radius: Optional[int] = None, gain: float = 2.0, floor: float = 0.25, ws=None) -> torch.Tensor:
     """the (h, w) float32 detail map of an (h, w, 3) image in [floor, 1]: the root of the windowed mean gradient energy of
     its luma over gain times that root's image mean, clamped at 1 (strotss_detail_map; three launches on the current stream,
     the same bits on every run).  radius None: max(1, longer side // 64), at most 64.  The workspace (8 bytes per pixel) is
-    a module-level one per device and size, zeroed when made; the library refuses a radius outside 1..64, a gain that is
-    not finite or <= 0 and a floor outside [0, 1]."""
+    one per device and size (Workspaces.zeroed); the library refuses a radius outside 1..64, a gain that is not finite or
+    <= 0 and a floor outside [0, 1]."""
     h, w = _rgb_image(img, "image")
     if radius is None:
         radius = max(1, min(64, max(h, w) // 64))
     lib = _hip.lib()
-    key = (str(img.device), h, w)
-    workspace = _detail_ws.get(key)
-    if workspace is None:
-        nb = int(lib.strotss_detail_map_workspace_bytes(h, w))
-        if nb == 0:
-            raise _hip.StrotssHipError(f"detail_map: bad size {h} x {w}")
-        workspace = _detail_ws[key] = torch.zeros(nb, dtype=torch.uint8, device=img.device)
+    nb = int(lib.strotss_detail_map_workspace_bytes(h, w))
+    if nb == 0:
+        raise _hip.StrotssHipError(f"detail_map: bad size {h} x {w}")
+    workspace = (ws or workspaces).zeroed("detail_map", (h, w), nb, img.device)
     out = torch.empty((h, w), dtype=torch.float32, device=img.device)
     check(lib.strotss_detail_map(ptr(img), h, w, int(radius), float(gain), float(floor), ptr(out), ptr(workspace),
                                  stream_ptr()), "detail_map")
@@ -605,19 +578,19 @@ def conv3x3_c3_fwd(img, w_kio, bias, out=None, mean=None, std=None, relu_bits_ou
     return out
 
 
-def conv3x3_relu_fwd(x, w_tok, bias, out=None, pool_out=None, pool_code=None):
+def conv3x3_relu_fwd(x, w_tok, bias, out=None, pool_out=None, pool_code=None, ws=None):
     """pool_out (split-K layers only, conv3x3_direct_splits): the finish kernel also writes maxpool2_fwd(out) (+ pool_code)."""
     require(x, "conv input"); h, w, cin = hwc(x)
     cout = bias.numel()
     if out is None:
         out = torch.empty((1, h, w, cout), dtype=torch.float32, device=x.device)
     nb = _hip.lib().strotss_conv3x3_workspace_bytes(h, w, cin, cout)
-    ws = workspaces.get("conv_splitk", nb, x.device) if nb else None
+    buf = (ws or workspaces).get("conv_splitk", nb, x.device) if nb else None
     if pool_out is not None:
         check(_hip.lib().strotss_conv3x3_relu_pool_fwd(ptr(x), h, w, cin, ptr(w_tok), ptr(bias), cout, ptr(out), ptr(pool_out),
-                                                       ptr(pool_code), ptr(ws), nb, stream_ptr()), "conv3x3_relu_pool_fwd")
+                                                       ptr(pool_code), ptr(buf), nb, stream_ptr()), "conv3x3_relu_pool_fwd")
         return out
-    check(_hip.lib().strotss_conv3x3_relu_fwd(ptr(x), h, w, cin, ptr(w_tok), ptr(bias), cout, ptr(out), ptr(ws), nb,
+    check(_hip.lib().strotss_conv3x3_relu_fwd(ptr(x), h, w, cin, ptr(w_tok), ptr(bias), cout, ptr(out), ptr(buf), nb,
                                               stream_ptr()), "conv3x3_relu_fwd")
     return out
 
@@ -633,27 +606,27 @@ def conv3x3_dgrad_accumulates(h: int, w: int, cout: int, cin: int) -> bool:
     return bool(_hip.load_library().strotss_conv3x3_dgrad_can_accumulate(h, w, cout, cin))
 
 
-def conv3x3_dgrad(gout, w_tik, cin, act_in=None, out=None, accumulate=False):
+def conv3x3_dgrad(gout, w_tik, cin, act_in=None, out=None, accumulate=False, ws=None):
     require(gout, "conv grad"); h, w, cout = hwc(gout)
     if out is None:
         out = torch.empty((1, h, w, cin), dtype=torch.float32, device=gout.device)
     nb = _hip.lib().strotss_conv3x3_workspace_bytes(h, w, cout, cin)
-    ws = workspaces.get("conv_splitk", nb, gout.device) if nb else None
+    buf = (ws or workspaces).get("conv_splitk", nb, gout.device) if nb else None
     check(_hip.lib().strotss_conv3x3_dgrad(ptr(gout), h, w, cout, ptr(w_tik), cin, ptr(act_in), ptr(out), int(accumulate),
-                                           ptr(ws), nb, stream_ptr()), "conv3x3_dgrad")
+                                           ptr(buf), nb, stream_ptr()), "conv3x3_dgrad")
     return out
 
 
-def conv3x3_dgrad_unpool(gout, w_tik, cin, pool_code, out_full, accumulate=False):
+def conv3x3_dgrad_unpool(gout, w_tik, cin, pool_code, out_full, accumulate=False, ws=None):
     """Data gradient of a split-K layer whose input came from the 2x2/2 max-pool, written through the pool's adjoint:
     out_full (1, H, W, cin) (+)= maxpool2_bwd(code=pool_code, conv^T(gout)); the pooled gradient is never stored."""
     require(gout, "conv grad"); h, w, cout = hwc(gout)
     require(out_full, "gradient in front of the pool"); fh, fw, fc = hwc(out_full)
     assert fc == cin and fh // 2 == h and fw // 2 == w, (out_full.shape, gout.shape, cin)
     nb = _hip.lib().strotss_conv3x3_workspace_bytes(h, w, cout, cin)
-    ws = workspaces.get("conv_splitk", nb, gout.device) if nb else None
+    buf = (ws or workspaces).get("conv_splitk", nb, gout.device) if nb else None
     check(_hip.lib().strotss_conv3x3_dgrad_unpool(ptr(gout), h, w, cout, ptr(w_tik), cin, ptr(pool_code), ptr(out_full), fh, fw,
-                                                  int(accumulate), ptr(ws), nb, stream_ptr()), "conv3x3_dgrad_unpool")
+                                                  int(accumulate), ptr(buf), nb, stream_ptr()), "conv3x3_dgrad_unpool")
     return out_full
 
 
@@ -667,9 +640,9 @@ def conv3x3_c3_dgrad(gout, w_tic, gimg=None, accumulate=False, std=None):
     return gimg
 
 
-def _wino_ws(h, w, cin, cout, tile_m, device):
+def _wino_ws(h, w, cin, cout, tile_m, device, ws=None):
     nb = _hip.lib().strotss_conv3x3_winograd_workspace_bytes(h, w, cin, cout, tile_m)
-    return workspaces.get("winograd", nb, device), nb
+    return (ws or workspaces).get("winograd", nb, device), nb
 
 
 def _tile_m(u: torch.Tensor) -> int:
@@ -732,7 +705,7 @@ def winograd_x3(u: torch.Tensor, h: int, w: int):
     return up
 
 
-def conv3x3_winograd_fwd(x, u_pok, bias, out=None, pool_out=None, pool_code=None, relu_bits_out=None):
+def conv3x3_winograd_fwd(x, u_pok, bias, out=None, pool_out=None, pool_code=None, relu_bits_out=None, ws=None):
     """u_pok: (16, cout, cin) -> F(2x2,3x3), (36, cout, cin) -> F(4x4,3x3).  pool_out: (1, h//2, w//2, cout) buffer
     that also receives the 2x2/2 max-pool of the result.  relu_bits_out (F(4x4) only): relu_bits_buffer that receives the
     sign words of the result, for the next layer's conv3x3_winograd_dgrad."""
@@ -742,16 +715,16 @@ def conv3x3_winograd_fwd(x, u_pok, bias, out=None, pool_out=None, pool_code=None
         out = torch.empty((1, h, w, cout), dtype=torch.float32, device=x.device)
     m = _tile_m(u_pok)
     assert u_pok.device == x.device, (u_pok.device, x.device)
-    ws, nb = _wino_ws(h, w, cin, cout, m, x.device)
+    buf, nb = _wino_ws(h, w, cin, cout, m, x.device, ws)
     check(_hip.lib().strotss_conv3x3_winograd_fwd(ptr(x), h, w, cin, ptr(u_pok), ptr(winograd_packed(u_pok)),
                                                   ptr(winograd_x3(u_pok, h, w)), ptr(bias),
-                                                  cout, m, ptr(out), ptr(pool_out), ptr(pool_code), ptr(relu_bits_out), ptr(ws), nb,
+                                                  cout, m, ptr(out), ptr(pool_out), ptr(pool_code), ptr(relu_bits_out), ptr(buf), nb,
                                                   stream_ptr()),
           "conv3x3_winograd_fwd")
     return out
 
 
-def conv3x3_winograd_dgrad(gout, u_pik, cin, act_in=None, out=None, relu_bits=None, accumulate=False):
+def conv3x3_winograd_dgrad(gout, u_pik, cin, act_in=None, out=None, relu_bits=None, accumulate=False, ws=None):
     """relu_bits (F(4x4) only): the sign words of the layer's input activation; the ReLU mask then comes from them instead of
     act_in (same result, 1/16 of the bytes)."""
     require(gout, "conv grad"); h, w, cout = hwc(gout)
@@ -759,10 +732,10 @@ def conv3x3_winograd_dgrad(gout, u_pik, cin, act_in=None, out=None, relu_bits=No
         out = torch.empty((1, h, w, cin), dtype=torch.float32, device=gout.device)
     m = _tile_m(u_pik)
     assert u_pik.device == gout.device, (u_pik.device, gout.device)
-    ws, nb = _wino_ws(h, w, cout, cin, m, gout.device)
+    buf, nb = _wino_ws(h, w, cout, cin, m, gout.device, ws)
     check(_hip.lib().strotss_conv3x3_winograd_dgrad(ptr(gout), h, w, cout, ptr(u_pik), ptr(winograd_packed(u_pik)),
                                                     ptr(winograd_x3(u_pik, h, w)), cin,
-                                                    m, ptr(act_in), ptr(relu_bits), ptr(out), int(accumulate), ptr(ws), nb,
+                                                    m, ptr(act_in), ptr(relu_bits), ptr(out), int(accumulate), ptr(buf), nb,
                                                     stream_ptr()),
           "conv3x3_winograd_dgrad")
     return out
@@ -944,25 +917,47 @@ def index_draw_counts(h: int, w: int, masks=None):
     return most, least
 
 
-class _WsCache:
-    """Grow-only workspace per (device, tag): the C ABI never allocates.  Growth REALLOCATES, which a captured hipGraph
-    must never see (the graph holds the old pointer): StepEngine.capture_graph therefore runs one full eager step on a
-    side stream first, so every workspace of the step has its final size before capture; sizes depend on the engine's
-    shapes only, never on the data."""
+class Workspaces:
+    """The scratch memory of one owner: the C ABI never allocates.  Whatever a captured hipGraph points into belongs to the
+    object that owns the graph -- a StepEngine and its trunk draw from an instance of their own -- so it is released with
+    that object and, once frozen, cannot be reallocated under the graph.  The module-level `workspaces` serves every caller
+    that passes no `ws`: one-off operators, feature extraction, the mask and colour tools."""
 
     def __init__(self):
-        self.bufs = {}
+        self.bufs = {}                   # (tag, device) -> grow-only scratch
+        self.fixed = {}                  # (tag, device, key) -> zeroed buffer of one layout
+        self.selfsim_record = None       # what the "selfsim" buffer holds (selfsim_fwd_bwd; _pred_panels_after_selfsim)
+        self.frozen = False
 
     def get(self, tag: str, nbytes: int, device) -> torch.Tensor:
+        """grow-only scratch of at least `nbytes` (and 256) per (tag, device); growth REALLOCATES, which a captured graph
+        must never see (it holds the old pointer): after freeze() it is an error"""
         key = (tag, str(device))
         b = self.bufs.get(key)
         if b is None or b.numel() < nbytes:
+            if b is not None and self.frozen:
+                raise _hip.StrotssHipError(f"workspace {tag!r} is frozen under a captured graph at {b.numel()} bytes and "
+                                           f"cannot grow to {nbytes}")
             b = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
             self.bufs[key] = b
         return b
 
+    def zeroed(self, tag: str, key, nbytes: int, device) -> torch.Tensor:
+        """the zero-initialised buffer of (tag, device, key), `key` the caller's shape key: never shared between shapes and
+        never grown.  A ticketed reduction leaves its counter at zero but its partials dirty, so only a buffer that is used
+        with one fixed layout stays valid from call to call."""
+        key = (tag, str(device), key)
+        b = self.fixed.get(key)
+        if b is None:
+            b = self.fixed[key] = _zeroed_workspace(nbytes, device)
+        return b
 
-workspaces = _WsCache()
+    def freeze(self) -> None:
+        """from now on a `get` that would have to grow a buffer raises; one that fits, and a new tag, are served as before"""
+        self.frozen = True
+
+
+workspaces = Workspaces()
 
 
 def row_inv_norm(x: torch.Tensor, n: int) -> torch.Tensor:
@@ -999,7 +994,7 @@ def kmeans_assign(x: torch.Tensor, inv_norm: torch.Tensor, n: int, d: int, centr
 
 
 def kmeans_update(x: torch.Tensor, inv_norm: torch.Tensor, label: torch.Tensor, n: int, d: int, k: int,
-                  centres: torch.Tensor) -> torch.Tensor:
+                  centres: torch.Tensor, ws: Optional["Workspaces"] = None) -> torch.Tensor:
     """strotss_kmeans_update: centres[j] <- the normalised float64 sum of the unit rows with label j, in place (an empty
     cluster keeps its centre); -> count (k,) int32.  label: (>= n,) int32; values outside 0..k-1 are skipped."""
     ld = _kmeans_rows(x, inv_norm, n, d, centres, k)
@@ -1009,16 +1004,16 @@ def kmeans_update(x: torch.Tensor, inv_norm: torch.Tensor, label: torch.Tensor, 
     nb = int(lib.strotss_kmeans_update_workspace_bytes(n, ld, k))
     if nb == 0:
         raise _hip.StrotssHipError(f"kmeans_update: bad sizes n {n}, ld {ld}, k {k}")
-    ws = workspaces.get("kmeans", nb, x.device)
+    buf = (ws or workspaces).get("kmeans", nb, x.device)
     count = torch.empty(k, dtype=torch.int32, device=x.device)
-    check(lib.strotss_kmeans_update(ptr(x), ptr(inv_norm), ptr(label), n, d, ld, k, ptr(centres), ptr(count), ptr(ws), nb,
+    check(lib.strotss_kmeans_update(ptr(x), ptr(inv_norm), ptr(label), n, d, ld, k, ptr(centres), ptr(count), ptr(buf), nb,
                                     stream_ptr()), "kmeans_update")
     return count
 
 
 # ------------------------------------------------------------------ mask refinement
 def refine_labels(img: torch.Tensor, grid: torch.Tensor, k: int, radius: int, sigma_s: float, sigma_r: float,
-                  votes: bool = False, means: bool = False):
+                  votes: bool = False, means: bool = False, ws: Optional["Workspaces"] = None):
     """strotss_refine_labels: the (gh, gw) int32 label grid of an (h, w, 3) image brought to (h, w) by a joint bilateral vote
     among the (2 radius + 1)^2 cells around each pixel's own.  -> (label (h, w) int32, count (k,) int32, best, second, mean):
     best / second (h, w) float64 with votes=True, mean the (gh, gw, 3) float32 cell colours with means=True, else None.  Two
@@ -1031,14 +1026,14 @@ def refine_labels(img: torch.Tensor, grid: torch.Tensor, k: int, radius: int, si
     nb = int(lib.strotss_refine_labels_workspace_bytes(h, w, gh, gw))
     if nb == 0:
         raise ValueError(f"refine_labels: a {gh} x {gw} label grid for an image of {h} x {w} (the grid may not be larger)")
-    ws = workspaces.get("refine", nb, img.device)
+    buf = (ws or workspaces).get("refine", nb, img.device)
     label = torch.empty((h, w), dtype=torch.int32, device=img.device)
     count = torch.empty(int(k), dtype=torch.int32, device=img.device) if 1 <= int(k) <= _hip.KMEANS_MAX_K else None
     best = torch.empty((h, w), dtype=torch.float64, device=img.device) if votes else None
     second = torch.empty((h, w), dtype=torch.float64, device=img.device) if votes else None
     check(lib.strotss_refine_labels(ptr(img), h, w, ptr(grid), gh, gw, int(k), int(radius), float(sigma_s), float(sigma_r),
-                                    ptr(label), ptr(best), ptr(second), ptr(count), ptr(ws), nb, stream_ptr()), "refine_labels")
-    mean = ws[:gh * gw * 12].view(torch.float32).reshape(gh, gw, 3).clone() if means else None
+                                    ptr(label), ptr(best), ptr(second), ptr(count), ptr(buf), nb, stream_ptr()), "refine_labels")
+    mean = buf[:gh * gw * 12].view(torch.float32).reshape(gh, gw, 3).clone() if means else None
     return label, count, best, second, mean
 
 
@@ -1098,7 +1093,7 @@ def kmeans_scores(x: torch.Tensor, inv_norm: torch.Tensor, n: int, d: int, centr
 
 
 def scribble_labels(img: torch.Tensor, stroke: torch.Tensor, scores: torch.Tensor, tau: float, lam: float, sigma: float,
-                    iters: int, iters_per_launch: int = 0, planes: bool = False):
+                    iters: int, iters_per_launch: int = 0, planes: bool = False, ws: Optional["Workspaces"] = None):
     """strotss_scribble_labels: the strokes of an (h, w, 3) image -- stroke (h, w) int32, a label 0..k-1 or anything else --
     spread over the image by `iters` Jacobi sweeps of a screened random walker whose unary is the softmax at temperature tau of
     the bilinearly sampled (gh, gw, k) score grid.  -> (label (h, w) int32, count (k,) int32, x): x the (k, h, w) float32
@@ -1115,12 +1110,12 @@ def scribble_labels(img: torch.Tensor, stroke: torch.Tensor, scores: torch.Tenso
     nb = int(lib.strotss_scribble_workspace_bytes(h, w, k))
     if nb == 0:
         raise ValueError(f"scribble_labels: {k} regions on an image of {h} x {w} (expected 2..{_hip.SCRIBBLE_MAX_K} regions)")
-    ws = workspaces.get("scribble", nb, img.device)
+    buf = (ws or workspaces).get("scribble", nb, img.device)
     label = torch.empty((h, w), dtype=torch.int32, device=img.device)
     count = torch.empty(k, dtype=torch.int32, device=img.device)
     x = torch.empty((k, h, w), dtype=torch.float32, device=img.device) if planes else None
     check(lib.strotss_scribble_labels(ptr(img), ptr(stroke), h, w, ptr(scores), gh, gw, k, float(tau), float(lam), float(sigma),
-                                      int(iters), int(iters_per_launch), ptr(label), ptr(count), ptr(x), ptr(ws), nb,
+                                      int(iters), int(iters_per_launch), ptr(label), ptr(count), ptr(x), ptr(buf), nb,
                                       stream_ptr()), "scribble_labels")
     return label, count, x
 
@@ -1162,87 +1157,89 @@ def cosine_distance_x3(xp, rx, nx, yp, ry, ny, ld) -> torch.Tensor:
     return Cm
 
 
-def selfsim_fwd_bwd(pred, content, n, d, gscale, gpred, loss_out):
+def selfsim_fwd_bwd(pred, content, n, d, gscale, gpred, loss_out, ws=None):
     l = _hip.lib()
     nb = l.strotss_selfsim_workspace_bytes(n, pred.shape[1])
-    ws = workspaces.get("selfsim", nb, pred.device)
+    buf = (ws or workspaces).get("selfsim", nb, pred.device)
     check(l.strotss_selfsim_fwd_bwd(ptr(pred), ptr(content), n, d, pred.shape[1], gscale, ptr(gpred),
-                                    ptr(loss_out), ptr(ws), nb, stream_ptr()), "selfsim_fwd_bwd")
-    # what the workspace now holds (reciprocal norms + x3 panels of exactly these prediction rows), for the borrower below
-    global _selfsim_record
-    _selfsim_record = (ws.data_ptr(), nb, ptr(pred), n, int(pred.shape[1]), stream_ptr())
+                                    ptr(loss_out), ptr(buf), nb, stream_ptr()), "selfsim_fwd_bwd")
+    _record_selfsim(ws, buf, nb, pred, n)
 
 
-def selfsim_weighted_fwd_bwd(pred, content, col_weight, n, d, gscale, gpred, loss_out):
+def selfsim_weighted_fwd_bwd(pred, content, col_weight, n, d, gscale, gpred, loss_out, ws=None):
     """selfsim_fwd_bwd with the content term weighted per sampled column (strotss_selfsim_weighted_fwd_bwd): col_weight is a
     float32 device vector of >= n values, finite and >= 0 (None: selfsim_fwd_bwd itself).  Same workspace, same record: the
     relaxed EMD borrows the prediction rows' norms and panels from it as after the unweighted call."""
     if col_weight is None:
-        return selfsim_fwd_bwd(pred, content, n, d, gscale, gpred, loss_out)
+        return selfsim_fwd_bwd(pred, content, n, d, gscale, gpred, loss_out, ws=ws)
     require(col_weight, "column weights")
     assert col_weight.numel() >= n
     l = _hip.lib()
     nb = l.strotss_selfsim_workspace_bytes(n, pred.shape[1])
-    ws = workspaces.get("selfsim", nb, pred.device)
+    buf = (ws or workspaces).get("selfsim", nb, pred.device)
     check(l.strotss_selfsim_weighted_fwd_bwd(ptr(pred), ptr(content), ptr(col_weight), n, d, pred.shape[1], gscale, ptr(gpred),
-                                             ptr(loss_out), ptr(ws), nb, stream_ptr()), "selfsim_weighted_fwd_bwd")
-    global _selfsim_record
-    _selfsim_record = (ws.data_ptr(), nb, ptr(pred), n, int(pred.shape[1]), stream_ptr())
+                                             ptr(loss_out), ptr(buf), nb, stream_ptr()), "selfsim_weighted_fwd_bwd")
+    _record_selfsim(ws, buf, nb, pred, n)
 
 
-_selfsim_record = None
+def _record_selfsim(ws, buf, nb, pred, n) -> None:
+    # what the selfsim buffer of `ws` now holds (reciprocal norms + x3 panels of exactly these prediction rows), for the borrower
+    (ws or workspaces).selfsim_record = (buf.data_ptr(), nb, ptr(pred), n, int(pred.shape[1]), stream_ptr())
+
+
 remd_borrow_stats = {"borrowed": 0, "plain": 0}      # which path remd_cos_fwd_bwd_after_selfsim took (tests read it)
 
 
-def remd_cos_fwd_bwd(style, rs, ns, pred, n, d, gscale, gpred, loss_out, swapped=False):
+def remd_cos_fwd_bwd(style, rs, ns, pred, n, d, gscale, gpred, loss_out, swapped=False, ws=None):
     """swapped: `pred` is the reference's FIRST argument (gradient to the target side; STROTSS_REMD_SWAPPED)"""
     l = _hip.lib()
     nb = l.strotss_remd_workspace_bytes(ns, n, pred.shape[1])
-    ws = workspaces.get("remd", nb, pred.device)
+    buf = (ws or workspaces).get("remd", nb, pred.device)
     check(l.strotss_remd_cos_fwd_bwd(ptr(style), ptr(rs), ns, ptr(pred), n, d, pred.shape[1], gscale,
-                                     ptr(gpred), ptr(loss_out), int(swapped), ptr(ws), nb, stream_ptr()), "remd_cos_fwd_bwd")
+                                     ptr(gpred), ptr(loss_out), int(swapped), ptr(buf), nb, stream_ptr()), "remd_cos_fwd_bwd")
 
 
-def _pred_panels_after_selfsim(pred, n, style_panels):
+def _pred_panels_after_selfsim(pred, n, style_panels, ws=None):
     """What selfsim_fwd_bwd is KNOWN to have left in its workspace for exactly these prediction rows: (reciprocal norms,
-    prediction panels, style panels) as pointers, or None where the record that call leaves does not match -- other rows, a
-    regrown or re-used buffer, another count or stride, another stream.  The panels come as a pair: both are None where the
-    library hands out none (the cost matrices on the f32 MFMA, STROTSS_X3=0) or the StyleTarget has none."""
+    prediction panels, style panels) as pointers, or None where the record that call leaves on `ws` does not match -- other
+    rows, a regrown or re-used buffer, another count or stride, another stream.  The panels come as a pair: both are None
+    where the library hands out none (the cost matrices on the f32 MFMA, STROTSS_X3=0) or the StyleTarget has none."""
     l = _hip.lib()
     ld = int(pred.shape[1])
     nb = l.strotss_selfsim_workspace_bytes(n, ld)
-    ws = workspaces.get("selfsim", nb, pred.device)
-    if _selfsim_record != (ws.data_ptr(), nb, ptr(pred), n, ld, stream_ptr()):
+    ws = ws or workspaces
+    buf = ws.get("selfsim", nb, pred.device)
+    if ws.selfsim_record != (buf.data_ptr(), nb, ptr(pred), n, ld, stream_ptr()):
         return None
     rp, xp = C.c_void_p(), C.c_void_p()
-    check(l.strotss_selfsim_pred_panels(ptr(ws), nb, n, ld, C.byref(rp), C.byref(xp)), "selfsim_pred_panels")
+    check(l.strotss_selfsim_pred_panels(ptr(buf), nb, n, ld, C.byref(rp), C.byref(xp)), "selfsim_pred_panels")
     both = style_panels is not None and bool(xp.value)
     return rp.value, xp.value if both else None, ptr(style_panels) if both else None
 
 
-def _pred_panels_or_raise(who, pred, n, style_panels):
+def _pred_panels_or_raise(who, pred, n, style_panels, ws=None):
     """_pred_panels_after_selfsim for the terms that have no plain call to fall back to: a mismatch is an error"""
-    got = _pred_panels_after_selfsim(pred, n, style_panels)
+    got = _pred_panels_after_selfsim(pred, n, style_panels, ws)
     if got is None:
         raise _hip.StrotssHipError(f"{who}: selfsim_fwd_bwd has not just run on these rows")
     return got
 
 
-def remd_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, gscale, gpred, loss_out):
+def remd_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, gscale, gpred, loss_out, ws=None):
     """remd_cos_fwd_bwd for the prediction rows that selfsim_fwd_bwd has just processed (_pred_panels_after_selfsim; a
     mismatch falls back to the plain call, which makes its own norms and panels): their reciprocal norms and x3 panels are
     taken from that workspace, the style rows' panels from `style_panels` (row_inv_norm_x3(style)[1], constant within a
     scale) -- bit for bit remd_cos_fwd_bwd, one launch and two passes over the rows less.  No pair of panels: the plain call."""
-    got = _pred_panels_after_selfsim(pred, n, style_panels)
+    got = _pred_panels_after_selfsim(pred, n, style_panels, ws)
     if got is None or got[1] is None:
         remd_borrow_stats["plain"] += 1
-        return remd_cos_fwd_bwd(style, rs, ns, pred, n, d, gscale, gpred, loss_out)
+        return remd_cos_fwd_bwd(style, rs, ns, pred, n, d, gscale, gpred, loss_out, ws=ws)
     rp, xp, sp = got
     remd_borrow_stats["borrowed"] += 1
     l = _hip.lib()
     ld = pred.shape[1]
     nbr = l.strotss_remd_workspace_bytes(ns, n, ld)
-    wsr = workspaces.get("remd", nbr, pred.device)
+    wsr = (ws or workspaces).get("remd", nbr, pred.device)
     check(l.strotss_remd_cos_fwd_bwd_panels(ptr(style), ptr(rs), sp, ns, ptr(pred), rp, xp, n, d, ld,
                                             gscale, ptr(gpred), ptr(loss_out), ptr(wsr), nbr, stream_ptr()),
           "remd_cos_fwd_bwd_panels")
@@ -1255,18 +1252,18 @@ def step_losses_available() -> bool:
 
 
 def step_losses_fwd_bwd(pred, content, n, d, style, rs, style_panels, ns, style_mean, style_cov, g_content, g_moment, g_remd,
-                        g_palette, gpred, loss_content, loss_moment, loss_remd, loss_palette):
+                        g_palette, gpred, loss_content, loss_moment, loss_remd, loss_palette, ws=None):
     """self_similarity + moment_matching + relaxed_emd (cosine) + the YUV palette relaxed_emd of one train step in ONE call
     (strotss_step_losses_fwd_bwd): one prologue launch, the three forward GEMMs in one launch, 13 launches in all; bit for
     bit selfsim_fwd_bwd, moment_fwd_bwd, remd_cos_fwd_bwd_after_selfsim, palette_remd_fwd_bwd in this order."""
     l = _hip.lib()
     ld = int(pred.shape[1])
     nb = l.strotss_step_losses_workspace_bytes(ns, n, ld)
-    ws = workspaces.get("step_losses", nb, pred.device)
+    buf = (ws or workspaces).get("step_losses", nb, pred.device)
     check(l.strotss_step_losses_fwd_bwd(ptr(pred), ptr(content), n, d, ld, ptr(style), ptr(rs), ptr(style_panels), ns,
                                         ptr(style_mean), ptr(style_cov), float(g_content), float(g_moment), float(g_remd),
                                         float(g_palette), ptr(gpred), ptr(loss_content), ptr(loss_moment), ptr(loss_remd),
-                                        ptr(loss_palette), ptr(ws), nb, stream_ptr()), "step_losses_fwd_bwd")
+                                        ptr(loss_palette), ptr(buf), nb, stream_ptr()), "step_losses_fwd_bwd")
 
 
 def make_style_set(targets, weights) -> "_hip.StyleSetT":
@@ -1284,7 +1281,7 @@ def make_style_set(targets, weights) -> "_hip.StyleSetT":
 
 
 def step_losses_blend_fwd_bwd(pred, content, n, d, style_set, g_content, g_moment, g_remd, g_palette, gpred, loss_content,
-                              loss_moment, loss_remd, loss_palette):
+                              loss_moment, loss_remd, loss_palette, ws=None):
     """The four loss terms against a weighted style set (make_style_set) in ONE call (strotss_step_losses_blend_fwd_bwd):
     the launch count of step_losses_fwd_bwd whatever the number of styles.  loss_moment / loss_remd / loss_palette receive
     one UNWEIGHTED value per style; gpred += g_content dLc + sum_k w_k (g_moment dLm_k + g_remd dLr_k + g_palette dLp_k)."""
@@ -1293,15 +1290,15 @@ def step_losses_blend_fwd_bwd(pred, content, n, d, style_set, g_content, g_momen
     nb = l.strotss_step_losses_blend_workspace_bytes(C.byref(style_set), n, ld)
     if nb == 0:
         raise _hip.StrotssHipError("step_losses_blend: invalid style set")
-    ws = workspaces.get("step_losses_blend", nb, pred.device)
+    buf = (ws or workspaces).get("step_losses_blend", nb, pred.device)
     check(l.strotss_step_losses_blend_fwd_bwd(ptr(pred), ptr(content), n, d, ld, C.byref(style_set), float(g_content),
                                               float(g_moment), float(g_remd), float(g_palette), ptr(gpred), ptr(loss_content),
-                                              ptr(loss_moment), ptr(loss_remd), ptr(loss_palette), ptr(ws), nb, stream_ptr()),
+                                              ptr(loss_moment), ptr(loss_remd), ptr(loss_palette), ptr(buf), nb, stream_ptr()),
           "step_losses_blend_fwd_bwd")
 
 
 def step_losses_cw_fwd_bwd(pred, content, n, d, col_weight, style_set, g_content, g_moment, g_remd, g_palette, gpred,
-                           loss_content, loss_moment, loss_remd, loss_palette):
+                           loss_content, loss_moment, loss_remd, loss_palette, ws=None):
     """step_losses_blend_fwd_bwd (any number of styles, one included) with the content term weighted per sampled column
     (strotss_step_losses_cw_fwd_bwd; col_weight: float32 device vector of >= n values, finite and >= 0, or None: the
     unweighted term).  One style: the single-style launches (of weight 1: bit for bit step_losses_fwd_bwd); several: the
@@ -1314,56 +1311,57 @@ def step_losses_cw_fwd_bwd(pred, content, n, d, col_weight, style_set, g_content
     nb = l.strotss_step_losses_blend_workspace_bytes(C.byref(style_set), n, ld)
     if nb == 0:
         raise _hip.StrotssHipError("step_losses_cw: invalid style set")
-    ws = workspaces.get("step_losses_blend", nb, pred.device)
+    buf = (ws or workspaces).get("step_losses_blend", nb, pred.device)
     check(l.strotss_step_losses_cw_fwd_bwd(ptr(pred), ptr(content), n, d, ld, ptr(col_weight), C.byref(style_set),
                                            float(g_content), float(g_moment), float(g_remd), float(g_palette), ptr(gpred),
-                                           ptr(loss_content), ptr(loss_moment), ptr(loss_remd), ptr(loss_palette), ptr(ws), nb,
+                                           ptr(loss_content), ptr(loss_moment), ptr(loss_remd), ptr(loss_palette), ptr(buf), nb,
                                            stream_ptr()), "step_losses_cw_fwd_bwd")
 
 
-def sinkhorn_cos_fwd_bwd(style, rs, ns, pred, n, d, l, n_iter, gscale, gpred, loss_out):
+def sinkhorn_cos_fwd_bwd(style, rs, ns, pred, n, d, l, n_iter, gscale, gpred, loss_out, ws=None):
     lib = _hip.lib()
     nb = lib.strotss_sinkhorn_workspace_bytes(ns, n, n_iter)
-    ws = workspaces.get("sinkhorn", nb, pred.device)
+    buf = (ws or workspaces).get("sinkhorn", nb, pred.device)
     check(lib.strotss_sinkhorn_cos_fwd_bwd(ptr(style), ptr(rs), ns, ptr(pred), n, d, pred.shape[1], float(l), int(n_iter),
-                                           gscale, ptr(gpred), ptr(loss_out), ptr(ws), nb, stream_ptr()),
+                                           gscale, ptr(gpred), ptr(loss_out), ptr(buf), nb, stream_ptr()),
           "sinkhorn_cos_fwd_bwd")
 
 
-def sinkhorn_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, l, n_iter, gscale, gpred, loss_out):
+def sinkhorn_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, l, n_iter, gscale, gpred, loss_out, ws=None):
     """The step's Sinkhorn term (strotss_sinkhorn_cos_fwd_bwd_panels) for the prediction rows that
     selfsim_fwd_bwd has just processed: their reciprocal norms and x3 panels come from that call's workspace, the style rows'
     panels from `style_panels` (_pred_panels_after_selfsim: both panels or neither).  Unlike the relaxed EMD there is no plain
     call to fall back to: rows other than those the content loss left its record for are an error."""
     l_ = _hip.lib()
     ld = pred.shape[1]
-    rp, xp, sp = _pred_panels_or_raise("sinkhorn_cos_fwd_bwd_after_selfsim", pred, n, style_panels)
+    rp, xp, sp = _pred_panels_or_raise("sinkhorn_cos_fwd_bwd_after_selfsim", pred, n, style_panels, ws)
     nbs = l_.strotss_sinkhorn_step_workspace_bytes(ns, n, int(n_iter))
-    wss = workspaces.get("sinkhorn_step", nbs, pred.device)
+    wss = (ws or workspaces).get("sinkhorn_step", nbs, pred.device)
     check(l_.strotss_sinkhorn_cos_fwd_bwd_panels(ptr(style), ptr(rs), sp, ns, ptr(pred), rp, xp, n, d, ld, float(l),
                                                  int(n_iter), float(gscale), ptr(gpred), ptr(loss_out), ptr(wss), nbs,
                                                  stream_ptr()),
           "sinkhorn_cos_fwd_bwd_panels")
 
 
-def sinkhorn_log_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, l, n_iter, gscale, gpred, loss_out):
+def sinkhorn_log_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, l, n_iter, gscale, gpred, loss_out, ws=None):
     """The step's Sinkhorn term in the log domain (strotss_sinkhorn_log_cos_fwd_bwd_panels), called as
     sinkhorn_cos_fwd_bwd_after_selfsim is: the prediction rows' norms and x3 panels from the content loss's workspace, both
     panels or neither, and rows other than those the content loss left its record for an error."""
     l_ = _hip.lib()
     ld = pred.shape[1]
-    rp, xp, sp = _pred_panels_or_raise("sinkhorn_log_cos_fwd_bwd_after_selfsim", pred, n, style_panels)
+    rp, xp, sp = _pred_panels_or_raise("sinkhorn_log_cos_fwd_bwd_after_selfsim", pred, n, style_panels, ws)
     nbs = l_.strotss_sinkhorn_log_step_workspace_bytes(ns, n, int(n_iter))
     if nbs == 0:
         raise _hip.StrotssHipError(f"sinkhorn_log_cos_fwd_bwd_after_selfsim: invalid sizes ns={ns} n={n} n_iter={n_iter}")
-    wss = workspaces.get("sinkhorn_log_step", nbs, pred.device)
+    wss = (ws or workspaces).get("sinkhorn_log_step", nbs, pred.device)
     check(l_.strotss_sinkhorn_log_cos_fwd_bwd_panels(ptr(style), ptr(rs), sp, ns, ptr(pred), rp, xp, n, d, ld, float(l),
                                                      int(n_iter), float(gscale), ptr(gpred), ptr(loss_out), ptr(wss), nbs,
                                                      stream_ptr()),
           "sinkhorn_log_cos_fwd_bwd_panels")
 
 
-def sliced_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, n_proj, seed, counter, gscale, gpred, loss_out):
+def sliced_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, n_proj, seed, counter, gscale, gpred, loss_out,
+                                     ws=None):
     """The step's sliced Wasserstein term (strotss_sliced_cos_fwd_bwd) for the prediction rows that
     selfsim_fwd_bwd has just processed: their reciprocal norms and x3 panels come from that call's workspace, the style rows'
     panels from `style_panels` (_pred_panels_after_selfsim: both panels or neither).  `counter`: one int32 on the device, the
@@ -1372,9 +1370,9 @@ def sliced_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, n_
     l_ = _hip.lib()
     ld = pred.shape[1]
     assert counter.dtype == torch.int32 and counter.numel() >= 1 and counter.is_cuda
-    rp, xp, sp = _pred_panels_or_raise("sliced_cos_fwd_bwd_after_selfsim", pred, n, style_panels)
+    rp, xp, sp = _pred_panels_or_raise("sliced_cos_fwd_bwd_after_selfsim", pred, n, style_panels, ws)
     nbs = l_.strotss_sliced_workspace_bytes(ns, n, ld, int(n_proj))
-    wss = workspaces.get("sliced_step", nbs, pred.device)
+    wss = (ws or workspaces).get("sliced_step", nbs, pred.device)
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     check(l_.strotss_sliced_cos_fwd_bwd(ptr(style), ptr(rs), sp, ns, ptr(pred), rp, xp, n, d, ld, int(n_proj),
                                         seed & 0xFFFFFFFF, seed >> 32, ptr(counter), float(gscale), ptr(gpred), ptr(loss_out),
@@ -1382,48 +1380,48 @@ def sliced_cos_fwd_bwd_after_selfsim(style, rs, style_panels, ns, pred, n, d, n_
           "sliced_cos_fwd_bwd")
 
 
-def sinkhorn_metric_fwd_bwd(style, ns, pred, n, d, metric: str, l, n_iter, gscale, gpred, loss_out):
+def sinkhorn_metric_fwd_bwd(style, ns, pred, n, d, metric: str, l, n_iter, gscale, gpred, loss_out, ws=None):
     lib = _hip.lib()
     nb = lib.strotss_sinkhorn_metric_workspace_bytes(ns, n, n_iter)
-    ws = workspaces.get("sinkhorn", nb, pred.device)
+    buf = (ws or workspaces).get("sinkhorn", nb, pred.device)
     check(lib.strotss_sinkhorn_metric_fwd_bwd(ptr(style), ns, ptr(pred), n, d, pred.shape[1], REMD_METRICS[metric], float(l),
-                                              int(n_iter), gscale, ptr(gpred), ptr(loss_out), ptr(ws), nb, stream_ptr()),
+                                              int(n_iter), gscale, ptr(gpred), ptr(loss_out), ptr(buf), nb, stream_ptr()),
           "sinkhorn_metric_fwd_bwd")
 
 
-def palette_remd_fwd_bwd(style, ns, pred, n, gscale, gpred, loss_out, rgb_to_yuv=True, swapped=False):
+def palette_remd_fwd_bwd(style, ns, pred, n, gscale, gpred, loss_out, rgb_to_yuv=True, swapped=False, ws=None):
     l = _hip.lib()
     nb = l.strotss_remd_workspace_bytes(ns, n, 0)
-    ws = workspaces.get("remd", nb, pred.device)
+    buf = (ws or workspaces).get("remd", nb, pred.device)
     assert style.shape[1] == pred.shape[1]
     check(l.strotss_palette_remd_fwd_bwd(ptr(style), ns, ptr(pred), n, pred.shape[1], int(rgb_to_yuv), gscale,
-                                         ptr(gpred), ptr(loss_out), int(swapped), ptr(ws), nb, stream_ptr()), "palette_remd_fwd_bwd")
+                                         ptr(gpred), ptr(loss_out), int(swapped), ptr(buf), nb, stream_ptr()), "palette_remd_fwd_bwd")
 
 
-def palette_sliced_fwd_bwd(style, ns, pred, n, dirs, gscale, gpred, loss_out, rgb_to_yuv=True):
+def palette_sliced_fwd_bwd(style, ns, pred, n, dirs, gscale, gpred, loss_out, rgb_to_yuv=True, ws=None):
     """The sliced palette term (strotss_palette_sliced_fwd_bwd) where palette_remd_fwd_bwd stands:
     dirs an (n_proj, 3) float32 device tensor of unit directions (rand.palette_directions)"""
     l = _hip.lib()
     assert style.shape[1] == pred.shape[1] and dirs.dtype == torch.float32 and dirs.is_contiguous() and dirs.shape[1] == 3
     n_proj = int(dirs.shape[0])
     nb = l.strotss_palette_sliced_workspace_bytes(ns, n, n_proj)
-    ws = workspaces.get("palette_sliced", nb, pred.device)
+    buf = (ws or workspaces).get("palette_sliced", nb, pred.device)
     check(l.strotss_palette_sliced_fwd_bwd(ptr(style), ns, ptr(pred), n, pred.shape[1], int(rgb_to_yuv), ptr(dirs), n_proj,
-                                           gscale, ptr(gpred), ptr(loss_out), ptr(ws), nb, stream_ptr()),
+                                           gscale, ptr(gpred), ptr(loss_out), ptr(buf), nb, stream_ptr()),
           "palette_sliced_fwd_bwd")
 
 
 REMD_METRICS = {"l2": 1, "both": 2}      # STROTSS_METRIC_L2 / STROTSS_METRIC_BOTH (include/strotss_hip.h)
 
 
-def remd_metric_fwd_bwd(style, ns, pred, n, d, metric: str, gscale, gpred, loss_out, swapped=False):
+def remd_metric_fwd_bwd(style, ns, pred, n, d, metric: str, gscale, gpred, loss_out, swapped=False, ws=None):
     """relaxed_emd with dist_metrics 'l2' / 'both' at any width (reference losses.py:18-28, 69-80)."""
     l = _hip.lib()
     nb = l.strotss_remd_metric_workspace_bytes(ns, n)
-    ws = workspaces.get("remd_metric", nb, pred.device)
+    buf = (ws or workspaces).get("remd_metric", nb, pred.device)
     assert style.shape[1] == pred.shape[1]
     check(l.strotss_remd_metric_fwd_bwd(ptr(style), ns, ptr(pred), n, d, pred.shape[1], REMD_METRICS[metric], gscale,
-                                        ptr(gpred), ptr(loss_out), int(swapped), ptr(ws), nb, stream_ptr()), "remd_metric_fwd_bwd")
+                                        ptr(gpred), ptr(loss_out), int(swapped), ptr(buf), nb, stream_ptr()), "remd_metric_fwd_bwd")
 
 
 def rows_gemm_bwd(W, k, B, x, r, q, n, g, dx):
@@ -1438,25 +1436,25 @@ def rows_gemm_bwd(W, k, B, x, r, q, n, g, dx):
                                            float(g), ptr(dx), stream_ptr()), "rows_gemm_bwd")
 
 
-def moment_stats(x, n, d):
+def moment_stats(x, n, d, ws=None):
     l = _hip.lib()
     ld = x.shape[1]
     nb = l.strotss_moment_workspace_bytes(n, ld)
-    ws = workspaces.get("moment", nb, x.device)
+    buf = (ws or workspaces).get("moment", nb, x.device)
     mean = torch.empty(ld, dtype=torch.float32, device=x.device)
     cov = torch.empty((ld, ld), dtype=torch.float32, device=x.device)
-    check(l.strotss_moment_stats(ptr(x), n, d, ld, ptr(mean), ptr(cov), ptr(ws), nb, stream_ptr()),
+    check(l.strotss_moment_stats(ptr(x), n, d, ld, ptr(mean), ptr(cov), ptr(buf), nb, stream_ptr()),
           "moment_stats")
     return mean, cov
 
 
-def moment_fwd_bwd(style_mean, style_cov, pred, n, d, gscale, gpred, loss_out):
+def moment_fwd_bwd(style_mean, style_cov, pred, n, d, gscale, gpred, loss_out, ws=None):
     l = _hip.lib()
     ld = pred.shape[1]
     nb = l.strotss_moment_workspace_bytes(n, ld)
-    ws = workspaces.get("moment", nb, pred.device)
+    buf = (ws or workspaces).get("moment", nb, pred.device)
     check(l.strotss_moment_fwd_bwd(ptr(style_mean), ptr(style_cov), ptr(pred), n, d, ld, gscale, ptr(gpred),
-                                   ptr(loss_out), ptr(ws), nb, stream_ptr()), "moment_fwd_bwd")
+                                   ptr(loss_out), ptr(buf), nb, stream_ptr()), "moment_fwd_bwd")
 
 
 # ------------------------------------------------------------------ optimiser / output

@@ -159,7 +159,8 @@ def extract_features(params: VGGParams, image: torch.Tensor) -> List[torch.Tenso
 
 class _Capture:
     """`torch.cuda.graph(g)` without its gc.collect() + torch.cuda.empty_cache() (12 ms per capture, five captures per run:
-    the step allocates nothing, so there is no allocator state to tidy up before a capture).  The cyclic collector is held
+    the step allocates nothing -- the warm-up has sized the engine's workspaces, which are frozen by now -- so there is no
+    allocator state to tidy up before a capture).  The cyclic collector is held
     off while the stream captures: an earlier scale's engine is cyclic garbage (its stage lists hold bound methods), and a
     collection that lands inside the capture would run the destructors of its graphs and buffers -- runtime calls that a
     capturing stream does not allow -- at a moment that only the allocation count decides."""
@@ -256,6 +257,9 @@ class StepEngine:
                  palette_projections: int = DEFAULT_PALETTE_PROJECTIONS, detail: Optional[DetailTarget] = None,
                  tv_weight: float = 0.0):
         dev = stylized.device
+        # the scratch memory of the losses and the trunk: the engine's own, so what its captured graphs point into lives and
+        # dies with it and no other caller can regrow it (capture_graph freezes it)
+        self._ws = _ops.Workspaces()
         check_palette_transport(palette_transport, palette_projections)
         check_style_transport(style_transport, sinkhorn_l, sinkhorn_iters, sliced_projections, sinkhorn_log)
         for chosen, what in ((palette_transport == "sliced", "the sliced palette term"),
@@ -364,7 +368,7 @@ class StepEngine:
             assert strips.h == h, "image strips: plan made for this scale"
         # halo-exchange strips: the trunk refreshes its window's outermost rows from the neighbours after every layer
         self._halo = parallel.HaloExchange(strips, dist_group) if (strips is not None and strips.halo) else None
-        self.trunk = VGGTrunk(params, win1 - win0, w, with_grad=True, halo=self._halo)
+        self.trunk = VGGTrunk(params, win1 - win0, w, with_grad=True, halo=self._halo, ws=self._ws)
         # region sharding (masked runs): pixel gradient + the regions' scalars in ONE buffer = one all-reduce
         self.group = dist_group
         self.rank, self.world = parallel.world_info(dist_group) if dist_group is not None else (0, 1)
@@ -514,25 +518,29 @@ class StepEngine:
         """The style term and the palette term of the separate entries, chosen once from the engine's transports: each is
         f(style target, pf, n, gscale, gp, out).  The relaxed EMD borrows the prediction rows' norms and x3 panels from the
         content loss's workspace (the moment term has its own) and the style rows' panels from the StyleTarget; so do the
-        Sinkhorn and the sliced term."""
+        Sinkhorn and the sliced term.  Every term draws its scratch from the engine's workspaces, whose record of the content
+        loss is therefore the engine's own."""
+        ws = self._ws
         if self.style_transport == "sinkhorn":
             entry = _ops.sinkhorn_log_cos_fwd_bwd_after_selfsim if self.sinkhorn_log else _ops.sinkhorn_cos_fwd_bwd_after_selfsim
 
             def style_term(st, pf, n, g, gp, out):
-                entry(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, self.sinkhorn_l, self.sinkhorn_iters, g, gp, out)
+                entry(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, self.sinkhorn_l, self.sinkhorn_iters, g, gp, out,
+                      ws=ws)
         elif self.style_transport == "sliced":
             def style_term(st, pf, n, g, gp, out):
                 _ops.sliced_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d,
-                                                      self.sliced_projections, self.sliced_seed, self._sliced_counter, g, gp, out)
+                                                      self.sliced_projections, self.sliced_seed, self._sliced_counter, g, gp, out,
+                                                      ws=ws)
         else:
             def style_term(st, pf, n, g, gp, out):
-                _ops.remd_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, g, gp, out)
+                _ops.remd_cos_fwd_bwd_after_selfsim(st.feats, st.inv_norm, st.panels, st.ns, pf, n, self.d, g, gp, out, ws=ws)
         if self.palette_transport == "sliced":
             def palette_term(st, pf, n, g, gp, out):
-                _ops.palette_sliced_fwd_bwd(st.feats, st.ns, pf, n, self._palette_dirs, g, gp, out)
+                _ops.palette_sliced_fwd_bwd(st.feats, st.ns, pf, n, self._palette_dirs, g, gp, out, ws=ws)
         else:
             def palette_term(st, pf, n, g, gp, out):
-                _ops.palette_remd_fwd_bwd(st.feats, st.ns, pf, n, g, gp, out)
+                _ops.palette_remd_fwd_bwd(st.feats, st.ns, pf, n, g, gp, out, ws=ws)
         return style_term, palette_term
 
     def _losses(self, r: int, n: int, zeroed: bool = False):
@@ -552,11 +560,11 @@ class StepEngine:
             # one call: 13 launches instead of 21, the three forward GEMMs in one of them (bit for bit the separate entries
             # below for one style); a blend in as many launches
             _ops.step_losses_cw_fwd_bwd(pf, cf, n, self.d, cw, self._style_sets[r], self.alpha * base, base, base,
-                                        self.inv_alpha * base, gp, sc[0:], *outs)
+                                        self.inv_alpha * base, gp, sc[0:], *outs, ws=self._ws)
             return
-        _ops.selfsim_weighted_fwd_bwd(pf, cf, cw, n, self.d, self.alpha * base, gp, sc[0:])
+        _ops.selfsim_weighted_fwd_bwd(pf, cf, cw, n, self.d, self.alpha * base, gp, sc[0:], ws=self._ws)
         for k, (st, w) in enumerate(zip(targets, weights)):
-            _ops.moment_fwd_bwd(st.mean, st.cov, pf, n, self.d, base * w, gp, outs[0][k:])
+            _ops.moment_fwd_bwd(st.mean, st.cov, pf, n, self.d, base * w, gp, outs[0][k:], ws=self._ws)
             self._style_term(st, pf, n, base * w, gp, outs[1][k:])
             self._palette_term(st, pf, n, self.inv_alpha * base * w, gp, outs[2][k:])
 
@@ -824,6 +832,8 @@ class StepEngine:
         sets are copied into static buffers before each replay; a step whose index counts differ from the captured ones runs
         eagerly.  The captured step does not advance the optimisation: the variables / RMSprop slots (and the draw counters)
         are snapshotted around the warm-up and capture passes; the warm-up is one whole eager step, collectives included.
+        It sizes the engine's own workspaces (self._ws), which are then frozen: the graphs point into memory that belongs to
+        this engine, that no other caller can regrow and that a later eager step of the engine's may not reallocate either.
         Sharded regions (world > 1): TWO graphs, [fold .. pixel gradient] and [temporal + fold adjoint + RMSprop], the
         all-reduce launched between their replays.  Image strips (recompute margin; example_offsets = the block offsets of
         example_indices): THREE graphs, [fold .. gathers], [losses .. pixel gradient of the window], [fold adjoint + RMSprop],
@@ -849,7 +859,15 @@ class StepEngine:
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):              # warm-up on the side stream: workspaces, collectives, library state
+            if any(n < self.sample_size for n in self._graph_n):
+                # a later step with other index counts runs eagerly and may bring more samples than the captured one: the
+                # loss workspaces take the size of the largest set first (on whatever the rows hold; the warm-up overwrites it)
+                for r in self.my_regions:
+                    self._losses(r, self.sample_size)
             self._run(stages)
+        # the warm-up has sized the engine's workspaces.  What protects the graphs from here on is ownership plus this freeze:
+        # nobody else draws from self._ws, and a request of the engine's own that would reallocate a buffer raises
+        self._ws.freeze()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         graphs = []

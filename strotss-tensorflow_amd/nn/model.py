@@ -275,10 +275,11 @@ class VGGTrunk:
     gradient of that tap into `grads[layer_index]` (ReLU-masked); returns the pixel gradient buffer
     into which `scatter(-1)` has added the image-channel part."""
 
-    def __init__(self, params: VGGParams, h: int, w: int, with_grad: bool = True, halo=None):
+    def __init__(self, params: VGGParams, h: int, w: int, with_grad: bool = True, halo=None, ws=None):
         """halo: a parallel.HaloExchange when (h, w) is the window of a halo-exchange strip: after every layer, forward
-        and backward, the window's outermost rows are refreshed from the neighbouring ranks."""
-        self.p, self.halo, self.h, self.w = params, halo, h, w
+        and backward, the window's outermost rows are refreshed from the neighbouring ranks.  ws: the _ops.Workspaces the
+        convolutions take their scratch from (a StepEngine passes its own; None: the module-level one)."""
+        self.p, self.halo, self.h, self.w, self.ws = params, halo, h, w, ws
         dev = params.device
         self.acts: List[torch.Tensor] = []
         self.pools: List[torch.Tensor] = []
@@ -401,9 +402,10 @@ class VGGTrunk:
                                     relu_bits_out=self.relu_bits[li])
             elif s.fwd == 'winograd':
                 _ops.conv3x3_winograd_fwd(x, L["u_fwd"][self.wtile[li]], L["bias"], out=self.acts[li],
-                                          pool_out=pool_out, pool_code=pool_code, relu_bits_out=self.relu_bits[li])
+                                          pool_out=pool_out, pool_code=pool_code, relu_bits_out=self.relu_bits[li], ws=self.ws)
             else:
-                _ops.conv3x3_relu_fwd(x, L["w_fwd"], L["bias"], out=self.acts[li], pool_out=pool_out, pool_code=pool_code)
+                _ops.conv3x3_relu_fwd(x, L["w_fwd"], L["bias"], out=self.acts[li], pool_out=pool_out, pool_code=pool_code,
+                                      ws=self.ws)
             if self.halo is not None:     # (the pooling launch that may follow then reads right rows only)
                 self.halo.refresh(self.acts[li], self.layer_level[li])
         return [self.acts[i] for i in self.taps]
@@ -439,7 +441,7 @@ class VGGTrunk:
                 scatter(-1)
             elif s.dgrad == 'unpool':
                 _ops.conv3x3_dgrad_unpool(g, L["w_bwd"], L["cin"], self.pool_codes[src[1]], self.grads[s.dst],
-                                          accumulate=pre and s.tapped)
+                                          accumulate=pre and s.tapped, ws=self.ws)
             else:
                 in_layer = src[0] == 'conv'
                 out = self.grads[s.dst] if in_layer else self.gpools[s.dst]
@@ -447,9 +449,10 @@ class VGGTrunk:
                 if s.dgrad == 'winograd':
                     _ops.conv3x3_winograd_dgrad(g, L["u_bwd"][self.wtile[li]], L["cin"], act_in=act_in, out=out,
                                                 relu_bits=None if s.mask is None else self.relu_bits[s.mask],
-                                                accumulate=pre and s.tapped)
+                                                accumulate=pre and s.tapped, ws=self.ws)
                 else:
-                    _ops.conv3x3_dgrad(g, L["w_bwd"], L["cin"], act_in=act_in, out=out, accumulate=pre and s.tapped)
+                    _ops.conv3x3_dgrad(g, L["w_bwd"], L["cin"], act_in=act_in, out=out, accumulate=pre and s.tapped,
+                                       ws=self.ws)
                 if s.tapped:
                     scatter(s.dst)
                 if self.halo is not None:

@@ -10,7 +10,8 @@ launch sequence is the yardstick) and say so in the commit:
     python tests/golden/make_trunk_trace.py 64x64 grad_all STROTSS_WINOGRAD=0      # prints one cell in full
 
 A record is `wrapper(arg=value, ...)` with every argument bound (`inspect.signature(...).bind(...).apply_defaults()`, so an
-omitted `relu_bits` and `relu_bits=None` are one record) and each tensor replaced by the trunk buffer it is (`acts[3]`,
+omitted `relu_bits` and `relu_bits=None` are one record; `ws=None`, the module-level workspaces that the trunk traced here
+draws from, is left out, another instance would show) and each tensor replaced by the trunk buffer it is (`acts[3]`,
 `grads[1]`, `gpools[0]`, `pool_codes[2]`, `relu_bits[4]`, `gimg`, `img`; a weight by kind, layer, tile and shape).
 `halo.refresh(...)`, `scatter(li)` and `scatter_all()` are records of their own, in sequence, and so is the first time the trunk
 takes a tile size out of a layer's `u_fwd` / `u_bwd` entry (`winograd_weights(u_fwd[5], tile_m=4)`: that is when the entry
@@ -123,7 +124,8 @@ class Tracer:
         def rec(*a, **k):
             b = self.sigs[name].bind(*a, **k)
             b.apply_defaults()
-            self.records.append("%s(%s)" % (name, ", ".join("%s=%s" % (n, self.show(v)) for n, v in b.arguments.items())))
+            self.records.append("%s(%s)" % (name, ", ".join("%s=%s" % (n, self.show(v)) for n, v in b.arguments.items()
+                                                             if not (n == "ws" and v is None))))
             return b.arguments.get("out", b.arguments.get("out_full", b.arguments.get("gimg")))
         return rec
 

@@ -157,8 +157,15 @@ def test_entry_refuses_bad_arguments_before_any_launch():
     from nn._ops import ptr
     lib = _hip.lib()
     h, w, H, W = 8, 8, 16, 24
-    img, lo, hi = torch.rand(h, w, 3, device=DEV), torch.rand(h, w, 3, device=DEV), torch.rand(H, W, 3, device=DEV)
-    out = torch.full((H, W, 3), 7.0, device=DEV)
+
+    def roomy(t):
+        """t with 16 spare bytes behind it: the misaligned pointers below (4 bytes on) then span their own allocation only,
+        wherever the allocator puts the others -- a span reaching into a neighbour is refused as an overlap, not as misaligned"""
+        flat = torch.empty(t.numel() + 4, dtype=t.dtype, device=DEV)
+        flat[:t.numel()] = t.flatten()
+        return flat[:t.numel()].view(t.shape)
+    img, lo, hi = roomy(torch.rand(h, w, 3, device=DEV)), roomy(torch.rand(h, w, 3, device=DEV)), roomy(torch.rand(H, W, 3, device=DEV))
+    out = roomy(torch.full((H, W, 3), 7.0, device=DEV))
     nbytes = int(lib.strotss_guided_upsample_workspace_bytes(h, w, 4))
     assert nbytes == 280 * h * w
     work = torch.full((nbytes + 16,), 5, dtype=torch.uint8, device=DEV)
