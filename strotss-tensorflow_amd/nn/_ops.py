@@ -274,11 +274,12 @@ def flow_params(**overrides) -> "_hip.FlowParamsT":
 
 
 def optical_flow(frame_a: torch.Tensor, frame_b: torch.Tensor, params: Optional["_hip.FlowParamsT"] = None,
-                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 out: Optional[torch.Tensor] = None, ws: Optional["Workspaces"] = None) -> torch.Tensor:
     """the dense optical flow (h, w, 2) = (u, v) with frame_a(p) ~ frame_b(p + flow(p)) (strotss_optical_flow, DESIGN.md
     section 14): frames (h, w, 3) or (1, h, w, 3) RGB in [0, 1]; params from flow_params(), None = the defaults.  The
     backward flow of frame t for strotss_flow_warp is optical_flow(frame_t, frame_{t-j}), the forward one
-    optical_flow(frame_{t-j}, frame_t)."""
+    optical_flow(frame_{t-j}, frame_t).  The workspace is a buffer of this call's own, or grow-only scratch of `ws` when one
+    is given."""
     require(frame_a, "frame a")
     require(frame_b, "frame b")
     h, w, c = hwc(frame_a)
@@ -294,7 +295,8 @@ def optical_flow(frame_a: torch.Tensor, frame_b: torch.Tensor, params: Optional[
         out = torch.empty((h, w, 2), dtype=torch.float32, device=frame_a.device)
     require(out, "flow")
     assert out.numel() == 2 * h * w
-    workspace = torch.empty(nb, dtype=torch.uint8, device=frame_a.device)
+    workspace = (torch.empty(nb, dtype=torch.uint8, device=frame_a.device) if ws is None
+                 else ws.get("optical_flow", nb, frame_a.device))
     check(lib.strotss_optical_flow(ptr(frame_a), ptr(frame_b), h, w, pp, ptr(out), ptr(workspace), nb, stream_ptr()),
           "optical_flow")
     return out
@@ -318,7 +320,8 @@ def _weight_plane(weight: Optional[torch.Tensor], h: int, w: int, name: str) -> 
     return weight
 
 
-def color_stats(img: torch.Tensor, weight: Optional[torch.Tensor] = None, ws: Optional["Workspaces"] = None) -> torch.Tensor:
+def color_stats(img: torch.Tensor, weight: Optional[torch.Tensor] = None, ws: Optional["Workspaces"] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """the ten float64 sums (W, S_0, S_1, S_2, S_00, S_01, S_02, S_11, S_12, S_22) of an (h, w, 3) image under an optional
     (h, w) weight plane, on the device (strotss_color_stats; one launch, the same bits on every run).  The workspace is
     one per device and size (Workspaces.zeroed)."""
@@ -329,7 +332,9 @@ def color_stats(img: torch.Tensor, weight: Optional[torch.Tensor] = None, ws: Op
     if nb == 0:
         raise _hip.StrotssHipError(f"color_stats: bad size {h} x {w}")
     workspace = (ws or workspaces).zeroed("color_stats", (h, w), nb, img.device)
-    out = torch.empty(10, dtype=torch.float64, device=img.device)
+    if out is None:
+        out = torch.empty(10, dtype=torch.float64, device=img.device)
+    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == 10
     check(lib.strotss_color_stats(ptr(img), ptr(weight), h, w, ptr(out), ptr(workspace), stream_ptr()), "color_stats")
     return out
 
@@ -517,7 +522,8 @@ def guided_upsample(img: torch.Tensor, guide_lo: torch.Tensor, guide_hi: torch.T
 
 
 # ------------------------------------------------------------------ detail map
-def detail_map(img: torch.Tensor, radius: Optional[int] = None, gain: float = 2.0, floor: float = 0.25, ws=None) -> torch.Tensor:
+def detail_map(img: torch.Tensor, radius: Optional[int] = None, gain: float = 2.0, floor: float = 0.25, ws=None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """the (h, w) float32 detail map of an (h, w, 3) image in [floor, 1]: the root of the windowed mean gradient energy of
     its luma over gain times that root's image mean, clamped at 1 (strotss_detail_map; three launches on the current stream,
     the same bits on every run).  radius None: max(1, longer side // 64), at most 64.  The workspace (8 bytes per pixel) is
@@ -531,7 +537,10 @@ def detail_map(img: torch.Tensor, radius: Optional[int] = None, gain: float = 2.
     if nb == 0:
         raise _hip.StrotssHipError(f"detail_map: bad size {h} x {w}")
     workspace = (ws or workspaces).zeroed("detail_map", (h, w), nb, img.device)
-    out = torch.empty((h, w), dtype=torch.float32, device=img.device)
+    if out is None:
+        out = torch.empty((h, w), dtype=torch.float32, device=img.device)
+    require(out, "detail map")
+    assert out.dtype == torch.float32 and out.numel() == h * w
     check(lib.strotss_detail_map(ptr(img), h, w, int(radius), float(gain), float(floor), ptr(out), ptr(workspace),
                                  stream_ptr()), "detail_map")
     return out
@@ -1093,12 +1102,13 @@ def kmeans_scores(x: torch.Tensor, inv_norm: torch.Tensor, n: int, d: int, centr
 
 
 def scribble_labels(img: torch.Tensor, stroke: torch.Tensor, scores: torch.Tensor, tau: float, lam: float, sigma: float,
-                    iters: int, iters_per_launch: int = 0, planes: bool = False, ws: Optional["Workspaces"] = None):
+                    iters: int, iters_per_launch: int = 0, planes: bool = False, ws: Optional["Workspaces"] = None,
+                    out=None):
     """strotss_scribble_labels: the strokes of an (h, w, 3) image -- stroke (h, w) int32, a label 0..k-1 or anything else --
     spread over the image by `iters` Jacobi sweeps of a screened random walker whose unary is the softmax at temperature tau of
     the bilinearly sampled (gh, gw, k) score grid.  -> (label (h, w) int32, count (k,) int32, x): x the (k, h, w) float32
     planes after the last sweep with planes=True, else None.  iters_per_launch: 0 (the library's choice), 1, 2, 4 or 8; the
-    same bits for each.  The library refuses k outside 2..7, a tau, lambda or sigma <= 0 and iters outside 1..1024."""
+    same bits for each.  out: None, or (label, count, x) to write into (x None without planes).  The library refuses k outside 2..7, a tau, lambda or sigma <= 0 and iters outside 1..1024."""
     h, w = _rgb_image(img, "image")
     _int32_on_device(stroke, h * w, "the stroke labels")
     require(scores, "score grid")
@@ -1111,9 +1121,18 @@ def scribble_labels(img: torch.Tensor, stroke: torch.Tensor, scores: torch.Tenso
     if nb == 0:
         raise ValueError(f"scribble_labels: {k} regions on an image of {h} x {w} (expected 2..{_hip.SCRIBBLE_MAX_K} regions)")
     buf = (ws or workspaces).get("scribble", nb, img.device)
-    label = torch.empty((h, w), dtype=torch.int32, device=img.device)
-    count = torch.empty(k, dtype=torch.int32, device=img.device)
-    x = torch.empty((k, h, w), dtype=torch.float32, device=img.device) if planes else None
+    if out is None:
+        label = torch.empty((h, w), dtype=torch.int32, device=img.device)
+        count = torch.empty(k, dtype=torch.int32, device=img.device)
+        x = torch.empty((k, h, w), dtype=torch.float32, device=img.device) if planes else None
+    else:
+        label, count, x = out
+        _int32_on_device(label, h * w, "the labels")
+        _int32_on_device(count, k, "the region counts")
+        assert (x is not None) == bool(planes)
+        if planes:
+            require(x, "the planes")
+            assert x.numel() == k * h * w
     check(lib.strotss_scribble_labels(ptr(img), ptr(stroke), h, w, ptr(scores), gh, gw, k, float(tau), float(lam), float(sigma),
                                       int(iters), int(iters_per_launch), ptr(label), ptr(count), ptr(x), ptr(buf), nb,
                                       stream_ptr()), "scribble_labels")

@@ -262,6 +262,7 @@ DEFAULT_CASES = [
     ('F4_fused_f32', 'fwd', 1024, 1024, 64, 64),
     ('F4_gemm_f32', 'dgrad', 32, 32, 512, 512),
     ('F4_gemm_f32', 'dgrad', 43, 61, 256, 512),
+    ('F4_gemm_f32', 'dgrad', 41, 65, 256, 512),
     ('F4_gemm_f32', 'dgrad', 42, 64, 128, 256),
     ('F4_gemm_f32', 'dgrad', 42, 64, 256, 256),
     ('F4_gemm_f32', 'dgrad', 42, 64, 256, 512),
@@ -283,6 +284,7 @@ DEFAULT_CASES = [
     ('F4_gemm_f32', 'fwd', 32, 32, 256, 512),
     ('F4_gemm_f32', 'fwd', 32, 32, 512, 512),
     ('F4_gemm_f32', 'fwd', 43, 61, 256, 512),
+    ('F4_gemm_f32', 'fwd', 41, 65, 256, 512),
     ('F4_gemm_f32', 'fwd', 42, 64, 128, 256),
     ('F4_gemm_f32', 'fwd', 42, 64, 256, 256),
     ('F4_gemm_f32', 'fwd', 42, 64, 256, 512),
@@ -299,12 +301,14 @@ DEFAULT_CASES = [
     ('F4_gemm_f32', 'fwd', 128, 85, 128, 128),
     ('F4_x3_gemm_128', 'dgrad', 128, 128, 512, 512),
     ('F4_x3_gemm_128', 'dgrad', 170, 255, 256, 256),
+    ('F4_x3_gemm_128', 'dgrad', 169, 257, 256, 256),
     ('F4_x3_gemm_128', 'dgrad', 170, 256, 256, 256),
     ('F4_x3_gemm_128', 'dgrad', 256, 170, 256, 256),
     ('F4_x3_gemm_128', 'dgrad', 256, 256, 256, 256),
     ('F4_x3_gemm_128', 'fwd', 128, 128, 256, 512),
     ('F4_x3_gemm_128', 'fwd', 128, 128, 512, 512),
     ('F4_x3_gemm_128', 'fwd', 170, 255, 256, 256),
+    ('F4_x3_gemm_128', 'fwd', 169, 257, 256, 256),
     ('F4_x3_gemm_128', 'fwd', 170, 256, 128, 256),
     ('F4_x3_gemm_128', 'fwd', 170, 256, 256, 256),
     ('F4_x3_gemm_128', 'fwd', 256, 170, 128, 256),
@@ -313,11 +317,13 @@ DEFAULT_CASES = [
     ('F4_x3_gemm_128', 'fwd', 256, 256, 256, 256),
     ('F4_x3_gemm_64', 'dgrad', 61, 67, 512, 512),
     ('F4_x3_gemm_64', 'dgrad', 64, 64, 512, 512),
+    ('F4_x3_gemm_64', 'dgrad', 65, 65, 512, 512),
     ('F4_x3_gemm_64', 'dgrad', 85, 128, 512, 512),
     ('F4_x3_gemm_64', 'dgrad', 128, 85, 512, 512),
     ('F4_x3_gemm_64', 'fwd', 61, 67, 512, 512),
     ('F4_x3_gemm_64', 'fwd', 64, 64, 256, 512),
     ('F4_x3_gemm_64', 'fwd', 64, 64, 512, 512),
+    ('F4_x3_gemm_64', 'fwd', 65, 65, 512, 512),
     ('F4_x3_gemm_64', 'fwd', 85, 128, 256, 512),
     ('F4_x3_gemm_64', 'fwd', 85, 128, 512, 512),
     ('F4_x3_gemm_64', 'fwd', 128, 85, 256, 512),

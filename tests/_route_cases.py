@@ -54,6 +54,15 @@ DEFAULT_CASES = [c for f, d, h, w, ci, co in _SCALE_1024 for c in ((f, "fwd", h,
     ("F4_x3_gemm_128", "dgrad", 170, 255, 256, 256),
     ("F4_x3_gemm_64", "fwd", 61, 67, 512, 512),
     ("F4_x3_gemm_64", "dgrad", 61, 67, 512, 512),
+    # the three F(4x4,3x3) GEMM routes at an ODD tile count T = ceil(h/4) ceil(w/4) (2795, 289, 187): T % 8 != 0 for the x3
+    # input transform's 8-tile groups, T % 128 != 0 and T % 64 != 0 for the GEMMs' row tiles (61 x 65 has T = 272);
+    # none has fewer multiply-adds than its route's ragged case above, which stays the smallest of its (route, direction)
+    ("F4_x3_gemm_128", "fwd", 169, 257, 256, 256),
+    ("F4_x3_gemm_128", "dgrad", 169, 257, 256, 256),
+    ("F4_x3_gemm_64", "fwd", 65, 65, 512, 512),
+    ("F4_x3_gemm_64", "dgrad", 65, 65, 512, 512),
+    ("F4_gemm_f32", "fwd", 41, 65, 256, 512),
+    ("F4_gemm_f32", "dgrad", 41, 65, 256, 512),
 ]
 
 SWITCH_CASES = {
