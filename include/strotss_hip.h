@@ -711,7 +711,10 @@ int strotss_optical_flow(const float* frame_a, const float* frame_b, int h, int 
 /* Images are (h, w, 3) float32 RGB, a weight plane is (h, w) float32 >= 0 (NULL = all ones); every pointer 16-byte aligned.
  * The three entries refuse, before anything is launched: STROTSS_EINVAL for a null required pointer, h or w <= 0,
  * 3 h w > INT_MAX; STROTSS_EALIGN for a pointer that is not 16-byte aligned. */
-/* bytes of the workspace of strotss_color_stats (0 for h, w <= 0 or 3 h w > INT_MAX) */
+/* bytes of the workspace of strotss_color_stats (0 for h, w <= 0 or 3 h w > INT_MAX): a 16-byte ticket header and ten doubles
+ * per block of 1024 pixels, at most 2048 blocks (COLOR_MAX_BLOCKS of csrc/color.hip) -- from h w > 2^21 on the size stays at
+ * 16 + 163840 bytes and the blocks stride over the image; the layout holds for every size the entry accepts only because of
+ * that cap (tests/test_hip_launch_caps.py runs the strided form). */
 size_t strotss_color_stats_workspace_bytes(int h, int w);
 /* The colour statistics of an image, in ONE launch:  out[0] = W = sum_p m(p),  out[1..3] = S_i = sum_p m(p) x_i(p),
  * out[4..9] = S_ij = sum_p m(p) x_i(p) x_j(p) for (i, j) = (0,0) (0,1) (0,2) (1,1) (1,2) (2,2), m = weight (NULL: 1).
