@@ -705,6 +705,28 @@ size_t strotss_flow_workspace_bytes(int h, int w, const strotss_flow_params_t* p
 int strotss_optical_flow(const float* frame_a, const float* frame_b, int h, int w, const strotss_flow_params_t* params,
                          float* flow_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The patch-matching stage (tests/_flow_match_ref.py is the statement): what the coarse-to-fine flow
+ * misses, an object that moves against its background and that the coarse levels no longer see.  At one level, with grey
+ * planes a, b (h, w) and the level's flow (u, v): for each pixel p and each whole offset d = (dx, dy) in [-R, R]^2,
+ *   C(p, d) = sum over the 5 x 5 window q around p (indices clamped, row-major) of |a(q) - bilinear(b, q + F(p) + d)|,
+ * the flow of the CENTRE pixel for all 25 taps, the 4-neighbour edge-clamped rule, F(p) split once into whole part and
+ * fraction (|F| clamped to 1e6 first).  d* = the first minimiser in scan order (dy outer, dx inner, ascending);
+ * F'(p) = F(p) + d* if C(p, d*) < C(p, 0) strictly, else F(p) itself: d = 0 wins every tie.  Every float32 operation is
+ * rounded on its own.
+ * strotss_flow_match_stage: the stage alone, (u, v) -> (u_out, v_out), all planes (h, w) and distinct.  Refused before
+ * anything is launched, the outputs untouched: STROTSS_EINVAL for a null pointer, h or w < 1, h w > 2^28, match_radius
+ * outside 1 .. STROTSS_FLOW_MATCH_MAX_RADIUS, an output that is an input or the other output; STROTSS_EALIGN for a pointer
+ * that is not 16-byte aligned. */
+#define STROTSS_FLOW_MATCH_MAX_RADIUS 4
+int strotss_flow_match_stage(const float* a, const float* b, int h, int w, const float* u, const float* v, int match_radius,
+                             float* u_out, float* v_out, void* stream);
+/* strotss_optical_flow with the stage at every level, on the level's starting flow (the upsampled one; zeros at the
+ * coarsest) and before its warps, written to the other half of the (u, v) ping-pong: the workspace is that of
+ * strotss_flow_workspace_bytes.  match_radius = 0 IS strotss_optical_flow: the same launches, the same bits.  Refusals as
+ * there, and STROTSS_EINVAL for a match_radius outside 0 .. STROTSS_FLOW_MATCH_MAX_RADIUS. */
+int strotss_optical_flow_match(const float* frame_a, const float* frame_b, int h, int w, const strotss_flow_params_t* params,
+                               int match_radius, float* flow_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Colour preservation: keep the content's colours, after Gatys et al. (2016)
  * --------------------------------------------------------------------------------------- */

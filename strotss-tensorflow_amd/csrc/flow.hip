@@ -7,6 +7,7 @@
 //   - flow_jacobi_kernel: one Jacobi sweep per launch, one thread per pixel (the plain form);
 //   - flow_jacobi_blocked_kernel<K>: K sweeps per launch on a 64 x 32 tile + a halo of K pixels held in LDS;
 //   - flow_pack_kernel: (u, v) planes -> (h, w, 2).
+// strotss_optical_flow_match adds flow_match.hip's stage between a level's upsample and its warps.
 // Both solver forms call hs_update, so they agree bit for bit.
 #include <algorithm>
 #include <cmath>
@@ -306,7 +307,15 @@ size_t strotss_flow_workspace_bytes(int h, int w, const strotss_flow_params_t* p
 
 int strotss_optical_flow(const float* frame_a, const float* frame_b, int h, int w, const strotss_flow_params_t* params,
                          float* flow_out, void* workspace, size_t workspace_bytes, void* stream) {
+  return strotss_optical_flow_match(frame_a, frame_b, h, w, params, 0, flow_out, workspace, workspace_bytes, stream);
+}
+
+// The one body.  match_radius R > 0: the patch-matching stage (flow_match.hip) at every level, on the
+// level's starting flow and before its warps, into the other half of the (u, v) ping-pong; R = 0 issues no such launch.
+int strotss_optical_flow_match(const float* frame_a, const float* frame_b, int h, int w, const strotss_flow_params_t* params,
+                               int match_radius, float* flow_out, void* workspace, size_t workspace_bytes, void* stream) {
   ST_CHECK_ARG(frame_a && frame_b && flow_out && workspace, STROTSS_EINVAL);
+  ST_CHECK_ARG(match_radius >= 0 && match_radius <= STROTSS_FLOW_MATCH_MAX_RADIUS, STROTSS_EINVAL);
   ST_CHECK_ARG(h >= 2 && w >= 2 && (long long)h * w <= (1LL << 28), STROTSS_EINVAL);
   const strotss_flow_params_t p = flow_params_or_default(params, h, w);
   ST_CHECK_ARG(flow_params_ok(p), STROTSS_EINVAL);
@@ -334,6 +343,10 @@ int strotss_optical_flow(const float* frame_a, const float* frame_b, int h, int 
     } else {
       hipLaunchKernelGGL(flow_upsample_kernel, per_pixel(hk, wk), dim3(256), 0, st, f.u[cur], f.v[cur], l.h[k + 1],
                          l.w[k + 1], f.u[cur ^ 1], f.v[cur ^ 1], hk, wk);
+      cur ^= 1;
+    }
+    if (match_radius > 0) {
+      st_flow_match_launch(f.a[k], f.b[k], hk, wk, f.u[cur], f.v[cur], match_radius, f.u[cur ^ 1], f.v[cur ^ 1], st);
       cur ^= 1;
     }
     for (int wi = 0; wi < p.warps; ++wi) {

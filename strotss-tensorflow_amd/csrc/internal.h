@@ -67,6 +67,10 @@ bool st_gemm_x3_f32a_ok(int M, int N, int batch, long min_tiles128);
 int st_gemm_x3_batched_f32a(const float* A, const void* B, float* C, int ldc, long long strideC, int M, int N, int K,
                             int batch, hipStream_t s, long min_tiles128);
 
+// flow_match.hip: the patch-matching stage of one pyramid level, radius 1..4 (checked by the callers), one launch
+void st_flow_match_launch(const float* a, const float* b, int h, int w, const float* u, const float* v, int radius,
+                          float* uo, float* vo, hipStream_t st);
+
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 // Bump allocator over a caller-provided workspace (256-byte aligned slices).

@@ -201,6 +201,8 @@ SIGNATURES = {
     "strotss_flow_default_params": (None, [C.POINTER(FlowParamsT)]),
     "strotss_flow_workspace_bytes": (_Z, [_I, _I, C.POINTER(FlowParamsT)]),
     "strotss_optical_flow": (_I, [_P, _P, _I, _I, C.POINTER(FlowParamsT), _P, _P, _Z, _P]),
+    "strotss_optical_flow_match": (_I, [_P, _P, _I, _I, C.POINTER(FlowParamsT), _I, _P, _P, _Z, _P]),
+    "strotss_flow_match_stage": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P, _P]),
     "strotss_color_stats_workspace_bytes": (_Z, [_I, _I]),
     "strotss_color_stats": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "strotss_color_affine": (_I, [_P, _P, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _P]),

@@ -273,12 +273,16 @@ def flow_params(**overrides) -> "_hip.FlowParamsT":
     return p
 
 
+FLOW_MATCH_MAX_RADIUS = 4          # STROTSS_FLOW_MATCH_MAX_RADIUS
+
+
 def optical_flow(frame_a: torch.Tensor, frame_b: torch.Tensor, params: Optional["_hip.FlowParamsT"] = None,
-                 out: Optional[torch.Tensor] = None, ws: Optional["Workspaces"] = None) -> torch.Tensor:
+                 out: Optional[torch.Tensor] = None, ws: Optional["Workspaces"] = None, match_radius: int = 0) -> torch.Tensor:
     """the dense optical flow (h, w, 2) = (u, v) with frame_a(p) ~ frame_b(p + flow(p)) (strotss_optical_flow, DESIGN.md
     section 14): frames (h, w, 3) or (1, h, w, 3) RGB in [0, 1]; params from flow_params(), None = the defaults.  The
     backward flow of frame t for strotss_flow_warp is optical_flow(frame_t, frame_{t-j}), the forward one
-    optical_flow(frame_{t-j}, frame_t).  The workspace is a buffer of this call's own, or grow-only scratch of `ws` when one
+    optical_flow(frame_{t-j}, frame_t).  match_radius R in 1..4: with the patch-matching stage at every level
+    (strotss_optical_flow_match); 0: without, the same launches as ever.  The workspace is a buffer of this call's own, or grow-only scratch of `ws` when one
     is given."""
     require(frame_a, "frame a")
     require(frame_b, "frame b")
@@ -286,6 +290,9 @@ def optical_flow(frame_a: torch.Tensor, frame_b: torch.Tensor, params: Optional[
     if c != 3 or frame_a.numel() != 3 * h * w or tuple(frame_b.shape[-3:]) != (h, w, 3) or frame_b.numel() != 3 * h * w:
         raise ValueError(f"frames of shape {tuple(frame_a.shape)} and {tuple(frame_b.shape)}: expected two (h, w, 3) images "
                          f"of one size")
+    match_radius = int(match_radius)
+    if not 0 <= match_radius <= FLOW_MATCH_MAX_RADIUS:
+        raise ValueError(f"optical_flow: match_radius {match_radius}, expected 0 (no stage) .. {FLOW_MATCH_MAX_RADIUS}")
     lib = _hip.lib()
     pp = None if params is None else C.byref(params)
     nb = int(lib.strotss_flow_workspace_bytes(h, w, pp))
@@ -297,9 +304,28 @@ def optical_flow(frame_a: torch.Tensor, frame_b: torch.Tensor, params: Optional[
     assert out.numel() == 2 * h * w
     workspace = (torch.empty(nb, dtype=torch.uint8, device=frame_a.device) if ws is None
                  else ws.get("optical_flow", nb, frame_a.device))
-    check(lib.strotss_optical_flow(ptr(frame_a), ptr(frame_b), h, w, pp, ptr(out), ptr(workspace), nb, stream_ptr()),
-          "optical_flow")
+    check(lib.strotss_optical_flow_match(ptr(frame_a), ptr(frame_b), h, w, pp, match_radius, ptr(out), ptr(workspace), nb,
+                                         stream_ptr()), "optical_flow")
     return out
+
+
+def flow_match_stage(a: torch.Tensor, b: torch.Tensor, u: torch.Tensor, v: torch.Tensor,
+                     match_radius: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the patch-matching stage alone (strotss_flow_match_stage): grey planes a, b and the flow
+    planes u, v, all (h, w) float32 -> new (u, v), each pixel's flow moved by the whole offset in [-R, R]^2 whose 5 x 5
+    window matches best (d = 0 wins ties)"""
+    for t, name in ((a, "a"), (b, "b"), (u, "u"), (v, "v")):
+        require(t, name)
+        if t.dim() != 2 or tuple(t.shape) != tuple(a.shape):
+            raise ValueError(f"flow_match_stage: {name} of shape {tuple(t.shape)}, expected four (h, w) planes of one size")
+    match_radius = int(match_radius)
+    if not 1 <= match_radius <= FLOW_MATCH_MAX_RADIUS:
+        raise ValueError(f"flow_match_stage: match_radius {match_radius}, expected 1 .. {FLOW_MATCH_MAX_RADIUS}")
+    h, w = int(a.shape[0]), int(a.shape[1])
+    uo, vo = torch.empty_like(u), torch.empty_like(v)
+    check(_hip.lib().strotss_flow_match_stage(ptr(a), ptr(b), h, w, ptr(u), ptr(v), match_radius, ptr(uo), ptr(vo),
+                                              stream_ptr()), "flow_match_stage")
+    return uo, vo
 
 
 # ------------------------------------------------------------------ colour preservation (DESIGN.md section 15)

@@ -52,6 +52,9 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
                     results' size (strotss_optical_flow, coarse-to-fine Horn-Schunck), backward and
                     forward for every --temporal_frames offset; no reliable_*.pgm is involved.  --flow_dir stays the way to
                     bring better flow from elsewhere.
+  --flow_match [R]  with --compute_flow: a patch-matching stage in every computed flow: at each
+                    pyramid level every pixel may move its flow by a whole offset of up to R pixels (1..4, 2 when R is
+                    left out) if its 5 x 5 window matches better there -- for objects that move against their background
   --save_flow DIR   with --compute_flow: also write the computed flows to DIR as backward_{t}_{t-j}.flo and
                     forward_{t-j}_{t}.flo (a later run with --flow_dir DIR reads the same floats back)
   --preserve_color {match,luminance,transfer}
@@ -687,7 +690,7 @@ def _video_inputs(args):
     --temporal_frames offsets (_temporal_frames), --video with --strips or under torchrun with WORLD_SIZE > 1, neither
     --flow_dir nor --compute_flow, a content_path that is not a directory of frames, frames of different sizes, a missing
     backward flow of any frame and offset (--flow_dir only); --compute_flow without --video or together with --flow_dir,
-    --save_flow without --compute_flow."""
+    --save_flow without --compute_flow, --flow_match without --compute_flow or outside 1..4."""
     video = bool(getattr(args, "video", False))
     lam = getattr(args, "temporal_weight", None)
     flow_dir = getattr(args, "flow_dir", None)
@@ -703,6 +706,7 @@ def _video_inputs(args):
         raise ValueError("--save_flow needs --compute_flow (it writes the flows the run computes)")
     if compute_flow and flow_dir:
         raise ValueError("--compute_flow and --flow_dir exclude each other: the flows are computed or read, not both")
+    _flow_match_radius(args)
     if not video:
         return None
     offsets = _temporal_frames(args)
@@ -738,6 +742,22 @@ def _video_inputs(args):
     return frames, lam
 
 
+FLOW_MATCH_RADII = (1, 4)           # --flow_match: strotss_optical_flow_match's radii (0 = no stage is the flag's absence)
+
+
+def _flow_match_radius(args) -> int:
+    """--flow_match [R]: the patch-matching radius of every computed flow, 0 without the flag.
+    ValueError without --compute_flow (there is no flow to match) or outside 1..4."""
+    r = getattr(args, "flow_match", None)
+    if r is None:
+        return 0
+    if not getattr(args, "compute_flow", False):
+        raise ValueError("--flow_match needs --compute_flow (it is a stage of the flows the run computes)")
+    if isinstance(r, bool) or int(r) != r or not FLOW_MATCH_RADII[0] <= int(r) <= FLOW_MATCH_RADII[1]:
+        raise ValueError(f"--flow_match must be a whole radius in {FLOW_MATCH_RADII[0]}..{FLOW_MATCH_RADII[1]}, got {r}")
+    return int(r)
+
+
 def _frame_at_result_size(args, path: str) -> torch.Tensor:
     """a content frame (h, w, 3) on the device at the size of a frame's final result: resized as _stylise makes the content
     of its last executed scale"""
@@ -747,13 +767,14 @@ def _frame_at_result_size(args, path: str) -> torch.Tensor:
 
 def _computed_flows(args, t: int, j: int, frames, h: int, w: int):
     """--compute_flow: (backward, forward) flow of frame t against frame t-j, both (h, w, 2), by strotss_optical_flow on the
-    content frames at the results' size.  frames: {1-based position: (h, w, 3) frame on the device}.  --save_flow DIR
+    content frames at the results' size (with --flow_match R: strotss_optical_flow_match).  frames: {1-based position: (h, w, 3) frame on the device}.  --save_flow DIR
     writes them as backward_{t}_{t-j}.flo and forward_{t-j}_{t}.flo."""
     cur, old = frames[t], frames[t - j]
     if tuple(cur.shape) != (h, w, 3) or tuple(old.shape) != (h, w, 3):
         raise ValueError(f"--compute_flow: frames of {tuple(cur.shape)} and {tuple(old.shape)}, the results are {h} x {w}")
-    fb = strotss_engine._ops.optical_flow(cur, old)
-    ff = strotss_engine._ops.optical_flow(old, cur)
+    radius = _flow_match_radius(args)
+    fb = strotss_engine._ops.optical_flow(cur, old, match_radius=radius)
+    ff = strotss_engine._ops.optical_flow(old, cur, match_radius=radius)
     save = getattr(args, "save_flow", None)
     if save:
         os.makedirs(save, exist_ok=True)
@@ -1270,6 +1291,9 @@ _FLAGS = (
                                        "result along backward_{t}_{t-j}.flo where no nearer frame covers the pixel")),
     (("--compute_flow",), dict(action='store_true', help="with --video, instead of --flow_dir: compute the optical flows between "
                                                          "the frames on the GPU (both directions, every --temporal_frames offset)")),
+    (("--flow_match",), dict(type=int, nargs='?', const=2, default=None, metavar='R',
+                             help="with --compute_flow: patch-matching stage of radius R (1..4, default 2) at every level of "
+                                  "the computed flows (DESIGN.md section 31)")),
     (("--save_flow",), dict(type=str, default=None, metavar='DIR',
                             help="with --compute_flow: write the computed flows there as backward_{t}_{t-j}.flo and "
                                  "forward_{t-j}_{t}.flo")),
