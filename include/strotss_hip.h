@@ -727,6 +727,43 @@ int strotss_flow_match_stage(const float* a, const float* b, int h, int w, const
 int strotss_optical_flow_match(const float* frame_a, const float* frame_b, int h, int w, const strotss_flow_params_t* params,
                                int match_radius, float* flow_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The robust form (tests/_flow_robust_ref.py is the statement and fixes the evaluation order):
+ * Charbonnier penalties on the data term and on the flow's gradient, minimised with lagged weights, so that a motion
+ * boundary is not smoothed away.  The pyramid, the upsampling, the warp and Ix, Iy, c are strotss_optical_flow's; alpha2 and
+ * inv are not used.  Per warp, `outer` times:  1. weights from the current (u, v), indices clamped: r = Ix u + Iy v + c,
+ *   d = 1 / sqrt(r^2 + eps_d^2), s = 1 / sqrt(|grad u|^2 + |grad v|^2 + eps_s^2) with central differences, for the 8
+ *   neighbours q of p g_q = w_q (s_p + s_q) / 2 (w_q = 1/6 for N, S, W, E and 1/12 for the diagonals), G = sum g_q,
+ *   k = d / (alpha G + d (Ix^2 + Iy^2));  2. iters / outer sweeps with s, 1 / G and k frozen: ub = (sum g_q u_q) / G, vb
+ *   likewise, t = (Ix ub + Iy vb + c) k, u <- ub - Ix t, v <- vb - Iy t.  Every float32 operation is rounded on its own. */
+typedef struct { float alpha, eps_d, eps_s; int outer; } strotss_flow_robust_params_t;
+#define STROTSS_FLOW_ROBUST_MAX_OUTER 8
+/* the defaults: alpha 0.06, eps_d 1e-3, eps_s 1e-2, outer 4 */
+void strotss_flow_robust_default_params(strotss_flow_robust_params_t* out);
+/* bytes of the workspace of strotss_optical_flow_robust: that of strotss_flow_workspace_bytes and, behind it, the planes s
+ * (h, w) and {1 / G, k} (h, w, 2) at the full size; 0 on bad arguments (see below).  robust == NULL: exactly
+ * strotss_flow_workspace_bytes(h, w, params). */
+size_t strotss_flow_robust_workspace_bytes(int h, int w, const strotss_flow_params_t* params,
+                                           const strotss_flow_robust_params_t* robust);
+/* strotss_optical_flow_match with the robust solver: one weight-update launch and (iters / outer) / iters_per_launch sweep
+ * launches, `outer` times per warp; iters_per_launch = 1 is one weighted sweep per launch, 2, 4, 8 the LDS-blocked form (bit
+ * for bit the results of 1).  robust == NULL IS strotss_optical_flow_match: the same launches, the same bits, the workspace
+ * of strotss_flow_workspace_bytes.  Refusals as there (nothing is launched or written), and STROTSS_EINVAL for alpha, eps_d
+ * or eps_s not finite or <= 0 (or an eps whose square is 0 in float32), outer outside 1 .. STROTSS_FLOW_ROBUST_MAX_OUTER or
+ * not dividing iters, iters_per_launch not dividing iters / outer, workspace_bytes below
+ * strotss_flow_robust_workspace_bytes(h, w, params, robust). */
+int strotss_optical_flow_robust(const float* frame_a, const float* frame_b, int h, int w, const strotss_flow_params_t* params,
+                                const strotss_flow_robust_params_t* robust, int match_radius, float* flow_out,
+                                void* workspace, size_t workspace_bytes, void* stream);
+/* One weight update on its own, for tests: coef (h, w, 4) = {Ix, Iy, c, unused} and the flow planes u, v (h, w) -> s_out
+ * (h, w), gk_out (h, w, 2) = {1 / G, k} and, after `sweeps` sweeps in launches of iters_per_launch, u_out, v_out (h, w).
+ * tmp: 2 h w floats of scratch.  robust == NULL: the defaults; its `outer` is not used.  Refused before anything is
+ * launched, the outputs untouched: STROTSS_EINVAL for a null pointer, h or w < 2, h w > 2^28, the parameters as above,
+ * iters_per_launch not in {1, 2, 4, 8} or not dividing sweeps, sweeps outside 1..1024, an output that is an input or
+ * another output; STROTSS_EALIGN for a pointer that is not 16-byte aligned. */
+int strotss_flow_robust_stage(const float* coef, const float* u, const float* v, int h, int w,
+                              const strotss_flow_robust_params_t* robust, int sweeps, int iters_per_launch, float* u_out,
+                              float* v_out, float* s_out, float* gk_out, float* tmp, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Colour preservation: keep the content's colours, after Gatys et al. (2016)
  * --------------------------------------------------------------------------------------- */

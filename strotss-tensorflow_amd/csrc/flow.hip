@@ -7,7 +7,8 @@
 //   - flow_jacobi_kernel: one Jacobi sweep per launch, one thread per pixel (the plain form);
 //   - flow_jacobi_blocked_kernel<K>: K sweeps per launch on a 64 x 32 tile + a halo of K pixels held in LDS;
 //   - flow_pack_kernel: (u, v) planes -> (h, w, 2).
-// strotss_optical_flow_match adds flow_match.hip's stage between a level's upsample and its warps.
+// strotss_optical_flow_match adds flow_match.hip's stage between a level's upsample and its warps;
+// strotss_optical_flow_robust replaces a warp's sweeps by flow_robust.hip's weight updates and weighted sweeps.
 // Both solver forms call hs_update, so they agree bit for bit.
 #include <algorithm>
 #include <cmath>
@@ -265,10 +266,13 @@ struct FlowBuffers {
   float* u[2];
   float* v[2];
   f32x4* coef;
+  float* s;                                             // the robust form's planes (flow_robust.hip): s (h, w), gk (h, w, 2)
+  float* gk;
 };
 
-// The workspace: both pyramids, the (u, v) ping-pong and the coefficients at the full size (the coarser levels reuse them).
-bool flow_carve(Workspace& ws, const FlowLevels& l, FlowBuffers& f) {
+// The workspace: both pyramids, the (u, v) ping-pong and the coefficients at the full size (the coarser levels reuse them);
+// robust: behind them, the weight planes at the full size.
+bool flow_carve(Workspace& ws, const FlowLevels& l, FlowBuffers& f, bool robust = false) {
   for (int k = 0; k < l.n; ++k) {
     f.a[k] = ws.take<float>((size_t)l.h[k] * l.w[k]);
     f.b[k] = ws.take<float>((size_t)l.h[k] * l.w[k]);
@@ -279,6 +283,8 @@ bool flow_carve(Workspace& ws, const FlowLevels& l, FlowBuffers& f) {
     f.v[i] = ws.take<float>(npix);
   }
   f.coef = ws.take<f32x4>(npix);
+  f.s = robust ? ws.take<float>(npix) : nullptr;
+  f.gk = robust ? ws.take<float>(2 * npix) : nullptr;
   return ws.ok();
 }
 
@@ -310,20 +316,43 @@ int strotss_optical_flow(const float* frame_a, const float* frame_b, int h, int 
   return strotss_optical_flow_match(frame_a, frame_b, h, w, params, 0, flow_out, workspace, workspace_bytes, stream);
 }
 
-// The one body.  match_radius R > 0: the patch-matching stage (flow_match.hip, DESIGN.md section 31) at every level, on the
-// level's starting flow and before its warps, into the other half of the (u, v) ping-pong; R = 0 issues no such launch.
 int strotss_optical_flow_match(const float* frame_a, const float* frame_b, int h, int w, const strotss_flow_params_t* params,
                                int match_radius, float* flow_out, void* workspace, size_t workspace_bytes, void* stream) {
+  return strotss_optical_flow_robust(frame_a, frame_b, h, w, params, nullptr, match_radius, flow_out, workspace,
+                                     workspace_bytes, stream);
+}
+
+size_t strotss_flow_robust_workspace_bytes(int h, int w, const strotss_flow_params_t* params,
+                                           const strotss_flow_robust_params_t* robust) {
+  if (!robust) return strotss_flow_workspace_bytes(h, w, params);
+  const strotss_flow_params_t p = flow_params_or_default(params, h, w);
+  if (h < 2 || w < 2 || (long long)h * w > (1LL << 28) || !flow_params_ok(p) ||
+      !st_flow_robust_params_ok(*robust, p.iters, p.iters_per_launch))
+    return 0;
+  Workspace plan = Workspace::planner();
+  FlowBuffers f;
+  flow_carve(plan, flow_levels(h, w, p), f, true);
+  return plan.off;
+}
+
+// The one body.  match_radius R > 0: the patch-matching stage (flow_match.hip, DESIGN.md section 31) at every level, on the
+// level's starting flow and before its warps, into the other half of the (u, v) ping-pong; R = 0 issues no such launch.
+// robust != NULL: a warp's `iters` sweeps are `outer` weight updates (flow_robust.hip), each followed
+// by iters / outer weighted sweeps in launches of iters_per_launch; NULL issues the launches it always issued.
+int strotss_optical_flow_robust(const float* frame_a, const float* frame_b, int h, int w, const strotss_flow_params_t* params,
+                                const strotss_flow_robust_params_t* robust, int match_radius, float* flow_out,
+                                void* workspace, size_t workspace_bytes, void* stream) {
   ST_CHECK_ARG(frame_a && frame_b && flow_out && workspace, STROTSS_EINVAL);
   ST_CHECK_ARG(match_radius >= 0 && match_radius <= STROTSS_FLOW_MATCH_MAX_RADIUS, STROTSS_EINVAL);
   ST_CHECK_ARG(h >= 2 && w >= 2 && (long long)h * w <= (1LL << 28), STROTSS_EINVAL);
   const strotss_flow_params_t p = flow_params_or_default(params, h, w);
   ST_CHECK_ARG(flow_params_ok(p), STROTSS_EINVAL);
+  ST_CHECK_ARG(!robust || st_flow_robust_params_ok(*robust, p.iters, p.iters_per_launch), STROTSS_EINVAL);
   ST_CHECK_ARG(aligned16(frame_a) && aligned16(frame_b) && aligned16(flow_out) && aligned16(workspace), STROTSS_EALIGN);
   const FlowLevels l = flow_levels(h, w, p);
   Workspace ws(workspace, workspace_bytes);
   FlowBuffers f;
-  ST_CHECK_ARG(flow_carve(ws, l, f), STROTSS_EINVAL);
+  ST_CHECK_ARG(flow_carve(ws, l, f, robust != nullptr), STROTSS_EINVAL);
   const hipStream_t st = (hipStream_t)stream;
 
   hipLaunchKernelGGL(flow_blur_kernel<true>, per_pixel(h, w), dim3(256), 0, st, frame_a, h, w, f.a[0], h, w, 1);
@@ -352,6 +381,17 @@ int strotss_optical_flow_match(const float* frame_a, const float* frame_b, int h
     for (int wi = 0; wi < p.warps; ++wi) {
       hipLaunchKernelGGL(flow_coef_kernel, per_pixel(hk, wk), dim3(256), 0, st, f.a[k], f.b[k], f.u[cur], f.v[cur], hk, wk,
                          p.alpha2, f.coef);
+      if (robust) {
+        for (int o = 0; o < robust->outer; ++o) {
+          st_flow_robust_weights_launch(f.coef, f.u[cur], f.v[cur], hk, wk, *robust, f.s, f.gk, st);
+          for (int it = 0; it < p.iters / robust->outer; it += p.iters_per_launch) {
+            st_flow_robust_sweeps_launch(f.u[cur], f.v[cur], f.coef, f.s, f.gk, hk, wk, p.iters_per_launch, f.u[cur ^ 1],
+                                         f.v[cur ^ 1], st);
+            cur ^= 1;
+          }
+        }
+        continue;
+      }
       for (int it = 0; it < p.iters; it += p.iters_per_launch) {
         switch (p.iters_per_launch) {
           case 1:

@@ -71,6 +71,16 @@ int st_gemm_x3_batched_f32a(const float* A, const void* B, float* C, int ldc, lo
 void st_flow_match_launch(const float* a, const float* b, int h, int w, const float* u, const float* v, int radius,
                           float* uo, float* vo, hipStream_t st);
 
+// flow_robust.hip: the robust form's weight update (-> s (h, w), gk (h, w, 2)) and `sweeps` weighted Jacobi sweeps in one
+// launch (1: the plain kernel; 2, 4, 8: the LDS-blocked one), (u, v) -> (uo, vo); the parameters checked by the callers with
+// st_flow_robust_params_ok (alpha, eps_d, eps_s finite and > 0, outer in 1..8 dividing iters, iters_per_launch dividing
+// iters / outer)
+bool st_flow_robust_params_ok(const strotss_flow_robust_params_t& r, int iters, int iters_per_launch);
+void st_flow_robust_weights_launch(const f32x4* coef, const float* u, const float* v, int h, int w,
+                                   const strotss_flow_robust_params_t& r, float* s, float* gk, hipStream_t st);
+void st_flow_robust_sweeps_launch(const float* u, const float* v, const f32x4* coef, const float* s, const float* gk, int h,
+                                  int w, int sweeps, float* uo, float* vo, hipStream_t st);
+
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 // Bump allocator over a caller-provided workspace (256-byte aligned slices).

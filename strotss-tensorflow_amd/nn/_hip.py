@@ -104,6 +104,11 @@ class FlowParamsT(C.Structure):
                 ("max_levels", C.c_int), ("iters_per_launch", C.c_int)]
 
 
+class FlowRobustParamsT(C.Structure):
+    """strotss_flow_robust_params_t (include/strotss_hip.h): the parameters of strotss_optical_flow_robust's solver"""
+    _fields_ = [("alpha", C.c_float), ("eps_d", C.c_float), ("eps_s", C.c_float), ("outer", C.c_int)]
+
+
 _P, _I, _F, _Z, _L, _U = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64, C.c_uint
 # name -> (restype, argtypes); must list EVERY symbol include/strotss_hip.h declares
 SIGNATURES = {
@@ -203,6 +208,11 @@ SIGNATURES = {
     "strotss_optical_flow": (_I, [_P, _P, _I, _I, C.POINTER(FlowParamsT), _P, _P, _Z, _P]),
     "strotss_optical_flow_match": (_I, [_P, _P, _I, _I, C.POINTER(FlowParamsT), _I, _P, _P, _Z, _P]),
     "strotss_flow_match_stage": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P, _P]),
+    "strotss_flow_robust_default_params": (None, [C.POINTER(FlowRobustParamsT)]),
+    "strotss_flow_robust_workspace_bytes": (_Z, [_I, _I, C.POINTER(FlowParamsT), C.POINTER(FlowRobustParamsT)]),
+    "strotss_optical_flow_robust": (_I, [_P, _P, _I, _I, C.POINTER(FlowParamsT), C.POINTER(FlowRobustParamsT), _I, _P, _P, _Z,
+                                         _P]),
+    "strotss_flow_robust_stage": (_I, [_P, _P, _P, _I, _I, C.POINTER(FlowRobustParamsT), _I, _I, _P, _P, _P, _P, _P, _P]),
     "strotss_color_stats_workspace_bytes": (_Z, [_I, _I]),
     "strotss_color_stats": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "strotss_color_affine": (_I, [_P, _P, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _P]),

@@ -276,14 +276,51 @@ def flow_params(**overrides) -> "_hip.FlowParamsT":
 FLOW_MATCH_MAX_RADIUS = 4          # STROTSS_FLOW_MATCH_MAX_RADIUS
 
 
+FLOW_ROBUST_FIELDS = ("alpha", "eps_d", "eps_s", "outer")          # strotss_flow_robust_params_t
+FLOW_ROBUST_MAX_OUTER = 8                                           # STROTSS_FLOW_ROBUST_MAX_OUTER
+
+
+def flow_robust_params(robust) -> Optional["_hip.FlowRobustParamsT"]:
+    """strotss_flow_robust_params_t of `robust`: None -> None (the quadratic flow); a dict with any of alpha, eps_d, eps_s,
+    outer (the others at the library's defaults, strotss_flow_robust_default_params; {} = all defaults), a tuple of the four
+    in that order, or the struct itself.  ValueError for another key or length, a value that is not finite and > 0, an outer
+    outside 1..8 (that outer divides iters is the library's check: it knows the flow parameters)."""
+    if robust is None or isinstance(robust, _hip.FlowRobustParamsT):
+        return robust
+    p = _hip.FlowRobustParamsT()
+    _hip.load_library().strotss_flow_robust_default_params(C.byref(p))
+    if isinstance(robust, dict):
+        unknown = sorted(set(robust) - set(FLOW_ROBUST_FIELDS))
+        if unknown:
+            raise ValueError(f"unknown robust flow parameter {unknown[0]!r}: expected one of {list(FLOW_ROBUST_FIELDS)}")
+        items = robust.items()
+    elif isinstance(robust, (tuple, list)) and len(robust) == len(FLOW_ROBUST_FIELDS):
+        items = zip(FLOW_ROBUST_FIELDS, robust)
+    else:
+        raise ValueError(f"robust = {robust!r}: expected None, a dict or a tuple of {list(FLOW_ROBUST_FIELDS)}")
+    for key, val in items:
+        if key == "outer":
+            if isinstance(val, bool) or int(val) != val or not 1 <= int(val) <= FLOW_ROBUST_MAX_OUTER:
+                raise ValueError(f"robust flow: outer = {val!r}, expected a whole number in 1..{FLOW_ROBUST_MAX_OUTER}")
+            p.outer = int(val)
+        else:
+            val = float(val)
+            if not (val == val and 0.0 < val < float("inf")):
+                raise ValueError(f"robust flow: {key} = {val}, expected a finite value > 0")
+            setattr(p, key, val)
+    return p
+
+
 def optical_flow(frame_a: torch.Tensor, frame_b: torch.Tensor, params: Optional["_hip.FlowParamsT"] = None,
-                 out: Optional[torch.Tensor] = None, ws: Optional["Workspaces"] = None, match_radius: int = 0) -> torch.Tensor:
+                 out: Optional[torch.Tensor] = None, ws: Optional["Workspaces"] = None, match_radius: int = 0,
+                 robust=None) -> torch.Tensor:
     """the dense optical flow (h, w, 2) = (u, v) with frame_a(p) ~ frame_b(p + flow(p)) (strotss_optical_flow, DESIGN.md
     section 14): frames (h, w, 3) or (1, h, w, 3) RGB in [0, 1]; params from flow_params(), None = the defaults.  The
     backward flow of frame t for strotss_flow_warp is optical_flow(frame_t, frame_{t-j}), the forward one
     optical_flow(frame_{t-j}, frame_t).  match_radius R in 1..4: with the patch-matching stage at every level
-    (strotss_optical_flow_match); 0: without, the same launches as ever.  The workspace is a buffer of this call's own, or grow-only scratch of `ws` when one
-    is given."""
+    (strotss_optical_flow_match); 0: without, the same launches as ever.  robust: None, or what
+    flow_robust_params takes: the robust solver (strotss_optical_flow_robust); None is the call it
+    always was.  The workspace is a buffer of this call's own, or grow-only scratch of `ws` when one is given."""
     require(frame_a, "frame a")
     require(frame_b, "frame b")
     h, w, c = hwc(frame_a)
@@ -295,7 +332,9 @@ def optical_flow(frame_a: torch.Tensor, frame_b: torch.Tensor, params: Optional[
         raise ValueError(f"optical_flow: match_radius {match_radius}, expected 0 (no stage) .. {FLOW_MATCH_MAX_RADIUS}")
     lib = _hip.lib()
     pp = None if params is None else C.byref(params)
-    nb = int(lib.strotss_flow_workspace_bytes(h, w, pp))
+    rp = flow_robust_params(robust)
+    nb = int(lib.strotss_flow_workspace_bytes(h, w, pp) if rp is None
+             else lib.strotss_flow_robust_workspace_bytes(h, w, pp, C.byref(rp)))
     if nb == 0:
         raise _hip.StrotssHipError(f"optical_flow: bad size {h} x {w} or parameters")
     if out is None:
@@ -304,9 +343,34 @@ def optical_flow(frame_a: torch.Tensor, frame_b: torch.Tensor, params: Optional[
     assert out.numel() == 2 * h * w
     workspace = (torch.empty(nb, dtype=torch.uint8, device=frame_a.device) if ws is None
                  else ws.get("optical_flow", nb, frame_a.device))
-    check(lib.strotss_optical_flow_match(ptr(frame_a), ptr(frame_b), h, w, pp, match_radius, ptr(out), ptr(workspace), nb,
-                                         stream_ptr()), "optical_flow")
+    if rp is None:
+        check(lib.strotss_optical_flow_match(ptr(frame_a), ptr(frame_b), h, w, pp, match_radius, ptr(out), ptr(workspace), nb,
+                                             stream_ptr()), "optical_flow")
+    else:
+        check(lib.strotss_optical_flow_robust(ptr(frame_a), ptr(frame_b), h, w, pp, C.byref(rp), match_radius, ptr(out),
+                                              ptr(workspace), nb, stream_ptr()), "optical_flow")
     return out
+
+
+def flow_robust_stage(coef: torch.Tensor, u: torch.Tensor, v: torch.Tensor, robust=None, sweeps: int = 8,
+                      iters_per_launch: int = 1):
+    """one weight update of the robust flow on its own (strotss_flow_robust_stage): coef (h, w, 4) =
+    {Ix, Iy, c, unused} and the flow planes u, v (h, w) -> (u', v', s (h, w), gk (h, w, 2) = {1 / G, k}) after `sweeps`
+    weighted sweeps in launches of iters_per_launch"""
+    for t, name in ((coef, "coef"), (u, "u"), (v, "v")):
+        require(t, name)
+    if u.dim() != 2 or tuple(v.shape) != tuple(u.shape) or tuple(coef.shape) != tuple(u.shape) + (4,):
+        raise ValueError(f"flow_robust_stage: coef {tuple(coef.shape)}, u {tuple(u.shape)}, v {tuple(v.shape)}: expected "
+                         f"(h, w, 4) and two (h, w) planes")
+    h, w = int(u.shape[0]), int(u.shape[1])
+    rp = flow_robust_params({} if robust is None else robust)
+    uo, vo, s = torch.empty_like(u), torch.empty_like(v), torch.empty_like(u)
+    gk = torch.empty((h, w, 2), dtype=torch.float32, device=u.device)
+    tmp = torch.empty((2, h, w), dtype=torch.float32, device=u.device)
+    check(_hip.lib().strotss_flow_robust_stage(ptr(coef), ptr(u), ptr(v), h, w, C.byref(rp), int(sweeps), int(iters_per_launch),
+                                               ptr(uo), ptr(vo), ptr(s), ptr(gk), ptr(tmp), stream_ptr()),
+          "flow_robust_stage")
+    return uo, vo, s, gk
 
 
 def flow_match_stage(a: torch.Tensor, b: torch.Tensor, u: torch.Tensor, v: torch.Tensor,

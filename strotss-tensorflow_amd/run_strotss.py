@@ -55,6 +55,11 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
   --flow_match [R]  with --compute_flow: a patch-matching stage in every computed flow: at each
                     pyramid level every pixel may move its flow by a whole offset of up to R pixels (1..4, 2 when R is
                     left out) if its 5 x 5 window matches better there -- for objects that move against their background
+  --flow_robust     with --compute_flow: every computed flow is solved with robust (Charbonnier) penalties on the data and
+                    the smoothness term (strotss_optical_flow_robust), so that an object moving against
+                    its background keeps its motion; combines with --flow_match
+  --flow_alpha A    with --flow_robust: its smoothness weight (finite, > 0; default 0.06)
+  --flow_outer N    with --flow_robust: weight updates per warp (1..8, a divisor of the 32 sweeps; default 4)
   --save_flow DIR   with --compute_flow: also write the computed flows to DIR as backward_{t}_{t-j}.flo and
                     forward_{t-j}_{t}.flo (a later run with --flow_dir DIR reads the same floats back)
   --preserve_color {match,luminance,transfer}
@@ -690,7 +695,8 @@ def _video_inputs(args):
     --temporal_frames offsets (_temporal_frames), --video with --strips or under torchrun with WORLD_SIZE > 1, neither
     --flow_dir nor --compute_flow, a content_path that is not a directory of frames, frames of different sizes, a missing
     backward flow of any frame and offset (--flow_dir only); --compute_flow without --video or together with --flow_dir,
-    --save_flow without --compute_flow, --flow_match without --compute_flow or outside 1..4."""
+    --save_flow without --compute_flow, --flow_match without --compute_flow or outside 1..4, --flow_robust without
+    --compute_flow, --flow_alpha / --flow_outer without --flow_robust or out of range (_flow_robust)."""
     video = bool(getattr(args, "video", False))
     lam = getattr(args, "temporal_weight", None)
     flow_dir = getattr(args, "flow_dir", None)
@@ -707,6 +713,7 @@ def _video_inputs(args):
     if compute_flow and flow_dir:
         raise ValueError("--compute_flow and --flow_dir exclude each other: the flows are computed or read, not both")
     _flow_match_radius(args)
+    _flow_robust(args)
     if not video:
         return None
     offsets = _temporal_frames(args)
@@ -758,6 +765,37 @@ def _flow_match_radius(args) -> int:
     return int(r)
 
 
+FLOW_ROBUST_OUTER = (1, 8)          # --flow_outer: strotss_flow_robust_params_t.outer, a divisor of the default 32 sweeps
+FLOW_SWEEPS = 32                    # strotss_flow_default_params' iters
+
+
+def _flow_robust(args):
+    """--flow_robust [--flow_alpha A] [--flow_outer N]: the `robust` argument of every computed flow:
+    None without the flag, else a dict of the values given (the others stay at the library's defaults).  ValueError for
+    --flow_robust without --compute_flow, a sub-flag without --flow_robust, an alpha that is not finite and > 0, an outer
+    outside 1..8 or not dividing the 32 sweeps of a warp."""
+    alpha, outer = getattr(args, "flow_alpha", None), getattr(args, "flow_outer", None)
+    if not getattr(args, "flow_robust", False):
+        for flag, val in (("--flow_alpha", alpha), ("--flow_outer", outer)):
+            if val is not None:
+                raise ValueError(f"{flag} needs --flow_robust (it is a parameter of the robust flow)")
+        return None
+    if not getattr(args, "compute_flow", False):
+        raise ValueError("--flow_robust needs --compute_flow (it is the solver of the flows the run computes)")
+    robust = {}
+    if alpha is not None:
+        if isinstance(alpha, bool) or not np.isfinite(alpha) or alpha <= 0:
+            raise ValueError(f"--flow_alpha must be finite and > 0, got {alpha}")
+        robust["alpha"] = float(alpha)
+    if outer is not None:
+        if (isinstance(outer, bool) or int(outer) != outer or not FLOW_ROBUST_OUTER[0] <= int(outer) <= FLOW_ROBUST_OUTER[1]
+                or FLOW_SWEEPS % int(outer)):
+            raise ValueError(f"--flow_outer must be a whole number in {FLOW_ROBUST_OUTER[0]}..{FLOW_ROBUST_OUTER[1]} that "
+                             f"divides the {FLOW_SWEEPS} sweeps of a warp, got {outer}")
+        robust["outer"] = int(outer)
+    return robust
+
+
 def _frame_at_result_size(args, path: str) -> torch.Tensor:
     """a content frame (h, w, 3) on the device at the size of a frame's final result: resized as _stylise makes the content
     of its last executed scale"""
@@ -767,14 +805,16 @@ def _frame_at_result_size(args, path: str) -> torch.Tensor:
 
 def _computed_flows(args, t: int, j: int, frames, h: int, w: int):
     """--compute_flow: (backward, forward) flow of frame t against frame t-j, both (h, w, 2), by strotss_optical_flow on the
-    content frames at the results' size (with --flow_match R: strotss_optical_flow_match).  frames: {1-based position: (h, w, 3) frame on the device}.  --save_flow DIR
+    content frames at the results' size (with --flow_match R: strotss_optical_flow_match; with --flow_robust:
+    strotss_optical_flow_robust).  frames: {1-based position: (h, w, 3) frame on the device}.  --save_flow DIR
     writes them as backward_{t}_{t-j}.flo and forward_{t-j}_{t}.flo."""
     cur, old = frames[t], frames[t - j]
     if tuple(cur.shape) != (h, w, 3) or tuple(old.shape) != (h, w, 3):
         raise ValueError(f"--compute_flow: frames of {tuple(cur.shape)} and {tuple(old.shape)}, the results are {h} x {w}")
     radius = _flow_match_radius(args)
-    fb = strotss_engine._ops.optical_flow(cur, old, match_radius=radius)
-    ff = strotss_engine._ops.optical_flow(old, cur, match_radius=radius)
+    robust = _flow_robust(args)
+    fb = strotss_engine._ops.optical_flow(cur, old, match_radius=radius, robust=robust)
+    ff = strotss_engine._ops.optical_flow(old, cur, match_radius=radius, robust=robust)
     save = getattr(args, "save_flow", None)
     if save:
         os.makedirs(save, exist_ok=True)
@@ -1294,6 +1334,13 @@ _FLAGS = (
     (("--flow_match",), dict(type=int, nargs='?', const=2, default=None, metavar='R',
                              help="with --compute_flow: patch-matching stage of radius R (1..4, default 2) at every level of "
                                   "the computed flows (DESIGN.md section 31)")),
+    (("--flow_robust",), dict(action='store_true', help="with --compute_flow: robust (Charbonnier) penalties in every computed "
+                                                        "flow, for objects that move against their background (DESIGN.md "
+                                                        "section 32); combines with --flow_match")),
+    (("--flow_alpha",), dict(type=float, default=None, metavar='A',
+                             help="with --flow_robust: the smoothness weight (finite, > 0; default 0.06)")),
+    (("--flow_outer",), dict(type=int, default=None, metavar='N',
+                             help="with --flow_robust: weight updates per warp (1..8, a divisor of 32; default 4)")),
     (("--save_flow",), dict(type=str, default=None, metavar='DIR',
                             help="with --compute_flow: write the computed flows there as backward_{t}_{t-j}.flo and "
                                  "forward_{t-j}_{t}.flo")),
