@@ -503,17 +503,36 @@ def _output_size_input(args):
     return dict(size=size, mode=mode, radius=None if radius is None else int(radius), eps=None if eps is None else float(eps))
 
 
-def _output_guides(args, upsample: dict, path: str, guide_lo=None):
-    """--output_size: (the content at the result's size, the content at the target size), both (h, w, 3) on the device.
-    ValueError for a target smaller than the result in either dimension or with 3 H W > INT_MAX."""
-    lo = _frame_at_result_size(args, path) if guide_lo is None else guide_lo
-    hi = utils.load_image(path, max_size=None if upsample["size"] == "full" else upsample["size"])[0].contiguous()
+def _written_guides(args, post, content_path: str, frame_lo=None):
+    """The guides of _written, loaded before the image's first step: (the content at the result's size, the content at
+    --output_size's target size), both (h, w, 3) on the device, each None where nothing needs it.  post: what
+    (_preserve_color_input, _photo_smooth_input, _output_size_input) returned.  frame_lo: the content at the result's size
+    where the caller holds it already (a --compute_flow frame).  ValueError for a target smaller than the result in either
+    dimension or with 3 H W > INT_MAX -- here, not after the optimisation."""
+    preserve, smooth, upsample = post
+    if not (upsample or smooth or preserve == "luminance"):
+        return None, None
+    lo = _frame_at_result_size(args, content_path) if frame_lo is None else frame_lo
+    if not upsample:
+        return lo, None
+    hi = utils.load_image(content_path, max_size=None if upsample["size"] == "full" else upsample["size"])[0].contiguous()
     strotss.check_upsample_sizes(int(lo.shape[0]), int(lo.shape[1]), int(hi.shape[0]), int(hi.shape[1]))
     return lo, hi
 
 
-def _upsampled(upsample: dict, image: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor) -> torch.Tensor:
-    return strotss.guided_upsample(image, lo, hi, upsample["radius"], upsample["eps"], upsample["mode"])
+def _written(stylized: torch.Tensor, post, guides) -> torch.Tensor:
+    """The uint8 image that is written for an optimiser's result, of a single image and of every frame of a sequence:
+    --photo_smooth's filter, then --output_size's upsampling, then --preserve_color luminance's merge at the written size,
+    then postprocess.  `stylized` itself stays as it is: the temporal targets and --temporal_init keep seeing it."""
+    (preserve, smooth, upsample), (guide, guide_hi) = post, guides
+    if smooth:                                               # the content's edges back into the result, then its colours
+        stylized = strotss.guided_smooth(stylized, guide, *smooth)
+    if upsample:                                             # to the target size, the content there as guide from here on
+        stylized = strotss.guided_upsample(stylized, guide, guide_hi, upsample["radius"], upsample["eps"], upsample["mode"])
+        guide = guide_hi
+    if preserve == "luminance":                              # the result's luma on the content's chroma
+        stylized = strotss.luminance_merge(stylized, guide)
+    return strotss.postprocess(stylized)
 
 
 def _refine_masks_input(args):
@@ -849,22 +868,28 @@ def _flow_warp_for_frame(args, t: int, previous: torch.Tensor, j: int = 1, frame
     return fb, warped, certainty
 
 
-def _temporal_for_frame(args, t: int, previous: torch.Tensor, j: int = 1, frames=None):
-    """(warped result of frame t-j, certainty) of frame t (1-based, t > j) at that result's size: _flow_warp_for_frame
-    without the flow"""
-    return _flow_warp_for_frame(args, t, previous, j, frames)[1:]
+def _pairs_for_frame(args, t: int, results, offsets, frames=None) -> dict:
+    """{j: (backward flow, warped result of frame t-j, raw certainty)} of frame t for the offsets j of `offsets` (ascending)
+    with t - j >= 1: one _flow_warp_for_frame call per pair, so each flow is read or computed -- and with --save_flow
+    written -- once per frame.  results[k]: the final result of frame t-1-k.  {} for the first frame.  The tracking
+    (entry offsets[0]) and the temporal list (_temporal_targets_for_frame) both take their pairs from this map; the flows
+    are the same bits on every run, so sharing an entry gives what computing it again gave."""
+    return {j: _flow_warp_for_frame(args, t, results[j - 1], j, frames) for j in offsets if t - j >= 1 and j <= len(results)}
 
 
-def _temporal_targets_for_frame(args, t: int, results, offsets, frames=None):
-    """[(warped result of frame t-j, combined certainty)] of frame t for the offsets j of `offsets` (ascending) with
-    t - j >= 1, nearest frame first.  results[k]: the final result of frame t-1-k.  Each pair is
-    _temporal_for_frame's; the certainties are combined once, at the frame's size (strotss_temporal_long_certainty), so
-    that a pixel a nearer frame covers does not pull toward an older one.  [] for the first frame."""
-    pairs = [_temporal_for_frame(args, t, results[j - 1], j, frames) for j in offsets if t - j >= 1 and j <= len(results)]
-    if len(pairs) <= 1:                     # nothing nearer to subtract: the raw certainty is the combined one
-        return pairs
-    combined = strotss_engine._ops.temporal_long_certainty(torch.stack([c.float().contiguous() for _, c in pairs]))
-    return [(warped, combined[k]) for k, (warped, _) in enumerate(pairs)]
+def _temporal_targets_for_frame(args, t: int, results, offsets, frames=None, pairs=None):
+    """[(warped result of frame t-j, combined certainty)] of frame t, nearest frame first, 0..4 of them: the one temporal
+    shape between the flows and _stylise.  pairs: the frame's _pairs_for_frame map where the caller
+    holds it already, built here otherwise.  With two pairs or more the certainties are combined once, at the frame's size
+    (strotss_temporal_long_certainty), so that a pixel a nearer frame covers does not pull toward an older one; one pair
+    keeps its raw certainty.  [] for the first frame."""
+    if pairs is None:
+        pairs = _pairs_for_frame(args, t, results, offsets, frames)
+    found = [pairs[j][1:] for j in sorted(pairs)]
+    if len(found) <= 1:                     # nothing nearer to subtract: the raw certainty is the combined one
+        return found
+    combined = strotss_engine._ops.temporal_long_certainty(torch.stack([c.float().contiguous() for _, c in found]))
+    return [(warped, combined[k]) for k, (warped, _) in enumerate(found)]
 
 
 def _resized_reliable(path: str, h: int, w: int) -> torch.Tensor:
@@ -1026,9 +1051,7 @@ def run(args: argparse.Namespace, trace=None):
     timer.start()
 
     cw_path = _content_weight_input(args)
-    preserve = _preserve_color_input(args)
-    smooth = _photo_smooth_input(args)
-    upsample = _output_size_input(args)
+    post = _preserve_color_input(args), _photo_smooth_input(args), _output_size_input(args)
     _video_inputs(args)                                      # the sequence flags without --video: ValueError
     seed = int(getattr(args, "seed", 0))
     rand.seed_everything(seed)
@@ -1041,18 +1064,8 @@ def run(args: argparse.Namespace, trace=None):
     dev = utils.device()
 
     vgg = VGG(use_keras_weight=args.use_keras_weight, weights=getattr(args, "weights", None), seed=seed, device=dev)
-    if upsample:                                             # the target's size is refused before the first step
-        guide, guide_hi = _output_guides(args, upsample, args.content_path)
-    stylized = _stylise(args, vgg, args.content_path, cw_path, dev, rank, world, trace)
-    if not upsample:
-        guide = _frame_at_result_size(args, args.content_path) if smooth or preserve == "luminance" else None
-    if smooth:                                               # the content's edges back into the result, then its colours
-        stylized = strotss.guided_smooth(stylized, guide, *smooth)
-    if upsample:                                             # --output_size: to the target size, the content as guide
-        stylized, guide = _upsampled(upsample, stylized, guide, guide_hi), guide_hi
-    if preserve == "luminance":                              # the result's luma on the content's chroma, at the written size
-        stylized = strotss.luminance_merge(stylized, guide)
-    final = strotss.postprocess(stylized)
+    guides = _written_guides(args, post, args.content_path)  # --output_size: the target's size is refused before the first step
+    final = _written(_stylise(args, vgg, args.content_path, cw_path, dev, rank, world, trace), post, guides)
     if torch.cuda.is_available():
         torch.cuda.synchronize()
     timer.stop()
@@ -1062,55 +1075,67 @@ def run(args: argparse.Namespace, trace=None):
     return final
 
 
-def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: int = 1, trace=None, temporal=None,
-             temporal_weight: float = 0.0, masks=None):
-    """The coarse-to-fine schedule on one content image -> the final image of the finest scale (1, h, w, 3).
-    temporal: (warped previous result, certainty) at that result's size, or None; every scale then carries the temporal
-    term with weight temporal_weight, and --temporal_init starts the first executed scale from the warped result.  A list
-    of 2..4 such pairs (combined certainties, nearest frame first) carries one term per pair, all
-    with weight temporal_weight; --temporal_init starts from the nearest.  masks: (content_masks, style_masks) of this
-    frame from the caller (--track_masks), in place of the regions found or loaded here."""
-    from nn import parallel
-    level, first = int(args.level), int(getattr(args, "start_level", 0))
-    scribbles = _scribble_masks_input(args)
-    if scribbles:                                            # the stroke files' own refusals, before any image is loaded
-        strokes = strotss.load_scribbles(scribbles[0], scribbles[1])
-    content = utils.load_image(content_path, max_size=args.max_size)
-    style_paths, style_weights = _style_inputs(args)
-    styles = [utils.load_image(p, max_size=args.max_size) for p in style_paths]
-    auto = _auto_masks_input(args)
+def _region_masks(args, vgg, content, style, strokes=None, masks=None):
+    """(content_masks, style_masks) of an image as loaded, from the first source there is: `masks` from the caller
+    (--track_masks), --auto_masks (the regions found), the scribble files (`strokes`: what load_scribbles read; the regions
+    grown from them), --content_mask / --style_mask (or [None], [None]).  --save_masks writes what was found or grown."""
     if masks is not None:
-        content_masks, style_masks = masks
-    elif auto:                                               # regions found on the images as loaded, in place of painted masks
-        refine = _refine_masks_input(args)
-        if refine is None:                                   # without --refine_masks the call is what it was
-            content_masks, style_masks = strotss.auto_masks(vgg.params, content, styles[0], auto[0])
-        else:
-            content_masks, style_masks = strotss.auto_masks(vgg.params, content, styles[0], auto[0], refine=refine)
+        return masks
+    auto = _auto_masks_input(args)
+    if auto:
+        refine = _refine_masks_input(args)                   # without --refine_masks the call carries no such keyword
+        content_masks, style_masks = strotss.auto_masks(vgg.params, content, style, auto[0],
+                                                        **({} if refine is None else dict(refine=refine)))
         if content_masks[0] is not None:
             utils.logger.info(f'Found {len(content_masks)} regions.')
             if auto[1]:
                 strotss.save_masks(auto[1], content_masks, style_masks)
-    elif scribbles:                                          # regions grown from the strokes, on the images as loaded
-        content_masks, style_masks = strotss.scribble_masks(vgg.params, content, styles[0], strokes[0], strokes[1],
-                                                            len(strokes[2]), strokes[2], scribbles[2], scribbles[3])
+        return content_masks, style_masks
+    if strokes:
+        _, _, sigma, iters = _scribble_masks_input(args)
+        content_masks, style_masks = strotss.scribble_masks(vgg.params, content, style, strokes[0], strokes[1],
+                                                            len(strokes[2]), strokes[2], sigma, iters)
         utils.logger.info(f'Grew {len(content_masks)} regions from the strokes.')
         if getattr(args, "save_masks", None):
             strotss.save_masks(args.save_masks, content_masks, style_masks)
-    else:
-        content_masks, style_masks = _load_masks(args)
+        return content_masks, style_masks
+    return _load_masks(args)
+
+
+def _sample_map(args, content, content_path: str, rank: int = 0):
+    """--sample_map: the map read from its path; with `auto` this image's own detail map (with --video every frame's), which
+    --save_sample_map DIR writes as sample_map.png (with --video sample_map_<frame stem>.png); None without the flag"""
+    auto = _auto_sample_input(args)
+    if not auto:
+        path = _sample_map_input(args)
+        return strotss.load_sample_map(path) if path else None
+    sm_map = strotss.auto_sample_map(content, *auto[:3])
+    if auto[3] and rank == 0:
+        stem = os.path.splitext(os.path.basename(content_path))[0]
+        name = f"sample_map_{stem}.png" if getattr(args, "video", False) else "sample_map.png"
+        strotss.save_sample_map(os.path.join(auto[3], name), sm_map)
+    return sm_map
+
+
+def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: int = 1, trace=None, temporal=None,
+             temporal_weight: float = 0.0, masks=None):
+    """The coarse-to-fine schedule on one content image -> the final image of the finest scale (1, h, w, 3).
+    temporal: _temporal_targets_for_frame's list of 0..4 (warped earlier result, certainty) pairs at that result's size,
+    nearest frame first; None and [] mean no term.  Every scale carries one temporal term per pair, all with weight
+    temporal_weight, and --temporal_init starts the first executed scale from the nearest pair's warped result.
+    masks: (content_masks, style_masks) of this frame from the caller (--track_masks), in place of those of _region_masks."""
+    from nn import parallel
+    level, first = int(args.level), int(getattr(args, "start_level", 0))
+    scribbles = _scribble_masks_input(args)                  # the stroke files' own refusals, before any image is loaded
+    strokes = strotss.load_scribbles(scribbles[0], scribbles[1]) if scribbles else None
+    content = utils.load_image(content_path, max_size=args.max_size)
+    style_paths, style_weights = _style_inputs(args)
+    styles = [utils.load_image(p, max_size=args.max_size) for p in style_paths]
+    content_masks, style_masks = _region_masks(args, vgg, content, styles[0], strokes, masks)
     # --preserve_color match / transfer, before any resize: every scale samples the recoloured styles
     styles = _recolour_styles(args, styles, content, content_masks, style_masks)
     cw_map = strotss.load_content_weight_map(cw_path) if cw_path else None
-    sm_path = _sample_map_input(args)
-    sm_map = strotss.load_sample_map(sm_path) if sm_path and sm_path != SAMPLE_MAP_AUTO else None
-    auto_sample = _auto_sample_input(args)
-    if auto_sample:                                          # --sample_map auto: this image's own detail map (per --video frame)
-        sm_map = strotss.auto_sample_map(content, *auto_sample[:3])
-        if auto_sample[3] and rank == 0:
-            stem = os.path.splitext(os.path.basename(content_path))[0]
-            name = f"sample_map_{stem}.png" if getattr(args, "video", False) else "sample_map.png"
-            strotss.save_sample_map(os.path.join(auto_sample[3], name), sm_map)
+    sm_map = _sample_map(args, content, content_path, rank)
     sampling = strotss.Sampling(SAMPLE_SIZE)
     masked = bool(getattr(args, "content_mask", None))
     transport = dict(_style_transport_input(args), **_palette_transport_input(args))
@@ -1128,43 +1153,35 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
         stylized, lr = _initial_image(position, position > 0 and i == level - 1, stylized, scl_content, scl_style,
                                       args.lr, style_weights)
         hs, ws = int(scl_content.shape[1]), int(scl_content.shape[2])
-        tt = None
-        if isinstance(temporal, list):
+        terms = dict(transport)                              # the engine's keywords of this scale, built afresh
+        if temporal:
             scaled = strotss.temporal_targets_at_scale(temporal, hs, ws)
-            tt = [strotss_engine.TemporalTarget(target, cert, temporal_weight) for target, cert in scaled]
+            terms["temporal"] = [strotss_engine.TemporalTarget(target, cert, temporal_weight) for target, cert in scaled]
             if position == 0 and getattr(args, "temporal_init", False):
-                stylized = scaled[0][0][None].contiguous()   # the nearest frame's warp
-        elif temporal is not None:
-            target, cert = strotss.temporal_target_at_scale(temporal[0], temporal[1], hs, ws)
-            tt = strotss_engine.TemporalTarget(target, cert, temporal_weight)
-            if position == 0 and getattr(args, "temporal_init", False):
-                stylized = target[None].contiguous()         # resize(omega) instead of Laplacian + mean style colour
+                stylized = scaled[0][0][None].contiguous()   # the nearest frame's warp instead of Laplacian + mean style colour
         # --strips: ONE image sharded by rows (the only sharding that cuts trunk work), with or without mask regions; where
         # a scale is too small for strips to pay (strip_plan -> None) a masked run falls back to dealing its regions out
         plan = (parallel.strip_plan(int(scl_content.shape[1]), world, rank, halo=bool(getattr(args, "halo", False)))
                 if world > 1 and getattr(args, "strips", False) else None)
         cw_scaled = None if cw_map is None else strotss.content_weight_at_scale(cw_map, hs, ws)
         if prior["detail"] is not None:                      # the detail target: this image's content at this scale
-            transport["detail"] = strotss_engine.DetailTarget(scl_content, prior["detail"][1], prior["detail"][0], cw_scaled)
+            terms["detail"] = strotss_engine.DetailTarget(scl_content, prior["detail"][1], prior["detail"][0], cw_scaled)
         if prior["tv"] > 0:
-            transport["tv_weight"] = prior["tv"]
+            terms["tv_weight"] = prior["tv"]
         eng = strotss_engine.StepEngine(
             vgg.params, strotss_engine.extract_features(vgg.params, scl_content),
             _style_targets(vgg.params, scl_style, style_masks, sampling, style_weights), stylized, alpha,
             loss_denom=2. + alpha + 1. / max(alpha, 1.), lr=lr, sample_size=SAMPLE_SIZE, strips=plan,
             dist_group=parallel.WORLD if (world > 1 and masked and plan is None) else None,
-            content_weight=cw_scaled, temporal=tt,
-            **transport)
+            content_weight=cw_scaled, **terms)
         rec = None
         if trace is not None:
             rec = dict(i=i, scl=scl, lr=lr, alpha=alpha, loss_denom=eng.loss_denom, init=stylized.clone(), steps=[],
                        hw=(eng.h, eng.w))
             trace.append(rec)
-        if sm_map is None:
-            _optimise_scale(eng, scl, content_masks, args, dev, quiet=rank != 0, step_trace=None if rec is None else rec["steps"])
-        else:                                                # --sample_map: the levels of this scale, rounded once
-            _optimise_scale(eng, scl, content_masks, args, dev, quiet=rank != 0, step_trace=None if rec is None else rec["steps"],
-                            sample_levels=strotss.sample_levels_at_scale(sm_map, hs, ws))
+        # --sample_map: the levels of this scale, rounded once
+        _optimise_scale(eng, scl, content_masks, args, dev, quiet=rank != 0, step_trace=None if rec is None else rec["steps"],
+                        sample_levels=None if sm_map is None else strotss.sample_levels_at_scale(sm_map, hs, ws))
         stylized = eng.stylized()
         if rec is not None:
             rec["final"] = stylized.clone()
@@ -1225,19 +1242,14 @@ def _tracked_masks(args, vgg, tracking: dict, t: int, frame: str, j: int, neares
 
 def run_video(args: argparse.Namespace, trace=None):
     """--video: every frame of the directory content_path through the schedule of run(), one VGG for the sequence, the
-    seeds reset for every frame (each frame draws the index stream a single-image run draws).  Frame t > 1 carries the
-    temporal term toward the previous result warped along the backward flow and, with
-    --temporal_frames, toward the results of frames t-j (the last max(J) results stay on the device).
-    With --compute_flow the flows come from strotss_optical_flow on the content frames at the results' size (DESIGN.md
-    section 14; the last max(J) + 1 of those frames stay on the device as well).  --preserve_color match and
-    transfer recolour the styles against every frame's own colours (in _stylise); luminance merges only what is written,
-    the temporal targets keep the unmerged results (DESIGN.md sections 15 and 23).  --photo_smooth filters only what is
-    written as well, before that merge.  --auto_masks K --track_masks: the regions of frame 1
-    followed through the sequence (_tracked_masks).  Writes
+    seeds reset for every frame (each frame draws the index stream a single-image run draws).  Per frame: the
+    (frame, offset) pairs of --temporal_frames, each read or computed once (_pairs_for_frame; the last max(J) results and,
+    with --compute_flow, the last max(J) + 1 content frames at the results' size stay on the device); with --track_masks
+    the frame's regions from the nearest pair (_tracked_masks); the temporal list from the same pairs
+    (_temporal_targets_for_frame); then the frame path of run(): _written_guides, _stylise, _written.  Only what is written
+    is filtered, upsampled or merged: the temporal targets and --temporal_init keep the optimiser's own results.  Writes
     <output dir>/<frame stem>.jpg; returns the list of the frames' uint8 results.  `trace`: one list per frame."""
-    preserve = _preserve_color_input(args)
-    smooth = _photo_smooth_input(args)
-    upsample = _output_size_input(args)
+    post = _preserve_color_input(args), _photo_smooth_input(args), _output_size_input(args)
     frames, lam = _video_inputs(args)
     cw_path = _content_weight_input(args)
     seed = int(getattr(args, "seed", 0))
@@ -1247,8 +1259,7 @@ def run_video(args: argparse.Namespace, trace=None):
     offsets = _temporal_frames(args)
     auto, inertia = _auto_masks_input(args), _track_masks_input(args)
     tracking = {} if auto else None         # --track_masks: the states of the last offsets[0] frames, by frame position
-    previous, outs = None, []
-    results = []                            # results[k]: the final image of frame t-1-k, the last max(offsets) of them
+    outs, results = [], []                  # results[k]: the final image of frame t-1-k, the last max(offsets) of them
     flow_frames = {} if getattr(args, "compute_flow", False) else None      # --compute_flow: the last max(offsets) + 1 frames
     for t, frame in enumerate(frames, start=1):
         timer = utils.Timer()
@@ -1257,37 +1268,19 @@ def run_video(args: argparse.Namespace, trace=None):
         if flow_frames is not None:
             flow_frames[t] = _frame_at_result_size(args, frame)
             flow_frames.pop(t - offsets[-1] - 1, None)
-        nearest = None                      # --track_masks: (flow, warped, certainty) against the nearest earlier frame
-        if tracking is not None and t > offsets[0]:
-            nearest = _flow_warp_for_frame(args, t, results[offsets[0] - 1], offsets[0], flow_frames)
-        if offsets == (1,) and nearest is not None:
-            temporal = nearest[1:]
-        elif offsets == (1,):
-            temporal = _temporal_for_frame(args, t, previous, frames=flow_frames) if previous is not None else None
-        else:
-            pairs = _temporal_targets_for_frame(args, t, results, offsets, flow_frames)
-            temporal = None if not pairs else pairs[0] if len(pairs) == 1 else pairs
+        pairs = _pairs_for_frame(args, t, results, offsets, flow_frames)
+        temporal = _temporal_targets_for_frame(args, t, results, offsets, flow_frames, pairs)
         rec = None
         if trace is not None:
             rec = []
             trace.append(rec)
         masks = None
-        if tracking is not None:
-            masks = _tracked_masks(args, vgg, tracking, t, frame, offsets[0], nearest, auto, inertia)
-        if upsample:                        # --output_size: the target's size is refused before the frame's first step
-            guide, guide_hi = _output_guides(args, upsample, frame, flow_frames[t] if flow_frames is not None else None)
-        previous = _stylise(args, vgg, frame, cw_path, dev, trace=rec, temporal=temporal, temporal_weight=lam, masks=masks)
-        results = [previous] + results[:offsets[-1] - 1]
-        written = previous                  # only what is written is filtered, upsampled or merged: the temporal targets
-        if not upsample and (smooth or preserve == "luminance"):     # and --temporal_init keep the optimiser's own results
-            guide = flow_frames[t] if flow_frames is not None else _frame_at_result_size(args, frame)
-        if smooth:
-            written = strotss.guided_smooth(written, guide, *smooth)
-        if upsample:
-            written, guide = _upsampled(upsample, written, guide, guide_hi), guide_hi
-        if preserve == "luminance":
-            written = strotss.luminance_merge(written, guide)
-        final = strotss.postprocess(written)
+        if tracking is not None:            # pairs.get: no prior for t <= offsets[0]
+            masks = _tracked_masks(args, vgg, tracking, t, frame, offsets[0], pairs.get(offsets[0]), auto, inertia)
+        guides = _written_guides(args, post, frame, None if flow_frames is None else flow_frames[t])
+        stylized = _stylise(args, vgg, frame, cw_path, dev, trace=rec, temporal=temporal, temporal_weight=lam, masks=masks)
+        results = [stylized] + results[:offsets[-1] - 1]
+        final = _written(stylized, post, guides)
         if torch.cuda.is_available():
             torch.cuda.synchronize()
         timer.stop()

@@ -330,7 +330,7 @@ def test_temporal_for_frame_reads_the_flow_files(tmp_path):
     args = RS.build_parser().parse_args([frames, "s.jpg", "--video", "--flow_dir", flows])
     for h, w in ((48, 64), (24, 32)):                   # at the frames' size, and at half of it: the flows scaled by 0.5
         prev = np.random.default_rng(h).random((h, w, 3)).astype(np.float32)
-        warped, cert = RS._temporal_for_frame(args, 2, _dev(prev)[None])
+        warped, cert = RS._flow_warp_for_frame(args, 2, _dev(prev)[None])[1:]
         torch.cuda.synchronize()
         k = h / 48
         fb = np.broadcast_to(np.float32([-3 * k, -2 * k]), (h, w, 2))
@@ -339,7 +339,7 @@ def test_temporal_for_frame_reads_the_flow_files(tmp_path):
         assert np.array_equal(cert.cpu().numpy(), T.certainty64(fb, ff).astype(np.float32))
     # reliable_2_1.pgm replaces the certainty: its value / 255
     Image.fromarray(np.full((48, 64), 128, dtype=np.uint8)).save(os.path.join(flows, "reliable_2_1.pgm"))
-    _, cert = RS._temporal_for_frame(args, 2, _dev(prev)[None])
+    _, cert = RS._flow_warp_for_frame(args, 2, _dev(prev)[None])[1:]
     assert tuple(cert.shape) == (24, 32) and torch.allclose(cert, torch.full_like(cert, 128 / 255))
 
 

@@ -352,7 +352,7 @@ def test_temporal_targets_for_frame_reads_and_combines(tmp_path):
     assert len(pairs) == 2
     raw = []
     for j, (warped, cert) in zip((1, 2), pairs):
-        w1, c1 = RS._temporal_for_frame(args, 3, results[j - 1], j)
+        w1, c1 = RS._flow_warp_for_frame(args, 3, results[j - 1], j)[1:]
         assert torch.equal(warped, w1)
         raw.append(c1.cpu().numpy())
     comb = TL.long_certainty32(np.stack(raw))
@@ -363,7 +363,7 @@ def test_temporal_targets_for_frame_reads_and_combines(tmp_path):
     assert hole.any() and (comb[0][hole] == 0).all() and (comb[1][hole] == 1).all()
     # frame 2: only j = 1 applies -- the one-target pair, raw
     one = RS._temporal_targets_for_frame(args, 2, results[1:], (1, 2))
-    assert len(one) == 1 and torch.equal(one[0][1], RS._temporal_for_frame(args, 2, results[1], 1)[1])
+    assert len(one) == 1 and torch.equal(one[0][1], RS._flow_warp_for_frame(args, 2, results[1], 1)[2])
 
 
 # ------------------------------------------------------------------ 4. --temporal_frames end to end

@@ -84,6 +84,70 @@ def test_temporal_frames_refusals(tmp_path, monkeypatch):
         RS._video_inputs(_args(*ok, "--temporal_frames", "2", content=frames))
 
 
+@pytest.mark.parametrize("track", (False, True), ids=("plain", "tracked"))
+@pytest.mark.parametrize("offsets", ((1, 2), (1,)))
+def test_each_frame_offset_pair_is_computed_once(tmp_path, monkeypatch, offsets, track):
+    """run_video on four frames with everything around the pairs stubbed: one _flow_warp_for_frame call per (t, j) with
+    t - j >= 1, its entry handed to the tracking and to the temporal list as the same objects, one pair with its raw
+    certainty, two combined by one temporal_long_certainty call with the planes nearest first."""
+    import torch
+    import run_strotss as RS
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    names = [f"f{t}.jpg" for t in (1, 2, 3, 4)]
+    results, made, tracked, stylised, combined = {}, {}, [], [], []
+
+    def flow_warp(args, t, previous, j=1, frames=None):
+        assert (t, j) not in made, f"pair {(t, j)} computed twice"
+        assert previous is results[t - j]                              # the optimiser's own result of frame t-j
+        made[(t, j)] = (object(), object(), torch.full((2, 3), float(10 * t + j)))
+        return made[(t, j)]
+
+    def long_certainty(stack):
+        combined.append(stack.clone())
+        return stack + 0.5
+
+    def stylise(args, vgg, frame, cw_path, dev, **kw):
+        t = names.index(frame) + 1
+        stylised.append((t, kw["temporal"], kw["masks"]))
+        results[t] = torch.full((1, 2, 3, 3), float(t))
+        return results[t]
+
+    def tracked_masks(args, vgg, tracking, t, frame, j, nearest, auto, inertia):
+        tracked.append((t, j, nearest))
+        return [None], [None]
+
+    monkeypatch.setattr(RS, "_video_inputs", lambda args: (names, 1.0))
+    monkeypatch.setattr(RS, "VGG", lambda **kw: None)
+    monkeypatch.setattr(RS, "_flow_warp_for_frame", flow_warp)
+    monkeypatch.setattr(RS.strotss_engine._ops, "temporal_long_certainty", long_certainty)
+    monkeypatch.setattr(RS, "_stylise", stylise)
+    monkeypatch.setattr(RS, "_tracked_masks", tracked_masks)
+    monkeypatch.setattr(RS, "_written", lambda stylized, post, guides: stylized)
+    monkeypatch.setattr(RS.utils, "write_image", lambda image, path: None)
+    extra = ("--auto_masks", "3", "--track_masks") if track else ()
+    outs = RS.run_video(_args("--video", "--flow_dir", "f", "--temporal_frames", *map(str, offsets), *extra,
+                              "-o", str(tmp_path / "out"), content="frames"))
+    assert len(outs) == 4
+    assert sorted(made) == [(t, j) for t in (1, 2, 3, 4) for j in offsets if t - j >= 1]
+    assert [t for t, _, _ in stylised] == [1, 2, 3, 4]
+    assert [(t, j) for t, j, _ in tracked] == ([(t, offsets[0]) for t in (1, 2, 3, 4)] if track else [])
+    for t, j, nearest in tracked:                                      # the tracking's pair is the map's entry itself
+        assert nearest is made.get((t, j))
+    n_combined = 0
+    for t, temporal, masks in stylised:
+        js = [j for j in offsets if t - j >= 1]                        # nearest frame first
+        assert len(temporal) == len(js) and (masks is not None) == track
+        assert all(pair[0] is made[(t, j)][1] for pair, j in zip(temporal, js))
+        if len(js) == 1:                                               # one pair: the raw certainty, untouched
+            assert temporal[0][1] is made[(t, js[0])][2]
+        elif js:
+            raw = torch.stack([made[(t, j)][2] for j in js])
+            assert torch.equal(combined[n_combined], raw)
+            assert all(torch.equal(pair[1], raw[k] + 0.5) for k, pair in enumerate(temporal))
+            n_combined += 1
+    assert len(combined) == n_combined == sum(1 for t in (1, 2, 3, 4) if sum(t - j >= 1 for j in offsets) >= 2)
+
+
 def test_the_occluder_sequence_is_what_it_says(tmp_path):
     from PIL import Image
     frames, flows = tmp_path / "f", tmp_path / "fl"
