@@ -675,6 +675,35 @@ int strotss_tv_fwd_bwd(const float* img, int h, int w, float eps, float gscale, 
                        void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The photorealism term of the step: the matting Laplacian of the content, L p = N (p - q)
+ * --------------------------------------------------------------------------------------- */
+#define STROTSS_MATTING_MAX_RADIUS 4
+/* bytes of the window statistics of strotss_matting_prepare: 36 per pixel (0 for h, w <= 0 or 3 h w > INT_MAX) */
+size_t strotss_matting_stats_bytes(int h, int w);
+/* The guide's window statistics, once per scale, ONE launch.  guide (h, w, 3) float32; window w_k the (2r+1) x (2r+1) box
+ * around pixel k clipped to the image (the windows of strotss_guided_smooth); eps at its float32 value.  stats: 9 planes of
+ * (h, w) float32: planes 0..2 mu_k = mean_w guide, planes 3..8 the entries 00, 01, 02, 11, 12, 22 of the inverse of
+ * Sigma_k = cov_w(guide) + eps Id, computed in float64 and rounded once.  Refused before the launch: STROTSS_EINVAL (null
+ * pointers, h, w <= 0, 3 h w > INT_MAX), STROTSS_ERANGE (r outside 1 .. STROTSS_MATTING_MAX_RADIUS, eps not finite or outside
+ * [1e-4, 1]), STROTSS_EALIGN (a pointer not 16-byte aligned). */
+int strotss_matting_prepare(const float* guide, int h, int w, int r, float eps, float* stats, void* stream);
+/* bytes of the workspace of strotss_matting_fwd_bwd (0 for h, w <= 0 or 3 h w > INT_MAX) */
+size_t strotss_matting_workspace_bytes(int h, int w);
+/* The photorealism term of one step in ONE launch (img, guide, gimg: (h, w, 3); stats from strotss_matting_prepare with the
+ * same guide, h, w and r).  Per window k and channel c: pbar = mean_w img_c, a = Sigma_k^{-1} cov_w(guide, img_c),
+ * b = pbar - a . mu_k; q_c(i) = abar_c(i) . guide(i) + bbar_c(i) with abar, bbar the means of a, b over the clipped window
+ * around i, N_i its pixel count:
+ *   loss_out[0] = (1 / (3 h w)) sum_i N_i sum_c img_c(i) (img_c(i) - q_c(i)),
+ *   gimg_c(i) += gscale (2 / (3 h w)) N_i (img_c(i) - q_c(i)).
+ * float32 throughout, covariances centred.  gscale == 0 stores nothing; a gradient value that is exactly 0 is not added (a
+ * 1 x 1 image: loss 0, gimg bit for bit).  Fixed-order reduction, no float atomics.  workspace:
+ * strotss_matting_workspace_bytes(h, w) bytes, 16-byte aligned, ZEROED before its first use (one call at a time).  Refused
+ * before the launch: STROTSS_EINVAL (null pointers, h, w <= 0, 3 h w > INT_MAX), STROTSS_ERANGE (r outside
+ * 1 .. STROTSS_MATTING_MAX_RADIUS), STROTSS_EALIGN (a pointer not 16-byte aligned). */
+int strotss_matting_fwd_bwd(const float* img, const float* guide, const float* stats, int h, int w, int r, float gscale,
+                            float* gimg, float* loss_out, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Optical flow between two frames: what strotss_flow_warp consumes, computed by the library
  * --------------------------------------------------------------------------------------- */
 /* Coarse-to-fine Horn-Schunck with warping, solved by Jacobi iterations (Meinhardt-Llopis, Sanchez, Kondermann, IPOL 2013,

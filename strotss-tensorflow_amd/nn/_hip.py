@@ -89,6 +89,7 @@ class TemporalSetT(C.Structure):
 
 MAX_DETAIL_POOLS = 3
 DETAIL_POOLS = (1, 2, 4, 8, 16)      # the pool sizes strotss_pool_mean and strotss_detail_fwd_bwd take
+MATTING_MAX_RADIUS = 4               # STROTSS_MATTING_MAX_RADIUS
 
 
 class DetailSetT(C.Structure):
@@ -203,6 +204,10 @@ SIGNATURES = {
     "strotss_detail_fwd_bwd": (_I, [_P, _I, _I, C.POINTER(DetailSetT), _P, _P, _P, _P]),
     "strotss_tv_workspace_bytes": (_Z, [_I, _I]),
     "strotss_tv_fwd_bwd": (_I, [_P, _I, _I, _F, _F, _P, _P, _P, _P]),
+    "strotss_matting_stats_bytes": (_Z, [_I, _I]),
+    "strotss_matting_prepare": (_I, [_P, _I, _I, _I, _F, _P, _P]),
+    "strotss_matting_workspace_bytes": (_Z, [_I, _I]),
+    "strotss_matting_fwd_bwd": (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P]),
     "strotss_flow_default_params": (None, [C.POINTER(FlowParamsT)]),
     "strotss_flow_workspace_bytes": (_Z, [_I, _I, C.POINTER(FlowParamsT)]),
     "strotss_optical_flow": (_I, [_P, _P, _I, _I, C.POINTER(FlowParamsT), _P, _P, _Z, _P]),

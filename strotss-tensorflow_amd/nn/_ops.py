@@ -260,6 +260,42 @@ def tv_fwd_bwd(img: torch.Tensor, gscale: float, gimg: torch.Tensor, loss_out: t
                                         stream_ptr()), "tv_fwd_bwd")
 
 
+# ------------------------------------------------------------------ photorealism term
+def matting_prepare(guide: torch.Tensor, radius: int, eps: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the window statistics of the (h, w, 3) guide for matting_fwd_bwd (strotss_matting_prepare, one launch, once per
+    scale): (9, h, w) float32, planes 0..2 the clipped window's mean, planes 3..8 the entries 00 01 02 11 12 22 of the
+    inverse of cov_w(guide) + eps Id, computed in float64.  The library refuses a radius outside 1..4 and an eps outside
+    [1e-4, 1]."""
+    h, w = _rgb_image(guide, "guide")
+    if out is None:
+        out = torch.empty((9, h, w), dtype=torch.float32, device=guide.device)
+    require(out, "window statistics")
+    assert 4 * out.numel() == _hip.lib().strotss_matting_stats_bytes(h, w)
+    check(_hip.lib().strotss_matting_prepare(ptr(guide), h, w, int(radius), float(eps), ptr(out), stream_ptr()),
+          "matting_prepare")
+    return out
+
+
+def matting_fwd_bwd(img: torch.Tensor, guide: torch.Tensor, stats: torch.Tensor, radius: int, gscale: float,
+                    gimg: torch.Tensor, loss_out: torch.Tensor, ws: Optional["Workspaces"] = None) -> None:
+    """loss_out[0] = L_photo = (1/(3hw)) sum_i N_i sum_c img_c(i) (img_c(i) - q_c(i)), q the guided filter of img by guide
+    over windows of radius `radius`; gimg += gscale * dL_photo/dimg (strotss_matting_fwd_bwd, one launch; img, guide, gimg
+    (h, w, 3) or (1, h, w, 3), stats = matting_prepare(guide, radius, eps)).  The workspace is the zeroed one per device and
+    size of `ws` (Workspaces.zeroed)."""
+    for t, name in ((img, "image"), (guide, "guide"), (stats, "window statistics"), (gimg, "pixel gradient"),
+                    (loss_out, "photo loss")):
+        require(t, name)
+    h, w, c = hwc(img)
+    assert c == 3 and guide.numel() == 3 * h * w and gimg.numel() == 3 * h * w and stats.numel() == 9 * h * w
+    lib = _hip.lib()
+    nb = int(lib.strotss_matting_workspace_bytes(h, w))
+    if nb == 0:
+        raise _hip.StrotssHipError(f"matting_fwd_bwd: bad size {h} x {w}")
+    workspace = (ws or workspaces).zeroed("matting", (h, w), nb, img.device)
+    check(lib.strotss_matting_fwd_bwd(ptr(img), ptr(guide), ptr(stats), h, w, int(radius), float(gscale), ptr(gimg),
+                                      ptr(loss_out), ptr(workspace), stream_ptr()), "matting_fwd_bwd")
+
+
 def flow_params(**overrides) -> "_hip.FlowParamsT":
     """strotss_flow_params_t with the library's defaults (strotss_flow_default_params; needs no GPU), fields overridden by
     name: alpha2, warps, iters, min_side, max_levels, iters_per_launch"""

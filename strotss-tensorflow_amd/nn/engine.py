@@ -149,6 +149,27 @@ class DetailTarget:
     cell_map: Optional[torch.Tensor] = None
 
 
+@dataclass
+class PhotoTarget:
+    """The photorealism term at one scale: `content` (h, w, 3) or (1, h, w, 3) the content image at this
+    scale (the guide), `radius` 1..4 and `eps` in [1e-4, 1] the windows and the regulariser of its matting Laplacian L,
+    `weight` >= 0.  The step adds weight * L_photo, L_photo = (1 / (3 h w)) sum_c x_c^T L x_c, to its loss: the folded image
+    may take any colours, but over every window it should be an affine function of the content's."""
+    content: torch.Tensor
+    radius: int
+    eps: float
+    weight: float
+
+
+def check_photo(radius, eps) -> None:
+    """ValueError unless radius is an integer in 1..MATTING_MAX_RADIUS and eps finite in [1e-4, 1] (at its float32 value)"""
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= _hip.MATTING_MAX_RADIUS:
+        raise ValueError(f"photo radius must be an integer in 1..{_hip.MATTING_MAX_RADIUS}, got {radius!r}")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)) or not np.isfinite(eps) or \
+            not np.float32(1e-4) <= np.float32(eps) <= np.float32(1.0):
+        raise ValueError(f"photo eps must be finite and in [1e-4, 1], got {eps!r}")
+
+
 def extract_features(params: VGGParams, image: torch.Tensor) -> List[torch.Tensor]:
     """[image] + vgg(image)  (run_strotss.py:95-96), taps cloned out of a temporary trunk."""
     h, w = int(image.shape[1]), int(image.shape[2])
@@ -241,7 +262,12 @@ class StepEngine:
     gradients join the pixel gradient right after the temporal term and before the fold adjoint -- the Laplacian detail term
     against the content (one pooling launch per pool size above 1 and one launch per pool size) and the total variation of
     the folded image (one launch).  Both are added once per step, not averaged over the regions.  A DetailTarget of weight 0
-    runs the term and leaves the step bit for bit; tv_weight 0 is no term.  One GPU only."""
+    runs the term and leaves the step bit for bit; tv_weight 0 is no term.  One GPU only.
+
+    `photo`: a PhotoTarget at this scale's size: the photorealism term, the matting Laplacian of the
+    content applied to the folded image, ONE launch after the detail and TV terms; the content's window statistics are made
+    once, here.  Added once per step, not averaged over the regions.  A PhotoTarget of weight 0 runs the term, reports it
+    and leaves the step bit for bit; None is no term.  One GPU only."""
 
     N_SCALARS = 4   # loss_c, l_moment, l_remd, l_palette per region
 
@@ -255,7 +281,7 @@ class StepEngine:
                  sinkhorn_iters: int = DEFAULT_SINKHORN_ITERS, sliced_projections: int = DEFAULT_SLICED_PROJECTIONS,
                  sliced_seed: int = 0, sinkhorn_log: bool = False, palette_transport: str = "remd",
                  palette_projections: int = DEFAULT_PALETTE_PROJECTIONS, detail: Optional[DetailTarget] = None,
-                 tv_weight: float = 0.0):
+                 tv_weight: float = 0.0, photo: Optional[PhotoTarget] = None):
         dev = stylized.device
         # the scratch memory of the losses and the trunk: the engine's own, so what its captured graphs point into lives and
         # dies with it and no other caller can regrow it (capture_graph freezes it)
@@ -352,6 +378,25 @@ class StepEngine:
         if tv_weight > 0:
             self._tv = dict(weight=float(tv_weight), loss=torch.zeros(1, dtype=torch.float32, device=dev),
                             ws=_ops.tv_workspace(h, w, dev))
+        self._photo = None
+        if photo is not None:
+            if not isinstance(photo, PhotoTarget):
+                raise ValueError(f"photo must be a PhotoTarget, got {type(photo).__name__}")
+            if strips is not None or dist_group is not None:
+                raise ValueError("the photorealism term runs on one GPU: image strips and region sharding are not supported "
+                                 "with it")
+            check_photo(photo.radius, photo.eps)
+            _check_prior_weight(photo.weight, "photo weight")
+            pc = photo.content
+            if pc.numel() != 3 * h * w or tuple(pc.shape[-3:]) != (h, w, 3):
+                raise ValueError(f"photo content of shape {tuple(pc.shape)}: expected ({h}, {w}, 3)")
+            # the engine's own fixed buffers (a captured graph reads them at replay): the guide, its window statistics, the
+            # scalar; the reduction's workspace is the engine's zeroed one for this size
+            guide = pc.float().to(dev).reshape(h, w, 3).contiguous().clone()
+            self._photo = dict(weight=float(photo.weight), radius=int(photo.radius), guide=guide,
+                               stats=_ops.matting_prepare(guide, int(photo.radius), float(photo.eps)),
+                               loss=torch.zeros(1, dtype=torch.float32, device=dev))
+            self._ws.zeroed("matting", (h, w), int(_hip.lib().strotss_matting_workspace_bytes(h, w)), dev)
         # --- variables = make_laplacian_pyramid(stylized) (run_strotss.py:89), rms slots start at 0
         from .strotss_utils import make_laplacian_pyramid
         self.variables = [v.contiguous() for v in make_laplacian_pyramid(stylized.contiguous(), levels)]
@@ -673,14 +718,17 @@ class StepEngine:
                                     t["ws"])                 # one launch for all the targets
 
     def _pixel_prior(self) -> None:
-        """gvars[0] += detail_weight * dL_detail/dx + tv_weight * dL_tv/dx and the terms' scalars, x the folded image of this
-        step (neither term: nothing)"""
-        d, t = self._detail, self._tv
+        """gvars[0] += detail_weight * dL_detail/dx + tv_weight * dL_tv/dx + photo_weight * dL_photo/dx and the terms' scalars,
+        x the folded image of this step (DESIGN.md sections 26 and 33; no term: nothing)"""
+        d, t, ph = self._detail, self._tv, self._photo
         if d is not None:
             _ops.detail_fwd_bwd(self.fold[0], d["pools"], d["contents"], d["cells"], d["gscales"], self.gvars[0], d["loss"],
                                 d["ws"])
         if t is not None:
             _ops.tv_fwd_bwd(self.fold[0], t["weight"], self.gvars[0], t["loss"], t["ws"])
+        if ph is not None:
+            _ops.matting_fwd_bwd(self.fold[0], ph["guide"], ph["stats"], ph["radius"], ph["weight"], self.gvars[0], ph["loss"],
+                                 ws=self._ws)
 
     def _fold_adjoint(self) -> None:
         """gvars[k] = up^T(gvars[k-1]): adjoint of the fold"""
@@ -930,6 +978,9 @@ class StepEngine:
         if self._tv is not None:
             out["loss_tv"] = float(self._tv["loss"].item())
             out["loss"] = out["loss"] + self._tv["weight"] * out["loss_tv"]
+        if self._photo is not None:
+            out["loss_photo"] = float(self._photo["loss"].item())
+            out["loss"] = out["loss"] + self._photo["weight"] * out["loss_photo"]
         return out
 
     def stylized(self) -> torch.Tensor:

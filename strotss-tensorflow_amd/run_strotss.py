@@ -189,6 +189,15 @@ Every reference flag is kept (run_strotss.py:165-178 there).  Additions:
   --tv_weight W     the total variation of the result, sqrt(dx^2 + dy^2 + (1/255)^2) per pixel and channel, as a term of
                     every step: penalises pixel-level grain.  Off unless given (finite, >= 0).
                     Combines as --detail_weight; one GPU, not with --strips.
+  --photo_weight W  the photorealism term of Luan et al. (2017) in every step: the matting Laplacian of
+                    the content (Levin et al. 2008) applied to the result -- the result may take any colours, but over every
+                    (2R+1) x (2R+1) window it should be an affine function of the content's colours, so straight edges stay
+                    straight and flat areas stay flat.  Off unless given (finite, >= 0).  Combines as --detail_weight,
+                    --photo_smooth included (that filters the written result, this shapes every step); with --video the
+                    guide is the current frame's content; one GPU, not with --strips.
+  --photo_radius R  with --photo_weight: the window radius, 1..4 (default 1: the 3 x 3 windows of Luan et al.)
+  --photo_eps E     with --photo_weight: the regulariser of the window covariances, 1e-4..1 (default 1e-4; a convention,
+                    not tuned)
 Under torchrun WITH masks (region-guided run, BASELINE config 4) the mask regions are dealt round-robin to the ranks:
 every rank runs the replicated trunk forward, its own regions' samples + losses and their data-gradient, ONE RCCL
 all-reduce sums the pixel gradient, every rank applies the identical update; rank 0 writes the output.
@@ -450,6 +459,30 @@ def _pixel_prior_input(args) -> dict:
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise ValueError(f"{flags} runs on one GPU: not under torchrun with WORLD_SIZE > 1")
     return dict(detail=None if dw is None else (float(dw), pools), tv=0.0 if tv is None else float(tv))
+
+
+DEFAULT_PHOTO_RADIUS, DEFAULT_PHOTO_EPS = 1, 1e-4      # the 3 x 3 windows of Luan et al.; conventions, not tuned
+
+
+def _photo_term_input(args):
+    """--photo_weight, --photo_radius, --photo_eps: (weight, radius, eps), or None when --photo_weight
+    is absent.  ValueError, before anything is loaded: a radius or an eps without the weight, a weight that is not finite or
+    negative, a radius outside 1..4, an eps outside [1e-4, 1], --strips, WORLD_SIZE > 1."""
+    weight, radius, eps = (getattr(args, k, None) for k in ("photo_weight", "photo_radius", "photo_eps"))
+    if weight is None:
+        if radius is not None or eps is not None:
+            raise ValueError("--photo_radius and --photo_eps need --photo_weight")
+        return None
+    if not np.isfinite(weight) or weight < 0:
+        raise ValueError(f"--photo_weight must be finite and >= 0, got {weight}")
+    radius = DEFAULT_PHOTO_RADIUS if radius is None else radius
+    eps = DEFAULT_PHOTO_EPS if eps is None else eps
+    strotss_engine.check_photo(radius, eps)
+    if getattr(args, "strips", False):
+        raise ValueError("--photo_weight cannot be combined with --strips")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("--photo_weight runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    return float(weight), int(radius), float(eps)
 
 
 def _photo_smooth_input(args):
@@ -1044,6 +1077,7 @@ def run(args: argparse.Namespace, trace=None):
     _style_transport_input(args)
     _palette_transport_input(args)
     _pixel_prior_input(args)
+    _photo_term_input(args)
     _auto_sample_input(args)                                 # --sample_map's refusals, then those of auto's four flags
     if getattr(args, "video", False):
         return run_video(args, trace)
@@ -1140,6 +1174,7 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
     masked = bool(getattr(args, "content_mask", None))
     transport = dict(_style_transport_input(args), **_palette_transport_input(args))
     prior = _pixel_prior_input(args)
+    photo = _photo_term_input(args)
 
     # alpha = 16 (x3500 with Keras weights), halved after every scale -- also after skipped ones
     alpha = args.alpha * 16.0 * (3500 if args.use_keras_weight else 1) / 2.0 ** first
@@ -1168,6 +1203,8 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
             terms["detail"] = strotss_engine.DetailTarget(scl_content, prior["detail"][1], prior["detail"][0], cw_scaled)
         if prior["tv"] > 0:
             terms["tv_weight"] = prior["tv"]
+        if photo is not None:                                # the photorealism term: this image's content as the guide
+            terms["photo"] = strotss_engine.PhotoTarget(scl_content, photo[1], photo[2], photo[0])
         eng = strotss_engine.StepEngine(
             vgg.params, strotss_engine.extract_features(vgg.params, scl_content),
             _style_targets(vgg.params, scl_style, style_masks, sampling, style_weights), stylized, alpha,
@@ -1415,6 +1452,14 @@ _FLAGS = (
     (("--strips",), dict(action='store_true', help="under torchrun: shard ONE image over the GPUs by image strips")),
     (("--halo",), dict(action='store_true', help="with --strips: per-layer halo EXCHANGE with the neighbouring ranks (16-row "
                                                  "windows margins, one row per layer and direction) instead of a 128-row recompute margin")),
+    (("--photo_weight",), dict(type=float, default=None, metavar='W',
+                               help="weight of the photorealism term: over every window the result should be an affine "
+                                    "function of the content's colours (off unless given; finite, >= 0)")),
+    (("--photo_radius",), dict(type=int, default=None, metavar='R',
+                               help=f"with --photo_weight: the window radius, 1..4 (default {DEFAULT_PHOTO_RADIUS})")),
+    (("--photo_eps",), dict(type=float, default=None, metavar='E',
+                            help=f"with --photo_weight: the covariance regulariser, 1e-4..1 (default {DEFAULT_PHOTO_EPS:g}, "
+                                 "not tuned)")),
     (("--sample_map",), dict(type=str, default=None, metavar='PATH',
                              help="greyscale image: where the step's sample coordinates are drawn (white densely, black only "
                                   "when nothing else is left), resized to every scale; or the word auto: a detail map "
