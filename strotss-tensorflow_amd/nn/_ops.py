@@ -106,25 +106,25 @@ def flow_warp(prev: torch.Tensor, flow_b: torch.Tensor, flow_f: Optional[torch.T
 
 
 def _zeroed_workspace(nbytes: int, device) -> torch.Tensor:
-    """a zeroed workspace of `nbytes` (at least 16) for one of the ticketed reductions: the call's ticket counter starts at 0
-    and every call leaves it there.  One per caller that may run concurrently (an engine owns its own)."""
+    """the allocator behind Workspaces.zeroed: `nbytes` (at least 16) of zeros; a ticketed reduction's counter returns to 0"""
     return torch.zeros(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
 
-def temporal_workspace(h: int, w: int, device) -> torch.Tensor:
-    """a zeroed workspace of strotss_temporal_fwd_bwd for (h, w): temporal_multi_workspace for one target"""
-    return temporal_multi_workspace(h, w, 1, device)
+def term_workspace(tag: str, h: int, w: int, device, ws: Optional["Workspaces"] = None, count: Optional[int] = None):
+    """the zeroed workspace (Workspaces.zeroed of `ws`, None: the module-level instance) of a pixel-space term for (h, w): tag
+    "temporal" (with `count` targets: the partials' layout depends on it), "detail", "tv" or "matting"; the library's bytes"""
+    key = (int(h), int(w)) + (() if count is None else (int(count),))
+    nb = getattr(_hip.lib(), f"strotss_{'temporal_multi' if tag == 'temporal' else tag}_workspace_bytes")(*key)
+    if nb == 0:
+        raise _hip.StrotssHipError(f"{tag} workspace: bad size {key}")
+    return (ws or workspaces).zeroed(tag, key, int(nb), device)
 
 
 def temporal_fwd_bwd(img: torch.Tensor, target: torch.Tensor, certainty: torch.Tensor, gscale: float, gimg: torch.Tensor,
                      loss_out: torch.Tensor, workspace: Optional[torch.Tensor] = None, ws: Optional["Workspaces"] = None) -> None:
     """loss_out[0] = (1/(3hw)) sum_p certainty(p) |img(p) - target(p)|^2, gimg += gscale * dloss/dimg: temporal_multi_fwd_bwd
-    with one target.  workspace: from temporal_workspace, or None for the one per device and size of `ws` (Workspaces.zeroed)."""
-    if workspace is None:
-        h, w, _ = hwc(img)
-        nb = _hip.lib().strotss_temporal_multi_workspace_bytes(h, w, 1)
-        workspace = (ws or workspaces).zeroed("temporal", (h, w), nb, img.device)
-    temporal_multi_fwd_bwd(img, [target], [certainty], [gscale], gimg, loss_out, workspace)
+    with one target (its zeroed workspace, without an explicit one, is the "temporal" one of key (h, w, 1))"""
+    temporal_multi_fwd_bwd(img, [target], [certainty], [gscale], gimg, loss_out, workspace, ws)
 
 
 def temporal_long_certainty(stack: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -143,17 +143,12 @@ def temporal_long_certainty(stack: torch.Tensor, out: Optional[torch.Tensor] = N
     return out
 
 
-def temporal_multi_workspace(h: int, w: int, count: int, device) -> torch.Tensor:
-    """a zeroed workspace of strotss_temporal_multi_fwd_bwd for (h, w) and `count` targets"""
-    return _zeroed_workspace(_hip.lib().strotss_temporal_multi_workspace_bytes(int(h), int(w), int(count)), device)
-
-
 def temporal_multi_fwd_bwd(img: torch.Tensor, targets: Sequence[torch.Tensor], certainties: Sequence[torch.Tensor],
                            gscales: Sequence[float], gimg: torch.Tensor, loss_out: torch.Tensor,
-                           workspace: torch.Tensor) -> None:
+                           workspace: Optional[torch.Tensor] = None, ws: Optional["Workspaces"] = None) -> None:
     """loss_out[j] = (1/(3hw)) sum_p certainties[j](p) |img(p) - targets[j](p)|^2 for every j, gimg += sum_j gscales[j] *
     dloss_j/dimg in ONE launch (strotss_temporal_multi_fwd_bwd; img, targets, gimg (h, w, 3) or (1, h, w, 3), certainties
-    (h, w)).  workspace: temporal_multi_workspace(h, w, len(targets))."""
+    (h, w)).  workspace: an explicit zeroed one of the library's size, or None for term_workspace's of `ws`."""
     count = len(targets)
     if not 1 <= count <= _hip.MAX_TEMPORAL or len(certainties) != count or len(gscales) != count:
         raise ValueError(f"{count} temporal targets, {len(certainties)} certainties, {len(gscales)} weights: expected "
@@ -162,6 +157,7 @@ def temporal_multi_fwd_bwd(img: torch.Tensor, targets: Sequence[torch.Tensor], c
         require(t, name)
     h, w, c = hwc(img)
     assert c == 3 and gimg.numel() == 3 * h * w and loss_out.numel() >= count
+    workspace = term_workspace("temporal", h, w, img.device, ws, count) if workspace is None else workspace
     s = _hip.TemporalSetT()
     s.count = count
     for j, (tg, ce, g) in enumerate(zip(targets, certainties, gscales)):
@@ -208,17 +204,12 @@ def pool_mean(img: torch.Tensor, p: int, out: Optional[torch.Tensor] = None) -> 
     return out
 
 
-def detail_workspace(h: int, w: int, device) -> torch.Tensor:
-    """a zeroed workspace of strotss_detail_fwd_bwd for (h, w)"""
-    return _zeroed_workspace(_hip.lib().strotss_detail_workspace_bytes(int(h), int(w)), device)
-
-
 def detail_fwd_bwd(img: torch.Tensor, pools: Sequence[int], contents: Sequence[torch.Tensor],
                    weights: Sequence[Optional[torch.Tensor]], gscales: Sequence[float], gimg: torch.Tensor,
-                   loss_out: torch.Tensor, workspace: torch.Tensor) -> None:
+                   loss_out: torch.Tensor, workspace: Optional[torch.Tensor] = None, ws: Optional["Workspaces"] = None) -> None:
     """loss_out[j] = the Laplacian detail term of pool size pools[j], gimg += sum_j gscales[j] * dloss_j/dimg
     (strotss_detail_fwd_bwd; img, gimg (h, w, 3) or (1, h, w, 3), contents[j] = pool_mean(content, pools[j]), weights[j] the
-    (hp, wp) cell weights or None).  workspace: detail_workspace(h, w)."""
+    (hp, wp) cell weights or None).  workspace: as temporal_multi_fwd_bwd's."""
     count = len(pools)
     if not 1 <= count <= _hip.MAX_DETAIL_POOLS or len(contents) != count or len(weights) != count or len(gscales) != count:
         raise ValueError(f"{count} pool sizes, {len(contents)} pooled contents, {len(weights)} cell weights, {len(gscales)} "
@@ -227,6 +218,7 @@ def detail_fwd_bwd(img: torch.Tensor, pools: Sequence[int], contents: Sequence[t
         require(t, name)
     h, w, c = hwc(img)
     assert c == 3 and gimg.numel() == 3 * h * w and loss_out.numel() >= count
+    workspace = term_workspace("detail", h, w, img.device, ws) if workspace is None else workspace
     s = _hip.DetailSetT()
     s.count = count
     for j, (p, ct, wt, g) in enumerate(zip(pools, contents, weights, gscales)):
@@ -243,19 +235,15 @@ def detail_fwd_bwd(img: torch.Tensor, pools: Sequence[int], contents: Sequence[t
                                             stream_ptr()), "detail_fwd_bwd")
 
 
-def tv_workspace(h: int, w: int, device) -> torch.Tensor:
-    """a zeroed workspace of strotss_tv_fwd_bwd for (h, w)"""
-    return _zeroed_workspace(_hip.lib().strotss_tv_workspace_bytes(int(h), int(w)), device)
-
-
-def tv_fwd_bwd(img: torch.Tensor, gscale: float, gimg: torch.Tensor, loss_out: torch.Tensor, workspace: torch.Tensor,
-               eps: float = TV_EPS) -> None:
+def tv_fwd_bwd(img: torch.Tensor, gscale: float, gimg: torch.Tensor, loss_out: torch.Tensor,
+               workspace: Optional[torch.Tensor] = None, ws: Optional["Workspaces"] = None, eps: float = TV_EPS) -> None:
     """loss_out[0] = (1/(3hw)) sum (sqrt(dx^2 + dy^2 + eps^2) - eps), gimg += gscale * dloss/dimg (strotss_tv_fwd_bwd; img,
-    gimg (h, w, 3) or (1, h, w, 3)).  workspace: tv_workspace(h, w)."""
+    gimg (h, w, 3) or (1, h, w, 3)).  workspace: as temporal_multi_fwd_bwd's."""
     for t, name in ((img, "image"), (gimg, "pixel gradient"), (loss_out, "tv loss")):
         require(t, name)
     h, w, c = hwc(img)
     assert c == 3 and gimg.numel() == 3 * h * w
+    workspace = term_workspace("tv", h, w, img.device, ws) if workspace is None else workspace
     check(_hip.lib().strotss_tv_fwd_bwd(ptr(img), h, w, float(eps), float(gscale), ptr(gimg), ptr(loss_out), ptr(workspace),
                                         stream_ptr()), "tv_fwd_bwd")
 
@@ -277,23 +265,19 @@ def matting_prepare(guide: torch.Tensor, radius: int, eps: float, out: Optional[
 
 
 def matting_fwd_bwd(img: torch.Tensor, guide: torch.Tensor, stats: torch.Tensor, radius: int, gscale: float,
-                    gimg: torch.Tensor, loss_out: torch.Tensor, ws: Optional["Workspaces"] = None) -> None:
+                    gimg: torch.Tensor, loss_out: torch.Tensor, workspace: Optional[torch.Tensor] = None,
+                    ws: Optional["Workspaces"] = None) -> None:
     """loss_out[0] = L_photo = (1/(3hw)) sum_i N_i sum_c img_c(i) (img_c(i) - q_c(i)), q the guided filter of img by guide
     over windows of radius `radius`; gimg += gscale * dL_photo/dimg (strotss_matting_fwd_bwd, one launch; img, guide, gimg
-    (h, w, 3) or (1, h, w, 3), stats = matting_prepare(guide, radius, eps)).  The workspace is the zeroed one per device and
-    size of `ws` (Workspaces.zeroed)."""
+    (h, w, 3) or (1, h, w, 3), stats = matting_prepare(guide, radius, eps)).  workspace: as temporal_multi_fwd_bwd's."""
     for t, name in ((img, "image"), (guide, "guide"), (stats, "window statistics"), (gimg, "pixel gradient"),
                     (loss_out, "photo loss")):
         require(t, name)
     h, w, c = hwc(img)
     assert c == 3 and guide.numel() == 3 * h * w and gimg.numel() == 3 * h * w and stats.numel() == 9 * h * w
-    lib = _hip.lib()
-    nb = int(lib.strotss_matting_workspace_bytes(h, w))
-    if nb == 0:
-        raise _hip.StrotssHipError(f"matting_fwd_bwd: bad size {h} x {w}")
-    workspace = (ws or workspaces).zeroed("matting", (h, w), nb, img.device)
-    check(lib.strotss_matting_fwd_bwd(ptr(img), ptr(guide), ptr(stats), h, w, int(radius), float(gscale), ptr(gimg),
-                                      ptr(loss_out), ptr(workspace), stream_ptr()), "matting_fwd_bwd")
+    workspace = term_workspace("matting", h, w, img.device, ws) if workspace is None else workspace
+    check(_hip.lib().strotss_matting_fwd_bwd(ptr(img), ptr(guide), ptr(stats), h, w, int(radius), float(gscale), ptr(gimg),
+                                             ptr(loss_out), ptr(workspace), stream_ptr()), "matting_fwd_bwd")
 
 
 def flow_params(**overrides) -> "_hip.FlowParamsT":

@@ -14,14 +14,17 @@ strotss_utils.py:83-121), so identical index streams give comparable trajectorie
 from __future__ import annotations
 
 import gc
+import os
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Union
 
 import numpy as np
 import torch
 
-from . import _hip, _ops, parallel, rand
+from . import _hip, _ops, parallel, pixel_terms, rand
 from .model import VGGParams, VGGTrunk
+from .pixel_terms import DetailTarget, PhotoTarget, TemporalTarget, _check_prior_weight, check_photo     # also for callers
+from .strotss_utils import check_content_weight, make_laplacian_pyramid
 
 
 @dataclass
@@ -119,55 +122,11 @@ def check_palette_transport(palette_transport, palette_projections=DEFAULT_PALET
                          f"got {palette_projections!r}")
 
 
-def _check_prior_weight(weight, name: str) -> None:
-    """ValueError unless `weight` is a real number, not a bool, finite and >= 0"""
-    if isinstance(weight, bool) or not isinstance(weight, (int, float, np.integer, np.floating)) or \
-            not np.isfinite(weight) or weight < 0:
-        raise ValueError(f"{name} must be finite and >= 0, got {weight!r}")
-
-
-@dataclass
-class TemporalTarget:
-    """The temporal term of a frame sequence at one scale: `target` (h, w, 3) the warped previous
-    frame, `certainty` (h, w) its certainty, `weight` lambda >= 0.  The step adds
-    lambda * L_t = lambda / (3 h w) * sum_p c(p) |x(p) - target(p)|^2 to its loss (strotss_utils.temporal_target_at_scale
-    builds the two arrays)."""
-    target: torch.Tensor
-    certainty: torch.Tensor
-    weight: float
-
-
-@dataclass
-class DetailTarget:
-    """The Laplacian detail term at one scale: `content` (h, w, 3) or (1, h, w, 3) the content image at
-    this scale, `pools` 1..3 distinct pool sizes of {1, 2, 4, 8, 16}, ascending, `weight` >= 0, `cell_map` an optional (h, w)
-    map, finite and >= 0, whose pooled values weigh the cells (the content-weight map at this scale).  The step adds
-    weight * sum_p L_p, L_p = (1 / (3 hp wp)) sum_k m_p(k) |L (P_p(x) - P_p(content))(k)|^2, to its loss."""
-    content: torch.Tensor
-    pools: Sequence[int]
-    weight: float
-    cell_map: Optional[torch.Tensor] = None
-
-
-@dataclass
-class PhotoTarget:
-    """The photorealism term at one scale: `content` (h, w, 3) or (1, h, w, 3) the content image at this
-    scale (the guide), `radius` 1..4 and `eps` in [1e-4, 1] the windows and the regulariser of its matting Laplacian L,
-    `weight` >= 0.  The step adds weight * L_photo, L_photo = (1 / (3 h w)) sum_c x_c^T L x_c, to its loss: the folded image
-    may take any colours, but over every window it should be an affine function of the content's."""
-    content: torch.Tensor
-    radius: int
-    eps: float
-    weight: float
-
-
-def check_photo(radius, eps) -> None:
-    """ValueError unless radius is an integer in 1..MATTING_MAX_RADIUS and eps finite in [1e-4, 1] (at its float32 value)"""
-    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= _hip.MATTING_MAX_RADIUS:
-        raise ValueError(f"photo radius must be an integer in 1..{_hip.MATTING_MAX_RADIUS}, got {radius!r}")
-    if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)) or not np.isfinite(eps) or \
-            not np.float32(1e-4) <= np.float32(eps) <= np.float32(1.0):
-        raise ValueError(f"photo eps must be finite and in [1e-4, 1], got {eps!r}")
+def _require_one_gpu(what: str, strips, dist_group, plural: bool = False) -> None:
+    """ValueError when an option that runs on one GPU (`what`; plural: "the ... run") meets image strips or region sharding"""
+    if strips is not None or dist_group is not None:
+        runs, it = ("run", "them") if plural else ("runs", "it")
+        raise ValueError(f"{what} {runs} on one GPU: image strips and region sharding are not supported with {it}")
 
 
 def extract_features(params: VGGParams, image: torch.Tensor) -> List[torch.Tensor]:
@@ -232,10 +191,11 @@ class StepEngine:
     builds it from a user's map): the content term of every region weights sample j's column of the self-similarity
     matrices by the map at sample j.  One GPU only: not with `strips` or `dist_group`.
 
-    `temporal`: a TemporalTarget at this scale's size: the pixel gradient gets lambda * dL_t/dx after the trunk (and the
-    all-reduce) and before the fold adjoint, in ONE launch.  One GPU only, as the map above.  A
-    sequence of 1..4 TemporalTargets (their certainties already combined, nearest frame first) adds
-    every term in ONE launch as well; one element is the TemporalTarget itself.
+    `temporal`, `detail`, `tv_weight`, `photo`: the pixel-space terms (nn/pixel_terms.py; DESIGN.md sections 12, 13, 26, 33) at
+    this scale's size: a TemporalTarget or a sequence of 1..4 (certainties already combined, nearest frame first; one element
+    is the TemporalTarget itself), a DetailTarget, the total variation's weight (0: no term), a PhotoTarget.  In that order
+    their gradients join the pixel gradient after the trunk (and the all-reduce) and before the fold adjoint, once per step, not
+    averaged over the regions; the bound terms there state the launches and what a weight of 0 does.  One GPU only, as the map.
 
     `style_transport`: "remd" (the relaxed EMD) or "sinkhorn" (DESIGN.md section 20): the entropic transport cost
     sinkhorn_knopp(target, prediction, 'cosine', sinkhorn_l, sinkhorn_iters) takes the place of the cosine relaxed EMD in
@@ -256,18 +216,7 @@ class StepEngine:
     every region and every style of a blend, with the same weight and in the same scalar slot (l_palette, also returned as
     l_palette_sliced).  It conserves mass, which the relaxed EMD does not.  With "sliced" every `style_transport` takes the
     separate entries: with "remd" that is their 21 launches (19 with the new term's 2 in place of the palette relaxed EMD's
-    4), not the grouped call's 13.  One GPU only.
-
-    `detail`: a DetailTarget at this scale's size, `tv_weight` > 0: two pixel-space priors whose
-    gradients join the pixel gradient right after the temporal term and before the fold adjoint -- the Laplacian detail term
-    against the content (one pooling launch per pool size above 1 and one launch per pool size) and the total variation of
-    the folded image (one launch).  Both are added once per step, not averaged over the regions.  A DetailTarget of weight 0
-    runs the term and leaves the step bit for bit; tv_weight 0 is no term.  One GPU only.
-
-    `photo`: a PhotoTarget at this scale's size: the photorealism term, the matting Laplacian of the
-    content applied to the folded image, ONE launch after the detail and TV terms; the content's window statistics are made
-    once, here.  Added once per step, not averaged over the regions.  A PhotoTarget of weight 0 runs the term, reports it
-    and leaves the step bit for bit; None is no term.  One GPU only."""
+    4), not the grouped call's 13.  One GPU only."""
 
     N_SCALARS = 4   # loss_c, l_moment, l_remd, l_palette per region
 
@@ -288,11 +237,16 @@ class StepEngine:
         self._ws = _ops.Workspaces()
         check_palette_transport(palette_transport, palette_projections)
         check_style_transport(style_transport, sinkhorn_l, sinkhorn_iters, sliced_projections, sinkhorn_log)
-        for chosen, what in ((palette_transport == "sliced", "the sliced palette term"),
-                             (style_transport == "sinkhorn", "the Sinkhorn style term"),
-                             (style_transport == "sliced", "the sliced style term")):
-            if chosen and (strips is not None or dist_group is not None):
-                raise ValueError(f"{what} runs on one GPU: image strips and region sharding are not supported with it")
+        _check_prior_weight(tv_weight, "tv_weight")
+        for chosen, what, plural in ((palette_transport == "sliced", "the sliced palette term", False),
+                                     (style_transport == "sinkhorn", "the Sinkhorn style term", False),
+                                     (style_transport == "sliced", "the sliced style term", False),
+                                     (content_weight is not None, "a content-weight map", False),
+                                     (temporal is not None, "the temporal term", False),
+                                     (detail is not None or tv_weight > 0, "the pixel-space priors (detail, tv_weight)", True),
+                                     (photo is not None, "the photorealism term", False)):
+            if chosen:
+                _require_one_gpu(what, strips, dist_group, plural)
         self.palette_transport, self.palette_projections = palette_transport, int(palette_projections)
         # the sliced palette term's directions: fixed for the life of the engine (a captured graph reads them at replay)
         self._palette_dirs = (torch.from_numpy(rand.palette_directions(self.palette_projections)).to(dev).contiguous()
@@ -313,99 +267,21 @@ class StepEngine:
         if self._blended and (self.R > 1 or strips is not None or dist_group is not None):
             raise ValueError("style blending runs one region on one GPU: masks, image strips and region sharding are not "
                              "supported with several styles")
-        h, w = int(stylized.shape[1]), int(stylized.shape[2])
-        self.h, self.w = h, w
+        h, w = self.h, self.w = int(stylized.shape[1]), int(stylized.shape[2])
         self._cw_map = None
         if content_weight is not None:
-            if strips is not None or dist_group is not None:
-                raise ValueError("a content-weight map runs on one GPU: image strips and region sharding are not supported "
-                                 "with it")
-            from .strotss_utils import check_content_weight
             self._cw_map = check_content_weight(content_weight, h, w).to(dev).clone()     # the engine's own copy
-        self._temporal = None
-        if temporal is not None:
-            # one target, or a list of them: long-term targets, nearest frame first
-            terms = [temporal] if isinstance(temporal, TemporalTarget) else list(temporal)
-            if not 1 <= len(terms) <= _hip.MAX_TEMPORAL:
-                raise ValueError(f"the temporal term takes 1..{_hip.MAX_TEMPORAL} targets, got {len(terms)}")
-            if strips is not None or dist_group is not None:
-                raise ValueError("the temporal term runs on one GPU: image strips and region sharding are not supported "
-                                 "with it")
-            for tt in terms:
-                if not isinstance(tt, TemporalTarget):
-                    raise ValueError(f"temporal targets must be TemporalTarget, got {type(tt).__name__}")
-                lam = float(tt.weight)
-                if not np.isfinite(lam) or lam < 0:
-                    raise ValueError(f"temporal weight must be finite and >= 0, got {tt.weight}")
-                tgt, cert = tt.target, tt.certainty
-                if tgt.numel() != 3 * h * w or tuple(tgt.shape[-3:]) != (h, w, 3):
-                    raise ValueError(f"temporal target of shape {tuple(tgt.shape)}: expected ({h}, {w}, 3)")
-                if cert.numel() != h * w or tuple(cert.shape[-2:]) != (h, w):
-                    raise ValueError(f"temporal certainty of shape {tuple(cert.shape)}: expected ({h}, {w})")
-            # the engine's own fixed buffers (a captured graph reads them at replay) + the scalars and the reduction's
-            # workspace
-            targets = [tt.target.float().to(dev).reshape(h, w, 3).contiguous().clone() for tt in terms]
-            certainties = [tt.certainty.float().to(dev).reshape(h, w).contiguous().clone() for tt in terms]
-            self._temporal = dict(weights=[float(tt.weight) for tt in terms], targets=targets, certainties=certainties,
-                                  loss=torch.zeros(len(terms), dtype=torch.float32, device=dev),
-                                  ws=_ops.temporal_multi_workspace(h, w, len(terms), dev))
-        self._detail = self._tv = None
-        _check_prior_weight(tv_weight, "tv_weight")
-        if (detail is not None or tv_weight > 0) and (strips is not None or dist_group is not None):
-            raise ValueError("the pixel-space priors (detail, tv_weight) run on one GPU: image strips and region sharding are "
-                             "not supported with them")
-        if detail is not None:
-            if not isinstance(detail, DetailTarget):
-                raise ValueError(f"detail must be a DetailTarget, got {type(detail).__name__}")
-            pools = _ops.check_detail_pools(detail.pools)
-            dwt = detail.weight
-            _check_prior_weight(dwt, "detail weight")
-            dc = detail.content
-            if dc.numel() != 3 * h * w or tuple(dc.shape[-3:]) != (h, w, 3):
-                raise ValueError(f"detail content of shape {tuple(dc.shape)}: expected ({h}, {w}, 3)")
-            cells = [None] * len(pools)
-            if detail.cell_map is not None:
-                from .strotss_utils import check_content_weight
-                cmap = check_content_weight(detail.cell_map, h, w).to(dev).reshape(h, w, 1).contiguous()
-                cells = [_ops.pool_mean(cmap, p).reshape(_ops.pooled_shape(h, w, p)) for p in pools]
-            # the engine's own fixed buffers (a captured graph reads them at replay): the content pooled by the kernel that
-            # pools the step's image, the pooled map, the scalars and the workspace
-            dc = dc.float().to(dev).reshape(h, w, 3).contiguous()
-            self._detail = dict(weight=float(dwt), pools=pools, contents=[_ops.pool_mean(dc, p) for p in pools], cells=cells,
-                                gscales=[float(dwt)] * len(pools),
-                                loss=torch.zeros(len(pools), dtype=torch.float32, device=dev),
-                                ws=_ops.detail_workspace(h, w, dev))
-        if tv_weight > 0:
-            self._tv = dict(weight=float(tv_weight), loss=torch.zeros(1, dtype=torch.float32, device=dev),
-                            ws=_ops.tv_workspace(h, w, dev))
-        self._photo = None
-        if photo is not None:
-            if not isinstance(photo, PhotoTarget):
-                raise ValueError(f"photo must be a PhotoTarget, got {type(photo).__name__}")
-            if strips is not None or dist_group is not None:
-                raise ValueError("the photorealism term runs on one GPU: image strips and region sharding are not supported "
-                                 "with it")
-            check_photo(photo.radius, photo.eps)
-            _check_prior_weight(photo.weight, "photo weight")
-            pc = photo.content
-            if pc.numel() != 3 * h * w or tuple(pc.shape[-3:]) != (h, w, 3):
-                raise ValueError(f"photo content of shape {tuple(pc.shape)}: expected ({h}, {w}, 3)")
-            # the engine's own fixed buffers (a captured graph reads them at replay): the guide, its window statistics, the
-            # scalar; the reduction's workspace is the engine's zeroed one for this size
-            guide = pc.float().to(dev).reshape(h, w, 3).contiguous().clone()
-            self._photo = dict(weight=float(photo.weight), radius=int(photo.radius), guide=guide,
-                               stats=_ops.matting_prepare(guide, int(photo.radius), float(photo.eps)),
-                               loss=torch.zeros(1, dtype=torch.float32, device=dev))
-            self._ws.zeroed("matting", (h, w), int(_hip.lib().strotss_matting_workspace_bytes(h, w)), dev)
+        # the pixel-space terms that are set, in the order they run and report; their zeroed workspaces are self._ws's
+        self._pixel_terms = [term(arg, h, w, dev, self._ws) for term, arg, on in (
+            (pixel_terms.TemporalTerm, temporal, temporal is not None), (pixel_terms.DetailTerm, detail, detail is not None),
+            (pixel_terms.TVTerm, tv_weight, tv_weight > 0), (pixel_terms.PhotoTerm, photo, photo is not None)) if on]
         # --- variables = make_laplacian_pyramid(stylized) (run_strotss.py:89), rms slots start at 0
-        from .strotss_utils import make_laplacian_pyramid
         self.variables = [v.contiguous() for v in make_laplacian_pyramid(stylized.contiguous(), levels)]
         self.rms = [torch.zeros_like(v) for v in self.variables]
         self.sizes = [(int(v.shape[1]), int(v.shape[2])) for v in self.variables]
         # fold temporaries: f[k] = v[k] + up(f[k+1]); f[0] is the image
         self.fold = [torch.empty_like(v) for v in self.variables[:-1]]
-        import os as _os
-        self._fold_one_launch = None if _os.environ.get("STROTSS_FOLD_ONE_LAUNCH", "1") != "0" else False
+        self._fold_one_launch = None if os.environ.get("STROTSS_FOLD_ONE_LAUNCH", "1") != "0" else False
         # image strips (nn/parallel.py): the trunk covers rows [win0, win1) only; everything else is full-size
         self.strips = strips
         win0, win1 = (strips.win0, strips.win1) if strips is not None else (0, h)
@@ -500,7 +376,6 @@ class StepEngine:
         self._idx: List[Optional[torch.Tensor]] = [None] * self.R
         # deterministic mode (STROTSS_DETERMINISTIC=1): the tap adjoint as a sorted scatter, one plan per region and step
         # (no float atomics -> bitwise reproducible steps; the reference asks TF for the same: nn/rand.py:4-8)
-        import os
         # default: off with a GPU to itself; ON when two ranks of the group sit on one card (parallel.ranks_share_a_gpu)
         env = os.environ.get("STROTSS_DETERMINISTIC")
         self.deterministic = bool(deterministic) if deterministic is not None else \
@@ -641,8 +516,8 @@ class StepEngine:
     def _stages(self, indices: Optional[Sequence[torch.Tensor]], apply: bool = True):
         """The step as [(device segment, host collective after it or None)], a segment a list of calls: what the eager step
         runs, capture_graph captures (one graph per segment) and a replay interleaves with the same collectives.
-            plain            [pixel gradient, temporal, pixel priors, fold adjoint]
-            region-sharded   [pixel gradient] | all-reduce _reduce_buf | [temporal, pixel priors, fold adjoint]
+            plain            [pixel gradient, pixel terms, fold adjoint]
+            region-sharded   [pixel gradient] | all-reduce _reduce_buf | [pixel terms, fold adjoint]
             image strips     [_strip_stage_a] | all-reduce _pf_all | [_strip_stage_b] | all-reduce gimg_full | [fold adjoint]
         apply: apply_gradients ends the last segment.  indices: the index sets of the pixel gradient, None = the draw kernel
         at the head of the step (image strips: the sets _strip_inputs has put in place)."""
@@ -653,7 +528,7 @@ class StepEngine:
                     ([self._strip_stage_b], lambda: parallel.allreduce_sum_(self.gimg_full, self.group)),
                     (end, None)]
         head = [lambda: self._pixel_gradient(self._draw_indices() if indices is None else indices)]
-        tail = [self._temporal_term, self._pixel_prior] + end
+        tail = [self._run_pixel_terms] + end
         return [(head, self._reduce), (tail, None)] if self.sharded else [(head + tail, None)]
 
     @staticmethod
@@ -709,26 +584,10 @@ class StepEngine:
         if self._reduce_buf is not None:
             parallel.allreduce_sum_(self._reduce_buf, self.group)
 
-    def _temporal_term(self) -> None:
-        """gvars[0] += lambda * dL_t/dx and the scalar L_t, x the folded image of this step (no temporal target: nothing)"""
-        t = self._temporal
-        if t is None:
-            return
-        _ops.temporal_multi_fwd_bwd(self.fold[0], t["targets"], t["certainties"], t["weights"], self.gvars[0], t["loss"],
-                                    t["ws"])                 # one launch for all the targets
-
-    def _pixel_prior(self) -> None:
-        """gvars[0] += detail_weight * dL_detail/dx + tv_weight * dL_tv/dx + photo_weight * dL_photo/dx and the terms' scalars,
-        x the folded image of this step (DESIGN.md sections 26 and 33; no term: nothing)"""
-        d, t, ph = self._detail, self._tv, self._photo
-        if d is not None:
-            _ops.detail_fwd_bwd(self.fold[0], d["pools"], d["contents"], d["cells"], d["gscales"], self.gvars[0], d["loss"],
-                                d["ws"])
-        if t is not None:
-            _ops.tv_fwd_bwd(self.fold[0], t["weight"], self.gvars[0], t["loss"], t["ws"])
-        if ph is not None:
-            _ops.matting_fwd_bwd(self.fold[0], ph["guide"], ph["stats"], ph["radius"], ph["weight"], self.gvars[0], ph["loss"],
-                                 ws=self._ws)
+    def _run_pixel_terms(self) -> None:
+        """gvars[0] += weight * dL/dx and the scalars of every pixel-space term in turn, x the folded image of this step"""
+        for term in self._pixel_terms:
+            term.run(self.fold[0], self.gvars[0])
 
     def _fold_adjoint(self) -> None:
         """gvars[k] = up^T(gvars[k-1]): adjoint of the fold"""
@@ -882,7 +741,7 @@ class StepEngine:
         are snapshotted around the warm-up and capture passes; the warm-up is one whole eager step, collectives included.
         It sizes the engine's own workspaces (self._ws), which are then frozen: the graphs point into memory that belongs to
         this engine, that no other caller can regrow and that a later eager step of the engine's may not reallocate either.
-        Sharded regions (world > 1): TWO graphs, [fold .. pixel gradient] and [temporal + fold adjoint + RMSprop], the
+        Sharded regions (world > 1): TWO graphs, [fold .. pixel gradient] and [pixel terms + fold adjoint + RMSprop], the
         all-reduce launched between their replays.  Image strips (recompute margin; example_offsets = the block offsets of
         example_indices): THREE graphs, [fold .. gathers], [losses .. pixel gradient of the window], [fold adjoint + RMSprop],
         the two all-reduces between their replays; the block of samples a rank owns changes every step and is read from
@@ -963,24 +822,8 @@ class StepEngine:
             out["l_palette_sliced"] = out["l_palette"]
         if per_style is not None:
             out["per_style"] = per_style         # one dict per style of the blend: its weight and unweighted terms
-        t = self._temporal
-        if t is not None:                        # loss_t = sum_j L_j, loss + sum_j lambda_j L_j: once per step, not averaged
-            terms = [float(v) for v in t["loss"].tolist()]     # over the regions
-            out["loss_t"] = float(sum(terms))
-            if len(terms) > 1:
-                out["loss_t_terms"] = terms
-            out["loss"] = float(loss) + sum(lam * lt for lam, lt in zip(t["weights"], terms))
-        if self._detail is not None:             # the pixel-space priors: once per step as well
-            terms = [float(v) for v in self._detail["loss"].tolist()]
-            out["loss_detail"] = float(sum(terms))
-            out["loss_detail_terms"] = terms
-            out["loss"] = out["loss"] + self._detail["weight"] * out["loss_detail"]
-        if self._tv is not None:
-            out["loss_tv"] = float(self._tv["loss"].item())
-            out["loss"] = out["loss"] + self._tv["weight"] * out["loss_tv"]
-        if self._photo is not None:
-            out["loss_photo"] = float(self._photo["loss"].item())
-            out["loss"] = out["loss"] + self._photo["weight"] * out["loss_photo"]
+        for term in self._pixel_terms:           # once per step, not averaged over the regions; added in the list's order
+            out["loss"] = out["loss"] + term.report(out)
         return out
 
     def stylized(self) -> torch.Tensor:

@@ -4,7 +4,8 @@ tests/_pixel_prior_cases.py (losses to 1e-5 relative, gradients element-wise wit
 of max|ref|), the zero-weight, exact-copy and constant-image cases bit for bit, accumulation into a pre-filled gradient,
 every argument refusal, the engine's step with both terms against the float64 step of tests/_pixel_prior_step.py, zero
 weights against an engine without the terms (bit for bit, eager and captured), graph / eager / host-draw equality in
-deterministic mode, and --detail_weight / --tv_weight end to end.
+deterministic mode, two engines with all four pixel-space terms stepped alternately against one stepped alone, and
+--detail_weight / --tv_weight end to end.
 
 End to end at --max_size 64 --level 1 --max_iter 30, deterministic, on tests/golden's images (DESIGN.md section 26 records the
 same figures): E_d, the mean squared D_4 of the written result against the content, with --detail_weight off and at
@@ -56,13 +57,13 @@ def test_pool_mean_matches_float64(hw_p, ch):
 def _detail_call(P, x, gscales, g, weights="case", loss=None):
     """one strotss_detail_fwd_bwd on the case's content and cell weights -> the (count,) losses"""
     from nn import _ops
-    h, w, pools = P["h"], P["w"], P["pools"]
+    pools = P["pools"]
     cd = _dev(P["c"])
     contents = [_ops.pool_mean(cd, p) for p in pools]
     wts = P["weights"] if weights == "case" else weights
     cells = [None if m is None else _dev(m) for m in wts]
     loss = torch.full((len(pools),), -1.0, device=DEV) if loss is None else loss
-    _ops.detail_fwd_bwd(x, pools, contents, cells, gscales, g, loss, _ops.detail_workspace(h, w, DEV))
+    _ops.detail_fwd_bwd(x, pools, contents, cells, gscales, g, loss, ws=_ops.Workspaces())       # a fresh zeroed workspace
     torch.cuda.synchronize()
     return loss
 
@@ -134,7 +135,7 @@ def test_detail_of_a_bit_copy_of_the_content_is_exactly_zero(label):
 def _tv_call(P, x, gscale, g):
     from nn import _ops
     loss = torch.full((1,), -1.0, device=DEV)
-    _ops.tv_fwd_bwd(x, gscale, g, loss, _ops.tv_workspace(P["h"], P["w"], DEV))
+    _ops.tv_fwd_bwd(x, gscale, g, loss, ws=_ops.Workspaces())        # a fresh zeroed workspace
     torch.cuda.synchronize()
     return loss
 
@@ -291,11 +292,12 @@ def test_engine_step_with_both_terms_matches_the_float64_step(lb):
     # both terms are real parts of the step
     assert PS.DETAIL_WEIGHT * ref["loss_detail"] > 0.05 * float(ref["loss"])
     assert PS.TV_WEIGHT * ref["loss_tv"] > 0.05 * float(ref["loss"])
+    from nn import pixel_terms
+    cells = next(t for t in eng._pixel_terms if isinstance(t, pixel_terms.DetailTerm)).cells
     if PS.ROWS[lb][2]:                         # with the map the cells are weighed: some weigh 0, some do not
-        cells = eng._detail["cells"]
         assert all(c is not None and float(c.min()) == 0.0 and float(c.max()) > 0 for c in cells)
     else:
-        assert eng._detail["cells"] == [None] * len(PS.POOLS)
+        assert cells == [None] * len(PS.POOLS)
 
 
 @pytest.mark.parametrize("graph", [False, True], ids=["eager", "captured"])
@@ -368,7 +370,38 @@ def test_engine_refuses_bad_priors_and_sharding():
         engine.StepEngine(*args, sample_size=384, tv_weight=1.0, dist_group=object())
 
 
-# ------------------------------------------------------------------ 4. end to end
+# ------------------------------------------------------------------ 4. all four pixel-space terms in one engine
+def test_two_engines_stepped_alternately_are_each_the_engine_stepped_alone():
+    """the terms' zeroed workspaces are each engine's own: nothing of them lives in the module-level instance, no two engines
+    hold the same buffer, and interleaving two engines' steps changes no bit of either"""
+    from _pixel_terms_cases import all_terms_engine, all_terms_indices, all_terms_state
+    from nn import _ops
+    idx = all_terms_indices(3)
+    shared_before = {k: b.data_ptr() for k, b in _ops.workspaces.fixed.items()}
+    a, b, alone = all_terms_engine(), all_terms_engine(), all_terms_engine()
+    assert [type(t).__name__ for t in a._pixel_terms] == ["TemporalTerm", "DetailTerm", "TVTerm", "PhotoTerm"]
+    for i in idx:
+        a.step(i)
+        b.step(i)
+    for i in idx:
+        alone.step(i)
+    torch.cuda.synchronize()
+    want = all_terms_state(alone)
+    for eng in (a, b):
+        got = all_terms_state(eng)
+        assert len(got) == len(want) == 6 + 6 + 1 + 4
+        for x, y in zip(got, want):
+            assert torch.equal(_bits(x), _bits(y))
+    assert a.losses() == b.losses() == alone.losses() and all(a.losses()[k] > 0 for k in ("loss_t", "loss_detail", "loss_tv",
+                                                                                             "loss_photo"))
+    ptrs = [t.workspace.data_ptr() for eng in (a, b, alone) for t in eng._pixel_terms]
+    assert len(set(ptrs)) == 12
+    assert all(t.workspace.data_ptr() in {v.data_ptr() for v in eng._ws.fixed.values()}
+               for eng in (a, b, alone) for t in eng._pixel_terms)
+    assert {k: v.data_ptr() for k, v in _ops.workspaces.fixed.items()} == shared_before
+
+
+# ------------------------------------------------------------------ 5. end to end
 SUGGESTED_DETAIL_WEIGHT, SUGGESTED_TV_WEIGHT = 10.0, 0.1     # DESIGN.md section 26's suggested starting values
 DETAIL_RATIO = 0.299        # E_d(on) < ratio * E_d(off): measured 0.000988 / 0.011034 = 0.0895, sqrt(0.0895 * 1)
 TV_RATIO = 0.932            # E_tv(on) < ratio * E_tv(off): measured 0.097291 / 0.112037 = 0.868, sqrt(0.868 * 1)

@@ -24,7 +24,8 @@ Sinkhorn case modules have no n = 1024 case with a float64 reference: that count
 tv_fwd_bwd, detail_fwd_bwd, temporal_fwd_bwd, temporal_multi_fwd_bwd (four targets), guided_smooth, guided_upsample (both
 modes), optical_flow, color_stats, detail_map and scribble_labels at their case module's smallest size and at one with both
 sides odd.  The engine: a 64 px deterministic StepEngine whose Workspaces is the guarded class, eager, captured and
-replayed, bit for bit the run on the product's class.
+replayed, bit for bit the run on the product's class; and a 42 x 64 one with all four pixel-space terms, whose zeroed
+workspaces are the engine's and of exactly the library's sizes.
 
 Each run appends (entry, shape, tag, declared bytes, high-water mark) to profiles/scratch_contracts.txt when the whole file
 ran; nothing is asserted on it."""
@@ -789,20 +790,28 @@ def test_scribble_labels_inside_its_workspace(ops, ws, case):                   
 
 
 # ------------------------------------------------------------------ the engine
-@pytest.mark.parametrize("transport", ["remd", "sinkhorn"])
+@pytest.mark.parametrize("transport", ["remd", "sinkhorn", "pixel_terms"])
 def test_engine_inside_its_workspaces_eager_captured_and_replayed(ops, monkeypatch, transport):
     """the product's real sequence of tags and sizes -- one tag asked for different sizes by different layers, the borrow, the
     frozen arena -- on exact buffers: three eager steps, capture, three replays; guards after each phase; variables,
-    gradients and scalars bit for bit those of the same run on nn._ops.Workspaces"""
+    gradients and scalars bit for bit those of the same run on nn._ops.Workspaces.  "pixel_terms": _pixel_terms_cases'
+    42 x 64 engine with two temporal targets, the detail term with a cell map, TV and the photo term: their four zeroed
+    workspaces are blocks of the engine's instance, each of exactly the library's byte count, and the terms' scalars are
+    compared as well"""
+    import _pixel_terms_cases as TPP
     import test_hip_workspaces as TW
-    P = TR.step_problem(TW.H, TW.W, TW.N, 21)
-    idx = TW._indices(3, 6)
+    terms = transport == "pixel_terms"
+    P = None if terms else TR.step_problem(TW.H, TW.W, TW.N, 21)
+    idx = TPP.all_terms_indices(3) if terms else TW._indices(3, 6)
+    zeroed = {}
 
     def run(guard):
         with monkeypatch.context() as m:
             if guard:
                 m.setattr(ops, "Workspaces", SG.GuardedWorkspaces)
-            eng = TW._engine(P, transport=transport, deterministic=True)
+            eng = TPP.all_terms_engine() if terms else TW._engine(P, transport=transport, deterministic=True)
+        if guard:
+            zeroed.update({(tag, key): blk.nbytes for (tag, _, key), blk in eng._ws.fixed_blocks.items()})
         assert isinstance(eng._ws, SG.GuardedWorkspaces) == guard and eng.trunk.ws is eng._ws
         out, marks = [], {}
         phase = lambda: checked(eng._ws) if guard else torch.cuda.synchronize()
@@ -817,11 +826,21 @@ def test_engine_inside_its_workspaces_eager_captured_and_replayed(ops, monkeypat
             eng.step(i)
             out.append(eng.scalars.clone())
         marks = phase()
-        return out + [v.clone() for v in eng.variables] + [g.clone() for g in eng.gvars], marks
+        return out + [v.clone() for v in eng.variables] + [g.clone() for g in eng.gvars] + \
+            [t.loss.clone() for t in eng._pixel_terms], marks
     guarded, marks = run(True)
     plain, _ = run(False)
-    assert len(guarded) == len(plain)
+    assert len(guarded) == len(plain) == 6 + 6 + 6 + (4 if terms else 0)
     for a, b in zip(guarded, plain):
         assert torch.equal(a.view(torch.int32), b.view(torch.int32))
     assert len({k.split("[")[0] for k in marks}) < len(marks), "no tag was asked for two sizes: not the trunk's sequence"
-    record("engine", f"StepEngine {transport}", f"{TW.H}px n{TW.N}", marks)
+    if terms:
+        from nn import _hip
+        (h, w), lib = TPP.ALL_TERMS_HW, _hip.lib()
+        assert zeroed == {("temporal", (h, w, 2)): lib.strotss_temporal_multi_workspace_bytes(h, w, 2),
+                          ("detail", (h, w)): lib.strotss_detail_workspace_bytes(h, w),
+                          ("tv", (h, w)): lib.strotss_tv_workspace_bytes(h, w),
+                          ("matting", (h, w)): lib.strotss_matting_workspace_bytes(h, w)}
+        record("engine", "StepEngine pixel terms", f"{h}x{w} n300", marks)
+    else:
+        record("engine", f"StepEngine {transport}", f"{TW.H}px n{TW.N}", marks)

@@ -163,7 +163,7 @@ def test_remd_cases_without_the_grouped_entry_borrow_after_the_weighted_entry(lb
 # ------------------------------------------------------------------ 3. three forms of the step give the same bits
 def _state(eng):
     return [v.clone() for v in eng.variables] + [g.clone() for g in eng.gvars] + [eng.scalars.clone()] + \
-        ([eng._temporal["loss"].clone()] if eng._temporal is not None else [])
+        [t.loss.clone() for t in eng._pixel_terms]                # the temporal term's scalars, where there is one
 
 
 @pytest.mark.parametrize("lb", BORROWING)

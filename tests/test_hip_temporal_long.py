@@ -66,11 +66,10 @@ def _multi_inputs(h, w, count, seed):
 
 
 def _multi(xd, tds, cds, gs, g, loss, ws=None):
+    """ws: the Workspaces of an earlier call (its zeroed workspace is used again), None: a fresh one; -> the one used"""
     from nn import _ops
-    h, w = int(xd.shape[0]), int(xd.shape[1])
-    if ws is None:
-        ws = _ops.temporal_multi_workspace(h, w, len(tds), DEV)
-    _ops.temporal_multi_fwd_bwd(xd, tds, cds, gs, g, loss, ws)
+    ws = _ops.Workspaces() if ws is None else ws
+    _ops.temporal_multi_fwd_bwd(xd, tds, cds, gs, g, loss, ws=ws)
     return ws
 
 
@@ -123,7 +122,7 @@ def test_count_one_is_the_single_term_kernel(hw):
     xd, td, cd = _dev(x), _dev(tg[0]), _dev(cs[0])
     g1, g2 = _dev(g0), _dev(g0)
     l1, l2 = torch.zeros(1, device=DEV), torch.zeros(1, device=DEV)
-    _ops.temporal_fwd_bwd(xd, td, cd, 3.5, g1, l1, _ops.temporal_workspace(h, w, DEV))
+    _ops.temporal_fwd_bwd(xd, td, cd, 3.5, g1, l1, ws=_ops.Workspaces())
     _multi(xd, [td], [cd], [3.5], g2, l2)
     torch.cuda.synchronize()
     assert torch.equal(l1.view(torch.int32), l2.view(torch.int32))

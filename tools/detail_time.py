@@ -69,23 +69,22 @@ def kernels(iters):
     x, c, tgt, gimg = (torch.rand(h, w, 3, generator=g).to(DEV) for _ in range(4))
     cert = (torch.rand(h, w, generator=g) > 0.2).float().to(DEV)
     loss = torch.zeros(4, device=DEV)
-    ws_d, ws_tv, ws_t = ops.detail_workspace(h, w, DEV), ops.tv_workspace(h, w, DEV), ops.temporal_workspace(h, w, DEV)
     px = h * w
     calls, nbytes = {}, {}
     for pools in ((1,), (2,), (4,), (8,), (16,), (1, 4)):
         contents = [ops.pool_mean(c, p) for p in pools]
         name = "detail_p" + "_".join(str(p) for p in pools)
         calls[name] = (lambda pools=pools, contents=contents: ops.detail_fwd_bwd(
-            x, list(pools), contents, [None] * len(pools), [1.0] * len(pools), gimg, loss, ws_d))
+            x, list(pools), contents, [None] * len(pools), [1.0] * len(pools), gimg, loss))
         # per pool size: gimg read and written (24 B / pixel); p = 1: x and c read once (24); p > 1: x read by the pooling
         # launch (12), the pooled planes written once and read twice (x's) or once (c's): 12 * 4 / p^2
         nbytes[name] = sum(px * (24 + (24 if p == 1 else 12 + 48 / (p * p))) for p in pools)
-    calls["tv"] = lambda: ops.tv_fwd_bwd(x, 1.0, gimg, loss, ws_tv)
+    calls["tv"] = lambda: ops.tv_fwd_bwd(x, 1.0, gimg, loss)
     nbytes["tv"] = px * 36                              # x read, gimg read and written
     pooled = ops.pool_mean(x, 4)
     calls["pool_mean_p4"] = lambda: ops.pool_mean(x, 4, pooled)
     nbytes["pool_mean_p4"] = px * (12 + 12 / 16)
-    calls["temporal"] = lambda: ops.temporal_fwd_bwd(x, tgt, cert, 1000.0, gimg, loss, ws_t)
+    calls["temporal"] = lambda: ops.temporal_fwd_bwd(x, tgt, cert, 1000.0, gimg, loss)
     nbytes["temporal"] = px * (3 * 4 * 4 + 4)
     for rep in range(3):                                # alternated
         for name, fn in calls.items():

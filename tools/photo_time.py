@@ -65,7 +65,6 @@ def kernels(h, w, iters):
     x, c, tgt, gimg, out = (torch.rand(h, w, 3, generator=g).to(DEV) for _ in range(5))
     cert = (torch.rand(h, w, generator=g) > 0.2).float().to(DEV)
     loss = torch.zeros(4, device=DEV)
-    ws_t = ops.temporal_workspace(h, w, DEV)
     px = h * w
     calls, nbytes = {}, {}
     for r in (1, 2, 4):
@@ -77,7 +76,7 @@ def kernels(h, w, iters):
         nbytes[f"matting_prepare_r{r}"] = px * (12 + 36)
         calls[f"guided_smooth_r{r}"] = lambda r=r: ops.guided_smooth(x, c, r, EPS, out=out)
         nbytes[f"guided_smooth_r{r}"] = px * (24 + 2 * 216 + 12)      # its 216 B / pixel workspace written and read
-    calls["temporal"] = lambda: ops.temporal_fwd_bwd(x, tgt, cert, 1000.0, gimg, loss, ws_t)
+    calls["temporal"] = lambda: ops.temporal_fwd_bwd(x, tgt, cert, 1000.0, gimg, loss)
     nbytes["temporal"] = px * (3 * 4 * 4 + 4)
     for rep in range(3):                                # alternated
         for name, fn in calls.items():

@@ -67,12 +67,11 @@ def kernels(iters, repeats=3):
     raw = (torch.rand(4, h, w, generator=g) > 0.2).float().to(DEV)
     certs = list(ops.temporal_long_certainty(raw).unbind(0))
     loss = torch.zeros(4, device=DEV)
-    ws = {n: ops.temporal_multi_workspace(h, w, n, DEV) for n in (1, 2, 3, 4)}
     comb = torch.empty_like(raw)
     for rep in range(repeats):
         out = {"what": "kernels", "h": h, "w": w, "rep": rep}
         for n in (1, 2, 3, 4):
-            us = _time(lambda: ops.temporal_multi_fwd_bwd(x, tgts[:n], certs[:n], [1000.0] * n, gimg, loss, ws[n]), iters)
+            us = _time(lambda: ops.temporal_multi_fwd_bwd(x, tgts[:n], certs[:n], [1000.0] * n, gimg, loss), iters)
             out[f"multi_{n}_us"] = round(us, 2)
             out[f"multi_{n}_GBps"] = round(h * w * (3 * 3 * 4 + n * (3 * 4 + 4)) / us / 1e3, 1)    # x, gimg r/w
         for n in (2, 3, 4):

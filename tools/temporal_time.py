@@ -70,14 +70,13 @@ def kernels(iters):
     x, tgt, gimg = (torch.rand(h, w, 3, generator=g).to(DEV) for _ in range(3))
     cert = (torch.rand(h, w, generator=g) > 0.2).float().to(DEV)
     loss = torch.zeros(1, device=DEV)
-    ws = ops.temporal_workspace(h, w, DEV)
     ys, xs = np.mgrid[0:h, 0:w].astype(np.float32)
     fb = torch.from_numpy(np.stack([3 * np.sin(xs / 40), 2 * np.cos(ys / 30)], -1).astype(np.float32)).to(DEV)
     ff = -fb
     prev = x[None].contiguous()
     warped, c_out = torch.empty_like(prev), torch.empty(h, w, device=DEV)
     out = {"what": "kernels", "h": h, "w": w}
-    out["temporal_fwd_bwd_us"] = round(_time(lambda: ops.temporal_fwd_bwd(x, tgt, cert, 1000.0, gimg, loss, ws), iters), 2)
+    out["temporal_fwd_bwd_us"] = round(_time(lambda: ops.temporal_fwd_bwd(x, tgt, cert, 1000.0, gimg, loss), iters), 2)
     out["flow_warp_us"] = round(_time(lambda: ops.flow_warp(prev, fb, None, warped, c_out), iters), 2)
     out["flow_warp_fwd_check_us"] = round(_time(lambda: ops.flow_warp(prev, fb, ff, warped, c_out), iters), 2)
     nbytes = h * w * (3 * 4 * 4 + 4)                   # x, target, gimg read + gimg written, certainty
