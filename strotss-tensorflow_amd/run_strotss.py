@@ -271,6 +271,15 @@ class BlendedStyleLoss:
 
 
 # --------------------------------------------------------------------------------------------------
+def _one_gpu(args, what: str, verb: str = "runs"):
+    """the refusal every one-GPU flag family shares: ValueError for `what` with --strips, then under torchrun with
+    WORLD_SIZE > 1.  Where a validator calls it decides which of its refusals wins."""
+    if getattr(args, "strips", False):
+        raise ValueError(f"{what} cannot be combined with --strips")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError(f"{what} {verb} on one GPU: not under torchrun with WORLD_SIZE > 1")
+
+
 def _style_inputs(args):
     """(style paths, normalised weights) of the run: style_path alone, or style_path + --style_mix with --style_weights
     (1 + len(style_mix) values, default equal).  Zero-weight styles are dropped here, before anything is loaded or sampled,
@@ -302,10 +311,7 @@ def _content_weight_input(args):
     path = getattr(args, "content_weight_map", None)
     if not path:
         return None
-    if getattr(args, "strips", False):
-        raise ValueError("--content_weight_map cannot be combined with --strips")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise ValueError("--content_weight_map runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    _one_gpu(args, "--content_weight_map")
     return path
 
 
@@ -316,10 +322,7 @@ def _sample_map_input(args):
     path = getattr(args, "sample_map", None)
     if not path:
         return None
-    if getattr(args, "strips", False):
-        raise ValueError("--sample_map cannot be combined with --strips")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise ValueError("--sample_map runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    _one_gpu(args, "--sample_map")
     if path == SAMPLE_MAP_AUTO:
         return path
     if not os.path.isfile(path):
@@ -363,10 +366,7 @@ def _preserve_color_input(args):
         return None
     if mode not in PRESERVE_COLOR_MODES:
         raise ValueError(f"--preserve_color takes one of {PRESERVE_COLOR_MODES}, got {mode!r}")
-    if getattr(args, "strips", False):
-        raise ValueError("--preserve_color cannot be combined with --strips")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise ValueError("--preserve_color runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    _one_gpu(args, "--preserve_color")
     return mode
 
 
@@ -394,19 +394,12 @@ def _style_transport_input(args) -> dict:
             not 1 <= proj <= strotss_engine.SLICED_MAX_PROJECTIONS:
         raise ValueError(f"--sliced_projections must be a whole number in 1..{strotss_engine.SLICED_MAX_PROJECTIONS}, "
                          f"got {proj!r}")
+    if transport in ("sliced", "sinkhorn"):
+        _one_gpu(args, f"--style_transport {transport}")
     if transport == "sliced":
-        if getattr(args, "strips", False):
-            raise ValueError("--style_transport sliced cannot be combined with --strips")
-        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            raise ValueError("--style_transport sliced runs on one GPU: not under torchrun with WORLD_SIZE > 1")
         return dict(style_transport=transport, sinkhorn_l=float(reg), sinkhorn_iters=int(iters),
                     sliced_projections=int(proj), sliced_seed=int(getattr(args, "seed", 0) or 0))
-    if transport == "sinkhorn":
-        if getattr(args, "strips", False):
-            raise ValueError("--style_transport sinkhorn cannot be combined with --strips")
-        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            raise ValueError("--style_transport sinkhorn runs on one GPU: not under torchrun with WORLD_SIZE > 1")
-    kw = dict(style_transport=transport, sinkhorn_l=float(reg), sinkhorn_iters=int(iters))
+    kw =dict(style_transport=transport, sinkhorn_l=float(reg), sinkhorn_iters=int(iters))
     return dict(kw, sinkhorn_log=True) if log else kw
 
 
@@ -427,10 +420,7 @@ def _palette_transport_input(args) -> dict:
             not 1 <= proj <= strotss_engine.PALETTE_MAX_PROJECTIONS:
         raise ValueError(f"--palette_projections must be a whole number in 1..{strotss_engine.PALETTE_MAX_PROJECTIONS}, "
                          f"got {proj!r}")
-    if getattr(args, "strips", False):
-        raise ValueError("--palette_transport sliced cannot be combined with --strips")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise ValueError("--palette_transport sliced runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    _one_gpu(args, "--palette_transport sliced")
     return dict(palette_transport=transport, palette_projections=int(proj))
 
 
@@ -453,11 +443,7 @@ def _pixel_prior_input(args) -> dict:
     from nn import _ops
     if dw is not None:
         pools = _ops.check_detail_pools(list(DEFAULT_DETAIL_POOLS) if pools is None else list(pools))
-    flags = " / ".join(f for f, v in (("--detail_weight", dw), ("--tv_weight", tv)) if v is not None)
-    if getattr(args, "strips", False):
-        raise ValueError(f"{flags} cannot be combined with --strips")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise ValueError(f"{flags} runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    _one_gpu(args, " / ".join(f for f, v in (("--detail_weight", dw), ("--tv_weight", tv)) if v is not None))
     return dict(detail=None if dw is None else (float(dw), pools), tv=0.0 if tv is None else float(tv))
 
 
@@ -478,10 +464,7 @@ def _photo_term_input(args):
     radius = DEFAULT_PHOTO_RADIUS if radius is None else radius
     eps = DEFAULT_PHOTO_EPS if eps is None else eps
     strotss_engine.check_photo(radius, eps)
-    if getattr(args, "strips", False):
-        raise ValueError("--photo_weight cannot be combined with --strips")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise ValueError("--photo_weight runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    _one_gpu(args, "--photo_weight")
     return float(weight), int(radius), float(eps)
 
 
@@ -494,10 +477,7 @@ def _photo_smooth_input(args):
             raise ValueError("--smooth_radius and --smooth_eps need --photo_smooth")
         return None
     strotss.check_smooth_parameters(radius, eps)
-    if getattr(args, "strips", False):
-        raise ValueError("--photo_smooth cannot be combined with --strips")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise ValueError("--photo_smooth runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    _one_gpu(args, "--photo_smooth")
     return (None if radius is None else int(radius)), (strotss.DEFAULT_SMOOTH_EPS if eps is None else float(eps))
 
 
@@ -529,43 +509,8 @@ def _output_size_input(args):
             strotss.check_smooth_parameters(**kw)
         except ValueError as e:
             raise ValueError(f"{flag}: {e}") from None
-    if getattr(args, "strips", False):
-        raise ValueError("--output_size cannot be combined with --strips")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise ValueError("--output_size runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    _one_gpu(args, "--output_size")
     return dict(size=size, mode=mode, radius=None if radius is None else int(radius), eps=None if eps is None else float(eps))
-
-
-def _written_guides(args, post, content_path: str, frame_lo=None):
-    """The guides of _written, loaded before the image's first step: (the content at the result's size, the content at
-    --output_size's target size), both (h, w, 3) on the device, each None where nothing needs it.  post: what
-    (_preserve_color_input, _photo_smooth_input, _output_size_input) returned.  frame_lo: the content at the result's size
-    where the caller holds it already (a --compute_flow frame).  ValueError for a target smaller than the result in either
-    dimension or with 3 H W > INT_MAX -- here, not after the optimisation."""
-    preserve, smooth, upsample = post
-    if not (upsample or smooth or preserve == "luminance"):
-        return None, None
-    lo = _frame_at_result_size(args, content_path) if frame_lo is None else frame_lo
-    if not upsample:
-        return lo, None
-    hi = utils.load_image(content_path, max_size=None if upsample["size"] == "full" else upsample["size"])[0].contiguous()
-    strotss.check_upsample_sizes(int(lo.shape[0]), int(lo.shape[1]), int(hi.shape[0]), int(hi.shape[1]))
-    return lo, hi
-
-
-def _written(stylized: torch.Tensor, post, guides) -> torch.Tensor:
-    """The uint8 image that is written for an optimiser's result, of a single image and of every frame of a sequence:
-    --photo_smooth's filter, then --output_size's upsampling, then --preserve_color luminance's merge at the written size,
-    then postprocess.  `stylized` itself stays as it is: the temporal targets and --temporal_init keep seeing it."""
-    (preserve, smooth, upsample), (guide, guide_hi) = post, guides
-    if smooth:                                               # the content's edges back into the result, then its colours
-        stylized = strotss.guided_smooth(stylized, guide, *smooth)
-    if upsample:                                             # to the target size, the content there as guide from here on
-        stylized = strotss.guided_upsample(stylized, guide, guide_hi, upsample["radius"], upsample["eps"], upsample["mode"])
-        guide = guide_hi
-    if preserve == "luminance":                              # the result's luma on the content's chroma
-        stylized = strotss.luminance_merge(stylized, guide)
-    return strotss.postprocess(stylized)
 
 
 def _refine_masks_input(args):
@@ -644,24 +589,24 @@ def _scribble_masks_input(args):
         raise ValueError("scribbles cannot be combined with --style_mix: masks and blends exclude each other")
     if getattr(args, "video", False):
         raise ValueError("scribbles cannot be combined with --video: the strokes belong to one image")
-    if getattr(args, "strips", False):
-        raise ValueError("scribbles cannot be combined with --strips")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise ValueError("scribbles run on one GPU: not under torchrun with WORLD_SIZE > 1")
+    _one_gpu(args, "scribbles", verb="run")
     return (c, s_, strotss.SCRIBBLE_SIGMA if sigma is None else float(sigma),
             strotss.SCRIBBLE_ITERS if iters is None else int(iters))
 
 
-def _auto_masks_input(args):
+def _auto_masks_input(args, found=None):
     """--auto_masks K, --save_masks DIR: (K, DIR or None), or None without --auto_masks.  ValueError, before anything is
     loaded: K outside 2..8, --save_masks without --auto_masks, --auto_masks with --content_mask / --style_mask, --style_mix,
     --video without --track_masks, --strips or under torchrun with WORLD_SIZE > 1, and the refusals of --refine_masks /
     --refine_sigma (_refine_masks_input), of --track_masks / --mask_inertia (_track_masks_input) and of the scribble flags
-    (_scribble_masks_input, with which --save_masks is allowed too)."""
+    (_scribble_masks_input, with which --save_masks is allowed too).  found: a dict that receives what those three
+    returned, as refine, inertia and scribbles (_resolve's way to them: they are entered here and nowhere else)."""
     k, save = getattr(args, "auto_masks", None), getattr(args, "save_masks", None)
-    _refine_masks_input(args)
+    refine = _refine_masks_input(args)
     track = _track_masks_input(args)
     scribbles = _scribble_masks_input(args)
+    if found is not None:
+        found.update(refine=refine, inertia=track, scribbles=scribbles)
     if k is None:
         if save and scribbles is None:
             raise ValueError("--save_masks needs --auto_masks (it writes the regions the run finds)")
@@ -676,48 +621,8 @@ def _auto_masks_input(args):
     if getattr(args, "video", False) and track is None:
         raise ValueError("--auto_masks cannot be combined with --video: clustering every frame on its own would flicker "
                          "(--track_masks follows the first frame's regions through the sequence)")
-    if getattr(args, "strips", False):
-        raise ValueError("--auto_masks cannot be combined with --strips")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise ValueError("--auto_masks runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    _one_gpu(args, "--auto_masks")
     return int(k), (save or None)
-
-
-def _match_styles(styles, content, content_masks, style_masks, recolour=None):
-    """--preserve_color match: every style image recoloured toward the content's colour mean and covariance
-    (strotss_utils.match_colour), each style on its own.  With masks region by region: the statistics of the style pixels
-    in style mask r and of the content pixels in content mask r, the map applied to style mask r's pixels only (the masks
-    resized to the images as mask_at_scale resizes them to a scale); pixels in no region stay.  recolour: another
-    (style, content, style_mask, content_mask) -> style in match_colour's place (_recolour_styles)."""
-    recolour = recolour or strotss.match_colour
-    if list(content_masks) == [None]:
-        return [recolour(s_k, content) for s_k in styles]
-    ch, cw = int(content.shape[1]), int(content.shape[2])
-    out = []
-    for s_k in styles:
-        sh, sw = int(s_k.shape[1]), int(s_k.shape[2])
-        for c_mask, s_mask in zip(content_masks, style_masks):
-            cm = torch.from_numpy(strotss.mask_at_scale(c_mask, ch, cw).astype(np.float32))
-            sm = torch.from_numpy(strotss.mask_at_scale(s_mask, sh, sw).astype(np.float32))
-            s_k = recolour(s_k, content, sm, cm)
-        out.append(s_k)
-    return out
-
-
-def _recolour_styles(args, styles, content, content_masks, style_masks):
-    """the styles as --preserve_color leaves them before anything is sampled: recoloured by match or by transfer
-    (--transfer_iters bases, DESIGN.md section 23) exactly where and as _match_styles recolours them, untouched otherwise"""
-    mode = _preserve_color_input(args)
-    if mode == "match":
-        return _match_styles(styles, content, content_masks, style_masks)
-    if mode == "transfer":
-        iters = getattr(args, "transfer_iters", None)
-        iters = strotss.DEFAULT_TRANSFER_ITERS if iters is None else int(iters)
-
-        def transfer(style, content, style_mask=None, content_mask=None):
-            return strotss.transfer_colour(style, content, style_mask, content_mask, iters=iters)
-        return _match_styles(styles, content, content_masks, style_masks, recolour=transfer)
-    return styles
 
 
 DEFAULT_TEMPORAL_WEIGHT = 1000.0          # DESIGN.md section 12: chosen on the MI355X with the consistency error
@@ -741,14 +646,16 @@ def _temporal_frames(args):
     return tuple(sorted(offsets))
 
 
-def _video_inputs(args):
+def _video_inputs(args, found=None):
     """--video: (sorted frame paths, temporal weight); None without --video.  Refused with a ValueError before anything is
     optimised: --temporal_weight / --flow_dir / --temporal_init / --temporal_frames without --video, a negative weight, bad
     --temporal_frames offsets (_temporal_frames), --video with --strips or under torchrun with WORLD_SIZE > 1, neither
     --flow_dir nor --compute_flow, a content_path that is not a directory of frames, frames of different sizes, a missing
     backward flow of any frame and offset (--flow_dir only); --compute_flow without --video or together with --flow_dir,
     --save_flow without --compute_flow, --flow_match without --compute_flow or outside 1..4, --flow_robust without
-    --compute_flow, --flow_alpha / --flow_outer without --flow_robust or out of range (_flow_robust)."""
+    --compute_flow, --flow_alpha / --flow_outer without --flow_robust or out of range (_flow_robust).  found: a dict that
+    receives what _flow_match_radius, _flow_robust and (with --video) _temporal_frames returned, as match_radius, robust and
+    offsets (_resolve's way to them: they are entered here and nowhere else)."""
     video = bool(getattr(args, "video", False))
     lam = getattr(args, "temporal_weight", None)
     flow_dir = getattr(args, "flow_dir", None)
@@ -764,18 +671,16 @@ def _video_inputs(args):
         raise ValueError("--save_flow needs --compute_flow (it writes the flows the run computes)")
     if compute_flow and flow_dir:
         raise ValueError("--compute_flow and --flow_dir exclude each other: the flows are computed or read, not both")
-    _flow_match_radius(args)
-    _flow_robust(args)
+    match_radius, robust = _flow_match_radius(args), _flow_robust(args)
+    offsets = _temporal_frames(args) if video else None
+    if found is not None:
+        found.update(match_radius=match_radius, robust=robust, offsets=offsets)
     if not video:
         return None
-    offsets = _temporal_frames(args)
     lam = DEFAULT_TEMPORAL_WEIGHT if lam is None else float(lam)
     if not np.isfinite(lam) or lam < 0:
         raise ValueError(f"--temporal_weight must be finite and >= 0, got {lam}")
-    if getattr(args, "strips", False):
-        raise ValueError("--video cannot be combined with --strips")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise ValueError("--video runs on one GPU: not under torchrun with WORLD_SIZE > 1")
+    _one_gpu(args, "--video")
     if not flow_dir and not compute_flow:
         raise ValueError("--video needs --flow_dir (the optical flow between consecutive frames)")
     if not os.path.isdir(args.content_path):
@@ -848,14 +753,117 @@ def _flow_robust(args):
     return robust
 
 
-def _frame_at_result_size(args, path: str) -> torch.Tensor:
+def _resolve(args) -> argparse.Namespace:
+    """The job of a run, made once: the namespace as given (the parser's, or a partial one) completed with the parser's own
+    defaults, plus what every validator above returns.  Each validator is entered once, in the order in which run() and
+    run_video() have always reached them -- of two wrong flags the same one is reported -- and before a device or an image
+    is touched.  Everything below this function reads the job; nothing below validates or asks whether a flag is there.
+        auto, refine, inertia, scribbles    _auto_masks_input and the three validators it enters
+        engine_terms                        StepEngine's keywords of --style_transport and of --palette_transport, merged
+        prior, photo, auto_sample           _pixel_prior_input, _photo_term_input, _auto_sample_input
+        content_weight                      _content_weight_input: the map's path or None
+        preserve, smooth, upsample          _preserve_color_input, _photo_smooth_input, _output_size_input
+        frames, temporal_weight             _video_inputs; frames is None without --video
+        offsets, match_radius, robust       the three validators _video_inputs enters; offsets is None without --video
+        styles                              _style_inputs: (paths, weights)
+    sample_map stays the flag (_sample_map_input has passed it); transfer_iters has its default with --preserve_color
+    transfer."""
+    job = argparse.Namespace(**{**vars(build_parser().parse_args(["", ""])), **vars(args)})
+    found = {}
+    job.auto = _auto_masks_input(job, found)
+    job.engine_terms = dict(_style_transport_input(job), **_palette_transport_input(job))
+    job.prior = _pixel_prior_input(job)
+    job.photo = _photo_term_input(job)
+    job.auto_sample = _auto_sample_input(job)
+    if not job.video:                                        # a sequence reaches this one after _video_inputs
+        job.content_weight = _content_weight_input(job)
+    job.preserve = _preserve_color_input(job)
+    job.smooth = _photo_smooth_input(job)
+    job.upsample = _output_size_input(job)
+    job.frames, job.temporal_weight = _video_inputs(job, found) or (None, job.temporal_weight)
+    if job.video:
+        job.content_weight = _content_weight_input(job)
+    vars(job).update(found)
+    if job.preserve == "transfer":
+        job.transfer_iters = strotss.DEFAULT_TRANSFER_ITERS if job.transfer_iters is None else int(job.transfer_iters)
+    job.styles = _style_inputs(job)
+    if bool(job.content_mask) != bool(job.style_mask):
+        raise ValueError('Either both content and style masks must be provided or neither.')
+    return job
+
+
+def _written_guides(job, content_path: str, frame_lo=None):
+    """The guides of _written, loaded before the image's first step: (the content at the result's size, the content at
+    --output_size's target size), both (h, w, 3) on the device, each None where nothing needs it.  frame_lo: the content at
+    the result's size where the caller holds it already (a --compute_flow frame).  ValueError for a target smaller than the
+    result in either dimension or with 3 H W > INT_MAX -- here, not after the optimisation."""
+    upsample = job.upsample
+    if not (upsample or job.smooth or job.preserve == "luminance"):
+        return None, None
+    lo = _frame_at_result_size(job, content_path) if frame_lo is None else frame_lo
+    if not upsample:
+        return lo, None
+    hi = utils.load_image(content_path, max_size=None if upsample["size"] == "full" else upsample["size"])[0].contiguous()
+    strotss.check_upsample_sizes(int(lo.shape[0]), int(lo.shape[1]), int(hi.shape[0]), int(hi.shape[1]))
+    return lo, hi
+
+
+def _written(stylized: torch.Tensor, job, guides) -> torch.Tensor:
+    """The uint8 image that is written for an optimiser's result, of a single image and of every frame of a sequence:
+    --photo_smooth's filter, then --output_size's upsampling, then --preserve_color luminance's merge at the written size,
+    then postprocess.  `stylized` itself stays as it is: the temporal targets and --temporal_init keep seeing it."""
+    upsample, (guide, guide_hi) = job.upsample, guides
+    if job.smooth:                                           # the content's edges back into the result, then its colours
+        stylized = strotss.guided_smooth(stylized, guide, *job.smooth)
+    if upsample:                                             # to the target size, the content there as guide from here on
+        stylized = strotss.guided_upsample(stylized, guide, guide_hi, upsample["radius"], upsample["eps"], upsample["mode"])
+        guide = guide_hi
+    if job.preserve == "luminance":                          # the result's luma on the content's chroma
+        stylized = strotss.luminance_merge(stylized, guide)
+    return strotss.postprocess(stylized)
+
+
+def _match_styles(styles, content, content_masks, style_masks, recolour=None):
+    """--preserve_color match: every style image recoloured toward the content's colour mean and covariance
+    (strotss_utils.match_colour), each style on its own.  With masks region by region: the statistics of the style pixels
+    in style mask r and of the content pixels in content mask r, the map applied to style mask r's pixels only (the masks
+    resized to the images as mask_at_scale resizes them to a scale); pixels in no region stay.  recolour: another
+    (style, content, style_mask, content_mask) -> style in match_colour's place (_recolour_styles)."""
+    recolour = recolour or strotss.match_colour
+    if list(content_masks) == [None]:
+        return [recolour(s_k, content) for s_k in styles]
+    ch, cw = int(content.shape[1]), int(content.shape[2])
+    out = []
+    for s_k in styles:
+        sh, sw = int(s_k.shape[1]), int(s_k.shape[2])
+        for c_mask, s_mask in zip(content_masks, style_masks):
+            cm = torch.from_numpy(strotss.mask_at_scale(c_mask, ch, cw).astype(np.float32))
+            sm = torch.from_numpy(strotss.mask_at_scale(s_mask, sh, sw).astype(np.float32))
+            s_k = recolour(s_k, content, sm, cm)
+        out.append(s_k)
+    return out
+
+
+def _recolour_styles(job, styles, content, content_masks, style_masks):
+    """the styles as --preserve_color leaves them before anything is sampled: recoloured by match or by transfer
+    (--transfer_iters bases, DESIGN.md section 23) exactly where and as _match_styles recolours them, untouched otherwise"""
+    if job.preserve == "match":
+        return _match_styles(styles, content, content_masks, style_masks)
+    if job.preserve == "transfer":
+        def transfer(style, content, style_mask=None, content_mask=None):
+            return strotss.transfer_colour(style, content, style_mask, content_mask, iters=job.transfer_iters)
+        return _match_styles(styles, content, content_masks, style_masks, recolour=transfer)
+    return styles
+
+
+def _frame_at_result_size(job, path: str) -> torch.Tensor:
     """a content frame (h, w, 3) on the device at the size of a frame's final result: resized as _stylise makes the content
     of its last executed scale"""
-    scl = 2 << (5 + int(args.level) - 1)
-    return utils.resize(utils.load_image(path, max_size=args.max_size), scl)[0].contiguous()
+    scl = 2 << (5 + int(job.level) - 1)
+    return utils.resize(utils.load_image(path, max_size=job.max_size), scl)[0].contiguous()
 
 
-def _computed_flows(args, t: int, j: int, frames, h: int, w: int):
+def _computed_flows(job, t: int, j: int, frames, h: int, w: int):
     """--compute_flow: (backward, forward) flow of frame t against frame t-j, both (h, w, 2), by strotss_optical_flow on the
     content frames at the results' size (with --flow_match R: strotss_optical_flow_match; with --flow_robust:
     strotss_optical_flow_robust).  frames: {1-based position: (h, w, 3) frame on the device}.  --save_flow DIR
@@ -863,19 +871,16 @@ def _computed_flows(args, t: int, j: int, frames, h: int, w: int):
     cur, old = frames[t], frames[t - j]
     if tuple(cur.shape) != (h, w, 3) or tuple(old.shape) != (h, w, 3):
         raise ValueError(f"--compute_flow: frames of {tuple(cur.shape)} and {tuple(old.shape)}, the results are {h} x {w}")
-    radius = _flow_match_radius(args)
-    robust = _flow_robust(args)
-    fb = strotss_engine._ops.optical_flow(cur, old, match_radius=radius, robust=robust)
-    ff = strotss_engine._ops.optical_flow(old, cur, match_radius=radius, robust=robust)
-    save = getattr(args, "save_flow", None)
-    if save:
-        os.makedirs(save, exist_ok=True)
-        strotss.write_flo(os.path.join(save, f"backward_{t}_{t - j}.flo"), fb)
-        strotss.write_flo(os.path.join(save, f"forward_{t - j}_{t}.flo"), ff)
+    fb = strotss_engine._ops.optical_flow(cur, old, match_radius=job.match_radius, robust=job.robust)
+    ff = strotss_engine._ops.optical_flow(old, cur, match_radius=job.match_radius, robust=job.robust)
+    if job.save_flow:
+        os.makedirs(job.save_flow, exist_ok=True)
+        strotss.write_flo(os.path.join(job.save_flow, f"backward_{t}_{t - j}.flo"), fb)
+        strotss.write_flo(os.path.join(job.save_flow, f"forward_{t - j}_{t}.flo"), ff)
     return fb, ff
 
 
-def _flow_warp_for_frame(args, t: int, previous: torch.Tensor, j: int = 1, frames=None):
+def _flow_warp_for_frame(job, t: int, previous: torch.Tensor, j: int = 1, frames=None):
     """(backward flow (h, w, 2), warped result of frame t-j, certainty) of frame t (1-based, t > j) at that result's size:
     the flows of --flow_dir resized to that size (strotss_utils.resize_flow), the warp and certainty in one launch; a
     reliable_{t}_{t-j}.pgm, when there is one, replaces the certainty (its value / 255, resized).  `previous`: the final
@@ -883,41 +888,41 @@ def _flow_warp_for_frame(args, t: int, previous: torch.Tensor, j: int = 1, frame
     read."""
     h, w = int(previous.shape[1]), int(previous.shape[2])
     dev = previous.device
-    if getattr(args, "compute_flow", False):
-        fb, ff = _computed_flows(args, t, j, frames, h, w)
+    if job.compute_flow:
+        fb, ff = _computed_flows(job, t, j, frames, h, w)
         return (fb,) + tuple(strotss_engine._ops.flow_warp(previous.contiguous(), fb, ff))
-    flow_b = strotss.read_flo(os.path.join(args.flow_dir, f"backward_{t}_{t - j}.flo"))
+    flow_b = strotss.read_flo(os.path.join(job.flow_dir, f"backward_{t}_{t - j}.flo"))
     big = tuple(flow_b.shape[:2])
-    fwd_path = os.path.join(args.flow_dir, f"forward_{t - j}_{t}.flo")
+    fwd_path = os.path.join(job.flow_dir, f"forward_{t - j}_{t}.flo")
     flow_f = strotss.read_flo(fwd_path) if os.path.exists(fwd_path) else None
     if flow_f is not None and tuple(flow_f.shape[:2]) != big:
         raise ValueError(f"{fwd_path}: a {tuple(flow_f.shape[:2])} flow, the backward one is {big}")
     fb = strotss.resize_flow(flow_b.to(dev), h, w).contiguous()
     ff = None if flow_f is None else strotss.resize_flow(flow_f.to(dev), h, w).contiguous()
     warped, certainty = strotss_engine._ops.flow_warp(previous.contiguous(), fb, ff)
-    rel = os.path.join(args.flow_dir, f"reliable_{t}_{t - j}.pgm")
+    rel = os.path.join(job.flow_dir, f"reliable_{t}_{t - j}.pgm")
     if os.path.exists(rel):
         certainty = _resized_reliable(rel, h, w)
     return fb, warped, certainty
 
 
-def _pairs_for_frame(args, t: int, results, offsets, frames=None) -> dict:
-    """{j: (backward flow, warped result of frame t-j, raw certainty)} of frame t for the offsets j of `offsets` (ascending)
+def _pairs_for_frame(job, t: int, results, frames=None) -> dict:
+    """{j: (backward flow, warped result of frame t-j, raw certainty)} of frame t for the offsets j of job.offsets (ascending)
     with t - j >= 1: one _flow_warp_for_frame call per pair, so each flow is read or computed -- and with --save_flow
     written -- once per frame.  results[k]: the final result of frame t-1-k.  {} for the first frame.  The tracking
     (entry offsets[0]) and the temporal list (_temporal_targets_for_frame) both take their pairs from this map; the flows
     are the same bits on every run, so sharing an entry gives what computing it again gave."""
-    return {j: _flow_warp_for_frame(args, t, results[j - 1], j, frames) for j in offsets if t - j >= 1 and j <= len(results)}
+    return {j: _flow_warp_for_frame(job, t, results[j - 1], j, frames) for j in job.offsets if t - j >= 1 and j <= len(results)}
 
 
-def _temporal_targets_for_frame(args, t: int, results, offsets, frames=None, pairs=None):
+def _temporal_targets_for_frame(job, t: int, results, frames=None, pairs=None):
     """[(warped result of frame t-j, combined certainty)] of frame t, nearest frame first, 0..4 of them: the one temporal
     shape between the flows and _stylise.  pairs: the frame's _pairs_for_frame map where the caller
     holds it already, built here otherwise.  With two pairs or more the certainties are combined once, at the frame's size
     (strotss_temporal_long_certainty), so that a pixel a nearer frame covers does not pull toward an older one; one pair
     keeps its raw certainty.  [] for the first frame."""
     if pairs is None:
-        pairs = _pairs_for_frame(args, t, results, offsets, frames)
+        pairs = _pairs_for_frame(job, t, results, frames)
     found = [pairs[j][1:] for j in sorted(pairs)]
     if len(found) <= 1:                     # nothing nearer to subtract: the raw certainty is the combined one
         return found
@@ -933,13 +938,11 @@ def _resized_reliable(path: str, h: int, w: int) -> torch.Tensor:
     return c.contiguous()
 
 
-def _load_masks(args):
-    """(content_masks, style_masks) or ([None], [None]); one of the two flags alone is an error."""
-    if bool(args.content_mask) != bool(args.style_mask):
-        raise ValueError('Either both content and style masks must be provided or neither.')
-    if not args.content_mask:
+def _load_masks(job):
+    """(content_masks, style_masks) or ([None], [None]); one of the two flags alone was refused by _resolve."""
+    if not job.content_mask:
         return [None], [None]
-    c_masks, s_masks = strotss.load_mask(args.content_mask, args.style_mask, max_size=args.max_size)
+    c_masks, s_masks = strotss.load_mask(job.content_mask, job.style_mask, max_size=job.max_size)
     utils.logger.info(f'Loaded {len(c_masks)} masks.')
     return c_masks, s_masks
 
@@ -994,7 +997,7 @@ def _optimise_scale(eng, scl: int, content_masks, args, dev, quiet: bool = False
     below then draw the same weighted sequence."""
     from nn import parallel
     masks_here = [None if m is None else strotss.mask_at_scale(m, eng.h, eng.w) for m in content_masks]
-    log_every = max(1, int(getattr(args, "log_every", 10)))
+    log_every = max(1, int(args.log_every))
     # The index sets are drawn on the host (as make_indices does in the reference's step).  Uploading them from pageable
     # memory would block the host until the previous step has drained, leaving the GPU idle while the next draw is
     # computed (~0.3 ms per step, a quarter of a 64-px step): a small ring of pinned buffers + asynchronous copies lets
@@ -1003,12 +1006,12 @@ def _optimise_scale(eng, scl: int, content_masks, args, dev, quiet: bool = False
     # Philox stream whose host twin is rand.index_rng, so the sequence is the one the host loop below would draw) -- wherever
     # the sample count cannot vary from step to step.  No upload, no ring, nothing for the host to do per step.
     stream = rand.index_rng
-    if (dev.type == "cuda" and not getattr(args, "host_draw", False) and isinstance(stream, rand.PhiloxStream)
+    if (dev.type == "cuda" and not args.host_draw and isinstance(stream, rand.PhiloxStream)
             and (eng.enable_device_draw(stream.seed, stream.t, masks_here) if sample_levels is None else
                  eng.enable_device_draw(stream.seed, stream.t, masks_here, sample_levels=sample_levels))):
         with tqdm(range(args.max_iter), disable=quiet) as bar:
             for it in bar:
-                if it == 0 and not getattr(args, "no_graph", False):
+                if it == 0 and not args.no_graph:
                     eng.capture_graph()
                 eng.step()
                 if step_trace is not None:
@@ -1049,7 +1052,7 @@ def _optimise_scale(eng, scl: int, content_masks, args, dev, quiet: bool = False
                 ev = torch.cuda.Event()
                 ev.record()
                 slots[(r, it % ring)] = (buf, ev)
-            if it == 0 and not getattr(args, "no_graph", False):
+            if it == 0 and not args.no_graph:
                 eng.capture_graph(idx, offsets)
             eng.step(idx, offsets)
             if step_trace is not None:
@@ -1072,112 +1075,95 @@ def _logged_terms(eng):
 def run(args: argparse.Namespace, trace=None):
     """The reference's run(args) (run_strotss.py:43-161).  `trace` (a list) receives one dict per executed scale:
     scale index and size, lr, alpha, loss_denom, the image the scale starts from, every step's losses and the
-    result -- what the parity test of the schedule compares with the oracle's run_scales.  --video: run_video."""
-    _auto_masks_input(args)                                  # refusals first, --video among them
-    _style_transport_input(args)
-    _palette_transport_input(args)
-    _pixel_prior_input(args)
-    _photo_term_input(args)
-    _auto_sample_input(args)                                 # --sample_map's refusals, then those of auto's four flags
-    if getattr(args, "video", False):
-        return run_video(args, trace)
+    result -- what the parity test of the schedule compares with the oracle's run_scales.  The command line is resolved
+    once (_resolve); with --video the job goes to run_video's frame loop."""
+    job = _resolve(args)                                     # every refusal, before anything is loaded
+    if job.video:
+        return _run_frames(job, trace)
     timer = utils.Timer()
     timer.start()
-
-    cw_path = _content_weight_input(args)
-    post = _preserve_color_input(args), _photo_smooth_input(args), _output_size_input(args)
-    _video_inputs(args)                                      # the sequence flags without --video: ValueError
-    seed = int(getattr(args, "seed", 0))
-    rand.seed_everything(seed)
+    rand.seed_everything(job.seed)
     from nn import parallel
     rank, world = 0, 1
-    masked = bool(getattr(args, "content_mask", None))
-    if (getattr(args, "strips", False) or masked) and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+    if (job.strips or job.content_mask) and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
         rank, world = parallel.init_from_env(torch.cuda.current_device())
     dev = utils.device()
 
-    vgg = VGG(use_keras_weight=args.use_keras_weight, weights=getattr(args, "weights", None), seed=seed, device=dev)
-    guides = _written_guides(args, post, args.content_path)  # --output_size: the target's size is refused before the first step
-    final = _written(_stylise(args, vgg, args.content_path, cw_path, dev, rank, world, trace), post, guides)
+    vgg = VGG(use_keras_weight=job.use_keras_weight, weights=job.weights, seed=job.seed, device=dev)
+    guides = _written_guides(job, job.content_path)          # --output_size: the target's size is refused before the first step
+    final = _written(_stylise(job, vgg, job.content_path, dev, rank, world, trace), job, guides)
     if torch.cuda.is_available():
         torch.cuda.synchronize()
     timer.stop()
     if rank == 0:
         utils.logger.info(f"Done in {timer.elapsed_time:.2f}s.")
-        utils.write_image(final, args.output_path)
+        utils.write_image(final, job.output_path)
     return final
 
 
-def _region_masks(args, vgg, content, style, strokes=None, masks=None):
+def _region_masks(job, vgg, content, style, strokes=None, masks=None):
     """(content_masks, style_masks) of an image as loaded, from the first source there is: `masks` from the caller
     (--track_masks), --auto_masks (the regions found), the scribble files (`strokes`: what load_scribbles read; the regions
     grown from them), --content_mask / --style_mask (or [None], [None]).  --save_masks writes what was found or grown."""
     if masks is not None:
         return masks
-    auto = _auto_masks_input(args)
-    if auto:
-        refine = _refine_masks_input(args)                   # without --refine_masks the call carries no such keyword
-        content_masks, style_masks = strotss.auto_masks(vgg.params, content, style, auto[0],
-                                                        **({} if refine is None else dict(refine=refine)))
+    if job.auto:
+        k, save = job.auto                                   # without --refine_masks the call carries no such keyword
+        content_masks, style_masks = strotss.auto_masks(vgg.params, content, style, k,
+                                                        **({} if job.refine is None else dict(refine=job.refine)))
         if content_masks[0] is not None:
             utils.logger.info(f'Found {len(content_masks)} regions.')
-            if auto[1]:
-                strotss.save_masks(auto[1], content_masks, style_masks)
+            if save:
+                strotss.save_masks(save, content_masks, style_masks)
         return content_masks, style_masks
     if strokes:
-        _, _, sigma, iters = _scribble_masks_input(args)
+        _, _, sigma, iters = job.scribbles
         content_masks, style_masks = strotss.scribble_masks(vgg.params, content, style, strokes[0], strokes[1],
                                                             len(strokes[2]), strokes[2], sigma, iters)
         utils.logger.info(f'Grew {len(content_masks)} regions from the strokes.')
-        if getattr(args, "save_masks", None):
-            strotss.save_masks(args.save_masks, content_masks, style_masks)
+        if job.save_masks:
+            strotss.save_masks(job.save_masks, content_masks, style_masks)
         return content_masks, style_masks
-    return _load_masks(args)
+    return _load_masks(job)
 
 
-def _sample_map(args, content, content_path: str, rank: int = 0):
+def _sample_map(job, content, content_path: str, rank: int = 0):
     """--sample_map: the map read from its path; with `auto` this image's own detail map (with --video every frame's), which
     --save_sample_map DIR writes as sample_map.png (with --video sample_map_<frame stem>.png); None without the flag"""
-    auto = _auto_sample_input(args)
+    auto = job.auto_sample
     if not auto:
-        path = _sample_map_input(args)
-        return strotss.load_sample_map(path) if path else None
+        return strotss.load_sample_map(job.sample_map) if job.sample_map else None
     sm_map = strotss.auto_sample_map(content, *auto[:3])
     if auto[3] and rank == 0:
         stem = os.path.splitext(os.path.basename(content_path))[0]
-        name = f"sample_map_{stem}.png" if getattr(args, "video", False) else "sample_map.png"
+        name = f"sample_map_{stem}.png" if job.video else "sample_map.png"
         strotss.save_sample_map(os.path.join(auto[3], name), sm_map)
     return sm_map
 
 
-def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: int = 1, trace=None, temporal=None,
-             temporal_weight: float = 0.0, masks=None):
+def _stylise(job, vgg, content_path: str, dev, rank: int = 0, world: int = 1, trace=None, temporal=None, masks=None):
     """The coarse-to-fine schedule on one content image -> the final image of the finest scale (1, h, w, 3).
     temporal: _temporal_targets_for_frame's list of 0..4 (warped earlier result, certainty) pairs at that result's size,
     nearest frame first; None and [] mean no term.  Every scale carries one temporal term per pair, all with weight
-    temporal_weight, and --temporal_init starts the first executed scale from the nearest pair's warped result.
+    job.temporal_weight, and --temporal_init starts the first executed scale from the nearest pair's warped result.
     masks: (content_masks, style_masks) of this frame from the caller (--track_masks), in place of those of _region_masks."""
     from nn import parallel
-    level, first = int(args.level), int(getattr(args, "start_level", 0))
-    scribbles = _scribble_masks_input(args)                  # the stroke files' own refusals, before any image is loaded
-    strokes = strotss.load_scribbles(scribbles[0], scribbles[1]) if scribbles else None
-    content = utils.load_image(content_path, max_size=args.max_size)
-    style_paths, style_weights = _style_inputs(args)
-    styles = [utils.load_image(p, max_size=args.max_size) for p in style_paths]
-    content_masks, style_masks = _region_masks(args, vgg, content, styles[0], strokes, masks)
+    level, first = int(job.level), int(job.start_level)
+    strokes = strotss.load_scribbles(*job.scribbles[:2]) if job.scribbles else None
+    content = utils.load_image(content_path, max_size=job.max_size)
+    style_paths, style_weights = job.styles
+    styles = [utils.load_image(p, max_size=job.max_size) for p in style_paths]
+    content_masks, style_masks = _region_masks(job, vgg, content, styles[0], strokes, masks)
     # --preserve_color match / transfer, before any resize: every scale samples the recoloured styles
-    styles = _recolour_styles(args, styles, content, content_masks, style_masks)
-    cw_map = strotss.load_content_weight_map(cw_path) if cw_path else None
-    sm_map = _sample_map(args, content, content_path, rank)
+    styles = _recolour_styles(job, styles, content, content_masks, style_masks)
+    cw_map = strotss.load_content_weight_map(job.content_weight) if job.content_weight else None
+    sm_map = _sample_map(job, content, content_path, rank)
     sampling = strotss.Sampling(SAMPLE_SIZE)
-    masked = bool(getattr(args, "content_mask", None))
-    transport = dict(_style_transport_input(args), **_palette_transport_input(args))
-    prior = _pixel_prior_input(args)
-    photo = _photo_term_input(args)
+    prior, photo = job.prior, job.photo
 
     # alpha = 16 (x3500 with Keras weights), halved after every scale -- also after skipped ones
-    alpha = args.alpha * 16.0 * (3500 if args.use_keras_weight else 1) / 2.0 ** first
+    alpha = job.alpha * 16.0 * (3500 if job.use_keras_weight else 1) / 2.0 ** first
     stylized = None
     for position, i in enumerate(range(first, level)):
         scl = 2 << (5 + i)                                   # long side 64, 128, 256, ...
@@ -1186,18 +1172,18 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
         if len(scl_style) == 1:
             scl_style = scl_style[0]
         stylized, lr = _initial_image(position, position > 0 and i == level - 1, stylized, scl_content, scl_style,
-                                      args.lr, style_weights)
+                                      job.lr, style_weights)
         hs, ws = int(scl_content.shape[1]), int(scl_content.shape[2])
-        terms = dict(transport)                              # the engine's keywords of this scale, built afresh
+        terms = dict(job.engine_terms)                       # the engine's keywords of this scale, built afresh
         if temporal:
             scaled = strotss.temporal_targets_at_scale(temporal, hs, ws)
-            terms["temporal"] = [strotss_engine.TemporalTarget(target, cert, temporal_weight) for target, cert in scaled]
-            if position == 0 and getattr(args, "temporal_init", False):
+            terms["temporal"] = [strotss_engine.TemporalTarget(target, cert, job.temporal_weight) for target, cert in scaled]
+            if position == 0 and job.temporal_init:
                 stylized = scaled[0][0][None].contiguous()   # the nearest frame's warp instead of Laplacian + mean style colour
         # --strips: ONE image sharded by rows (the only sharding that cuts trunk work), with or without mask regions; where
         # a scale is too small for strips to pay (strip_plan -> None) a masked run falls back to dealing its regions out
-        plan = (parallel.strip_plan(int(scl_content.shape[1]), world, rank, halo=bool(getattr(args, "halo", False)))
-                if world > 1 and getattr(args, "strips", False) else None)
+        plan = (parallel.strip_plan(int(scl_content.shape[1]), world, rank, halo=bool(job.halo))
+                if world > 1 and job.strips else None)
         cw_scaled = None if cw_map is None else strotss.content_weight_at_scale(cw_map, hs, ws)
         if prior["detail"] is not None:                      # the detail target: this image's content at this scale
             terms["detail"] = strotss_engine.DetailTarget(scl_content, prior["detail"][1], prior["detail"][0], cw_scaled)
@@ -1209,7 +1195,7 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
             vgg.params, strotss_engine.extract_features(vgg.params, scl_content),
             _style_targets(vgg.params, scl_style, style_masks, sampling, style_weights), stylized, alpha,
             loss_denom=2. + alpha + 1. / max(alpha, 1.), lr=lr, sample_size=SAMPLE_SIZE, strips=plan,
-            dist_group=parallel.WORLD if (world > 1 and masked and plan is None) else None,
+            dist_group=parallel.WORLD if (world > 1 and job.content_mask and plan is None) else None,
             content_weight=cw_scaled, **terms)
         rec = None
         if trace is not None:
@@ -1217,7 +1203,7 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
                        hw=(eng.h, eng.w))
             trace.append(rec)
         # --sample_map: the levels of this scale, rounded once
-        _optimise_scale(eng, scl, content_masks, args, dev, quiet=rank != 0, step_trace=None if rec is None else rec["steps"],
+        _optimise_scale(eng, scl, content_masks, job, dev, quiet=rank != 0, step_trace=None if rec is None else rec["steps"],
                         sample_levels=None if sm_map is None else strotss.sample_levels_at_scale(sm_map, hs, ws))
         stylized = eng.stylized()
         if rec is not None:
@@ -1227,22 +1213,22 @@ def _stylise(args, vgg, content_path: str, cw_path, dev, rank: int = 0, world: i
     return stylized
 
 
-def _tracked_masks(args, vgg, tracking: dict, t: int, frame: str, j: int, nearest, auto, inertia: float):
+def _tracked_masks(job, vgg, tracking: dict, t: int, frame: str, nearest):
     """--track_masks: (content_masks, style_masks) of frame t.  tracking: {frame position: state} of the
-    last j frames plus the sequence's constants under "style" (the style masks of all kept regions) -- or {"off": True} once
-    frame 1 gave fewer than two regions (the whole sequence then runs unmasked).  Frame 1: auto_mask_regions jointly with
-    style_path, the masks of both images as a single-image run makes them.  Frame t > 1: strotss_utils.track_regions
-    against the state of frame t-j along `nearest` = (backward flow, warped result, certainty) of that pair (None for
-    t <= j: no prior), then the content masks of the present regions with the matching style masks.  --save_masks DIR:
-    style_mask.png once, content_mask_<frame stem>.png per frame (of a frame that runs unmasked: its label grid)."""
+    last j frames (j = job.offsets[0], the nearest offset) plus the sequence's constants under "style" (the style masks of
+    all kept regions) -- or {"off": True} once frame 1 gave fewer than two regions (the whole sequence then runs unmasked).
+    Frame 1: auto_mask_regions jointly with style_path, the masks of both images as a single-image run makes them.
+    Frame t > 1: strotss_utils.track_regions against the state of frame t-j along `nearest` = (backward flow, warped
+    result, certainty) of that pair (None for t <= j: no prior), then the content masks of the present regions with the
+    matching style masks.  --save_masks DIR: style_mask.png once, content_mask_<frame stem>.png per frame (of a frame that
+    runs unmasked: its label grid)."""
     if tracking.get("off"):
         return [None], [None]
-    k, save = auto
-    refine = _refine_masks_input(args)
-    content = utils.load_image(frame, max_size=args.max_size)
+    (k, save), refine, j = job.auto, job.refine, job.offsets[0]
+    content = utils.load_image(frame, max_size=job.max_size)
     stem = os.path.splitext(os.path.basename(frame))[0]
     if t == 1:
-        style = utils.load_image(args.style_path, max_size=args.max_size)
+        style = utils.load_image(job.style_path, max_size=job.max_size)
         found = strotss.auto_mask_regions(vgg.params, content, style, k)
         if not found["kept"]:
             utils.logger.warning(f"--auto_masks {k}: fewer than two clusters hold {strotss.AUTO_MASK_MIN_SHARE:.3f} of both "
@@ -1260,7 +1246,7 @@ def _tracked_masks(args, vgg, tracking: dict, t: int, frame: str, j: int, neares
         return content_masks, style_masks
     source = tracking[t - j] if nearest is not None else tracking[1]      # t <= j: frame 1's state is still held
     flow, certainty = (nearest[0], nearest[2].float().contiguous()) if nearest is not None else (None, None)
-    state = strotss.track_regions(source, vgg.params, content, flow, certainty, inertia)
+    state = strotss.track_regions(source, vgg.params, content, flow, certainty, job.inertia)
     tracking[t] = state
     tracking.pop(t - j, None)
     present = state["present"]
@@ -1286,43 +1272,43 @@ def run_video(args: argparse.Namespace, trace=None):
     (_temporal_targets_for_frame); then the frame path of run(): _written_guides, _stylise, _written.  Only what is written
     is filtered, upsampled or merged: the temporal targets and --temporal_init keep the optimiser's own results.  Writes
     <output dir>/<frame stem>.jpg; returns the list of the frames' uint8 results.  `trace`: one list per frame."""
-    post = _preserve_color_input(args), _photo_smooth_input(args), _output_size_input(args)
-    frames, lam = _video_inputs(args)
-    cw_path = _content_weight_input(args)
-    seed = int(getattr(args, "seed", 0))
+    return _run_frames(_resolve(args), trace)
+
+
+def _run_frames(job, trace=None):
+    """run_video on the resolved job: run() hands over its own, so a sequence is resolved once as well"""
     dev = utils.device()
-    os.makedirs(args.output_path, exist_ok=True)
-    vgg = VGG(use_keras_weight=args.use_keras_weight, weights=getattr(args, "weights", None), seed=seed, device=dev)
-    offsets = _temporal_frames(args)
-    auto, inertia = _auto_masks_input(args), _track_masks_input(args)
-    tracking = {} if auto else None         # --track_masks: the states of the last offsets[0] frames, by frame position
+    os.makedirs(job.output_path, exist_ok=True)
+    vgg = VGG(use_keras_weight=job.use_keras_weight, weights=job.weights, seed=job.seed, device=dev)
+    offsets = job.offsets
+    tracking = {} if job.auto else None     # --track_masks: the states of the last offsets[0] frames, by frame position
     outs, results = [], []                  # results[k]: the final image of frame t-1-k, the last max(offsets) of them
-    flow_frames = {} if getattr(args, "compute_flow", False) else None      # --compute_flow: the last max(offsets) + 1 frames
-    for t, frame in enumerate(frames, start=1):
+    flow_frames = {} if job.compute_flow else None      # --compute_flow: the last max(offsets) + 1 frames
+    for t, frame in enumerate(job.frames, start=1):
         timer = utils.Timer()
         timer.start()
-        rand.seed_everything(seed)
+        rand.seed_everything(job.seed)
         if flow_frames is not None:
-            flow_frames[t] = _frame_at_result_size(args, frame)
+            flow_frames[t] = _frame_at_result_size(job, frame)
             flow_frames.pop(t - offsets[-1] - 1, None)
-        pairs = _pairs_for_frame(args, t, results, offsets, flow_frames)
-        temporal = _temporal_targets_for_frame(args, t, results, offsets, flow_frames, pairs)
+        pairs = _pairs_for_frame(job, t, results, flow_frames)
+        temporal = _temporal_targets_for_frame(job, t, results, flow_frames, pairs)
         rec = None
         if trace is not None:
             rec = []
             trace.append(rec)
         masks = None
         if tracking is not None:            # pairs.get: no prior for t <= offsets[0]
-            masks = _tracked_masks(args, vgg, tracking, t, frame, offsets[0], pairs.get(offsets[0]), auto, inertia)
-        guides = _written_guides(args, post, frame, None if flow_frames is None else flow_frames[t])
-        stylized = _stylise(args, vgg, frame, cw_path, dev, trace=rec, temporal=temporal, temporal_weight=lam, masks=masks)
+            masks = _tracked_masks(job, vgg, tracking, t, frame, pairs.get(offsets[0]))
+        guides = _written_guides(job, frame, None if flow_frames is None else flow_frames[t])
+        stylized = _stylise(job, vgg, frame, dev, trace=rec, temporal=temporal, masks=masks)
         results = [stylized] + results[:offsets[-1] - 1]
-        final = _written(stylized, post, guides)
+        final = _written(stylized, job, guides)
         if torch.cuda.is_available():
             torch.cuda.synchronize()
         timer.stop()
-        out = os.path.join(args.output_path, os.path.splitext(os.path.basename(frame))[0] + ".jpg")
-        utils.logger.info(f"Frame {t}/{len(frames)} done in {timer.elapsed_time:.2f}s.")
+        out = os.path.join(job.output_path, os.path.splitext(os.path.basename(frame))[0] + ".jpg")
+        utils.logger.info(f"Frame {t}/{len(job.frames)} done in {timer.elapsed_time:.2f}s.")
         utils.write_image(final, out)
         outs.append(final)
     return outs

@@ -230,7 +230,7 @@ def _read(path):
 
 def _content_at_output_size(RS, path):
     args = RS.build_parser().parse_args([path, STYLE] + SETTINGS)
-    return RS._frame_at_result_size(args, path).cpu().numpy().astype(np.float64)
+    return RS._frame_at_result_size(RS._resolve(args), path).cpu().numpy().astype(np.float64)
 
 
 def test_cli_preserve_color_single_image(tmp_path, monkeypatch):

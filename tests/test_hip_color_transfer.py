@@ -292,7 +292,7 @@ def test_transfer_region_by_region():
     content[:, w // 2:] *= np.float32([0.3, 0.5, 1.0])
     style = (0.5 + 0.2 * rng.standard_normal((sh, sw, 3))).astype(np.float32)
     c_masks, s_masks = _halves(h, w), _halves(sh, sw, gap=4)
-    args = RS.build_parser().parse_args(["c.jpg", "s.jpg", "--preserve_color", "transfer"])
+    args = RS._resolve(RS.build_parser().parse_args(["c.jpg", "s.jpg", "--preserve_color", "transfer"]))
     styles, cd = [_dev(style)[None]], _dev(content)[None]
     (out,) = RS._recolour_styles(args, styles, cd, c_masks, s_masks)
     (again,) = RS._recolour_styles(args, styles, cd, c_masks, s_masks)
@@ -322,7 +322,7 @@ def _read(path):
 
 def _content_at_output_size(RS, path):
     args = RS.build_parser().parse_args([path, STYLE] + SETTINGS)
-    return RS._frame_at_result_size(args, path).cpu().numpy().astype(np.float64)
+    return RS._frame_at_result_size(RS._resolve(args), path).cpu().numpy().astype(np.float64)
 
 
 def test_cli_transfer_single_image(tmp_path, monkeypatch):

@@ -44,7 +44,7 @@ def test_suggested_weight_lowers_the_matting_energy(tmp_path, monkeypatch):
     for name, extra in (("off", ()), ("on", ("--photo_weight", f"{SUGGESTED_PHOTO_WEIGHT:g}"))):
         out, args = _parse(tmp_path, name, *extra)
         RS.run(args)
-        content = RS._frame_at_result_size(args, args.content_path).cpu().numpy().astype(np.float64)
+        content = RS._frame_at_result_size(RS._resolve(args), args.content_path).cpu().numpy().astype(np.float64)
         e.append(_e_m(out, content))
     print(f"MEASURE end to end: E_m off {e[0]:.6e} on {e[1]:.6e} ratio {e[1] / e[0]:.4f} (bound {PHOTO_RATIO})")
     assert e[1] < PHOTO_RATIO * e[0], e

@@ -416,7 +416,7 @@ def _run(tmp_path, name, *extra):
                                          "--max_iter", "30", "-o", out] + list(extra))
     RS.run(args)
     result = np.asarray(Image.open(out).convert("RGB"), dtype=np.float64) / 255.0
-    content = RS._frame_at_result_size(args, args.content_path).cpu().numpy().astype(np.float64)
+    content = RS._frame_at_result_size(RS._resolve(args), args.content_path).cpu().numpy().astype(np.float64)
     return result, content
 
 

@@ -327,7 +327,7 @@ def test_temporal_for_frame_reads_the_flow_files(tmp_path):
     from PIL import Image
     frames, flows = str(tmp_path / "frames"), str(tmp_path / "flows")
     T.translated_sequence(frames, flows, n_frames=2, h=48, w=64, shift=(3, 2))
-    args = RS.build_parser().parse_args([frames, "s.jpg", "--video", "--flow_dir", flows])
+    args = RS._resolve(RS.build_parser().parse_args([frames, "s.jpg", "--video", "--flow_dir", flows]))
     for h, w in ((48, 64), (24, 32)):                   # at the frames' size, and at half of it: the flows scaled by 0.5
         prev = np.random.default_rng(h).random((h, w, 3)).astype(np.float32)
         warped, cert = RS._flow_warp_for_frame(args, 2, _dev(prev)[None])[1:]

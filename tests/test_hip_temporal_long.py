@@ -343,10 +343,11 @@ def test_temporal_targets_for_frame_reads_and_combines(tmp_path):
     import run_strotss as RS
     frames, flows = str(tmp_path / "frames"), str(tmp_path / "flows")
     paths, occluder = TL.occluder_sequence(frames, flows, n_frames=3, offsets=(1, 2))
-    args = RS.build_parser().parse_args([frames, "s.jpg", "--video", "--flow_dir", flows, "--temporal_frames", "1", "2"])
+    args = RS._resolve(RS.build_parser().parse_args([frames, "s.jpg", "--video", "--flow_dir", flows,
+                                                     "--temporal_frames", "1", "2"]))
     rng = np.random.default_rng(1)
     results = [_dev(rng.random((1, 48, 64, 3))) for _ in range(2)]     # frames 2 and 1
-    pairs = RS._temporal_targets_for_frame(args, 3, results, (1, 2))
+    pairs = RS._temporal_targets_for_frame(args, 3, results)
     torch.cuda.synchronize()
     assert len(pairs) == 2
     raw = []
@@ -361,7 +362,7 @@ def test_temporal_targets_for_frame_reads_and_combines(tmp_path):
     hole = occluder(2) & ~occluder(3) & ~occluder(1)
     assert hole.any() and (comb[0][hole] == 0).all() and (comb[1][hole] == 1).all()
     # frame 2: only j = 1 applies -- the one-target pair, raw
-    one = RS._temporal_targets_for_frame(args, 2, results[1:], (1, 2))
+    one = RS._temporal_targets_for_frame(args, 2, results[1:])
     assert len(one) == 1 and torch.equal(one[0][1], RS._flow_warp_for_frame(args, 2, results[1], 1)[2])
 
 

@@ -106,17 +106,21 @@ def test_each_frame_offset_pair_is_computed_once(tmp_path, monkeypatch, offsets,
         combined.append(stack.clone())
         return stack + 0.5
 
-    def stylise(args, vgg, frame, cw_path, dev, **kw):
+    def stylise(job, vgg, frame, dev, **kw):
         t = names.index(frame) + 1
         stylised.append((t, kw["temporal"], kw["masks"]))
         results[t] = torch.full((1, 2, 3, 3), float(t))
         return results[t]
 
-    def tracked_masks(args, vgg, tracking, t, frame, j, nearest, auto, inertia):
-        tracked.append((t, j, nearest))
+    def tracked_masks(job, vgg, tracking, t, frame, nearest):
+        tracked.append((t, job.offsets[0], nearest))
         return [None], [None]
 
-    monkeypatch.setattr(RS, "_video_inputs", lambda args: (names, 1.0))
+    def video_inputs(args, found):                                     # no frame files: the names, the offsets as parsed
+        found.update(match_radius=0, robust=None, offsets=RS._temporal_frames(args))
+        return names, 1.0
+
+    monkeypatch.setattr(RS, "_video_inputs", video_inputs)
     monkeypatch.setattr(RS, "VGG", lambda **kw: None)
     monkeypatch.setattr(RS, "_flow_warp_for_frame", flow_warp)
     monkeypatch.setattr(RS.strotss_engine._ops, "temporal_long_certainty", long_certainty)

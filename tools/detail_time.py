@@ -111,7 +111,7 @@ def sweep():
                 trace = []
                 RS.run(args, trace)
                 res = np.asarray(Image.open(out).convert("RGB"), dtype=np.float64) / 255.0
-                content = RS._frame_at_result_size(args, args.content_path).cpu().numpy().astype(np.float64)
+                content = RS._frame_at_result_size(RS._resolve(args), args.content_path).cpu().numpy().astype(np.float64)
                 d4 = PR.laplacian(PR.pool(res, 4) - PR.pool(content, 4))
                 d1 = PR.laplacian(res - content)
                 last = trace[-1]["steps"][-1] if trace and trace[-1]["steps"] else {}

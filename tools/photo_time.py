@@ -106,7 +106,7 @@ def sweep():
             trace = []
             RS.run(args, trace)
             res = np.asarray(Image.open(out).convert("RGB"), dtype=np.float64) / 255.0
-            content = RS._frame_at_result_size(args, args.content_path).cpu().numpy().astype(np.float64)
+            content = RS._frame_at_result_size(RS._resolve(args), args.content_path).cpu().numpy().astype(np.float64)
             last = trace[-1]["steps"][-1] if trace and trace[-1]["steps"] else {}
             print(json.dumps({"what": "sweep", "max_iter": iters, "weight": v, "E_m": round(e_m(res, content), 7),
                               "loss_c": round(float(last.get("loss_c", float("nan"))), 5),
